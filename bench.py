@@ -8,15 +8,18 @@ Workload (BASELINE.json configs[2]): the secp256k1 ECDSA-verify circuit of
 Default (`--circuit real`): the REAL circuit, rebuilt gadget for gadget in Python (plonky2-lib_amd/gadgets_ecdsa.py) on the host
 BEFORE the timed region, with a valid witness of random signatures.  At this repository's gate density (98 687 rows per signature;
 row count against plonky2's own builder: parity unpinned) a 2^20-row trace holds TEN signatures, not the twenty of `perf.rs`: the
-twenty-signature batch is a 2^21-row trace and is timed, verified, as `variants.perf_rs_batch_20`; `signatures_per_proof` and
-`signatures_per_sec` are top-level fields of the JSON line.  `--circuit stand-in` times the gate-mix circuit of the same shape that
-rounds 1-2 used (`variants.gate_mix_stand_in` in the default run).
+twenty-signature batch is a 2^21-row trace and is timed, verified, as `variants.perf_rs_batch_20` (--full); `signatures_per_proof`
+and `signatures_per_sec` are top-level fields of the JSON line.  `--circuit stand-in` times the gate-mix circuit of the same shape that
+rounds 1-2 used (`variants.gate_mix_stand_in` in a --full run).
 
-One "step" = one complete prove() (everything after witness generation) from an HBM-resident witness.  After the timed loop every
-rank checks its last proof with glp_verify (`"verified"`), rank 0 also with the oracle's verifier (inside `cpu_baseline`).
-Usage: python bench.py --gpus N --steps K --warmup W
+One "step" = one complete prove() (everything after witness generation) from an HBM-resident witness.  A plain run sets up, warms
+up, times the K steps and prints the result line, nothing else.  With --full, every rank then checks its last proof with glp_verify
+(`"verified"`) and rank 0 adds the extra measurements (`variants`) and the CPU baseline (`cpu_baseline`, which also runs the oracle's
+verifier on the GPU proof); a plain run reports `"verified": null`.
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1 under torch.distributed.run (RANK / WORLD_SIZE set): this process is one rank.
   N > 1 started bare: bench.py starts the N ranks itself (fresh child processes, before anything touches a GPU).
+  --dump-outputs DIR: rank 0 writes the proofs of its last timed step as DIR/*.npy (see dump_outputs()).
 """
 import argparse
 import json
@@ -37,9 +40,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also verify the proofs and run every extra measurement (variants, cpu_baseline, "
+                         "prove_plus_verify); a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the proofs of the last timed step as DIR/<name>.npy (float64, see dump_outputs())")
     ap.add_argument("--log-n", type=int, default=20, help="trace rows = 2^log_n (headline: 20)")
     ap.add_argument("--cpu-sample-log-n", type=int, default=13, help="rows of the whole-prove() leg of the CPU baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--workload", default="ecdsa", choices=["ecdsa", "zkdsa-batch", "keccak256", "smt"],
                     help="ecdsa: the headline 2^20-row proof (default); zkdsa-batch: BASELINE config 5, a batch of independent "
                          "simple-signature proofs sharded over the ranks; keccak256: BASELINE config 2, the reference's Keccak-256 "
@@ -62,8 +70,8 @@ def parse():
     ap.add_argument("--inflight", type=int, default=1,
                     help="ecdsa: independent proofs proved concurrently per GPU (own context/stream/host thread each); a step is "
                          "then a batch of that many proofs.  Default 1 keeps the per-stage timings free of overlap")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra measurements after the timed region (host witness, two in flight, stand-in, perf.rs batch)")
-    ap.add_argument("--no-perf-rs", action="store_true", help="skip variants.perf_rs_batch_20 (a 2^21-row circuit: ~40 s of host-side circuit building)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the extra measurements after the timed region (host witness, two in flight, stand-in, perf.rs batch)")
+    ap.add_argument("--no-perf-rs", action="store_true", help="with --full: skip variants.perf_rs_batch_20 (a 2^21-row circuit: ~40 s of host-side circuit building)")
     ap.add_argument("--own-witness", action="store_true", help="ecdsa, several ranks: every rank builds its own circuit and witness in Python "
                     "instead of mapping the hand-off file rank 0 writes")
     ap.add_argument("--dist-backend", default=None, help="override the torch.distributed backend (rehearsals: gloo)")
@@ -73,6 +81,26 @@ def parse():
 
 SHAPES = (("wires", 136), ("zs_partial_products", 20), ("quotient_chunks", 16))
 BATCH_STAGES = ("intt", "copy_coeffs", "bitrev_coeffs", "lde", "merkle_leaves", "merkle_levels")
+DUMP_LIMIT_BYTES = 60 * 10 ** 6         # --dump-outputs payload; the .npy headers stay well inside 64 MB
+
+
+def dump_outputs(path, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: `outputs` maps a name to a uint64 array of proof words (one proof, or one proof per row of a batch).
+    A Goldilocks word does not fit a float64 mantissa, so every array is written as two exact float64 halves,
+    DIR/<name>_lo32.npy and DIR/<name>_hi32.npy (word = hi32 * 2^32 + lo32).  If the whole would exceed `limit` bytes, the
+    batches are cut to a fixed seeded sample of their rows (proofs), and the rows kept are written as DIR/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    outputs = {k: np.ascontiguousarray(v, dtype=np.uint64) for k, v in outputs.items()}
+    total = sum(16 * a.size for a in outputs.values())
+    for name, a in outputs.items():
+        if total > limit and a.ndim > 1:
+            keep = max(1, int(a.shape[0] * limit / total))
+            rows = np.sort(np.random.default_rng(SEED).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + "_lo32.npy"), (a & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        np.save(os.path.join(path, name + "_hi32.npy"), (a >> np.uint64(32)).astype(np.float64))
 
 
 def pmc_traffic_file():
@@ -448,45 +476,53 @@ def zkdsa_batch(a, grp, local_rank, glp, synth, gdist, torch):
     for _ in range(a.warmup):
         step()
     dt = gdist.timed_steps(grp, step, a.steps, 0, device_sync)
-    # every proof of the last step is checked by the library's batch verifier (glp_verify_batch: transcripts on host threads, every
-    # query round of every proof in one GPU launch), a sample of them also by the host verifier; outside the timed region
-    ok = all(bool(w[1].verify_batch(w[5]).all()) and all(bool(w[1].verify(p)) for p in w[5][:4]) for w in workers if w[5] is not None)
-
-    # prove THEN verify, as every reference driver does [REF src/zkdsa/circuits/mod.rs:341-347]: the same step with glp_verify_batch
-    # behind each glp_prove_batch, timed on its own (never `value`)
-    verdicts = []
-
-    def step_pv():
-        def run(w):
-            ctx, circuit, sub, wires, pis, out = w
-            if not sub:
-                return
-            for i0 in range(0, len(sub), a.sub_batch):
-                circuit.prove_batch(wires[i0:i0 + a.sub_batch], pis[i0:i0 + a.sub_batch], out=out[i0:i0 + a.sub_batch])
-                verdicts.append(bool(circuit.verify_batch(out[i0:i0 + a.sub_batch]).all()))
-        th = [threading.Thread(target=run, args=(w,)) for w in workers]
-        for t in th:
-            t.start()
-        for t in th:
-            t.join()
-    dt_pv = None
-    if not a.per_proof:
-        step_pv()
-        dt_pv = gdist.timed_steps(grp, step_pv, a.steps, 0, device_sync)
-        ok = ok and all(verdicts)
-    pv = {"value": a.batch * a.steps / dt_pv, "unit": "proofs proved and verified / sec", "ms_per_step": dt_pv / a.steps * 1e3,
-          "note": "glp_prove_batch followed by glp_verify_batch (query rounds on the GPU) per sub-batch; not the headline value"} if dt_pv else None
-    if keccak and mine:
-        # the public inputs of every proof are the Keccak-256 digest of its message (GPU Keccak of the product library as the second opinion)
-        want = [workers[0][0].keccak256([m])[0] for m in msgs]
-        got = {}
+    if a.dump_outputs and grp.rank == 0 and mine:
+        proofs = np.empty((len(mine), workers[0][1].proof_words), np.uint64)      # rank 0's shard in batch order: worker t holds t, t + nthr, ..
         for t, w in enumerate(workers):
-            for i, p in enumerate(w[5] if w[5] is not None else []):
-                got[t + i * nthr] = b"".join(int(v).to_bytes(4, "little") for v in p[-8:])
-        ok = ok and all(got[i] == want[i] for i in range(len(msgs)))
-    if smt and mine:
-        ok = ok and all([int(x) for x in p[-12:-8]] == list(tree.root) for w in workers if w[5] is not None for p in w[5])
-    ok_all = grp.max_over_ranks(0.0 if ok else 1.0) == 0.0
+            if w[5] is not None:
+                proofs[t::nthr] = w[5]
+        dump_outputs(a.dump_outputs, {"proofs": proofs})
+    ok_all, pv = None, None
+    if a.full:
+        # every proof of the last step is checked by the library's batch verifier (glp_verify_batch: transcripts on host threads, every
+        # query round of every proof in one GPU launch), a sample of them also by the host verifier; outside the timed region
+        ok = all(bool(w[1].verify_batch(w[5]).all()) and all(bool(w[1].verify(p)) for p in w[5][:4]) for w in workers if w[5] is not None)
+
+        # prove THEN verify, as every reference driver does [REF src/zkdsa/circuits/mod.rs:341-347]: the same step with glp_verify_batch
+        # behind each glp_prove_batch, timed on its own (never `value`)
+        verdicts = []
+
+        def step_pv():
+            def run(w):
+                ctx, circuit, sub, wires, pis, out = w
+                if not sub:
+                    return
+                for i0 in range(0, len(sub), a.sub_batch):
+                    circuit.prove_batch(wires[i0:i0 + a.sub_batch], pis[i0:i0 + a.sub_batch], out=out[i0:i0 + a.sub_batch])
+                    verdicts.append(bool(circuit.verify_batch(out[i0:i0 + a.sub_batch]).all()))
+            th = [threading.Thread(target=run, args=(w,)) for w in workers]
+            for t in th:
+                t.start()
+            for t in th:
+                t.join()
+        dt_pv = None
+        if not a.per_proof:
+            step_pv()
+            dt_pv = gdist.timed_steps(grp, step_pv, a.steps, 0, device_sync)
+            ok = ok and all(verdicts)
+        pv = {"value": a.batch * a.steps / dt_pv, "unit": "proofs proved and verified / sec", "ms_per_step": dt_pv / a.steps * 1e3,
+              "note": "glp_prove_batch followed by glp_verify_batch (query rounds on the GPU) per sub-batch; not the headline value"} if dt_pv else None
+        if keccak and mine:
+            # the public inputs of every proof are the Keccak-256 digest of its message (GPU Keccak of the product library as the second opinion)
+            want = [workers[0][0].keccak256([m])[0] for m in msgs]
+            got = {}
+            for t, w in enumerate(workers):
+                for i, p in enumerate(w[5] if w[5] is not None else []):
+                    got[t + i * nthr] = b"".join(int(v).to_bytes(4, "little") for v in p[-8:])
+            ok = ok and all(got[i] == want[i] for i in range(len(msgs)))
+        if smt and mine:
+            ok = ok and all([int(x) for x in p[-12:-8]] == list(tree.root) for w in workers if w[5] is not None for p in w[5])
+        ok_all = grp.max_over_ranks(0.0 if ok else 1.0) == 0.0
     if grp.rank == 0 and keccak:
         d0 = descs[0]
         print(json.dumps({
@@ -533,7 +569,7 @@ def zkdsa_batch(a, grp, local_rank, glp, synth, gdist, torch):
             w[1].free()
         w[0].close()
     grp.close()
-    if not ok_all:
+    if ok_all is False:
         raise SystemExit("bench.py: glp_verify REJECTED a proof of the batch")
 
 
@@ -541,6 +577,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(a)                 # never returns; nothing above this line touches a GPU
     import numpy as np
@@ -611,7 +649,7 @@ def main():
     for _ in range(max(a.inflight, 1) - 1):
         c2 = glp.Context(local_rank)
         extra.append((c2, glp.Circuit(c2, desc_full)))
-    keep_for_variant = world == 1 and max(a.inflight, 1) == 1 and not a.no_variants
+    keep_for_variant = a.full and world == 1 and max(a.inflight, 1) == 1 and not a.no_variants
     last_proof = [None]
 
     def step():
@@ -637,11 +675,15 @@ def main():
             c2.synchronize()
         torch.cuda.synchronize()
     dt = gdist.timed_steps(grp, step, a.steps, 0, device_sync)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"proof": last_proof[0]})
 
-    # every rank checks the last proof of its timed loop with the library's verifier (`data.verify(proof)`, host code,
+    # --full: every rank checks the last proof of its timed loop with the library's verifier (`data.verify(proof)`, host code,
     # [REF src/ecdsa/gadgets/ecdsa.rs:349-352]: prove THEN verify); outside the timed region
-    ok_local = bool(circuit.verify(last_proof[0])) if last_proof[0] is not None else False
-    ok_all = grp.max_over_ranks(0.0 if ok_local else 1.0) == 0.0
+    ok_all = None
+    if a.full:
+        ok_local = bool(circuit.verify(last_proof[0])) if last_proof[0] is not None else False
+        ok_all = grp.max_over_ranks(0.0 if ok_local else 1.0) == 0.0
 
     # per-stage device times (hipEvents on the library's own stream), averaged per launch
     stages, order, stage_out = stage_table(ctx.stages(), a.steps)
@@ -670,7 +712,8 @@ def main():
             "dtype": "u64 (Goldilocks, 64-bit modular integer)",
             "data": "synthetic",
             "verified": ok_all,
-            "verified_by": "glp_verify (CircuitData::verify restatement, host code) on the last proof of every rank's timed loop",
+            "verified_by": ("glp_verify (CircuitData::verify restatement, host code) on the last proof of every rank's timed loop" if a.full
+                            else "not checked: a plain run only times (--full verifies)"),
             "signatures_per_proof": nsig if real else None,
             "signatures_per_sec": (nsig * world * max(a.inflight, 1) * a.steps / dt) if real else None,
             "config": ({
@@ -809,13 +852,13 @@ def main():
                 del sw
             if real and lg == 20 and not a.no_perf_rs:
                 out["variants"]["perf_rs_batch_20"] = perf_rs_variant(glp, ctx, torch, dev, np)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             desc.circuit_digest = circuit.digest()
             out["cpu_baseline"] = cpu_baseline(lg, a.cpu_sample_log_n, gpu_proof=last_proof[0], gpu_circuit_desc=desc,
                                                cs_cap=circuit.constants_sigmas_cap(), real=real)
         print(json.dumps(out))
         sys.stdout.flush()
-    if not ok_all:
+    if ok_all is False:
         raise SystemExit("bench.py: glp_verify REJECTED a proof from the timed loop")
     for c2, cc in extra:
         cc.free()
