@@ -43,7 +43,10 @@ _GATE_META = {
 
 
 def gate_degree(t, p0=0, p1=0):
-    """`Gate::degree`: fixed per type except BaseSumGate<B> (the range product has B factors)."""
+    """`Gate::degree`: fixed per type except BaseSumGate<B> (the range product has B factors) and ComparisonGate (the
+    range product of a chunk has 2^chunk_bits factors)."""
+    if t == GATE_COMPARISON:
+        return 1 << -(-p0 // p1)
     return p1 if t == GATE_BASE_SUM else _GATE_META[t][0]
 
 
@@ -198,34 +201,27 @@ def _digits(v, base_bits, count):
     return [(v >> (base_bits * j)) & ((1 << base_bits) - 1) for j in range(count)]
 
 
-def fill_ecdsa_gate_rows(b, first_row, rows_per_gate=2, only=None):
-    """Rows of the seven remaining gate types of the secp256k1 circuit [REF src/ecdsa/gadgets/ecdsa.rs:72-96]
-    with the parameters `standard_ecc_config` gives them (136 wires / 80 routed / 2 constants), each with a
-    satisfying witness built from the gate's definition.  Returns the next free row."""
-    cfg, w, rng = b.cfg, b.wires, b.rng
-    nw, nr = cfg.num_wires, cfg.num_routed_wires
+def fill_gate_row(b, row, t, p0, p1=0, equal_inputs=False):
+    """One row of gate (t, p0, p1) with a satisfying witness built from the gate's definition, for the gates whose
+    parameters vary: U32Arithmetic(num_ops), U32AddMany(num_addends, num_ops), U32Subtraction(num_ops),
+    U32RangeCheck(num_input_limbs), Comparison(num_bits, num_chunks; equal_inputs: both inputs the same value),
+    BaseSum(num_limbs, base) and RandomAccess(bits, copies | num_extra_constants << 16)."""
+    w, rng = b.wires, b.rng
     M32 = (1 << 32) - 1
     ri = lambda hi: int(rng.integers(0, hi))
-    row = first_row
-    want = lambda t: only is None or t in only
-    # U32ArithmeticGate: m0*m1 + addend = out_hi 2^32 + out_lo
-    n_ops = min(nr // 6, nw // 38)
-    for _ in range(rows_per_gate if want(GATE_U32_ARITHMETIC) else 0):
-        b.set_rows(np.array([row]), GATE_U32_ARITHMETIC, n_ops)
-        for i in range(n_ops):
+    b.set_rows(np.array([row]), t, p0, p1)
+    if t == GATE_U32_ARITHMETIC:                # m0*m1 + addend = out_hi 2^32 + out_lo
+        for i in range(p0):
             m0, m1, ad = ri(1 << 32), ri(1 << 32), ri(1 << 32)
             prod = m0 * m1 + ad
             lo, hi = prod & M32, prod >> 32
             w[6 * i:6 * i + 6, row] = [m0, m1, ad, lo, hi, pow((M32 - hi) % P, P - 2, P)]
-            w[6 * n_ops + 32 * i:6 * n_ops + 32 * i + 32, row] = _digits(prod, 2, 32)
-        row += 1
-    # U32AddManyGate, 3 addends
-    na = 3
-    n_ops = min(nr // (na + 3), nw // (na + 3 + 18))
-    for _ in range(rows_per_gate if want(GATE_U32_ADD_MANY) else 0):
-        b.set_rows(np.array([row]), GATE_U32_ADD_MANY, na, n_ops)
+            w[6 * p0 + 32 * i:6 * p0 + 32 * i + 32, row] = _digits(prod, 2, 32)
+    elif t == GATE_U32_ADD_MANY:                # sum of the addends and the carry in = carry out 2^32 + result
+        na, n_ops = p0, p1
+        top = 1 << 32 if na < 16 else 1 << 31   # the carry out has two base-4 limbs: the sum stays below 2^36
         for i in range(n_ops):
-            vals = [ri(1 << 32) for _ in range(na + 1)]
+            vals = [ri(top) for _ in range(na + 1)]
             tot = sum(vals)
             o = (na + 3) * i
             w[o:o + na + 1, row] = vals
@@ -233,35 +229,24 @@ def fill_ecdsa_gate_rows(b, first_row, rows_per_gate=2, only=None):
             lo = (na + 3) * n_ops + 18 * i
             w[lo:lo + 16, row] = _digits(tot & M32, 2, 16)
             w[lo + 16:lo + 18, row] = _digits(tot >> 32, 2, 2)
-        row += 1
-    # U32SubtractionGate
-    n_ops = min(nr // 5, nw // 21)
-    for _ in range(rows_per_gate if want(GATE_U32_SUBTRACTION) else 0):
-        b.set_rows(np.array([row]), GATE_U32_SUBTRACTION, n_ops)
-        for i in range(n_ops):
+    elif t == GATE_U32_SUBTRACTION:
+        for i in range(p0):
             x, y, bi = ri(1 << 32), ri(1 << 32), ri(2)
             d = x - y - bi
             bo = 1 if d < 0 else 0
             res = d + (bo << 32)
             w[5 * i:5 * i + 5, row] = [x, y, bi, res, bo]
-            w[5 * n_ops + 16 * i:5 * n_ops + 16 * i + 16, row] = _digits(res, 2, 16)
-        row += 1
-    # U32RangeCheckGate, 8 limbs (exactly 136 wires)
-    n_in = min(8, nw // 17)
-    for _ in range(rows_per_gate if want(GATE_U32_RANGE_CHECK) else 0):
-        b.set_rows(np.array([row]), GATE_U32_RANGE_CHECK, n_in)
-        for i in range(n_in):
+            w[5 * p0 + 16 * i:5 * p0 + 16 * i + 16, row] = _digits(res, 2, 16)
+    elif t == GATE_U32_RANGE_CHECK:
+        for i in range(p0):
             v = ri(1 << 32)
             w[i, row] = v
-            w[n_in + 16 * i:n_in + 16 * i + 16, row] = _digits(v, 2, 16)
-        row += 1
-    # ComparisonGate(32 bits, 16 chunks)
-    nbits, nch = 32, 16
-    cb = nbits // nch
-    for k in range(rows_per_gate if want(GATE_COMPARISON) else 0):
-        b.set_rows(np.array([row]), GATE_COMPARISON, nbits, nch)
-        first, second = ri(1 << 32), ri(1 << 32)
-        if k == 1:
+            w[p0 + 16 * i:p0 + 16 * i + 16, row] = _digits(v, 2, 16)
+    elif t == GATE_COMPARISON:
+        nbits, nch = p0, p1
+        cb = -(-nbits // nch)
+        first, second = ri(1 << nbits), ri(1 << nbits)
+        if equal_inputs:
             second = first                      # all chunks equal
         a, bb = _digits(first, cb, nch), _digits(second, cb, nch)
         ed, ce, iv, msd = [], [], [], 0
@@ -281,21 +266,14 @@ def fill_ecdsa_gate_rows(b, first_row, rows_per_gate=2, only=None):
             w[o:o + len(arr), row] = arr
             o += len(arr)
         assert bits[cb] == (1 if first <= second else 0)
-        row += 1
-    # BaseSumGate<4>, 16 limbs
-    for _ in range(rows_per_gate if want(GATE_BASE_SUM) else 0):
-        b.set_rows(np.array([row]), GATE_BASE_SUM, 16, 4)
-        v = ri(1 << 32)
+    elif t == GATE_BASE_SUM:
+        nl, base = p0, p1
+        v = ri(base ** nl)
         w[0, row] = v
-        w[1:17, row] = _digits(v, 2, 16)
-        row += 1
-    # RandomAccessGate(bits = 4)
-    bits_ra = 4
-    vs = 1 << bits_ra
-    copies = min(nr // (2 + vs), nw // (2 + vs + bits_ra))
-    nextra = min(nr - copies * (2 + vs), cfg.num_constants)
-    for _ in range(rows_per_gate if want(GATE_RANDOM_ACCESS) else 0):
-        b.set_rows(np.array([row]), GATE_RANDOM_ACCESS, bits_ra, copies | (nextra << 16))
+        w[1:1 + nl, row] = [(v // base ** j) % base for j in range(nl)]
+    elif t == GATE_RANDOM_ACCESS:
+        bits_ra, copies, nextra = p0, p1 & 0xFFFF, p1 >> 16
+        vs = 1 << bits_ra
         for c in range(copies):
             idx = ri(vs)
             lst = [int(x) for x in gl.rand(rng, vs)]
@@ -306,7 +284,33 @@ def fill_ecdsa_gate_rows(b, first_row, rows_per_gate=2, only=None):
         ex = [int(x) for x in gl.rand(rng, nextra)]
         b.gate_consts[:nextra, row] = ex
         w[(2 + vs) * copies:(2 + vs) * copies + nextra, row] = ex
-        row += 1
+    else:
+        raise ValueError("fill_gate_row: gate type %d has no parametrised witness here" % t)
+    return row + 1
+
+
+def fill_ecdsa_gate_rows(b, first_row, rows_per_gate=2, only=None):
+    """Rows of the seven remaining gate types of the secp256k1 circuit [REF src/ecdsa/gadgets/ecdsa.rs:72-96]
+    with the parameters `standard_ecc_config` gives them (136 wires / 80 routed / 2 constants), each with a
+    satisfying witness built from the gate's definition.  Returns the next free row."""
+    cfg = b.cfg
+    nw, nr = cfg.num_wires, cfg.num_routed_wires
+    na = 3                                      # U32AddManyGate, 3 addends
+    bits_ra = 4                                 # RandomAccessGate(bits = 4)
+    copies = min(nr // (2 + (1 << bits_ra)), nw // (2 + (1 << bits_ra) + bits_ra))
+    nextra = min(nr - copies * (2 + (1 << bits_ra)), cfg.num_constants)
+    kinds = [(GATE_U32_ARITHMETIC, min(nr // 6, nw // 38), 0),
+             (GATE_U32_ADD_MANY, na, min(nr // (na + 3), nw // (na + 3 + 18))),
+             (GATE_U32_SUBTRACTION, min(nr // 5, nw // 21), 0),
+             (GATE_U32_RANGE_CHECK, min(8, nw // 17), 0),           # 8 limbs: exactly 136 wires
+             (GATE_COMPARISON, 32, 16),
+             (GATE_BASE_SUM, 16, 4),
+             (GATE_RANDOM_ACCESS, bits_ra, copies | (nextra << 16))]
+    row = first_row
+    for t, p0, p1 in kinds:
+        if only is None or t in only:
+            for k in range(rows_per_gate):
+                row = fill_gate_row(b, row, t, p0, p1, equal_inputs=(t == GATE_COMPARISON and k == 1))
     return row
 
 
@@ -589,11 +593,11 @@ def poseidon_chain_circuit(log_n, config=None, seed=6):
     return b.build()
 
 
-def _fill_arith_rows(b, rows_a):
-    """ArithmeticGate rows (20 ops wide at 80 routed wires): per-row constants c0, c1; out_j = c0 m0 m1 + c1 addend, each
+def _fill_arith_rows(b, rows_a, num_ops=None):
+    """ArithmeticGate rows (by default 20 ops wide at 80 routed wires): per-row constants c0, c1; out_j = c0 m0 m1 + c1 addend, each
     output copy-constrained into the next op's addend; m1 of op 0 is one cycle through all rows."""
     cfg = b.cfg
-    num_ops = cfg.num_routed_wires // 4
+    num_ops = num_ops or cfg.num_routed_wires // 4
     na = len(rows_a)
     if na == 0:
         return
