@@ -143,7 +143,8 @@ GLP_API int glp_batch_digests(const glp_batch *b, uint64_t *out);
  * `builder.build::<C>()` returns at [REF src/ecdsa/gadgets/ecdsa.rs:298].  Scope of this build:
  * no lookup tables, zero_knowledge = false, quotient_degree_factor a power of two <= 2^rate_bits,
  * D = 2, Poseidon hashing (PoseidonGoldilocksConfig, the `type C` of every reference driver but
- * one [REF src/hash/keccak256.rs:281]).  Gate types a circuit may contain: see GLP_GATE_*. */
+ * one [REF src/hash/keccak256.rs:281]).  Gate types a circuit may contain: see GLP_GATE_* (0..18; a larger type is
+ * GLP_ERR_UNSUPPORTED: CosetInterpolationGate, ExponentiationGate, PoseidonMdsGate, the lookup gates). */
 enum {
     GLP_GATE_NOOP = 0,             /* plonky2 gates/noop.rs */
     GLP_GATE_CONSTANT = 1,         /* gates/constant.rs, p0 = num_consts */
@@ -161,7 +162,13 @@ enum {
     GLP_GATE_U32_RANGE_CHECK = 11, /* plonky2_u32 gates/range_check_u32.rs, p0 = num_input_limbs */
     GLP_GATE_COMPARISON = 12,      /* plonky2_u32 gates/comparison.rs, p0 = num_bits, p1 = num_chunks */
     GLP_GATE_BASE_SUM = 13,        /* plonky2 gates/base_sum.rs, p0 = num_limbs, p1 = base */
-    GLP_GATE_RANDOM_ACCESS = 14    /* plonky2 gates/random_access.rs, p0 = bits, p1 = num_copies | num_extra_constants << 16 */
+    GLP_GATE_RANDOM_ACCESS = 14,   /* plonky2 gates/random_access.rs, p0 = bits, p1 = num_copies | num_extra_constants << 16 */
+    /* plonky2's extension-field arithmetic (D = 2: an F_p^2 value occupies two consecutive wires), what the builder emits for
+     * every `*_extension` operation and for `reduce` / `reduce_ext` (recursion and aggregation circuits) */
+    GLP_GATE_ARITHMETIC_EXTENSION = 15, /* gates/arithmetic_extension.rs, p0 = num_ops (>= 1) */
+    GLP_GATE_MUL_EXTENSION = 16,        /* gates/multiplication_extension.rs, p0 = num_ops (>= 1) */
+    GLP_GATE_REDUCING = 17,             /* gates/reducing.rs, p0 = num_coeffs (>= 1, 6 + num_coeffs <= num_routed_wires) */
+    GLP_GATE_REDUCING_EXTENSION = 18    /* gates/reducing_extension.rs, p0 = num_coeffs (>= 1, 6 + 2 num_coeffs <= num_routed_wires) */
 };
 
 typedef struct {
@@ -292,7 +299,8 @@ GLP_API int glp_prove_batch(glp_ctx *ctx, const glp_circuit *circuit, uint32_t n
  *     [REF src/u32/gates/uninterleave_to_b32.rs:335-372];
  *   plonky2_u32 (recalled) U32Arithmetic / U32AddMany / U32Subtraction / U32RangeCheck / Comparison generators;
  *   plonky2 (recalled)     BaseSplitGenerator, ArithmeticBaseGenerator, RandomAccessGenerator, PoseidonGenerator,
- *                          ConstantGenerator.
+ *                          ConstantGenerator, ArithmeticExtensionGenerator, MulExtensionGenerator, ReducingGenerator,
+ *                          ReducingExtensionGenerator.
  * Each generator reads its dependencies (glp_witness_columns role 2) from the row and writes its outputs (role 1):
  * bits, base-4 limbs, inverses, S-box traces, u32 results.  only_advice != 0: only non-routed columns
  * (index >= num_routed_wires) are written, for a caller whose CPU pass already resolved every routed wire -- then the

@@ -703,6 +703,44 @@ __device__ __forceinline__ void gate_terms(const QArgs &a, const QProof &p, cons
             for (u32 e = 0; e < nextra; e++) { EMIT(k, sub(GC[(size_t)e * N], W[(size_t)((2 + vs) * copies + e) * N])); k++; }
             break;
         }
+        // plonky2's extension-field gates (D = 2; recalled, unpinned: DESIGN.md).  On the LDE coset every wire is a base-field
+        // value, so an ext value at wires [a, a+1] is the F_p^2 element W[a] + W[a+1] X; the two constraints of an op are the
+        // two components of one difference.  Each op's wire planes are loaded before any of them is used.
+        case GLP_GATE_ARITHMETIC_EXTENSION: {        // output - (c0 m0 m1 + c1 addend), wires [8i, 8i+8)
+            const u64 c0 = GC[0], c1 = GC[N];
+            for (u32 i = 0; i < g.p0; i++) {
+                const u64 *o = W + (size_t)(8 * i) * N;
+                const u64 w0 = o[0], w1 = o[N], w2 = o[2 * N], w3 = o[3 * N], w4 = o[4 * N], w5 = o[5 * N], w6 = o[6 * N], w7 = o[7 * N];
+                const ext2 t = e_add(e_scale(e_mul(e_make(w0, w1), e_make(w2, w3)), c0), e_scale(e_make(w4, w5), c1));
+                EMIT(2 * i, sub(w6, t.a)); EMIT(2 * i + 1, sub(w7, t.b));
+            }
+            break;
+        }
+        case GLP_GATE_MUL_EXTENSION: {               // output - c0 m0 m1, wires [6i, 6i+6)
+            const u64 c0 = GC[0];
+            for (u32 i = 0; i < g.p0; i++) {
+                const u64 *o = W + (size_t)(6 * i) * N;
+                const u64 w0 = o[0], w1 = o[N], w2 = o[2 * N], w3 = o[3 * N], w4 = o[4 * N], w5 = o[5 * N];
+                const ext2 t = e_scale(e_mul(e_make(w0, w1), e_make(w2, w3)), c0);
+                EMIT(2 * i, sub(w4, t.a)); EMIT(2 * i + 1, sub(w5, t.b));
+            }
+            break;
+        }
+        case GLP_GATE_REDUCING:                      // acc_{i-1} alpha + coeff_i - acc_i; output [0,2), alpha [2,4), old_acc [4,6)
+        case GLP_GATE_REDUCING_EXTENSION: {          // coeffs from 6 (1 or 2 wires each), then acc_0 .. acc_{N-2}; acc_{N-1} = output
+            const u32 nco = g.p0, cw = TYPE == GLP_GATE_REDUCING ? 1u : TYPE == GLP_GATE_REDUCING_EXTENSION ? 2u : (g.type == GLP_GATE_REDUCING ? 1u : 2u);
+            const u32 accs = 6 + cw * nco;
+            const ext2 alpha = e_make(W[2 * N], W[3 * N]);
+            ext2 acc = e_make(W[4 * N], W[5 * N]);
+            for (u32 i = 0; i < nco; i++) {
+                const u64 *co = W + (size_t)(6 + cw * i) * N, *ac = W + (size_t)(i + 1 < nco ? accs + 2 * i : 0) * N;
+                const u64 k0v = co[0], k1v = cw == 2 ? co[N] : 0, a0 = ac[0], a1 = ac[N];
+                const ext2 t = e_add(e_mul(acc, alpha), e_make(k0v, k1v));
+                EMIT(2 * i, sub(t.a, a0)); EMIT(2 * i + 1, sub(t.b, a1));
+                acc = e_make(a0, a1);
+            }
+            break;
+        }
         default: break;   // NOOP
         }
 #undef LIMBS4_DESC
@@ -1680,6 +1718,8 @@ struct glp_session {
                         GLP_GATE_LAUNCH(GLP_GATE_UNINTERLEAVE_B32) GLP_GATE_LAUNCH(GLP_GATE_U32_ARITHMETIC) GLP_GATE_LAUNCH(GLP_GATE_U32_ADD_MANY)
                         GLP_GATE_LAUNCH(GLP_GATE_U32_SUBTRACTION) GLP_GATE_LAUNCH(GLP_GATE_U32_RANGE_CHECK) GLP_GATE_LAUNCH(GLP_GATE_COMPARISON)
                         GLP_GATE_LAUNCH(GLP_GATE_BASE_SUM) GLP_GATE_LAUNCH(GLP_GATE_RANDOM_ACCESS)
+                        GLP_GATE_LAUNCH(GLP_GATE_ARITHMETIC_EXTENSION) GLP_GATE_LAUNCH(GLP_GATE_MUL_EXTENSION)
+                        GLP_GATE_LAUNCH(GLP_GATE_REDUCING) GLP_GATE_LAUNCH(GLP_GATE_REDUCING_EXTENSION)
                     default: break;   // NoopGate: no constraints
                     }
 #undef GLP_GATE_LAUNCH
@@ -2179,6 +2219,11 @@ int glp_circuit_create(glp_ctx *c, const glp_circuit_desc *desc, glp_circuit **o
             wires = (2 + (1u << p0)) * copies + nextra + p0 * copies; consts = nextra; constraints = copies * (p0 + 2) + nextra;
             return true;
         }
+        // the extension-field gates: p0 = num_ops / num_coeffs, bounded so that the wire counts below cannot wrap
+        case GLP_GATE_ARITHMETIC_EXTENSION: wires = 8 * p0; consts = 2; constraints = 2 * p0; return p0 >= 1 && p0 <= 4096;
+        case GLP_GATE_MUL_EXTENSION: wires = 6 * p0; consts = 1; constraints = 2 * p0; return p0 >= 1 && p0 <= 4096;
+        case GLP_GATE_REDUCING: wires = 3 * p0 + 4; constraints = 2 * p0; return p0 >= 1 && p0 <= 4096;
+        case GLP_GATE_REDUCING_EXTENSION: wires = 4 * p0 + 4; constraints = 2 * p0; return p0 >= 1 && p0 <= 4096;
         default: return false;
         }
     };
@@ -2188,7 +2233,7 @@ int glp_circuit_create(glp_ctx *c, const glp_circuit_desc *desc, glp_circuit **o
         {
             u32 gw = 0, gcn = 0, gk = 0;
             if (!gate_shape(g, gw, gcn, gk))
-                return set_error(g.type > GLP_GATE_RANDOM_ACCESS ? GLP_ERR_UNSUPPORTED : GLP_ERR_ARG,
+                return set_error(g.type > GLP_GATE_REDUCING_EXTENSION ? GLP_ERR_UNSUPPORTED : GLP_ERR_ARG,
                                  "gate %u: type %u with parameters (%u, %u) is not supported", i, g.type, g.p0, g.p1);
             GLP_REQUIRE(gw <= d.num_wires, "gate %u (type %u) needs %u wires, circuit has %u", i, g.type, gw, d.num_wires);
             GLP_REQUIRE(d.num_selectors + gcn <= d.num_constants, "gate %u (type %u) needs %u constants", i, g.type, gcn);
@@ -2203,6 +2248,13 @@ int glp_circuit_create(glp_ctx *c, const glp_circuit_desc *desc, glp_circuit **o
         case GLP_GATE_RANDOM_ACCESS:
             GLP_REQUIRE(g.p0 >= 1 && g.p0 <= 5, "RandomAccessGate bits outside 1..5");
             break;
+        case GLP_GATE_ARITHMETIC_EXTENSION: case GLP_GATE_MUL_EXTENSION: break;
+        case GLP_GATE_REDUCING: case GLP_GATE_REDUCING_EXTENSION: {
+            const u32 routed = 6 + (g.type == GLP_GATE_REDUCING ? 1 : 2) * g.p0;     // output, alpha, old_acc, coefficients
+            GLP_REQUIRE(routed <= d.num_routed_wires, "gate %u (type %u): %u routed inputs, circuit has %u routed wires", i, g.type, routed,
+                        d.num_routed_wires);
+            break;
+        }
         default: break;
         }
         GLP_REQUIRE(g.selector_index < d.num_selectors && g.group_start <= g.row && g.row < g.group_end, "bad selector data for gate %u", i);

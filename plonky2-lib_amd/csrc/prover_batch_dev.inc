@@ -148,6 +148,8 @@ int prove_batch_impl_dev(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *de
                 GLP_GATE_LAUNCH(GLP_GATE_UNINTERLEAVE_B32) GLP_GATE_LAUNCH(GLP_GATE_U32_ARITHMETIC) GLP_GATE_LAUNCH(GLP_GATE_U32_ADD_MANY)
                 GLP_GATE_LAUNCH(GLP_GATE_U32_SUBTRACTION) GLP_GATE_LAUNCH(GLP_GATE_U32_RANGE_CHECK) GLP_GATE_LAUNCH(GLP_GATE_COMPARISON)
                 GLP_GATE_LAUNCH(GLP_GATE_BASE_SUM) GLP_GATE_LAUNCH(GLP_GATE_RANDOM_ACCESS)
+                GLP_GATE_LAUNCH(GLP_GATE_ARITHMETIC_EXTENSION) GLP_GATE_LAUNCH(GLP_GATE_MUL_EXTENSION)
+                GLP_GATE_LAUNCH(GLP_GATE_REDUCING) GLP_GATE_LAUNCH(GLP_GATE_REDUCING_EXTENSION)
             default: break;
             }
 #undef GLP_GATE_LAUNCH

@@ -39,6 +39,11 @@ E range_product(E v, u32 bound) {
     for (u32 x = 0; x < bound; x++) p = p * (v - E((u64)x));
     return p;
 }
+// ExtensionAlgebra<F_p^2, 2> product: (a0 + a1 Y)(b0 + b1 Y) = (a0 b0 + 7 a1 b1) + (a0 b1 + a1 b0) Y
+void alg_mul(E a0, E a1, E b0, E b1, E &r0, E &r1) {
+    r0 = a0 * b0 + a1 * b1 * glf::W;
+    r1 = a0 * b1 + a1 * b0;
+}
 E sbox7(E x) { const E x2 = x * x, x4 = x2 * x2, x3 = x * x2; return x3 * x4; }
 void mds(E s[12]) {     // circulant + diagonal, entries < 64: both coordinates accumulate unreduced in 128 bits, one reduction per row and coordinate
     static const u64 C[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
@@ -243,6 +248,41 @@ void gate_constraints(const glp_gate &g, const E *gc, const E *w, const u64 pih[
             emit(list[0] - base[1]);
         }
         for (u32 e = 0; e < nextra; e++) emit(gc[e] - w[(2 + vs) * copies + e]);
+        break;
+    }
+    // Extension-field gates at zeta: each wire opening is in F_p^2, so an ext value at wires [a, a+1] is an element of plonky2's
+    // ExtensionAlgebra (w[a], w[a+1]) over F_p^2, Y^2 = 7; a constant scales both coefficients, a base coefficient lifts to (c, 0).
+    // The two constraints of an op are the two algebra coefficients (recalled, unpinned: DESIGN.md).
+    case GLP_GATE_ARITHMETIC_EXTENSION:
+        for (u32 i = 0; i < g.p0; i++) {
+            const E *o = w + 8 * i;
+            E p0, p1;
+            alg_mul(o[0], o[1], o[2], o[3], p0, p1);
+            emit(o[6] - (p0 * gc[0] + o[4] * gc[1]));
+            emit(o[7] - (p1 * gc[0] + o[5] * gc[1]));
+        }
+        break;
+    case GLP_GATE_MUL_EXTENSION:
+        for (u32 i = 0; i < g.p0; i++) {
+            const E *o = w + 6 * i;
+            E p0, p1;
+            alg_mul(o[0], o[1], o[2], o[3], p0, p1);
+            emit(o[4] - p0 * gc[0]);
+            emit(o[5] - p1 * gc[0]);
+        }
+        break;
+    case GLP_GATE_REDUCING:
+    case GLP_GATE_REDUCING_EXTENSION: {
+        const u32 nco = g.p0, cw = g.type == GLP_GATE_REDUCING ? 1u : 2u, accs = 6 + cw * nco;
+        E a0 = w[4], a1 = w[5];
+        for (u32 i = 0; i < nco; i++) {
+            const E *co = w + 6 + cw * i, *ac = w + (i + 1 < nco ? accs + 2 * i : 0);
+            E p0, p1;
+            alg_mul(a0, a1, w[2], w[3], p0, p1);
+            emit(p0 + co[0] - ac[0]);
+            emit(cw == 2 ? p1 + co[1] - ac[1] : p1 - ac[1]);
+            a0 = ac[0]; a1 = ac[1];
+        }
         break;
     }
     default: break;    // NoopGate

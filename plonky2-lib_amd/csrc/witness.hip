@@ -16,7 +16,8 @@
 //                           U32RangeCheckGenerator, ComparisonGenerator
 //   plonky2 (crate absent, recalled)      BaseSplitGenerator (gates/base_sum.rs), ArithmeticBaseGenerator,
 //                           RandomAccessGenerator, PoseidonGenerator, ConstantGenerator (gates/constant.rs and the
-//                           extra constants of RandomAccessGate)
+//                           extra constants of RandomAccessGate), ArithmeticExtensionGenerator, MulExtensionGenerator,
+//                           ReducingGenerator, ReducingExtensionGenerator (F_p^2 values on wire pairs)
 // Every value written is a canonical field element; inputs are read as canonical u64 exactly as
 // `to_canonical_u64()` hands them to the Rust generators.
 #include "common.h"
@@ -226,6 +227,44 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         for (u32 e = 0; e < nextra; e++) WR((2 + vs) * copies + e, GC[(size_t)e * n]);
         break;
     }
+    case GLP_GATE_ARITHMETIC_EXTENSION: {
+        // gates/arithmetic_extension.rs ArithmeticExtensionGenerator: output = c0 m0 m1 + c1 addend over F_p^2
+        const u64 c0 = GC[0], c1 = GC[n];
+        for (u32 i = 0; i < g.p0; i++) {
+            const u32 o = 8 * i;
+            const ext2 t = e_add(e_scale(e_mul(e_make(RD(o), RD(o + 1)), e_make(RD(o + 2), RD(o + 3))), c0), e_scale(e_make(RD(o + 4), RD(o + 5)), c1));
+            WR(o + 6, t.a);
+            WR(o + 7, t.b);
+        }
+        break;
+    }
+    case GLP_GATE_MUL_EXTENSION: {
+        // gates/multiplication_extension.rs MulExtensionGenerator: output = c0 m0 m1 over F_p^2
+        const u64 c0 = GC[0];
+        for (u32 i = 0; i < g.p0; i++) {
+            const u32 o = 6 * i;
+            const ext2 t = e_scale(e_mul(e_make(RD(o), RD(o + 1)), e_make(RD(o + 2), RD(o + 3))), c0);
+            WR(o + 4, t.a);
+            WR(o + 5, t.b);
+        }
+        break;
+    }
+    case GLP_GATE_REDUCING:
+    case GLP_GATE_REDUCING_EXTENSION: {
+        // gates/reducing.rs ReducingGenerator, gates/reducing_extension.rs ReducingExtensionGenerator: acc_i = acc_{i-1} alpha +
+        // coeff_i from acc_{-1} = old_acc; acc_0 .. acc_{N-2} from wire 6 + cw N (routed or advice), acc_{N-1} = output (wires 0, 1)
+        const u32 nco = g.p0, cw = g.type == GLP_GATE_REDUCING ? 1u : 2u, accs = 6 + cw * nco;
+        const ext2 alpha = e_make(RD(2), RD(3));
+        ext2 acc = e_make(RD(4), RD(5));
+        for (u32 i = 0; i < nco; i++) {
+            const u32 co = 6 + cw * i;
+            acc = e_add(e_mul(acc, alpha), e_make(RD(co), cw == 2 ? RD(co + 1) : 0));
+            const u32 dst = i + 1 < nco ? accs + 2 * i : 0;
+            WR(dst, acc.a);
+            WR(dst + 1, acc.b);
+        }
+        break;
+    }
     default: break;     // NoopGate; PublicInputGate (its wires are set from the public-input hash through copy constraints)
     }
 #undef WR
@@ -281,6 +320,13 @@ extern "C" int glp_witness_columns(const glp_circuit *cc, uint32_t gate_index, u
         for (u32 cpy = 0; cpy < copies; cpy++) { const u32 o = (2 + vs) * cpy; in(o, 1); out(o + 1, 1); in(o + 2, vs); }
         out((2 + vs) * copies, nextra);
         out((2 + vs) * copies + nextra, bits * copies);
+        break;
+    }
+    case GLP_GATE_ARITHMETIC_EXTENSION: for (u32 i = 0; i < g.p0; i++) { in(8 * i, 6); out(8 * i + 6, 2); } break;
+    case GLP_GATE_MUL_EXTENSION: for (u32 i = 0; i < g.p0; i++) { in(6 * i, 4); out(6 * i + 4, 2); } break;
+    case GLP_GATE_REDUCING: case GLP_GATE_REDUCING_EXTENSION: {
+        const u32 cw = g.type == GLP_GATE_REDUCING ? 1u : 2u;
+        out(0, 2); in(2, 4 + cw * g.p0); out(6 + cw * g.p0, 2 * (g.p0 - 1));
         break;
     }
     default: break;

@@ -21,6 +21,9 @@ GATE_NOOP, GATE_CONSTANT, GATE_PUBLIC_INPUT, GATE_ARITHMETIC, GATE_POSEIDON = 0,
 GATE_U32_INTERLEAVE, GATE_UNINTERLEAVE_U32, GATE_UNINTERLEAVE_B32 = 5, 6, 7
 GATE_U32_ARITHMETIC, GATE_U32_ADD_MANY, GATE_U32_SUBTRACTION, GATE_U32_RANGE_CHECK = 8, 9, 10, 11
 GATE_COMPARISON, GATE_BASE_SUM, GATE_RANDOM_ACCESS = 12, 13, 14
+# plonky2's extension-field arithmetic (D = 2: an F_p^2 value a + b X, X^2 = 7, on two consecutive wires)
+GATE_ARITHMETIC_EXTENSION, GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING_EXTENSION = 15, 16, 17, 18
+EXT_GATES = (GATE_ARITHMETIC_EXTENSION, GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING_EXTENSION)
 
 # (degree, id string as plonky2's `Gate::id` prints it) -- the build() sort key
 _GATE_META = {
@@ -39,6 +42,10 @@ _GATE_META = {
     GATE_COMPARISON: (4, "ComparisonGate {{ num_bits: {p0}, num_chunks: {p1} }}"),
     GATE_BASE_SUM: (4, "BaseSumGate {{ num_limbs: {p0} }} + Base: {p1}"),
     GATE_RANDOM_ACCESS: (5, "RandomAccessGate {{ bits: {p0} }}"),
+    GATE_ARITHMETIC_EXTENSION: (3, "ArithmeticExtensionGate {{ num_ops: {p0} }}"),
+    GATE_MUL_EXTENSION: (3, "MulExtensionGate {{ num_ops: {p0} }}"),
+    GATE_REDUCING: (2, "ReducingGate {{ num_coeffs: {p0} }}"),
+    GATE_REDUCING_EXTENSION: (2, "ReducingExtensionGate {{ num_coeffs: {p0} }}"),
 }
 
 
@@ -60,6 +67,8 @@ def gate_num_constraints(t, p0, p1=0):
         return 1 + p0
     if t == GATE_RANDOM_ACCESS:
         return (p1 & 0xFFFF) * (p0 + 2) + (p1 >> 16)
+    if t in EXT_GATES:
+        return 2 * p0
     return {GATE_NOOP: 0, GATE_CONSTANT: p0, GATE_PUBLIC_INPUT: 4, GATE_ARITHMETIC: p0, GATE_POSEIDON: 123,
             GATE_U32_INTERLEAVE: p0 * 34, GATE_UNINTERLEAVE_U32: p0 * 67, GATE_UNINTERLEAVE_B32: p0 * 67,
             GATE_U32_ARITHMETIC: p0 * 36, GATE_U32_SUBTRACTION: p0 * 19, GATE_U32_RANGE_CHECK: p0 * 17}[t]
@@ -284,9 +293,153 @@ def fill_gate_row(b, row, t, p0, p1=0, equal_inputs=False):
         ex = [int(x) for x in gl.rand(rng, nextra)]
         b.gate_consts[:nextra, row] = ex
         w[(2 + vs) * copies:(2 + vs) * copies + nextra, row] = ex
+    elif t in EXT_GATES:
+        _fill_ext_rows(b, np.array([row]), t, p0)
     else:
         raise ValueError("fill_gate_row: gate type %d has no parametrised witness here" % t)
     return row + 1
+
+
+def ext_gate_params(cfg):
+    """The widest instance of each extension-field gate a config fits (plonky2's `new_from_config` /
+    `max_coeffs_len`): ArithmeticExtension routed/8 ops, MulExtension routed/6 ops, Reducing
+    min(routed - 6, (wires - 4)/3) base coefficients, ReducingExtension min((routed - 6)/2, (wires - 4)/4) ext
+    coefficients."""
+    nw, nr = cfg.num_wires, cfg.num_routed_wires
+    return {GATE_ARITHMETIC_EXTENSION: nr // 8, GATE_MUL_EXTENSION: nr // 6,
+            GATE_REDUCING: min(nr - 6, (nw - 4) // 3), GATE_REDUCING_EXTENSION: min((nr - 6) // 2, (nw - 4) // 4)}
+
+
+def ext_gate_wires(t, p0):
+    """Wire columns a row of extension-field gate (t, p0) uses."""
+    return {GATE_ARITHMETIC_EXTENSION: 8 * p0, GATE_MUL_EXTENSION: 6 * p0, GATE_REDUCING: 3 * p0 + 4,
+            GATE_REDUCING_EXTENSION: 4 * p0 + 4}[t]
+
+
+def ext_mul(a0, a1, b0, b1):
+    """(a0 + a1 X)(b0 + b1 X) in F_p[X]/(X^2 - 7), elementwise over arrays."""
+    return (gl.add(gl.mul(a0, b0), gl.mul(np.uint64(7), gl.mul(a1, b1))), gl.add(gl.mul(a0, b1), gl.mul(a1, b0)))
+
+
+def _reducing_acc_col(p0, cw, i):
+    """Wire of accumulator i of a Reducing(Extension)Gate: acc_{N-1} is the output (wires 0, 1)."""
+    return 6 + cw * p0 + 2 * i if i + 1 < p0 else 0
+
+
+def _fill_ext_rows(b, rows, t, p0, chain=True):
+    """Rows `rows` of extension-field gate (t, p0): the outputs / accumulators follow from the inputs already in the
+    wires (the row-local generators).  ArithmeticExtension / MulExtension draw their gate constants here, and with
+    `chain` op i's output is copy-constrained into op i + 1 (its addend, resp. its second multiplicand)."""
+    w = b.wires
+    rows = np.asarray(rows)
+    b.set_rows(rows, t, p0)
+    if len(rows) == 0:
+        return
+    if t in (GATE_ARITHMETIC_EXTENSION, GATE_MUL_EXTENSION):
+        ae = t == GATE_ARITHMETIC_EXTENSION
+        st = 8 if ae else 6
+        cst = gl.rand(b.rng, (2 if ae else 1, len(rows)))
+        b.gate_consts[:cst.shape[0], rows] = cst
+        for i in range(p0):
+            o = st * i
+            if chain and i:
+                dst = o + (4 if ae else 2)
+                w[dst:dst + 2, rows] = w[o - 2:o, rows]
+                for k in range(2):
+                    b.connect_pairs(rows, o - 2 + k, rows, dst + k)
+            p0_, p1_ = ext_mul(w[o, rows], w[o + 1, rows], w[o + 2, rows], w[o + 3, rows])
+            r0, r1 = gl.mul(p0_, cst[0]), gl.mul(p1_, cst[0])
+            if ae:
+                r0, r1 = gl.add(r0, gl.mul(w[o + 4, rows], cst[1])), gl.add(r1, gl.mul(w[o + 5, rows], cst[1]))
+            w[o + st - 2, rows], w[o + st - 1, rows] = r0, r1
+    else:
+        cw = 1 if t == GATE_REDUCING else 2
+        al0, al1 = w[2, rows], w[3, rows]
+        a0, a1 = w[4, rows], w[5, rows]
+        for i in range(p0):
+            c = 6 + cw * i
+            a0, a1 = ext_mul(a0, a1, al0, al1)
+            a0 = gl.add(a0, w[c, rows])
+            if cw == 2:
+                a1 = gl.add(a1, w[c + 1, rows])
+            dst = _reducing_acc_col(p0, cw, i)
+            w[dst, rows], w[dst + 1, rows] = a0, a1
+
+
+def ext_gates_circuit(log_n, config=None, seed=11, num_challenges=2, public_inputs=(), pi_hash=None, gates=EXT_GATES,
+                      witness_seed=None):
+    """A recursion-shaped circuit of plonky2's extension-field gates, each at the widest instance the config fits
+    (ext_gate_params), with satisfying witnesses and copy constraints between them:
+    [PublicInput][Constant x2][unit ...][Noop x3 from 16 rows on], a unit being ArithmeticExtension, MulExtension,
+    Reducing, Reducing, ReducingExtension, ReducingExtension (restricted to `gates`; a single Reducing type keeps its pair).
+    The last ArithmeticExtension op of a unit feeds the first MulExtension op's first multiplicand; within a row op i's
+    output feeds op i + 1; the second Reducing(Extension) row of a unit continues the first one's reduction (its old_acc is
+    the first one's output and both share alpha), as plonky2's chunked `reduce` does.  2^3 .. 2^20 rows, both presets.
+    witness_seed: draw the free wire values from their own seed -- the same circuit (gate constants, sigmas) with another
+    satisfying witness, as a batch of proofs of one circuit needs."""
+    import copy
+    cfg = copy.copy(config or Config.standard_recursion_config())
+    cfg.num_challenges = num_challenges
+    b = Builder(cfg, log_n, seed)
+    n = b.n
+    if witness_seed is not None:
+        b.wires = gl.rand(np.random.default_rng(witness_seed), b.wires.shape)
+    gates = tuple(gates)
+    if not gates or any(t not in EXT_GATES for t in gates):
+        raise ValueError("gates must be a non-empty subset of EXT_GATES")
+    par = ext_gate_params(cfg)
+    pi = np.asarray(public_inputs, dtype=np.uint64)
+    b.public_inputs = pi
+    if pi_hash is None:
+        if len(pi):
+            raise ValueError("pass pi_hash = hash_no_pad(public_inputs) when public inputs are non-empty")
+        pi_hash = np.zeros(4, np.uint64)
+    num_noop = 3 if n >= 16 else 0
+    rows_c = np.array([1, 2])
+    body = np.arange(3, n - num_noop)
+    if len(body) < 2:
+        raise ValueError("log_n too small")
+    # PublicInputGate wires = hash, copy-constrained to the constant cells that hold it
+    b.set_rows(np.array([0]), GATE_PUBLIC_INPUT, 0)
+    b.set_rows(rows_c, GATE_CONSTANT, cfg.num_constants)
+    cvals = gl.rand(b.rng, (cfg.num_constants, 2))
+    cvals[0, 0], cvals[1, 0], cvals[0, 1], cvals[1, 1] = pi_hash[0], pi_hash[1], pi_hash[2], pi_hash[3]
+    b.gate_consts[:, rows_c] = cvals
+    b.wires[:cfg.num_constants, rows_c] = cvals
+    b.wires[:4, 0] = pi_hash
+    for k in range(4):
+        b.connect_pairs(np.array([0]), k, np.array([rows_c[k // 2]]), k % 2)
+    unit = [t for t in (GATE_ARITHMETIC_EXTENSION, GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING, GATE_REDUCING_EXTENSION,
+                        GATE_REDUCING_EXTENSION) if t in gates]
+    slot = np.arange(len(body)) % len(unit)                    # position of each body row in its unit
+
+    def rows_at(pos):
+        return body[slot == pos]
+    w = b.wires
+    pos = {t: [i for i, u in enumerate(unit) if u == t] for t in gates}
+    if GATE_ARITHMETIC_EXTENSION in gates:
+        _fill_ext_rows(b, rows_at(pos[GATE_ARITHMETIC_EXTENSION][0]), GATE_ARITHMETIC_EXTENSION, par[GATE_ARITHMETIC_EXTENSION])
+    if GATE_MUL_EXTENSION in gates:
+        rm = rows_at(pos[GATE_MUL_EXTENSION][0])
+        if GATE_ARITHMETIC_EXTENSION in gates:
+            ra = rows_at(pos[GATE_ARITHMETIC_EXTENSION][0])[:len(rm)]
+            rm2 = rm[:len(ra)]
+            o = 8 * par[GATE_ARITHMETIC_EXTENSION] - 2
+            w[0:2, rm2] = w[o:o + 2, ra]
+            for k in range(2):
+                b.connect_pairs(ra, o + k, rm2, k)
+        _fill_ext_rows(b, rm, GATE_MUL_EXTENSION, par[GATE_MUL_EXTENSION])
+    for t in (GATE_REDUCING, GATE_REDUCING_EXTENSION):
+        if t not in gates:
+            continue
+        r1, r2 = rows_at(pos[t][0]), rows_at(pos[t][1])
+        _fill_ext_rows(b, r1, t, par[t])
+        r1 = r1[:len(r2)]
+        w[2:6, r2] = w[np.ix_([2, 3, 0, 1], r1)]                 # same alpha; old_acc = the first row's output
+        for src, dst in ((2, 2), (3, 3), (0, 4), (1, 5)):
+            b.connect_pairs(r1, src, r2, dst)
+        _fill_ext_rows(b, r2, t, par[t])
+    return b.build()
 
 
 def fill_ecdsa_gate_rows(b, first_row, rows_per_gate=2, only=None):
