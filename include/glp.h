@@ -63,6 +63,11 @@ GLP_API void glp_ctx_destroy(glp_ctx *ctx);
 GLP_API int glp_ctx_synchronize(glp_ctx *ctx);
 /* The HIP stream (hipStream_t) every kernel of this ctx is launched on. */
 GLP_API void *glp_ctx_stream(glp_ctx *ctx);
+/* Seed of the salts of zero-knowledge proofs (GLP_CIRCUIT_ZERO_KNOWLEDGE; rule at glp_batch_from_values_salted).  NULL (the default):
+ * every glp_prove* call, session and glp_prove_batch call draws a fresh seed from the OS (getrandom).  A fixed seed makes proofs
+ * reproducible, for tests; proving two different witnesses of one circuit with the same fixed seed reuses the salts and breaks
+ * hiding.  Seed words are taken mod p. */
+GLP_API int glp_ctx_set_salt_seed(glp_ctx *ctx, const uint64_t seed[4]);
 
 /* Device buffers for the *_device entry points, for callers that do not link a HIP runtime themselves (a Rust / Go host
  * that keeps a witness resident in HBM across proofs).  Memory comes from and returns to the context's pool. */
@@ -99,8 +104,8 @@ GLP_API int glp_fill_random_device(glp_ctx *ctx, uint64_t *dev_out, size_t count
  * glp_batch_from_values  = PolynomialBatch::from_values  (ifft, lde x 2^rate_bits on the coset 7*H,
  *                          transpose + bit-reverse, MerkleTree::new(leaves, cap_height))
  * glp_batch_from_coeffs  = PolynomialBatch::from_coeffs
- * Input layout: column-major [ncols][n], n = 2^log_n, natural order.  No blinding
- * (zero_knowledge = false in every CircuitConfig the reference uses).
+ * Input layout: column-major [ncols][n], n = 2^log_n, natural order.  No blinding (the salted form is
+ * glp_batch_from_values_salted below).
  * The *_device variants take a device pointer on the ctx's GPU (input already resident in HBM). */
 GLP_API int glp_batch_from_values(glp_ctx *ctx, const uint64_t *values, uint32_t ncols, uint32_t log_n,
                           uint32_t rate_bits, uint32_t cap_height, glp_batch **out);
@@ -116,6 +121,27 @@ GLP_API int glp_batch_from_coeffs_device(glp_ctx *ctx, const uint64_t *dev_coeff
  * last word zero), so caps, paths and digest arrays keep their shapes.  The *_h entry points are the ones above with the hash named. */
 GLP_API int glp_batch_from_values_h(glp_ctx *ctx, const uint64_t *values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
                                     uint32_t cap_height, uint32_t hasher, glp_batch **out);
+/* ---- salted (blinded) commitments: zero-knowledge proving --------------------------------------------------------------
+ * plonky2 `PolynomialBatch::from_values(.., blinding = true)` (fri/oracle.rs, recalled from plonky2 0.1.x, unpinned): the LDE gets
+ * SALT_SIZE = 4 extra columns of random values, one value per LDE point, after the polynomial columns; Merkle leaf j is
+ * (ncols polynomial values, s0, s1, s2, s3) and its hash covers all of it.  The salts have no coefficients: they are never opened.
+ * This library derives them from a keyed PRF, one Poseidon permutation per leaf (plonky2 draws them from the OS RNG; a salt only has
+ * to be unpredictable, so a proof made here is a valid plonky2 proof):
+ *     salt(seed, tag, leaf)[0..4) = the first four outputs of
+ *         Poseidon([seed0, seed1, seed2, seed3 + k mod p, tag, leaf & 0xffffffff, leaf >> 32, 0, 0, 0, 0, 0])
+ * leaf = the Merkle leaf index (merkle_tree.leaves[leaf], not the LDE point), k = the proof's index in a glp_prove_batch call (0
+ * otherwise), tag = GLP_SALT_TAG_* below.  Seed words are taken mod p. */
+#define GLP_SALT_SIZE 4
+#define GLP_SALT_TAG_WIRES 0           /* wires_commitment */
+#define GLP_SALT_TAG_ZS 1              /* partial_products_and_zs_commitment */
+#define GLP_SALT_TAG_QUOTIENT 2        /* quotient_polys_commitment */
+#define GLP_SALT_TAG_BATCH 3           /* glp_batch_from_values_salted */
+/* from_values with blinding = true under `hasher`, salts from `seed`.  glp_batch_leaf returns glp_batch_leaf_len() = ncols + 4 words
+ * for such a batch; glp_batch_info / glp_batch_coeffs keep counting the ncols polynomials. */
+GLP_API int glp_batch_from_values_salted(glp_ctx *ctx, const uint64_t *values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
+                                         uint32_t cap_height, uint32_t hasher, const uint64_t seed[4], glp_batch **out);
+/* words of one Merkle leaf: ncols, or ncols + GLP_SALT_SIZE for a salted batch (0 for NULL) */
+GLP_API uint32_t glp_batch_leaf_len(const glp_batch *b);
 GLP_API int glp_batch_from_coeffs_h(glp_ctx *ctx, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
                                     uint32_t cap_height, uint32_t hasher, glp_batch **out);
 /* Keccak-256 of `count` messages of `len` bytes each (msgs [count][len], digests_out [count][32]) on the GPU: the primitive under
@@ -129,7 +155,7 @@ GLP_API int glp_batch_cap(const glp_batch *b, uint64_t *cap_out);
 /* `polynomials[col].coeffs`, natural order, for cols [col_begin, col_begin + ncols) -> [ncols][n] */
 GLP_API int glp_batch_coeffs(const glp_batch *b, uint32_t col_begin, uint32_t ncols, uint64_t *out);
 /* merkle_tree.leaves[leaf_index] (= `MerkleTree::get`): the ncols LDE values of row bitrev(leaf_index) */
-GLP_API int glp_batch_leaf(const glp_batch *b, uint64_t leaf_index, uint64_t *out);
+GLP_API int glp_batch_leaf(const glp_batch *b, uint64_t leaf_index, uint64_t *out /* [glp_batch_leaf_len(b)] */);
 /* `MerkleTree::prove(leaf_index)`: (log_n + rate_bits - cap_height) sibling digests, bottom-up, [k][4] */
 GLP_API int glp_batch_merkle_proof(const glp_batch *b, uint64_t leaf_index, uint64_t *siblings_out);
 /* every digest bottom-up: level 0 (leaf digests, index = leaf index) ... cap level; count =
@@ -141,7 +167,7 @@ GLP_API int glp_batch_digests(const glp_batch *b, uint64_t *out);
  * glp_circuit_desc carries the parts of plonky2's CommonCircuitData / ProverOnlyCircuitData /
  * VerifierOnlyCircuitData that `prove` reads (plonk/circuit_data.rs), i.e. what
  * `builder.build::<C>()` returns at [REF src/ecdsa/gadgets/ecdsa.rs:298].  Scope of this build:
- * no lookup tables, zero_knowledge = false, quotient_degree_factor a power of two <= 2^rate_bits,
+ * no lookup tables, zero_knowledge = false unless asked for (glp_circuit_create_ex), quotient_degree_factor a power of two <= 2^rate_bits,
  * D = 2, Poseidon hashing (PoseidonGoldilocksConfig, the `type C` of every reference driver but
  * one [REF src/hash/keccak256.rs:281]).  Gate types a circuit may contain: see GLP_GATE_* (0..18; a larger type is
  * GLP_ERR_UNSUPPORTED: CosetInterpolationGate, ExponentiationGate, PoseidonMdsGate, the lookup gates). */
@@ -211,6 +237,19 @@ typedef struct glp_circuit glp_circuit;
  * (`constants_sigmas_commitment`) and, if desc->circuit_digest is all zero, derives the digest as
  * hash_no_pad(cap.flatten() ++ hash_pad([]) ++ [degree_bits]) (plonk/circuit_builder.rs). */
 GLP_API int glp_circuit_create(glp_ctx *ctx, const glp_circuit_desc *desc, glp_circuit **out);
+/* CircuitConfig { zero_knowledge: true, .. } (recalled from plonky2 0.1.x plonk/prover.rs, unpinned): the wires,
+ * plonk_zs_partial_products and quotient commitments are salted (blinding = true; constants_sigmas is not).  The salts are never
+ * opened at zeta; each query round's initial-tree proof carries the full salted leaves of oracles 1..3, salts last, so
+ * glp_proof_words / glp_proof_bytes_len grow by 3 * 4 * num_query_rounds.  Transcript, proof of work and circuit digest do not
+ * change.  The circuit itself must carry plonky2's blinding rows (the Rust builder and synth.py's zk configs add them).
+ * glp_circuit_create(..) = glp_circuit_create_ex(.., 0).  Every path honours the flag: glp_prove, glp_prove_device,
+ * glp_prove_staged (full witnesses only: the blinding rows' random advice wires come from no generator, so GLP_WITNESS_ROUTED_ONLY
+ * is GLP_ERR_ARG), the session, glp_prove_batch (member k salts with seed3 + k), glp_verify / _n, glp_verify_batch and the byte
+ * format.  Salt rule and seed: glp_batch_from_values_salted, glp_ctx_set_salt_seed. */
+#define GLP_CIRCUIT_ZERO_KNOWLEDGE 1u
+GLP_API int glp_circuit_create_ex(glp_ctx *ctx, const glp_circuit_desc *desc, uint32_t flags, glp_circuit **out);
+/* 1 if the circuit was created with GLP_CIRCUIT_ZERO_KNOWLEDGE, else 0 */
+GLP_API int glp_circuit_zero_knowledge(const glp_circuit *circuit);
 GLP_API void glp_circuit_free(glp_circuit *circuit);
 GLP_API int glp_circuit_digest(const glp_circuit *circuit, uint64_t digest_out[4]);
 GLP_API int glp_circuit_constants_sigmas_cap(const glp_circuit *circuit, uint64_t *cap_out);
@@ -243,7 +282,8 @@ GLP_API const uint64_t *glp_circuit_file_public_inputs(const glp_circuit_file *f
  *     wires_cap | plonk_zs_partial_products_cap | quotient_polys_cap           each [2^cap_height][4]
  *     openings: constants, plonk_sigmas, wires, plonk_zs, plonk_zs_next, partial_products, quotient_polys   (ext each)
  *     commit_phase_merkle_caps [num_reductions][2^cap_height][4]
- *     query_round_proofs [num_query_rounds]: 4 x (leaf values, merkle path) then per reduction (evals, merkle path)
+ *     query_round_proofs [num_query_rounds]: 4 x (leaf values, merkle path) then per reduction (evals, merkle path);
+ *                        a zk circuit's leaves of oracles 1..3 end with their 4 salts
  *     final_poly (ext coefficients) | pow_witness | public_inputs
  * The FRI proof-of-work witness is the SMALLEST valid one (the Rust prover's rayon `find_any`
  * returns an arbitrary valid one; every other word of the proof is a deterministic function of

@@ -101,13 +101,19 @@ def load_library():
         "glp_batch_leaf": [vp, u64, vp],
         "glp_batch_merkle_proof": [vp, u64, vp],
         "glp_batch_digests": [vp, vp],
+        "glp_batch_from_values_salted": [vp, vp, u32, u32, u32, u32, u32, vp, C.POINTER(vp)],
+        "glp_ctx_set_salt_seed": [vp, vp],
     }
+    L.glp_batch_leaf_len.restype = u32
+    L.glp_batch_leaf_len.argtypes = [vp]
     L.glp_proof_words.restype = sz
     L.glp_proof_words.argtypes = [vp]
     L.glp_proof_bytes_len.restype = sz
     L.glp_proof_bytes_len.argtypes = [vp]
     sigs.update({
         "glp_circuit_create": [vp, C.POINTER(_CircuitDesc), C.POINTER(vp)],
+        "glp_circuit_create_ex": [vp, C.POINTER(_CircuitDesc), u32, C.POINTER(vp)],
+        "glp_circuit_zero_knowledge": [vp],
         "glp_circuit_free": [vp],
         "glp_circuit_digest": [vp, vp],
         "glp_circuit_constants_sigmas_cap": [vp, vp],
@@ -302,6 +308,31 @@ class Context:
     def batch_from_values(self, values, rate_bits=3, cap_height=4, hasher=0):
         return Batch._make(self, "glp_batch_from_values_h", values, rate_bits, cap_height, hasher)
 
+    def batch_from_values_salted(self, values, seed, rate_bits=3, cap_height=4, hasher=0):
+        """PolynomialBatch::from_values(.., blinding = true): 4 salt columns after the polynomials, salts from `seed` (glp.h)"""
+        a = _a(values)
+        if a.ndim != 2 or a.shape[1] & (a.shape[1] - 1) or a.shape[1] == 0:
+            raise GlpError(-1, "expected a [ncols][n] array, n a power of two")
+        sd = _a(seed)
+        if sd.size != 4:
+            raise GlpError(-1, "the salt seed is 4 words")
+        ncols, n = a.shape
+        h = C.c_void_p()
+        _chk(load_library().glp_batch_from_values_salted(self._h, _p(a), ncols, n.bit_length() - 1, rate_bits, cap_height, int(hasher),
+                                                         _p(sd), C.byref(h)))
+        return Batch(self, h, ncols, n.bit_length() - 1, rate_bits, cap_height)
+
+    def set_salt_seed(self, seed=None):
+        """glp_ctx_set_salt_seed: a fixed seed for the salts of zero-knowledge proofs (tests, reproducibility), None = a fresh OS seed
+        per call (the default).  Reusing a fixed seed across witnesses breaks hiding."""
+        if seed is None:
+            _chk(load_library().glp_ctx_set_salt_seed(self._h, None))
+            return
+        sd = _a(seed)
+        if sd.size != 4:
+            raise GlpError(-1, "the salt seed is 4 words")
+        _chk(load_library().glp_ctx_set_salt_seed(self._h, _p(sd)))
+
     def batch_from_coeffs(self, coeffs, rate_bits=3, cap_height=4, hasher=0):
         return Batch._make(self, "glp_batch_from_coeffs_h", coeffs, rate_bits, cap_height, hasher)
 
@@ -377,8 +408,13 @@ class Batch:
         _chk(load_library().glp_batch_coeffs(self._h, col_begin, ncols, _p(out)))
         return out
 
+    @property
+    def leaf_len(self):
+        """words of one Merkle leaf: ncols, + 4 salts for a salted batch"""
+        return int(load_library().glp_batch_leaf_len(self._h))
+
     def leaf(self, index):
-        out = np.empty(self.ncols, np.uint64)
+        out = np.empty(self.leaf_len, np.uint64)
         _chk(load_library().glp_batch_leaf(self._h, int(index), _p(out)))
         return out
 
@@ -516,7 +552,11 @@ class Circuit:
         self._wire_elems = int(desc.num_wires) * n
         self._num_pis = int(len(desc.public_inputs))
         self._h = C.c_void_p()
-        _chk(L.glp_circuit_create(ctx._h, C.byref(d), C.byref(self._h)))
+        self.zero_knowledge = bool(getattr(desc, "zero_knowledge", False))
+        if self.zero_knowledge:
+            _chk(L.glp_circuit_create_ex(ctx._h, C.byref(d), 1, C.byref(self._h)))     # GLP_CIRCUIT_ZERO_KNOWLEDGE
+        else:
+            _chk(L.glp_circuit_create(ctx._h, C.byref(d), C.byref(self._h)))
         del keep
         self.proof_words = L.glp_proof_words(self._h)
 

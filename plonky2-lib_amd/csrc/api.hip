@@ -1,6 +1,8 @@
 // api.hip -- the extern "C" boundary of libglprover.so (declared in include/glp.h): context,
 // device-memory pool, stage timers, primitive entry points and PolynomialBatch.
 #include <stdarg.h>
+#include <errno.h>
+#include <sys/random.h>
 #include <string.h>
 #include "batch.h"
 #include "common.h"
@@ -342,6 +344,31 @@ extern "C" int glp_keccak256(glp_ctx *c, const uint8_t *msgs, size_t count, size
     return GLP_OK;
 }
 
+namespace glp {
+int salt_seed_draw(glp_ctx *c, u64 out[4]) {
+    if (c->salt_seed_fixed) { memcpy(out, c->salt_seed, 32); return GLP_OK; }
+    u64 w[4];
+    size_t got = 0;
+    while (got < sizeof(w)) {
+        const ssize_t r = getrandom(reinterpret_cast<char *>(w) + got, sizeof(w) - got, 0);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            return set_error(GLP_ERR_PROVE, "getrandom failed (errno %d): no salt seed for a zero-knowledge proof", errno);
+        }
+        got += (size_t)r;
+    }
+    for (int i = 0; i < 4; i++) out[i] = glf::canon(w[i]);
+    return GLP_OK;
+}
+}  // namespace glp
+
+extern "C" int glp_ctx_set_salt_seed(glp_ctx *c, const uint64_t seed[4]) {
+    GLP_REQUIRE(c, "null context");
+    c->salt_seed_fixed = seed != nullptr;
+    for (int i = 0; i < 4; i++) c->salt_seed[i] = seed ? glf::canon(seed[i]) : 0;
+    return GLP_OK;
+}
+
 extern "C" int glp_fill_random_device(glp_ctx *c, uint64_t *dev_out, size_t count, uint64_t seed) {
     GLP_REQUIRE(c && (dev_out || !count), "null argument");
     GLP_TRY(bind(c));
@@ -370,7 +397,7 @@ void batch_destroy(glp_batch *b) {
 // host_src != nullptr (BATCH_VALUES only): the values are still in host memory; they are copied into dev_in in column
 // chunks on the copy stream while the transforms of the chunks already on the device run on the compute stream.
 int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg, int rate_bits, int cap_height,
-                glp_batch **out, const u64 *host_src, u32 K, int hasher) {
+                glp_batch **out, const u64 *host_src, u32 K, int hasher, const u64 *salt_seed, u32 salt_tag) {
     GLP_REQUIRE(out, "out is null");
     *out = nullptr;
     if (hasher != GLP_HASH_POSEIDON && hasher != GLP_HASH_KECCAK25) return set_error(GLP_ERR_UNSUPPORTED, "hasher %d is not one of GLP_HASH_*", hasher);
@@ -382,17 +409,35 @@ int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg
         const size_t n = (size_t)1 << lg, N = n << rate_bits;
         std::unique_ptr<glp_batch, void (*)(glp_batch *)> b(new glp_batch(), batch_destroy);
         b->ctx = c; b->ncols = ncols; b->lg = lg; b->rate_bits = rate_bits; b->cap_height = cap_height; b->K = K; b->hasher = hasher;
+        b->salt = salt_seed ? SALT_SIZE : 0;
         b->ndigests = merkle_num_digests(N, cap_height);
-        const size_t tot = (size_t)K * ncols;
+        const size_t tot = (size_t)K * ncols, leaf_len = ncols + b->salt;
         GLP_REQUIRE(tot <= 0x7FFFFFFFu, "batch too wide");
         GLP_TRY(c->alloc((void **)&b->coeffs, tot * n * 8));
-        GLP_TRY(c->alloc((void **)&b->lde, tot * N * 8));
+        GLP_TRY(c->alloc((void **)&b->lde, (size_t)K * leaf_len * N * 8));
         GLP_TRY(c->alloc((void **)&b->digests, (size_t)K * b->ndigests * 32));
         if (input_kind == BATCH_VALUES) GLP_TRY(intt_values_to_coeffs(c, dev_in, b->coeffs, (u32)tot, lg));
         else if (input_kind == BATCH_COEFFS_NATURAL) GLP_TRY(bitrev_copy(c, dev_in, b->coeffs, (u32)tot, lg));
         else GLP_HIP(hipMemcpyAsync(b->coeffs, dev_in, tot * n * 8, hipMemcpyDeviceToDevice, c->stream));
-        GLP_TRY(lde_coeffs(c, b->coeffs, b->lde, (u32)tot, lg, rate_bits, glf::GEN));
-        GLP_TRY(merkle_from_lde(c, b->lde, ncols, lg, rate_bits, cap_height, b->digests, K, (size_t)ncols * N, b->ndigests * 4, hasher));
+        if (!b->salt) {
+            GLP_TRY(lde_coeffs(c, b->coeffs, b->lde, (u32)tot, lg, rate_bits, glf::GEN));
+        } else {
+            // the salt columns of proof k sit between its polynomial columns and those of proof k + 1: one wide LDE into scratch, then
+            // one strided copy into place (K LDE calls of one proof each underfill the device: profiles/r05_zero_knowledge.txt)
+            void *t = nullptr;
+            GLP_TRY(c->alloc(&t, tot * N * 8));
+            int rc = lde_coeffs(c, b->coeffs, (u64 *)t, (u32)tot, lg, rate_bits, glf::GEN);
+            if (rc == GLP_OK) {
+                const hipError_t e = hipMemcpy2DAsync(b->lde, leaf_len * N * 8, t, (size_t)ncols * N * 8, (size_t)ncols * N * 8, K,
+                                                      hipMemcpyDeviceToDevice, c->stream);
+                if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "strided LDE copy: %s", hipGetErrorString(e));
+            }
+            (void)hipStreamSynchronize(c->stream);
+            c->release(t);
+            GLP_TRY(rc);
+            GLP_TRY(merkle_fill_salts(c, b->lde, ncols, lg, rate_bits, salt_seed, salt_tag, K, leaf_len * N));
+        }
+        GLP_TRY(merkle_from_lde(c, b->lde, (u32)leaf_len, lg, rate_bits, cap_height, b->digests, K, leaf_len * N, b->ndigests * 4, hasher));
         *out = b.release();
         return GLP_OK;
     }
@@ -403,9 +448,10 @@ int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg
     const size_t n = (size_t)1 << lg, N = n << rate_bits;
     std::unique_ptr<glp_batch, void (*)(glp_batch *)> b(new glp_batch(), batch_destroy);
     b->ctx = c; b->ncols = ncols; b->lg = lg; b->rate_bits = rate_bits; b->cap_height = cap_height; b->hasher = hasher;
+    b->salt = salt_seed ? SALT_SIZE : 0;
     b->ndigests = merkle_num_digests(N, cap_height);
     GLP_TRY(c->alloc((void **)&b->coeffs, (size_t)ncols * n * 8));
-    GLP_TRY(c->alloc((void **)&b->lde, (size_t)ncols * N * 8));
+    GLP_TRY(c->alloc((void **)&b->lde, (size_t)(ncols + b->salt) * N * 8));
     GLP_TRY(c->alloc((void **)&b->digests, b->ndigests * 32));
     if (input_kind == BATCH_VALUES && host_src != nullptr) {
         // chunking pays when a chunk's copy is long against a few launches: below 64 MB the witness goes up in one piece
@@ -434,7 +480,8 @@ int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg
         if (rc != GLP_OK || !evs.empty()) (void)hipStreamSynchronize(c->copy_stream);
         for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
         GLP_TRY(rc);
-        GLP_TRY(merkle_from_lde(c, b->lde, ncols, lg, rate_bits, cap_height, b->digests, 1, 0, 0, hasher));
+        if (b->salt) GLP_TRY(merkle_fill_salts(c, b->lde, ncols, lg, rate_bits, salt_seed, salt_tag));
+        GLP_TRY(merkle_from_lde(c, b->lde, ncols + b->salt, lg, rate_bits, cap_height, b->digests, 1, 0, 0, hasher));
         *out = b.release();
         return GLP_OK;
     }
@@ -452,13 +499,14 @@ int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg
         StageScope st(c, "lde", (8.0 * n + 8.0 * N) * ncols);
         GLP_TRY(lde_coeffs(c, b->coeffs, b->lde, ncols, lg, rate_bits, glf::GEN));
     }
-    GLP_TRY(merkle_from_lde(c, b->lde, ncols, lg, rate_bits, cap_height, b->digests, 1, 0, 0, hasher));
+    if (b->salt) GLP_TRY(merkle_fill_salts(c, b->lde, ncols, lg, rate_bits, salt_seed, salt_tag));
+    GLP_TRY(merkle_from_lde(c, b->lde, ncols + b->salt, lg, rate_bits, cap_height, b->digests, 1, 0, 0, hasher));
     *out = b.release();
     return GLP_OK;
 }
 
 static int batch_from_host(glp_ctx *c, const u64 *host, bool from_values, u32 ncols, u32 log_n, u32 rate_bits, u32 cap_height,
-                           glp_batch **out, int hasher = GLP_HASH_POSEIDON) {
+                           glp_batch **out, int hasher = GLP_HASH_POSEIDON, const u64 *salt_seed = nullptr, u32 salt_tag = 0) {
     GLP_REQUIRE(c && host && out, "null argument");
     GLP_TRY(bind(c));
     if (log_n > (u32)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
@@ -467,7 +515,8 @@ static int batch_from_host(glp_ctx *c, const u64 *host, bool from_values, u32 nc
     GLP_TRY(c->alloc(&d, tot * 8));
     int rc = GLP_OK;
     if (from_values) {       // upload pipelined with the transforms
-        rc = batch_build(c, (const u64 *)d, BATCH_VALUES, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, host, 1, hasher);
+        rc = batch_build(c, (const u64 *)d, BATCH_VALUES, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, host, 1, hasher,
+                         salt_seed, salt_tag);
     } else {
         hipError_t e = hipMemcpyAsync(d, host, tot * 8, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
@@ -498,6 +547,14 @@ int glp_batch_from_coeffs_h(glp_ctx *c, const uint64_t *coeffs, uint32_t ncols, 
                             uint32_t hasher, glp_batch **out) {
     return batch_from_host(c, coeffs, false, ncols, log_n, rate_bits, cap_height, out, (int)hasher);
 }
+int glp_batch_from_values_salted(glp_ctx *c, const uint64_t *values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
+                                 uint32_t cap_height, uint32_t hasher, const uint64_t seed[4], glp_batch **out) {
+    GLP_REQUIRE(c && values && seed && out, "null argument");
+    GLP_TRY(bind(c));
+    u64 s[4];
+    for (int i = 0; i < 4; i++) s[i] = glf::canon(seed[i]);
+    return batch_from_host(c, values, true, ncols, log_n, rate_bits, cap_height, out, (int)hasher, s, GLP_SALT_TAG_BATCH);
+}
 int glp_batch_from_values_device(glp_ctx *c, const uint64_t *dev_values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
                                  uint32_t cap_height, glp_batch **out) {
     GLP_REQUIRE(c && dev_values && out, "null argument");
@@ -520,6 +577,8 @@ int glp_batch_info(const glp_batch *b, uint32_t *ncols, uint32_t *log_n, uint32_
     if (cap_height) *cap_height = (u32)b->cap_height;
     return GLP_OK;
 }
+
+uint32_t glp_batch_leaf_len(const glp_batch *b) { return b ? b->ncols + b->salt : 0; }
 
 int glp_batch_cap(const glp_batch *b, uint64_t *cap_out) {
     GLP_REQUIRE(b && cap_out, "null argument");
@@ -557,10 +616,11 @@ int glp_batch_leaf(const glp_batch *b, uint64_t leaf_index, uint64_t *out) {
     Scratch s(c);
     u64 *idx, *t;
     GLP_TRY(s.get(&idx, 1));
-    GLP_TRY(s.get(&t, b->ncols));
+    const u32 leaf_len = b->ncols + b->salt;
+    GLP_TRY(s.get(&t, leaf_len));
     GLP_HIP(hipMemcpyAsync(idx, &leaf_index, 8, hipMemcpyHostToDevice, c->stream));
-    GLP_TRY(merkle_gather_lde_rows(c, b->lde, b->ncols, b->lg, b->rate_bits, idx, 1, t));
-    GLP_HIP(hipMemcpyAsync(out, t, (size_t)b->ncols * 8, hipMemcpyDeviceToHost, c->stream));
+    GLP_TRY(merkle_gather_lde_rows(c, b->lde, leaf_len, b->lg, b->rate_bits, idx, 1, t));
+    GLP_HIP(hipMemcpyAsync(out, t, (size_t)leaf_len * 8, hipMemcpyDeviceToHost, c->stream));
     GLP_HIP(hipStreamSynchronize(c->stream));
     return GLP_OK;
 }

@@ -7,7 +7,8 @@ struct glp_batch {
     u32 ncols = 0;
     int lg = 0, rate_bits = 0, cap_height = 0;
     u64 *coeffs = nullptr;    // [ncols][n]     bit-reversed coefficient order
-    u64 *lde = nullptr;       // [ncols][R][n]  coset-major LDE values
+    u64 *lde = nullptr;       // [ncols + salt][R][n]  coset-major LDE values, salt columns last
+    u32 salt = 0;             // SALT_SIZE = 4 for a blinded batch (PolynomialBatch blinding = true), else 0; leaves are ncols + salt wide
     u64 *digests = nullptr;   // [ndigests][4]  level 0 (leaf j at slot j) ... cap level
     size_t ndigests = 0;
     int hasher = GLP_HASH_POSEIDON;   // GenericConfig::Hasher of the tree
@@ -17,6 +18,8 @@ struct glp_batch {
 namespace glp {
 enum BatchInput { BATCH_VALUES = 0, BATCH_COEFFS_NATURAL = 1, BATCH_COEFFS_BITREV = 2 };
 int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg, int rate_bits, int cap_height,
-                glp_batch **out, const u64 *host_src = nullptr, u32 K = 1, int hasher = GLP_HASH_POSEIDON);
+                glp_batch **out, const u64 *host_src = nullptr, u32 K = 1, int hasher = GLP_HASH_POSEIDON,
+                const u64 *salt_seed = nullptr /* non-null: blinded, 4 salt columns (merkle_fill_salts) */, u32 salt_tag = 0);
+constexpr u32 SALT_SIZE = 4;
 void batch_destroy(glp_batch *b);
 }  // namespace glp

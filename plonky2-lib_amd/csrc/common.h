@@ -78,6 +78,8 @@ struct glp_ctx {
     void (*host_pool_free)(void *) = nullptr;
     bool profiling = false;
     std::vector<glp::Stage> stages;
+    bool salt_seed_fixed = false;        // glp_ctx_set_salt_seed: a fixed seed for every zk proof, else a fresh OS seed per call
+    u64 salt_seed[4] = {0, 0, 0, 0};
 
     int alloc(void **p, size_t bytes);
     void release(void *p);
@@ -92,6 +94,8 @@ struct StageScope {
     StageScope(glp_ctx *ctx, const char *name, double bytes) : c(ctx) { c->stage_begin(name, bytes); }
     ~StageScope() { c->stage_end(); }
 };
+// the salt seed of one zk proof or batch call: the context's fixed seed, or 4 fresh words from getrandom, reduced mod p (api.hip)
+int salt_seed_draw(glp_ctx *c, u64 out[4]);
 inline int bind(glp_ctx *c) {
     hipError_t e = hipSetDevice(c->device);
     return e == hipSuccess ? GLP_OK : set_error(GLP_ERR_HIP, "hipSetDevice(%d): %s", c->device, hipGetErrorString(e));

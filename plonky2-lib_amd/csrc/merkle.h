@@ -25,6 +25,9 @@ int merkle_gather_lde_rows(glp_ctx *c, const u64 *dev_lde, u32 ncols, int lg, in
 int merkle_gather_paths(glp_ctx *c, const u64 *dev_digests, size_t nleaves, int cap_height, const u64 *dev_leaf_idx,
                         u32 count, u64 *dev_out /*[count][depth][4]*/, size_t out_stride = 0 /* 0: 4 depth */,
                         u32 idx_shift = 0 /* leaf = idx >> idx_shift */, u32 K = 1, size_t dig_bstride = 0, size_t out_bstride = 0);
+// fills the SALT_SIZE = 4 salt columns ncols..ncols+3 of a blinded LDE matrix [ncols + 4][R][n] (rule in glp.h; seed words canonical;
+// tag: GLP_SALT_TAG_*; K > 1: proof k of a batch uses seed3 + k, its matrix starts k * lde_stride words further on)
+int merkle_fill_salts(glp_ctx *c, u64 *dev_lde, u32 ncols, int lg, int rate_bits, const u64 seed[4], u32 tag, u32 K = 1, size_t lde_stride = 0);
 int poseidon_permute_states(glp_ctx *c, u64 *dev_states, size_t count);
 
 }  // namespace glp

@@ -370,6 +370,36 @@ int merkle_gather_paths(glp_ctx *c, const u64 *dev_digests, size_t nleaves, int 
     return GLP_OK;
 }
 
+// ---- salts of a blinded oracle (PolynomialBatch with blinding = true, plonky2 fri/oracle.rs SALT_SIZE = 4) --------------------------
+// The 4 salt columns sit after the ncols polynomial columns of the LDE matrix [ncols + 4][R][n], so the leaf-hash kernels hash
+// (values.., s0, s1, s2, s3) without knowing about salts.  One Poseidon permutation per leaf, keyed by the seed (glp.h, salt rule):
+//   salt(seed, tag, leaf)[0..4) = Poseidon([seed0, seed1, seed2, seed3 + k, tag, leaf & 0xffffffff, leaf >> 32, 0, 0, 0, 0, 0])[0..4)
+// with leaf the Merkle leaf index (what the verifier sees) and k the proof index of a many-proofs batch (blockIdx.y).
+__global__ __launch_bounds__(256) void k_salt_lde(u64 *__restrict__ lde, u32 ncols, int lg, int rate_bits, size_t lde_stride,
+                                                  u64 seed0, u64 seed1, u64 seed2, u64 seed3, u32 tag) {
+    lde += (size_t)blockIdx.y * lde_stride;
+    const size_t N = (size_t)1 << (lg + rate_bits);
+    const size_t pos = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (pos >= N) return;
+    const u32 r = (u32)(pos >> lg), q = (u32)(pos & (((size_t)1 << lg) - 1));
+    const u64 leaf = ((u64)bitrev32(r, rate_bits) << lg) | bitrev32(q, lg);
+    u64 s[12] = {seed0, seed1, seed2, add(seed3, (u64)blockIdx.y), (u64)tag, leaf & 0xffffffffull, leaf >> 32, 0, 0, 0, 0, 0};
+    pos::permute(s);
+#pragma unroll
+    for (int i = 0; i < 4; i++) lde[(size_t)(ncols + i) * N + pos] = s[i];
+}
+
+int merkle_fill_salts(glp_ctx *c, u64 *dev_lde, u32 ncols, int lg, int rate_bits, const u64 seed[4], u32 tag, u32 K, size_t lde_stride) {
+    const size_t N = (size_t)1 << (lg + rate_bits);
+    GLP_REQUIRE(K >= 1 && K <= 65535, "batch of %u trees outside 1..65535", K);
+    for (int i = 0; i < 4; i++) GLP_REQUIRE(seed[i] < P, "salt seed word %d is not a canonical field element", i);
+    StageScope st(c, "salt", (double)N * K * 32.0);
+    hipLaunchKernelGGL(k_salt_lde, dim3((unsigned)((N + 255) / 256), K), dim3(256), 0, c->stream, dev_lde, ncols, lg, rate_bits, lde_stride,
+                       seed[0], seed[1], seed[2], seed[3], tag);
+    GLP_HIP(hipGetLastError());
+    return GLP_OK;
+}
+
 int poseidon_permute_states(glp_ctx *c, u64 *dev_states, size_t count) {
     if (!count) return GLP_OK;
     hipLaunchKernelGGL(k_permute_states, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, dev_states, count);

@@ -21,13 +21,14 @@
 #include "prover_types.h"
 
 namespace {
-void make_layout(const glp_circuit_desc &c, Layout &L) {
+void make_layout(const glp_circuit_desc &c, Layout &L, bool zk) {
     const u32 cap = 1u << c.cap_height, nch = c.num_challenges;
     memset(&L, 0, sizeof(L));
     L.oracle_cols[0] = c.num_constants + c.num_routed_wires;
     L.oracle_cols[1] = c.num_wires;
     L.oracle_cols[2] = nch * (1 + c.num_partial_products);
     L.oracle_cols[3] = nch * c.quotient_degree_factor;
+    for (int k = 0; k < 4; k++) L.leaf_len[k] = L.oracle_cols[k] + (zk && k > 0 ? SALT_SIZE : 0);
     L.nopen = (size_t)c.num_constants + c.num_routed_wires + c.num_wires + 2 * nch + nch * c.num_partial_products +
               nch * c.quotient_degree_factor;
     L.openings = 3 * (size_t)cap * 4;
@@ -36,7 +37,7 @@ void make_layout(const glp_circuit_desc &c, Layout &L) {
     const u32 lgN = c.degree_bits + c.rate_bits;
     L.depth0 = lgN - c.cap_height;
     size_t q = 0;
-    for (int k = 0; k < 4; k++) q += L.oracle_cols[k] + 4 * (size_t)L.depth0;
+    for (int k = 0; k < 4; k++) q += L.leaf_len[k] + 4 * (size_t)L.depth0;
     u32 lg = lgN;
     for (u32 i = 0; i < c.num_reductions; i++) {
         const u32 ab = c.reduction_arity_bits[i];
@@ -1553,6 +1554,8 @@ struct glp_session {
     u64 *owned_wires = nullptr;        // device copy made by begin() when the caller passed host memory
     const u64 *dev_wires = nullptr;
     u64 pih[4] = {0, 0, 0, 0};
+    u64 salt_seed[4] = {0, 0, 0, 0};   // zk circuit: the seed of this proof's salts (drawn in begin), else unused
+    const u64 *salt = nullptr;         // salt_seed for a zk circuit, nullptr otherwise
     BatchHolder wb, zb, qb;
     u64 betas[MAXCH] = {}, gammas[MAXCH] = {}, alphas[MAXCH] = {};
     ext2 zeta = {0, 0}, zeta_next = {0, 0};
@@ -1585,9 +1588,10 @@ struct glp_session {
         GLP_REQUIRE(stage == S_NEW, "session already begun");
         proof_words.assign(L.total, 0);
         dev_wires = wires_dev;
+        if (cc->zk) { GLP_TRY(salt_seed_draw(c, salt_seed)); salt = salt_seed; }
         host_hash_no_pad(public_inputs, d.num_public_inputs, pih);
         if (d.num_public_inputs) memcpy(proof() + L.pis, public_inputs, (size_t)d.num_public_inputs * 8);
-        GLP_TRY(batch_build(c, dev_wires, BATCH_VALUES, nw, lg, rb, (int)d.cap_height, &wb.b, host_wires, 1, hasher));
+        GLP_TRY(batch_build(c, dev_wires, BATCH_VALUES, nw, lg, rb, (int)d.cap_height, &wb.b, host_wires, 1, hasher, salt, GLP_SALT_TAG_WIRES));
         GLP_TRY(batch_cap_host(c, wb.b, cap));
         memcpy(proof() + L.caps, cap.data(), capn * 32);
         stage = S_WIRES;
@@ -1627,7 +1631,7 @@ struct glp_session {
                 GLP_HIP(hipGetLastError());
             }
         }
-        GLP_TRY(batch_build(c, zp, BATCH_VALUES, nzp, lg, rb, (int)d.cap_height, &zb.b, nullptr, 1, hasher));
+        GLP_TRY(batch_build(c, zp, BATCH_VALUES, nzp, lg, rb, (int)d.cap_height, &zb.b, nullptr, 1, hasher, salt, GLP_SALT_TAG_ZS));
         GLP_TRY(batch_cap_host(c, zb.b, cap));
         memcpy(proof() + L.caps + capn * 4, cap.data(), capn * 32);
         stage = S_ZS;
@@ -1741,7 +1745,7 @@ struct glp_session {
             hipLaunchKernelGGL(k_quotient_combine, dim3(nblk(n), nch), dim3(256), 0, c->stream, q);
             GLP_HIP(hipGetLastError());
         }
-        GLP_TRY(batch_build(c, qc, BATCH_COEFFS_BITREV, nch * qdf, lg, rb, (int)d.cap_height, &qb.b, nullptr, 1, hasher));
+        GLP_TRY(batch_build(c, qc, BATCH_COEFFS_BITREV, nch * qdf, lg, rb, (int)d.cap_height, &qb.b, nullptr, 1, hasher, salt, GLP_SALT_TAG_QUOTIENT));
         GLP_TRY(batch_cap_host(c, qb.b, cap));
         memcpy(proof() + L.caps + 2 * capn * 4, cap.data(), capn * 32);
         stage = S_QUOTIENT;
@@ -1914,7 +1918,7 @@ struct glp_session {
         GLP_TRY(h2d(c, dev_idx, xi.data(), nq * 8));
         size_t off = 0;   // word offset inside one query record
         for (int k = 0; k < 4; k++) {
-            const u32 ncol = ob[k]->ncols;
+            const u32 ncol = ob[k]->ncols + ob[k]->salt;     // the whole leaf: salts ride after the polynomial values
             GLP_TRY(merkle_gather_lde_rows(c, ob[k]->lde, ncol, lg, rb, dev_idx, nq, dev_q + off, stride));
             off += ncol;
             GLP_TRY(merkle_gather_paths(c, ob[k]->digests, N, (int)d.cap_height, dev_idx, nq, dev_q + off, stride, 0));
@@ -2036,7 +2040,7 @@ template <class F> void walk_proof(const glp_circuit *cc, F f) {
     for (u32 q = 0; q < d.num_query_rounds; q++) {
         size_t o = L.queries + (size_t)q * L.query_stride;
         for (int k = 0; k < 4; k++) {
-            f(o, (size_t)L.oracle_cols[k], PW_FIELD); o += L.oracle_cols[k];
+            f(o, (size_t)L.leaf_len[k], PW_FIELD); o += L.leaf_len[k];
             f(o, 4 * (size_t)L.depth0, PW_PATH); o += 4 * (size_t)L.depth0;
         }
         for (u32 r = 0; r < d.num_reductions; r++) {
@@ -2165,9 +2169,12 @@ void glp_circuit_free(glp_circuit *cc) {
     delete cc;
 }
 
-int glp_circuit_create(glp_ctx *c, const glp_circuit_desc *desc, glp_circuit **out) {
+int glp_circuit_create(glp_ctx *c, const glp_circuit_desc *desc, glp_circuit **out) { return glp_circuit_create_ex(c, desc, 0, out); }
+
+int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t flags, glp_circuit **out) {
     GLP_REQUIRE(c && desc && out, "null argument");
     *out = nullptr;
+    GLP_REQUIRE((flags & ~GLP_CIRCUIT_ZERO_KNOWLEDGE) == 0, "unknown circuit flags 0x%x", flags);
     GLP_TRY(bind(c));
     const glp_circuit_desc &d = *desc;
     GLP_REQUIRE(d.gates && d.k_is && d.constants && d.sigmas, "null array in circuit description");
@@ -2285,7 +2292,8 @@ int glp_circuit_create(glp_ctx *c, const glp_circuit_desc *desc, glp_circuit **o
             if (cc->k_is[j] != mul(cc->k_is[j - 1], (u64)cc->k_ratio)) { cc->k_ratio = 0; break; }
     }
     cc->d.gates = cc->gates.data(); cc->d.k_is = cc->k_is.data(); cc->d.constants = nullptr; cc->d.sigmas = nullptr;
-    make_layout(cc->d, cc->L);
+    cc->zk = (flags & GLP_CIRCUIT_ZERO_KNOWLEDGE) != 0;
+    make_layout(cc->d, cc->L, cc->zk);
     const size_t n = (size_t)1 << d.degree_bits;
     const u32 nc = d.num_constants, nr = d.num_routed_wires;
     GLP_TRY(c->alloc((void **)&cc->dev_gates, sizeof(DevGate) * std::max<u32>(d.num_gates, 1)));
@@ -2356,6 +2364,7 @@ int glp_circuit_constants_sigmas_cap(const glp_circuit *cc, uint64_t *cap_out) {
     return GLP_OK;
 }
 size_t glp_proof_words(const glp_circuit *cc) { return cc ? cc->L.total : 0; }
+int glp_circuit_zero_knowledge(const glp_circuit *cc) { return cc && cc->zk ? 1 : 0; }
 
 // bytes of one digest on the wire: a Poseidon HashOut is 4 field elements, a KeccakHash<25> digest 25 bytes
 static size_t digest_wire_bytes(const glp_circuit *cc) { return cc->d.hasher == GLP_HASH_KECCAK25 ? 25 : 32; }
@@ -2573,6 +2582,8 @@ int glp_witness_stage(glp_ctx *c, const glp_circuit *cc, const uint64_t *host_wi
     *out = nullptr;
     GLP_REQUIRE(cc->ctx == c, "circuit belongs to another context");
     GLP_REQUIRE((flags & ~GLP_WITNESS_ROUTED_ONLY) == 0, "unknown flags 0x%x", flags);
+    // the blinding rows of a zk circuit hold random advice wires that no generator derives: glp_witness_fill cannot rebuild them
+    GLP_REQUIRE(!(cc->zk && (flags & GLP_WITNESS_ROUTED_ONLY)), "GLP_WITNESS_ROUTED_ONLY: a zero-knowledge circuit needs its full witness");
     GLP_TRY(bind(c));
     const size_t n = (size_t)1 << cc->d.degree_bits;
     const u32 nw = cc->d.num_wires, nr = cc->d.num_routed_wires;

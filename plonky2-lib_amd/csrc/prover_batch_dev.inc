@@ -36,6 +36,9 @@ int prove_batch_impl_dev(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *de
     Tmp tmp(c);
     const int hasher = (int)d.hasher;
     BatchHolder wb, zb, qb;
+    u64 salt_seed[4] = {0, 0, 0, 0};     // zk circuit: one seed per call, proof k salts with seed3 + k (merkle_fill_salts)
+    const u64 *salt = nullptr;
+    if (cc->zk) { GLP_TRY(salt_seed_draw(c, salt_seed)); salt = salt_seed; }
     const unsigned tgrid = (K + 15) / 16;
     u64 *dch, *image;
     u32 *dev_err;
@@ -48,7 +51,7 @@ int prove_batch_impl_dev(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *de
     g.dch = dch; g.image = image; g.total = L.total; g.K = K; g.capn = capn; g.nch = nch;
 
     // ---- wires commitment, transcript 1
-    GLP_TRY(batch_build(c, dev_wires, BATCH_VALUES, nw, lg, rb, (int)d.cap_height, &wb.b, nullptr, K, hasher));
+    GLP_TRY(batch_build(c, dev_wires, BATCH_VALUES, nw, lg, rb, (int)d.cap_height, &wb.b, nullptr, K, hasher, salt, GLP_SALT_TAG_WIRES));
     const size_t ndig = wb.b->ndigests, cap_off = merkle_cap_offset(N, (int)d.cap_height);
     u64 *dev_chal, *dev_qpp;
     GLP_TRY(tmp.get(&dev_chal, (size_t)K * 2 * MAXCH));
@@ -84,7 +87,7 @@ int prove_batch_impl_dev(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *de
         }
         GLP_HIP(hipGetLastError());
     }
-    GLP_TRY(batch_build(c, zp, BATCH_VALUES, nzp, lg, rb, (int)d.cap_height, &zb.b, nullptr, K, hasher));
+    GLP_TRY(batch_build(c, zp, BATCH_VALUES, nzp, lg, rb, (int)d.cap_height, &zb.b, nullptr, K, hasher, salt, GLP_SALT_TAG_ZS));
     int qdb = 0;
     while ((1u << qdb) < qdf) qdb++;
     const u32 Rq = 1u << qdb, step = 1u << (rb - qdb);
@@ -111,7 +114,7 @@ int prove_batch_impl_dev(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *de
         memset(&qp, 0, sizeof(qp));
         a.cs = cc->cs->lde; a.gates = cc->dev_gates; a.k_is = cc->dev_k_is; a.k_ratio = cc->k_ratio;
         qp.wl = wb.b->lde; qp.zl = zb.b->lde; qp.out = qv; qp.apow = dev_apow; qp.apl = dev_apow + (size_t)K * apn;
-        qbt.pp = dev_qpp; qbt.wl_stride = (size_t)nw * N; qbt.zl_stride = (size_t)nzp * N; qbt.out_stride = qstride; qbt.apow_stride = (size_t)nch * nterms;
+        qbt.pp = dev_qpp; qbt.wl_stride = (size_t)(nw + wb.b->salt) * N; qbt.zl_stride = (size_t)(nzp + zb.b->salt) * N; qbt.out_stride = qstride; qbt.apow_stride = (size_t)nch * nterms;
         const u64 WN = root_of_unity(lg + rb), wR = root_of_unity(rb);
         for (u32 rq = 0; rq < Rq; rq++) {
             const u32 r = rq * step;
@@ -168,7 +171,7 @@ int prove_batch_impl_dev(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *de
         hipLaunchKernelGGL(k_quotient_combine, dim3(nblk(n), K * nch), dim3(256), 0, c->stream, q);
         GLP_HIP(hipGetLastError());
     }
-    GLP_TRY(batch_build(c, qc, BATCH_COEFFS_BITREV, nch * qdf, lg, rb, (int)d.cap_height, &qb.b, nullptr, K, hasher));
+    GLP_TRY(batch_build(c, qc, BATCH_COEFFS_BITREV, nch * qdf, lg, rb, (int)d.cap_height, &qb.b, nullptr, K, hasher, salt, GLP_SALT_TAG_QUOTIENT));
     const u64 wn = root_of_unity(lg);
     u64 *dev_zetas;
     GLP_TRY(tmp.get(&dev_zetas, (size_t)K * 4));
@@ -223,7 +226,7 @@ int prove_batch_impl_dev(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *de
     GLP_TRY(tmp.get(&fcoef, (size_t)K * 2 * n));
     {
         FVArgs a;
-        for (int b = 0; b < 4; b++) { a.lde[b] = ob[b]->lde; a.ncols[b] = ob[b]->ncols; a.lde_stride[b] = ostride[b] * ob[b]->ncols * N; }
+        for (int b = 0; b < 4; b++) { a.lde[b] = ob[b]->lde; a.ncols[b] = ob[b]->ncols; a.lde_stride[b] = ostride[b] * (ob[b]->ncols + ob[b]->salt) * N; }
         a.apow = dev_fap; a.out = fv;
         a.red0 = a.red1 = a.zeta = a.zeta_next = a.shift_acc = e_from(0);
         a.w_n = wn; a.g = GEN; a.lg = (u32)lg; a.rb = (u32)rb; a.nch = nch;
@@ -299,7 +302,7 @@ int prove_batch_impl_dev(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *de
     const size_t stride = L.query_stride, qsec = L.total;        // batch stride of the query records = one whole proof
     size_t off = 0;
     for (int b = 0; b < 4; b++) {
-        const u32 ncol = ob[b]->ncols;
+        const u32 ncol = ob[b]->ncols + ob[b]->salt;      // the whole leaf, salts last
         GLP_TRY(merkle_gather_lde_rows(c, ob[b]->lde, ncol, lg, rb, dev_idx, nq, dev_q + off, stride, K, ostride[b] * ncol * N, qsec));
         off += ncol;
         GLP_TRY(merkle_gather_paths(c, ob[b]->digests, N, (int)d.cap_height, dev_idx, nq, dev_q + off, stride, 0, K, ostride[b] * ndig * 4, qsec));

@@ -21,11 +21,13 @@ struct DevGate { u32 type, selector_index, group_start, group_end, row, num_cons
 struct Layout {
     size_t caps, openings, fri_caps, queries, final_poly, pow, pis, total, nopen, query_stride;
     u32 oracle_cols[4], depth0, step_depth[16], final_len;
+    u32 leaf_len[4];   // words of one Merkle leaf of oracle k: oracle_cols[k], + SALT_SIZE for the blinded oracles 1..3 of a zk circuit
 };
 
 struct glp_circuit {
     glp_ctx *ctx = nullptr;
     glp_circuit_desc d;            // scalars + host copies below
+    bool zk = false;               // GLP_CIRCUIT_ZERO_KNOWLEDGE: wires, Z / partial products and quotient oracles are salted
     std::vector<glp_gate> gates;
     std::vector<u64> k_is;
     u64 digest[4];

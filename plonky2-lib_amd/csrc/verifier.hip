@@ -334,7 +334,7 @@ int verify_canonical(const glp_circuit *cc, const u64 *proof) {
             for (size_t i = 0; i < L.queries; i++) is_dig[i] = in_caps(i);
             for (u32 q = 0; q < d.num_query_rounds; q++) {
                 size_t o = L.queries + (size_t)q * L.query_stride;
-                for (int k = 0; k < 4; k++) { o += L.oracle_cols[k]; for (size_t j = 0; j < 4 * (size_t)L.depth0; j++) is_dig[o + j] = 1; o += 4 * (size_t)L.depth0; }
+                for (int k = 0; k < 4; k++) { o += L.leaf_len[k]; for (size_t j = 0; j < 4 * (size_t)L.depth0; j++) is_dig[o + j] = 1; o += 4 * (size_t)L.depth0; }
                 for (u32 r = 0; r < d.num_reductions; r++) {
                     o += (size_t)2 << d.reduction_arity_bits[r];
                     for (size_t j = 0; j < 4 * (size_t)L.step_depth[r]; j++) is_dig[o + j] = 1;
@@ -513,9 +513,10 @@ int verify_fri_host(const glp_circuit *cc, const u64 *proof, const VChal &vc) {
         const u64 *evals[4];
         for (int k = 0; k < 4; k++) {
             evals[k] = w;
-            if (!merkle_ok((int)d.hasher, w, L.oracle_cols[k], x_index, caps4[k], w + L.oracle_cols[k], L.depth0))
+            // the Merkle path covers the whole leaf, salts included; fri_combine_initial reads its first oracle_cols values (unsalted_eval)
+            if (!merkle_ok((int)d.hasher, w, L.leaf_len[k], x_index, caps4[k], w + L.leaf_len[k], L.depth0))
                 FAIL(1 + (u32)k);
-            w += L.oracle_cols[k] + 4 * (size_t)L.depth0;
+            w += L.leaf_len[k] + 4 * (size_t)L.depth0;
         }
         u64 subgroup_x = mul(GEN, pow(wN, (u64)brev(x_index, lgN)));
         E old_eval;
@@ -596,6 +597,7 @@ struct VQArgs {
     size_t total, caps, fri_caps, queries, query_stride, final_poly;
     u32 vstride, nq, K, nch, lgN, cap_height, depth0, nred, final_len;
     u32 oracle_cols[4], ab[16], step_depth[16];
+    u32 leaf_len[4];        // oracle_cols, + 4 salts for oracles 1..3 of a zk circuit (Layout::leaf_len)
     u64 wN, gA[16];         // root_of_unity(lgN), root_of_unity(ab[r])
 };
 using pos::shfl64;
@@ -683,16 +685,16 @@ __global__ __launch_bounds__(256) void k_verify_queries(VQArgs a) {
     const ext2 al = e_pow(alpha, (u64)l);
     ext2 r0 = e_from(0), r1 = e_from(0), off = e_from(1);
     for (int t = 0; t < 4; t++) {
-        const u32 ncols = a.oracle_cols[t];
+        const u32 ncols = a.oracle_cols[t], leaf_len = a.leaf_len[t];     // the path covers the salted leaf, the combination its polynomials
         const u64 *cap = t == 0 ? a.cs_cap : proof + a.caps + (size_t)(t - 1) * capn4;
-        if (merkle_bad<HASHER>(w, ncols, x_index, w + ncols, a.depth0, cap, l, gb)) VQ_FAIL(1 + (u32)t);
+        if (merkle_bad<HASHER>(w, leaf_len, x_index, w + leaf_len, a.depth0, cap, l, gb)) VQ_FAIL(1 + (u32)t);
         ext2 part = e_from(0);                            // lane l: sum_i evals[l + 16 i] (alpha^16)^i, Horner from the top
         if ((u32)l < ncols)
             for (int j = (int)(((ncols - 1 - (u32)l) >> 4) << 4) + l; j >= 0; j -= 16) part = e_add(e_mul(part, a16), e_from(w[j]));
         r0 = e_add(r0, e_mul(off, group_sum(e_mul(part, al))));
         off = e_mul(off, e_pow(alpha, (u64)ncols));
         if (t == 2) { ext2 ap = e_from(1); for (u32 j = 0; j < a.nch; j++) { r1 = e_add(r1, e_scale(ap, w[j])); ap = e_mul(ap, alpha); } }
-        w += ncols + 4 * (size_t)a.depth0;
+        w += leaf_len + 4 * (size_t)a.depth0;
     }
     u64 subgroup_x = mul(GEN, dvpow(a.wN, (u64)(__brevll((unsigned long long)x_index) >> (64 - a.lgN))));
     ext2 old_eval;
@@ -865,7 +867,7 @@ extern "C" int glp_verify_batch(glp_ctx *c, const glp_circuit *cc, uint32_t K, c
     a.total = L.total; a.caps = L.caps; a.fri_caps = L.fri_caps; a.queries = L.queries; a.query_stride = L.query_stride; a.final_poly = L.final_poly;
     a.vstride = vstride; a.nq = nq; a.K = K; a.nch = d.num_challenges; a.lgN = d.degree_bits + d.rate_bits; a.cap_height = d.cap_height;
     a.depth0 = L.depth0; a.nred = nred; a.final_len = L.final_len;
-    for (int t = 0; t < 4; t++) a.oracle_cols[t] = L.oracle_cols[t];
+    for (int t = 0; t < 4; t++) { a.oracle_cols[t] = L.oracle_cols[t]; a.leaf_len[t] = L.leaf_len[t]; }
     for (u32 r = 0; r < nred; r++) { a.ab[r] = d.reduction_arity_bits[r]; a.step_depth[r] = L.step_depth[r]; a.gA[r] = root_of_unity((int)d.reduction_arity_bits[r]); }
     a.wN = root_of_unity((int)a.lgN);
     {

@@ -345,7 +345,8 @@ class GadgetBuilder:
         return bits[:num_bits]
 
     # ---- build(): rows -> synth.Builder (selectors, sigmas) + the witness
-    def build(self, min_log_n=0):
+    def build(self, min_log_n=0, blinding_seed=None):
+        """blinding_seed: with a zero_knowledge config, the seed of the blinding values (tests only; default: OS entropy)"""
         from . import poseidon_py as pp
         cfg = self.cfg
         # public-input hash in circuit: hash_n_to_hash_no_pad over the public inputs, PoseidonGate rows (rate 8, overwrite
@@ -360,7 +361,7 @@ class GadgetBuilder:
         pi_hash = [self.val[t] for t in digest]
         poseidon_rows = self._poseidon_rows
         nrows = len(self.rows)
-        log_n = max(min_log_n, 2, (nrows - 1).bit_length())
+        log_n = max(2, synth.zk_degree_bits(cfg, nrows, min_log_n))
         # padding rows (NoopGate) stay all-zero, as in plonky2, where `PartitionWitness::full_witness` leaves every unset wire at zero:
         # then each advice wire of the witness is either a row-local generator's output or zero, which is what lets the routed
         # columns alone reproduce the whole witness on the GPU (glp_witness_stage with GLP_WITNESS_ROUTED_ONLY)
@@ -436,6 +437,11 @@ class GadgetBuilder:
                     w[3 * self.n_ul + 64 * ii + k, rr] = (v >> np.uint64(63 - k)) & np.uint64(1)
         for row, inputs in poseidon_rows:
             synth._fill_poseidon_row(b, row, inputs)
+        if getattr(cfg, "zero_knowledge", False):
+            # plonky2's `randomize_unused_pi_wires` and `blind()`: random advice on the PublicInputGate row, then the blinding rows,
+            # fresh values per build.  Their random advice wires come from no generator, so such a witness cannot be rebuilt from its
+            # routed columns.
+            b.blind(nrows, pi_row=row_pi, seed=blinding_seed)
         b.public_inputs = np.array([self.val[t] for t in pis], dtype=np.uint64)
         c = b.build()
         c.pi_hash = np.array(pi_hash, dtype=np.uint64)

@@ -564,8 +564,8 @@ class EcdsaBuilder(GadgetBuilder):
         self.connect_biguint(r, point[0])
 
     # ---- build: the advice columns of the added gates, vectorised
-    def build(self, min_log_n=0):
-        c = super().build(min_log_n)
+    def build(self, min_log_n=0, blinding_seed=None):
+        c = super().build(min_log_n, blinding_seed)
         w = c.wires
         U = np.uint64
         if self._addmany:

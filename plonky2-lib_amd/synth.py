@@ -11,6 +11,8 @@ k_is[col'] * w^row'.
 
 Nothing here touches the GPU or the oracle.
 """
+import os
+
 import numpy as np
 
 from . import gl_numpy as gl
@@ -78,15 +80,21 @@ class Config:
     """plonk/circuit_data.rs `CircuitConfig` presets the reference selects in code."""
 
     def __init__(self, num_wires, num_routed_wires, num_constants=2, num_challenges=2, max_quotient_degree_factor=8,
-                 rate_bits=3, cap_height=4, proof_of_work_bits=16, num_query_rounds=28, arity_bits=4, final_poly_bits=5):
+                 rate_bits=3, cap_height=4, proof_of_work_bits=16, num_query_rounds=28, arity_bits=4, final_poly_bits=5,
+                 zero_knowledge=False):
         self.num_wires, self.num_routed_wires, self.num_constants = num_wires, num_routed_wires, num_constants
         self.num_challenges, self.max_quotient_degree_factor = num_challenges, max_quotient_degree_factor
         self.rate_bits, self.cap_height, self.proof_of_work_bits = rate_bits, cap_height, proof_of_work_bits
         self.num_query_rounds, self.arity_bits, self.final_poly_bits = num_query_rounds, arity_bits, final_poly_bits
+        self.zero_knowledge = zero_knowledge
 
     @classmethod
     def standard_recursion_config(cls, **kw):
         return cls(135, 80, **kw)
+
+    @classmethod
+    def standard_recursion_zk_config(cls, **kw):
+        return cls(135, 80, zero_knowledge=True, **kw)
 
     @classmethod
     def standard_ecc_config(cls, **kw):
@@ -99,6 +107,46 @@ class Config:
             out.append(self.arity_bits)
             d -= self.arity_bits
         return out
+
+
+D = 2   # extension degree of every config here
+
+
+def blinding_counts(cfg, num_gates):
+    """plonk/circuit_builder.rs `blinding_counts` (recalled from plonky2 0.1.x, unpinned): the rows `blind()` adds to a zero-knowledge
+    circuit of num_gates gate rows.  Searches degrees from 2^ceil(log2 num_gates) upwards until num_gates + r + 2 z fits, with
+    fri_openings = num_query_rounds (1 + D sum(arity - 1) + D final_poly_coeffs) at that degree, r = D + fri_openings (rows of
+    random wires) and z = 2 D + fri_openings (pairs of rows whose routed wires are random and copy-constrained to each other).
+    Returns (r, z, degree_bits)."""
+    lg = max(0, (int(num_gates) - 1).bit_length())
+    while True:
+        ab = cfg.reduction_arity_bits(lg)
+        folding = sum((1 << a) - 1 for a in ab)
+        final_poly_coeffs = 1 << (lg - sum(ab))
+        fri_openings = cfg.num_query_rounds * (1 + D * folding + D * final_poly_coeffs)
+        r, z = D + fri_openings, 2 * D + fri_openings
+        if num_gates + r + 2 * z <= 1 << lg:
+            return r, z, lg
+        lg += 1
+
+
+def blinding_values(shape, seed=None):
+    """Values of the blinding rows and of the unused PublicInputGate wires: plonky2 draws them per proof (RandomValueGenerator),
+    so they must be unpredictable to the verifier.  seed None (the default): OS entropy (os.urandom), reduced mod p.  A seed gives
+    reproducible values, for tests only: a known seed voids the hiding."""
+    count = int(np.prod(shape))
+    if seed is not None:
+        return gl.rand(np.random.default_rng(seed), shape)
+    raw = np.frombuffer(os.urandom(8 * count), dtype=np.uint64) if count else np.zeros(0, np.uint64)
+    return np.where(raw >= np.uint64(gl.P), raw - np.uint64(gl.P), raw).reshape(shape)
+
+
+def zk_degree_bits(cfg, num_gates, min_log_n=0):
+    """degree_bits of a circuit of num_gates gate rows under cfg: with zero_knowledge, large enough for the blinding rows"""
+    lg = max(min_log_n, (int(num_gates) - 1).bit_length())
+    if getattr(cfg, "zero_knowledge", False):
+        lg = max(lg, blinding_counts(cfg, num_gates)[2])
+    return lg
 
 
 class Circuit:
@@ -159,6 +207,30 @@ class Builder:
         self.sig_row[col_a, rows_a], self.sig_col[col_a, rows_a] = rows_b, col_b
         self.sig_row[col_b, rows_b], self.sig_col[col_b, rows_b] = rows_a, col_a
 
+    def blind(self, first_row, pi_row=None, seed=None):
+        """circuit_builder.rs `randomize_unused_pi_wires` (wires 4.. of the PublicInputGate row pi_row, if given) and `blind()`
+        (zero_knowledge): after the num_gates = first_row gate rows, r NoopGate rows of random wires, then z pairs of NoopGate rows
+        whose routed wires are random, each copy-constrained to the same wire of the other row.  The random values come from
+        blinding_values(.., seed): OS entropy unless a test passes a seed.  Returns the first row after the blinding rows."""
+        cfg, nr = self.cfg, self.cfg.num_routed_wires
+        r, z, _ = blinding_counts(cfg, first_row)
+        end = first_row + r + 2 * z
+        if end > self.n:
+            raise ValueError("%d gate rows and %d blinding rows do not fit 2^%d rows" % (first_row, r + 2 * z, self.log_n))
+        vals = blinding_values((cfg.num_wires * r + nr * z + (cfg.num_wires - 4 if pi_row is not None else 0),), seed)
+        if pi_row is not None:
+            self.wires[4:, pi_row] = vals[nr * z + cfg.num_wires * r:]
+        self.row_gate[first_row:end] = self._kind(GATE_NOOP, 0)
+        self.wires[:, first_row:first_row + r] = vals[:cfg.num_wires * r].reshape(cfg.num_wires, r)
+        r1 = first_row + r + 2 * np.arange(z, dtype=np.int64)
+        r2 = r1 + 1
+        self.wires[:nr, r1] = vals[cfg.num_wires * r:cfg.num_wires * r + nr * z].reshape(nr, z)
+        self.wires[:nr, r2] = self.wires[:nr, r1]
+        for col in range(nr):
+            self.connect_pairs(r1, col, r2, col)
+        self.blinded = True
+        return end
+
     def connect_cycle(self, rows, cols):
         """One cycle through fresh cells (rows[i], cols[i]) in the given order."""
         rows, cols = np.asarray(rows), np.asarray(cols)
@@ -203,6 +275,9 @@ class Builder:
         c.wires = self.wires
         c.public_inputs = self.public_inputs
         c.circuit_digest = None     # filled by the prover library / the oracle (needs the constants+sigmas cap)
+        c.zero_knowledge = bool(getattr(cfg, "zero_knowledge", False))
+        if c.zero_knowledge and not getattr(self, "blinded", False):
+            raise ValueError("a zero_knowledge config needs the blinding rows: call blind() before build()")
         return c
 
 
@@ -367,7 +442,7 @@ def _fill_ext_rows(b, rows, t, p0, chain=True):
 
 
 def ext_gates_circuit(log_n, config=None, seed=11, num_challenges=2, public_inputs=(), pi_hash=None, gates=EXT_GATES,
-                      witness_seed=None):
+                      witness_seed=None, blinding_seed=None):
     """A recursion-shaped circuit of plonky2's extension-field gates, each at the widest instance the config fits
     (ext_gate_params), with satisfying witnesses and copy constraints between them:
     [PublicInput][Constant x2][unit ...][Noop x3 from 16 rows on], a unit being ArithmeticExtension, MulExtension,
@@ -376,12 +451,15 @@ def ext_gates_circuit(log_n, config=None, seed=11, num_challenges=2, public_inpu
     output feeds op i + 1; the second Reducing(Extension) row of a unit continues the first one's reduction (its old_acc is
     the first one's output and both share alpha), as plonky2's chunked `reduce` does.  2^3 .. 2^20 rows, both presets.
     witness_seed: draw the free wire values from their own seed -- the same circuit (gate constants, sigmas) with another
-    satisfying witness, as a batch of proofs of one circuit needs."""
+    satisfying witness, as a batch of proofs of one circuit needs.
+    With config.zero_knowledge the 2^log_n gate rows above are followed by the blinding rows (Builder.blind, values from OS entropy
+    unless blinding_seed is given) and the circuit grows to the degree blinding_counts asks for."""
     import copy
     cfg = copy.copy(config or Config.standard_recursion_config())
     cfg.num_challenges = num_challenges
-    b = Builder(cfg, log_n, seed)
-    n = b.n
+    zk = bool(getattr(cfg, "zero_knowledge", False))
+    b = Builder(cfg, zk_degree_bits(cfg, 1 << log_n, log_n) if zk else log_n, seed)
+    n = 1 << log_n                                             # gate rows (all of them without zero_knowledge)
     if witness_seed is not None:
         b.wires = gl.rand(np.random.default_rng(witness_seed), b.wires.shape)
     gates = tuple(gates)
@@ -439,6 +517,8 @@ def ext_gates_circuit(log_n, config=None, seed=11, num_challenges=2, public_inpu
         for src, dst in ((2, 2), (3, 3), (0, 4), (1, 5)):
             b.connect_pairs(r1, src, r2, dst)
         _fill_ext_rows(b, r2, t, par[t])
+    if zk:
+        b.blind(n, pi_row=0, seed=blinding_seed)
     return b.build()
 
 
@@ -677,15 +757,18 @@ def _fill_poseidon_row(b, row, inputs):
     return out
 
 
-def zkdsa_circuit(log_n=3, config=None, seed=5, private_key=None, message=None):
+def zkdsa_circuit(log_n=3, config=None, seed=5, private_key=None, message=None, blinding_seed=None):
     """The reference's simple-signature circuit [REF src/zkdsa/circuits/mod.rs:24-43,
     src/zkdsa/gadgets/signature/mod.rs:49-62]: public_key = H(sk || sk), signature = H(sk || msg) with
     `poseidon_two_to_one` [REF src/poseidon/gadgets/mod.rs:7-22]; public inputs = message, public_key,
     signature (12 elements), whose in-circuit hash (two more permutations) feeds the PublicInputGate.
     Rows: PublicInputGate, 4 x PoseidonGate, ConstantGate (zero), NoopGate padding -- 2^3 rows like
-    the real circuit; gate placement and wiring are this builder's, not plonky2's."""
+    the real circuit; gate placement and wiring are this builder's, not plonky2's.  With config.zero_knowledge
+    (Config.standard_recursion_zk_config, what [REF src/zkdsa/circuits/mod.rs:412] leaves as a TODO) the blinding rows follow
+    the 6 gate rows and the circuit grows to 2^14 rows (blinding_counts), and wires 4.. of the PublicInputGate row are redrawn
+    (`randomize_unused_pi_wires`); both from OS entropy unless blinding_seed is given (tests only)."""
     cfg = config or Config.standard_recursion_config()
-    b = Builder(cfg, log_n, seed)
+    b = Builder(cfg, zk_degree_bits(cfg, 6, log_n), seed)
     rng = b.rng
     sk = [int(x) for x in (gl.rand(rng, 4) if private_key is None else private_key)]
     msg = [int(x) for x in (gl.rand(rng, 4) if message is None else message)]
@@ -714,6 +797,8 @@ def zkdsa_circuit(log_n=3, config=None, seed=5, private_key=None, message=None):
         cyc([(3, 12 + i), (4, i)])                         # sponge state carried into the second absorb
     zeros = [(row_c, 0)] + [(r, 24) for r in rows_p] + [(r, 8 + i) for r in (1, 2, 3) for i in range(4)]
     cyc(zeros)                                             # constant zero: swap flags and capacity lanes
+    if cfg.zero_knowledge:
+        b.blind(6, pi_row=0, seed=blinding_seed)
     return b.build()
 
 
