@@ -1511,32 +1511,8 @@ int batch_cap_host(glp_ctx *c, const glp_batch *b, std::vector<u64> &cap) {
     cap.resize((size_t)4 << b->cap_height);
     return d2h(c, cap.data(), b->digests + 4 * merkle_cap_offset(N, b->cap_height), cap.size() * 8);
 }
-// evaluate every polynomial of a batch at z: launch only; partial sums land in dev_partial [ncols][OPEN_BLOCKS][2]
-int open_batch_launch(glp_ctx *c, const glp_batch *b, const u64 *dev_zt, u64 *dev_partial, u32 first_cols = 0 /* 0: all */) {
-    dim3 g(open_blocks((size_t)1 << b->lg), first_cols ? first_cols : b->ncols);
-    hipLaunchKernelGGL(k_open_dot, g, dim3(256), 0, c->stream, b->coeffs, dev_zt, dev_partial, (u32)b->lg, (size_t)0, (size_t)0, (size_t)0);
-    GLP_HIP(hipGetLastError());
-    return GLP_OK;
-}
-// host side of the same: fold the OPEN_BLOCKS partial sums of each column
-void open_batch_finish(const u64 *h, u32 ncols, u32 nob, std::vector<ext2> &out) {
-    out.resize(ncols);
-    for (u32 col = 0; col < ncols; col++) {
-        u64 a = 0, bb = 0;
-        for (u32 k = 0; k < nob; k++) { a = add(a, h[2 * ((size_t)col * nob + k)]); bb = add(bb, h[2 * ((size_t)col * nob + k) + 1]); }
-        out[col] = e_make(a, bb);
-    }
-}
-int zeta_table(glp_ctx *c, ext2 z, int lg, u64 *dev_zt) {
-    ZTArgs za;
-    za.zt = dev_zt; za.lg = (u32)lg; za.zeta_b = nullptr; za.zeta_stride = 0;
-    ext2 p = z;
-    for (int b = 0; b < 24; b++) { za.zp2[b] = p; p = e_sqr(p); }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_zeta_table<false>), dim3(nblk((size_t)1 << lg)), dim3(256), 0, c->stream, za);
-    GLP_HIP(hipGetLastError());
-    return GLP_OK;
-}
 }  // namespace
+#include "prover_stages.inc"
 
 // One proof in flight, cut at the points where the Fiat-Shamir transcript needs something from the device or the device
 // needs a challenge.  glp_prove() drives it with the built-in Challenger; the glp_session_* entry points hand the same
@@ -1546,10 +1522,7 @@ struct glp_session {
     const glp_circuit *cc;
     const glp_circuit_desc &d;
     const Layout &L;
-    const int lg, rb;
-    const size_t n, N;
-    const u32 nch, nr, nw, nc, qdf, npp, capn, nzp;
-    const int hasher;
+    const ProveGeo g;                  // K = 1
     Tmp tmp;
     u64 *owned_wires = nullptr;        // device copy made by begin() when the caller passed host memory
     const u64 *dev_wires = nullptr;
@@ -1557,29 +1530,26 @@ struct glp_session {
     u64 salt_seed[4] = {0, 0, 0, 0};   // zk circuit: the seed of this proof's salts (drawn in begin), else unused
     const u64 *salt = nullptr;         // salt_seed for a zk circuit, nullptr otherwise
     BatchHolder wb, zb, qb;
-    u64 betas[MAXCH] = {}, gammas[MAXCH] = {}, alphas[MAXCH] = {};
+    u64 betas[MAXCH] = {}, gammas[MAXCH] = {};
     ext2 zeta = {0, 0}, zeta_next = {0, 0};
     const glp_batch *ob[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<ext2> open[4], zs_next;
-    u64 *fcoef = nullptr;
-    struct Layer { u64 *vals; u64 *dig; u32 lgL, ab; };
-    std::vector<Layer> layers;
-    u64 *cur = nullptr;
-    int lgcur = 0;
-    u64 shift = GEN;
+    FriState fri;
     bool layer_open = false;           // a commit-phase layer has been committed and waits for its beta
     std::vector<u64> proof_words;      // the proof being assembled (glp_proof_words(circuit) words)
     std::vector<u64> cap;
     enum Stage { S_NEW, S_WIRES, S_ZS, S_QUOTIENT, S_OPEN, S_FRI, S_FINAL, S_DONE } stage = S_NEW;
 
-    glp_session(glp_ctx *ctx, const glp_circuit *circ)
-        : c(ctx), cc(circ), d(circ->d), L(circ->L), lg((int)circ->d.degree_bits), rb((int)circ->d.rate_bits),
-          n((size_t)1 << circ->d.degree_bits), N(((size_t)1 << circ->d.degree_bits) << circ->d.rate_bits),
-          nch(circ->d.num_challenges), nr(circ->d.num_routed_wires), nw(circ->d.num_wires), nc(circ->d.num_constants),
-          qdf(circ->d.quotient_degree_factor), npp(circ->d.num_partial_products), capn(1u << circ->d.cap_height),
-          nzp(circ->d.num_challenges * (1 + circ->d.num_partial_products)), hasher((int)circ->d.hasher), tmp(ctx) {}
+    glp_session(glp_ctx *ctx, const glp_circuit *circ) : c(ctx), cc(circ), d(circ->d), L(circ->L), g(prove_geo(circ, 1)), tmp(ctx) {}
     ~glp_session() { if (owned_wires) { (void)hipStreamSynchronize(c->stream); c->release(owned_wires); } }
     u64 *proof() { return proof_words.data(); }
+    // commits an oracle of this proof; its cap -> cap and the proof's cap slot `slot`
+    int commit(const u64 *dev_in, int kind, u32 ncols, BatchHolder &out, u32 tag, u32 slot, const u64 *host_src = nullptr) {
+        GLP_TRY(batch_build(c, dev_in, kind, ncols, g.lg, g.rb, g.cap_height, &out.b, host_src, 1, g.hasher, salt, tag));
+        GLP_TRY(batch_cap_host(c, out.b, cap));
+        memcpy(proof() + L.caps + (size_t)slot * g.capn * 4, cap.data(), g.capn * 32);
+        return GLP_OK;
+    }
 
     // K1-K4 over the witness; wires cap -> proof, cap
     // host_wires != nullptr: the witness is still in host memory and is uploaded into wires_dev chunk by chunk, overlapped
@@ -1591,163 +1561,55 @@ struct glp_session {
         if (cc->zk) { GLP_TRY(salt_seed_draw(c, salt_seed)); salt = salt_seed; }
         host_hash_no_pad(public_inputs, d.num_public_inputs, pih);
         if (d.num_public_inputs) memcpy(proof() + L.pis, public_inputs, (size_t)d.num_public_inputs * 8);
-        GLP_TRY(batch_build(c, dev_wires, BATCH_VALUES, nw, lg, rb, (int)d.cap_height, &wb.b, host_wires, 1, hasher, salt, GLP_SALT_TAG_WIRES));
-        GLP_TRY(batch_cap_host(c, wb.b, cap));
-        memcpy(proof() + L.caps, cap.data(), capn * 32);
+        GLP_TRY(commit(dev_wires, BATCH_VALUES, g.nw, wb, GLP_SALT_TAG_WIRES, 0, host_wires));
         stage = S_WIRES;
         return GLP_OK;
     }
     // K5 + commitment of Z and the partial products
     int partial_products(const u64 *betas_in, const u64 *gammas_in) {
         GLP_REQUIRE(stage == S_WIRES, "partial_products: call after begin");
-        for (u32 i = 0; i < nch; i++) { betas[i] = betas_in[i]; gammas[i] = gammas_in[i]; }
-        u64 *zp, *tot;
-        const u32 nblocks = nblk(n);
-        u64 *dens;
-        GLP_TRY(tmp.get(&zp, (size_t)nzp * n));
-        GLP_TRY(tmp.get(&dens, (size_t)nzp * n));
-        GLP_TRY(tmp.get(&tot, (size_t)nch * nblocks));
+        for (u32 i = 0; i < g.nch; i++) { betas[i] = betas_in[i]; gammas[i] = gammas_in[i]; }
+        u64 *zp, *dens, *tot;
+        GLP_TRY(tmp.get(&zp, (size_t)g.nzp * g.n));
+        GLP_TRY(tmp.get(&dens, (size_t)g.nzp * g.n));
+        GLP_TRY(tmp.get(&tot, (size_t)g.nch * nblk(g.n)));
         {
-            StageScope st(c, "partial_products", 8.0 * n * (2.0 * nr + nzp));
-            PPArgs a;
-            a.wires = dev_wires; a.sigmas = cc->dev_sigmas; a.k_is = cc->dev_k_is; a.zp = zp; a.dens = dens;
-            for (u32 i = 0; i < nch; i++) { a.betas[i] = betas[i]; a.gammas[i] = gammas[i]; }
-            a.w_n = root_of_unity(lg); a.lg = (u32)lg; a.nr = nr; a.nch = nch; a.npp = npp; a.qdf = qdf;
-            a.chal = nullptr; a.wires_stride = 0; a.zp_stride = 0;
-            const size_t small_lds = (size_t)2 * nch * (npp + 2) * n * sizeof(u64);       // k_pp_rows_small: chunk products, row products and running products of one proof in LDS
-            const bool small = lg <= 7 && small_lds <= 64 * 1024;
-            if (small) hipLaunchKernelGGL(k_pp_rows_small, dim3(1, 1), dim3(256), small_lds, c->stream, a);      // rows AND the running product over them
-            else switch (nch) {
-            case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pp_rows<1>), dim3(nblocks), dim3(256), 0, c->stream, a); break;
-            case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pp_rows<2>), dim3(nblocks), dim3(256), 0, c->stream, a); break;
-            case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pp_rows<3>), dim3(nblocks), dim3(256), 0, c->stream, a); break;
-            default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pp_rows<4>), dim3(nblocks), dim3(256), 0, c->stream, a); break;
-            }
-            GLP_HIP(hipGetLastError());
-            if (!small) {
-                hipLaunchKernelGGL(k_pp_block_tot, dim3(nblocks, nch), dim3(256), 0, c->stream, zp, tot, (u32)lg, nblocks, (size_t)0);
-                hipLaunchKernelGGL(k_pp_scan_tot, dim3(nch), dim3(256), 0, c->stream, tot, nblocks);
-                hipLaunchKernelGGL(k_pp_apply, dim3(nblocks, nch), dim3(256), 0, c->stream, zp, tot, (u32)lg, nblocks, nch, npp, (size_t)0);
-                GLP_HIP(hipGetLastError());
-            }
+            StageScope st(c, "partial_products", 8.0 * g.n * (2.0 * g.nr + g.nzp));
+            GLP_TRY(stage_partial_products(c, g, dev_wires, betas, gammas, nullptr, zp, dens, tot));
         }
-        GLP_TRY(batch_build(c, zp, BATCH_VALUES, nzp, lg, rb, (int)d.cap_height, &zb.b, nullptr, 1, hasher, salt, GLP_SALT_TAG_ZS));
-        GLP_TRY(batch_cap_host(c, zb.b, cap));
-        memcpy(proof() + L.caps + capn * 4, cap.data(), capn * 32);
+        GLP_TRY(commit(zp, BATCH_VALUES, g.nzp, zb, GLP_SALT_TAG_ZS, 1));
         stage = S_ZS;
         return GLP_OK;
     }
     // K6 + commitment of the quotient chunks
-    int quotient(const u64 *alphas_in) {
+    int quotient(const u64 *alphas) {
         GLP_REQUIRE(stage == S_ZS, "quotient: call after partial_products");
-        for (u32 i = 0; i < nch; i++) alphas[i] = alphas_in[i];
-        int qdb = 0;
-        while ((1u << qdb) < qdf) qdb++;
-        const u32 Rq = 1u << qdb, step = 1u << (rb - qdb);
-        const u32 nchunks = npp + 1, nterms = nch + nch * nchunks + d.num_gate_constraints;
-        // alpha powers twice: whole (permutation terms) and as 22-bit limbs of m and m 2^32 (gate constraints, AccHL): [1 + APL_WORDS][nch * nterms] words
-        std::vector<u64> apow((size_t)(1 + APL_WORDS) * nch * nterms);
-        for (u32 i = 0; i < nch; i++) {
-            u64 x = 1;
-            for (u32 k = 0; k < nterms; k++) {
-                const size_t e = (size_t)i * nterms + k;
-                apow[e] = x;
-                apl_words(x, &apow[(size_t)nch * nterms + APL_WORDS * e]);
-                x = mul(x, alphas[i]);
-            }
-        }
+        const u32 nch = g.nch;
+        const size_t apn = (size_t)nch * g.nterms, qlen = (size_t)nch * g.Rq * g.n;
+        std::vector<u64> apow((1 + APL_WORDS) * apn);
+        alpha_power_table(alphas, nch, g.nterms, apow.data(), apow.data() + apn);
         u64 *dev_apow, *qv, *qV, *qc;
         GLP_TRY(tmp.get(&dev_apow, apow.size()));
         GLP_TRY(h2d(c, dev_apow, apow.data(), apow.size() * 8));
-        GLP_TRY(tmp.get(&qv, (size_t)nch * Rq * n));
-        GLP_TRY(tmp.get(&qV, (size_t)nch * Rq * n));
-        GLP_TRY(tmp.get(&qc, (size_t)nch * Rq * n));
-        QArgs a;
+        GLP_TRY(tmp.get(&qv, qlen));
+        GLP_TRY(tmp.get(&qV, qlen));
+        GLP_TRY(tmp.get(&qc, qlen));
         QProof qp;
         QBatch qbt;
-        memset(&qp, 0, sizeof(qp));
-        memset(&qbt, 0, sizeof(qbt));                    // pp == nullptr: one proof, described by qp
-        a.cs = cc->cs->lde; qp.wl = wb.b->lde; qp.zl = zb.b->lde; qp.out = qv;
-        a.gates = cc->dev_gates; a.k_is = cc->dev_k_is; qp.apow = dev_apow; qp.apl = dev_apow + (size_t)nch * nterms; a.k_ratio = cc->k_ratio;
+        quotient_proof_args(g, wb.b, zb.b, qv, dev_apow, nullptr, qp, qbt);      // pp == nullptr: one proof, described by qp
         for (u32 i = 0; i < nch; i++) { qp.betas[i] = betas[i]; qp.gammas[i] = gammas[i]; }
         memcpy(qp.pih, pih, 32);
-        const u64 WN = root_of_unity(lg + rb), gn = pow(GEN, (u64)n), wR = root_of_unity(rb);
-        for (u32 rq = 0; rq < Rq; rq++) {
-            const u32 r = rq * step;
-            a.shift_r[rq] = mul(GEN, pow(WN, (u64)r));
-            a.zh[rq] = sub(mul(gn, pow(wR, (u64)r)), 1);      // Z_H(g W^(qR + r)) = g^n w_R^r - 1
-            a.zh_inv[rq] = inv(a.zh[rq]);
-        }
-        a.w_n = root_of_unity(lg); a.n_field = (u64)n % P;
-        a.lg = (u32)lg; a.rb = (u32)rb; a.step = step; a.nc = nc; a.nsel = d.num_selectors; a.nr = nr; a.nw = nw;
-        a.nch = nch; a.npp = npp; a.qdf = qdf; a.num_gates = d.num_gates; a.nterms = nterms;
-        a.many_selectors = d.num_selectors > 1;
         {
-            StageScope st(c, "quotient_eval", 8.0 * n * Rq * (nc + nr + nw + nzp + 2.0 * nch));
-            // two challenges (every preset the reference uses): permutation terms in one launch, then one launch per
-            // gate type compiled on its own; other challenge counts take the monolithic kernel
-            a.gate_mode = nch == 2 ? 1 : 0;
+            StageScope st(c, "quotient_eval", 8.0 * g.n * g.Rq * (g.nc + g.nr + g.nw + g.nzp + 2.0 * nch));
             u64 *l0t;
-            GLP_TRY(tmp.get(&l0t, (size_t)Rq * n));
-            a.l0 = l0t;
-            hipLaunchKernelGGL(k_l0_table, dim3(nblk(n)), dim3(256), 0, c->stream, a, l0t, Rq);
-            GLP_HIP(hipGetLastError());
-            LightArgs lg_;
-            lg_.count = cc->light_count; lg_.arith_gi = cc->arith_gi; lg_.arith_ops = cc->arith_ops;
-            for (u32 i = 0; i < 8; i++) lg_.gi[i] = cc->light_gi[i];
-            switch (nch) {
-            case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient<1, 1>), dim3(nblk(n), Rq), dim3(256), 0, c->stream, a, qp, qbt, lg_); break;
-            case 2:
-                if (cc->light_count || cc->arith_ops) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient<2, 2>), dim3(nblk(n), Rq), dim3(256), 0, c->stream, a, qp, qbt, lg_);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient<2, 0>), dim3(nblk(n), Rq), dim3(256), 0, c->stream, a, qp, qbt, lg_);
-                break;
-            case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient<3, 1>), dim3(nblk(n), Rq), dim3(256), 0, c->stream, a, qp, qbt, lg_); break;
-            default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient<4, 1>), dim3(nblk(n), Rq), dim3(256), 0, c->stream, a, qp, qbt, lg_); break;
-            }
-            GLP_HIP(hipGetLastError());
-            if (a.gate_mode == 1) {
-                if (cc->limb_count) {
-                    LimbArgs la;
-                    limb_args(cc, la);
-                    la.extra_count = cc->limb_extra_count;
-                    for (int i = 0; i < 4; i++) la.extra_gi[i] = cc->limb_extra_gi[i];
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient_limbs<2>), dim3(nblk(n), Rq), dim3(256), 0, c->stream, a, qp, qbt, la);
-                    GLP_HIP(hipGetLastError());
-                }
-                for (u32 gi : cc->single_gates) {
-#define GLP_GATE_LAUNCH(T) case T: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient_gate<2, T>), dim3(nblk(n), Rq), dim3(256), 0, c->stream, a, qp, qbt, gi); break;
-                    switch (cc->gates[gi].type) {
-                        GLP_GATE_LAUNCH(GLP_GATE_CONSTANT) GLP_GATE_LAUNCH(GLP_GATE_PUBLIC_INPUT) GLP_GATE_LAUNCH(GLP_GATE_ARITHMETIC)
-                        GLP_GATE_LAUNCH(GLP_GATE_POSEIDON) GLP_GATE_LAUNCH(GLP_GATE_U32_INTERLEAVE) GLP_GATE_LAUNCH(GLP_GATE_UNINTERLEAVE_U32)
-                        GLP_GATE_LAUNCH(GLP_GATE_UNINTERLEAVE_B32) GLP_GATE_LAUNCH(GLP_GATE_U32_ARITHMETIC) GLP_GATE_LAUNCH(GLP_GATE_U32_ADD_MANY)
-                        GLP_GATE_LAUNCH(GLP_GATE_U32_SUBTRACTION) GLP_GATE_LAUNCH(GLP_GATE_U32_RANGE_CHECK) GLP_GATE_LAUNCH(GLP_GATE_COMPARISON)
-                        GLP_GATE_LAUNCH(GLP_GATE_BASE_SUM) GLP_GATE_LAUNCH(GLP_GATE_RANDOM_ACCESS)
-                        GLP_GATE_LAUNCH(GLP_GATE_ARITHMETIC_EXTENSION) GLP_GATE_LAUNCH(GLP_GATE_MUL_EXTENSION)
-                        GLP_GATE_LAUNCH(GLP_GATE_REDUCING) GLP_GATE_LAUNCH(GLP_GATE_REDUCING_EXTENSION)
-                    default: break;   // NoopGate: no constraints
-                    }
-#undef GLP_GATE_LAUNCH
-                    GLP_HIP(hipGetLastError());
-                }
-            }
-            GLP_HIP(hipGetLastError());
+            GLP_TRY(tmp.get(&l0t, (size_t)g.Rq * g.n));
+            GLP_TRY(stage_quotient_eval(c, g, qp, qbt, l0t));
         }
         {
-            StageScope st(c, "quotient_intt", 16.0 * n * Rq * nch);
-            GLP_TRY(intt_values_to_coeffs(c, qv, qV, nch * Rq, lg));
-            QCArgs q;
-            q.V = qV; q.out = qc; q.lg = (u32)lg; q.Rq = Rq;
-            q.wM_inv = inv(root_of_unity(lg + qdb)); q.wR_inv = inv(root_of_unity(qdb)); q.g_inv = inv(GEN);
-            q.rq_inv = inv((u64)Rq);
-            const u64 gni = inv(gn);
-            u64 x = 1;
-            for (u32 cidx = 0; cidx < Rq; cidx++) { q.gn_inv_pow[cidx] = x; x = mul(x, gni); }
-            hipLaunchKernelGGL(k_quotient_combine, dim3(nblk(n), nch), dim3(256), 0, c->stream, q);
-            GLP_HIP(hipGetLastError());
+            StageScope st(c, "quotient_intt", 16.0 * g.n * g.Rq * nch);
+            GLP_TRY(stage_quotient_coeffs(c, g, qv, qV, qc));
         }
-        GLP_TRY(batch_build(c, qc, BATCH_COEFFS_BITREV, nch * qdf, lg, rb, (int)d.cap_height, &qb.b, nullptr, 1, hasher, salt, GLP_SALT_TAG_QUOTIENT));
-        GLP_TRY(batch_cap_host(c, qb.b, cap));
-        memcpy(proof() + L.caps + 2 * capn * 4, cap.data(), capn * 32);
+        GLP_TRY(commit(qc, BATCH_COEFFS_BITREV, nch * g.qdf, qb, GLP_SALT_TAG_QUOTIENT, 2));
         stage = S_QUOTIENT;
         return GLP_OK;
     }
@@ -1757,118 +1619,54 @@ struct glp_session {
         zeta = zeta_in;
         {
             ext2 zp = zeta;
-            for (int i = 0; i < lg; i++) zp = e_sqr(zp);
+            for (int i = 0; i < g.lg; i++) zp = e_sqr(zp);
             if (e_eq(zp, e_from(1))) return set_error(GLP_ERR_PROVE, "Opening point is in the subgroup.");
         }
-        zeta_next = e_scale(zeta, root_of_unity(lg));
+        zeta_next = e_scale(zeta, root_of_unity(g.lg));
         ob[0] = cc->cs; ob[1] = wb.b; ob[2] = zb.b; ob[3] = qb.b;
-        {
-        StageScope st(c, "openings", 8.0 * n * (L.oracle_cols[0] + L.oracle_cols[1] + L.oracle_cols[2] + L.oracle_cols[3] + nch));
+        StageScope st(c, "openings", 8.0 * g.n * (L.oracle_cols[0] + L.oracle_cols[1] + L.oracle_cols[2] + L.oracle_cols[3] + g.nch));
         // five evaluations (four batches at zeta, the Z batch at g zeta) queued back to back, one copy back
         u64 *zt, *partial;
-        GLP_TRY(tmp.get(&zt, 2 * n));
-        const u32 nob = open_blocks(n);
-        size_t poff[6] = {0, 0, 0, 0, 0, 0};
-        for (int k = 0; k < 5; k++) poff[k + 1] = poff[k] + (size_t)(k < 4 ? ob[k]->ncols : nch) * nob * 2;    // at g zeta: only the Z columns
+        size_t poff[6];
+        open_offsets(g, ob, poff);
+        GLP_TRY(tmp.get(&zt, 2 * g.n));
         GLP_TRY(tmp.get(&partial, poff[5]));
-        GLP_TRY(zeta_table(c, zeta, lg, zt));
-        for (int k = 0; k < 4; k++) GLP_TRY(open_batch_launch(c, ob[k], zt, partial + poff[k]));
-        GLP_TRY(zeta_table(c, zeta_next, lg, zt));
-        GLP_TRY(open_batch_launch(c, zb.b, zt, partial + poff[4], nch));
+        const ext2 points[2] = {zeta, zeta_next};
+        GLP_TRY(stage_open(c, g, ob, points, nullptr, zt, partial, poff));
         std::vector<u64> hp(poff[5]);
         GLP_TRY(d2h(c, hp.data(), partial, hp.size() * 8));
-        for (int k = 0; k < 4; k++) open_batch_finish(hp.data() + poff[k], ob[k]->ncols, nob, open[k]);
-        std::vector<ext2> all;
-        open_batch_finish(hp.data() + poff[4], nch, nob, all);
-        zs_next.assign(all.begin(), all.begin() + nch);
-    }
-        {
-            u64 *op = proof() + L.openings;
-            size_t o = 0;
-            auto put = [&](ext2 e) { op[o++] = e.a; op[o++] = e.b; };
-            for (u32 k = 0; k < nc + nr; k++) put(open[0][k]);
-            for (u32 k = 0; k < nw; k++) put(open[1][k]);
-            for (u32 k = 0; k < nch; k++) put(open[2][k]);
-            for (u32 k = 0; k < nch; k++) put(zs_next[k]);
-            for (u32 k = 0; k < nch * npp; k++) put(open[2][nch + k]);
-            for (u32 k = 0; k < nch * qdf; k++) put(open[3][k]);
-        }
+        openings_to_proof(g, ob, hp.data(), poff, open, zs_next, proof() + L.openings);
         stage = S_OPEN;
         return GLP_OK;
     }
     // K8: alpha-combination of all openings batches, quotient by (X - zeta) / (X - g zeta) -> FRI polynomial
     int fri_combine(ext2 alpha) {
         GLP_REQUIRE(stage == S_OPEN, "fri_combine: call after open");
-        GLP_TRY(tmp.get(&fcoef, 2 * n));
-    {
-        StageScope st(c, "fri_combine", 8.0 * n * (L.oracle_cols[0] + L.oracle_cols[1] + L.oracle_cols[2] + L.oracle_cols[3]));
-        size_t total_cols = 0;
-        for (int k = 0; k < 4; k++) total_cols += ob[k]->ncols;
-        std::vector<u64> ap(2 * total_cols);
-        ext2 x = e_from(1), red0 = e_from(0), red1 = e_from(0);
-        size_t j = 0;
-        for (int k = 0; k < 4; k++)
-            for (u32 col = 0; col < ob[k]->ncols; col++, j++) {
-                ap[2 * j] = x.a; ap[2 * j + 1] = x.b;
-                red0 = e_add(red0, e_mul(x, open[k][col]));
-                x = e_mul(x, alpha);
-            }
-        x = e_from(1);
-        for (u32 col = 0; col < nch; col++) { red1 = e_add(red1, e_mul(x, zs_next[col])); x = e_mul(x, alpha); }
-        u64 *dev_ap, *fv;
-        GLP_TRY(tmp.get(&dev_ap, ap.size()));
-        GLP_TRY(h2d(c, dev_ap, ap.data(), ap.size() * 8));
-        GLP_TRY(tmp.get(&fv, 2 * n));
-        FVArgs a;
-        for (int k = 0; k < 4; k++) { a.lde[k] = ob[k]->lde; a.ncols[k] = ob[k]->ncols; }
-        a.apow = dev_ap; a.out = fv; a.red0 = red0; a.red1 = red1; a.zeta = zeta; a.zeta_next = zeta_next;
-        a.shift_acc = e_pow(alpha, nch);
-        a.w_n = root_of_unity(lg); a.g = GEN; a.lg = (u32)lg; a.rb = (u32)rb; a.nch = nch;
-        a.pp = nullptr; a.apow_stride = a.out_stride = 0;
-        for (int k = 0; k < 4; k++) a.lde_stride[k] = 0;
-        if (lg >= 2 && lg <= 7) hipLaunchKernelGGL(k_final_values_small, dim3(1, 1), dim3(256), 0, c->stream, a);      // 4..128 points: 256 / n lanes per point
-        else hipLaunchKernelGGL(k_final_values, dim3(nblk(n)), dim3(256), 0, c->stream, a);
-        GLP_HIP(hipGetLastError());
-        GLP_TRY(intt_values_to_coeffs(c, fv, fcoef, 2, lg));
-        hipLaunchKernelGGL(k_scale_bitrev_pow, dim3(nblk(n), 2), dim3(256), 0, c->stream, fcoef, inv(GEN), (u32)lg);
-        GLP_HIP(hipGetLastError());
-    }
-
-        cur = fcoef; lgcur = lg; shift = GEN;
+        u64 *fcoef, *dev_ap, *fv;
+        GLP_TRY(tmp.get(&fcoef, 2 * g.n));
+        {
+            StageScope st(c, "fri_combine", 8.0 * g.n * (L.oracle_cols[0] + L.oracle_cols[1] + L.oracle_cols[2] + L.oracle_cols[3]));
+            std::vector<u64> ap(2 * oracle_cols(ob));
+            ext2 pt[5];
+            fri_alpha_powers(g, ob, open, zs_next, alpha, zeta, zeta_next, ap.data(), pt);
+            GLP_TRY(tmp.get(&dev_ap, ap.size()));
+            GLP_TRY(h2d(c, dev_ap, ap.data(), ap.size() * 8));
+            GLP_TRY(tmp.get(&fv, 2 * g.n));
+            GLP_TRY(stage_fri_values(c, g, ob, dev_ap, pt, nullptr, fv, fcoef));
+        }
+        fri.start(fcoef, g.lg);
         stage = S_FRI;
         return GLP_OK;
     }
     // K9, first half: LDE of the current polynomial on its coset, Merkle tree over arity-sized leaves; cap -> proof, cap
     int fri_commit_layer() {
-        GLP_REQUIRE(stage == S_FRI && !layer_open && layers.size() < d.num_reductions, "fri_commit: no layer left or beta pending");
+        GLP_REQUIRE(stage == S_FRI && !layer_open && fri.layers.size() < d.num_reductions, "fri_commit: no layer left or beta pending");
         StageScope st(c, "fri_commit", 0.0);
-        const u32 r = (u32)layers.size();
-        const u32 ab = d.reduction_arity_bits[r];
-        const u32 lgL = (u32)(lgcur + rb);
-        const size_t Lsz = (size_t)1 << lgL, nleaves = Lsz >> ab;
-        Layer ly;
-        ly.lgL = lgL; ly.ab = ab;
-        GLP_TRY(tmp.get(&ly.vals, 2 * Lsz));
-        GLP_TRY(tmp.get(&ly.dig, merkle_num_digests(nleaves, (int)d.cap_height) * 4));
-        GLP_TRY(lde_coeffs(c, cur, ly.vals, 2, lgcur, rb, shift));
-        if (hasher == GLP_HASH_KECCAK25)
-            hipLaunchKernelGGL(k_fri_leaf_hash_keccak, dim3(nblk(nleaves)), dim3(256), 0, c->stream, ly.vals, ly.dig, lgL, (u32)rb, ab, (size_t)0,
-                               (size_t)0);
-        else if (nleaves <= c->merkle_coop_max)
-            hipLaunchKernelGGL(k_fri_leaf_hash_coop, dim3((unsigned)((nleaves + 15) / 16)), dim3(256), 0, c->stream, ly.vals, ly.dig, lgL,
-                               (u32)rb, ab, (size_t)0, (size_t)0);
-        else if (nleaves <= c->merkle_quad_max)
-            hipLaunchKernelGGL(k_fri_leaf_hash_quad, dim3((unsigned)((nleaves + 63) / 64)), dim3(256), 0, c->stream, ly.vals, ly.dig, lgL,
-                               (u32)rb, ab, (size_t)0, (size_t)0);
-        else
-            hipLaunchKernelGGL(k_fri_leaf_hash, dim3(nblk(nleaves)), dim3(256), 0, c->stream, ly.vals, ly.dig, lgL, (u32)rb, ab, (size_t)0,
-                               (size_t)0);
-        GLP_HIP(hipGetLastError());
-        GLP_TRY(merkle_levels(c, ly.dig, nleaves, (int)d.cap_height, 1, 0, hasher));
-        cap.resize((size_t)capn * 4);
-        GLP_TRY(d2h(c, cap.data(), ly.dig + 4 * merkle_cap_offset(nleaves, (int)d.cap_height), (size_t)capn * 32));
-        memcpy(proof() + L.fri_caps + (size_t)r * capn * 4, cap.data(), (size_t)capn * 32);
-        layers.push_back(ly);
+        const size_t r = fri.layers.size();
+        GLP_TRY(stage_fri_commit(c, g, tmp, fri));
+        cap.resize((size_t)g.capn * 4);
+        GLP_TRY(d2h(c, cap.data(), fri_layer_cap(g, fri.layers.back()), (size_t)g.capn * 32));
+        memcpy(proof() + L.fri_caps + r * g.capn * 4, cap.data(), (size_t)g.capn * 32);
         layer_open = true;
         return GLP_OK;
     }
@@ -1876,26 +1674,19 @@ struct glp_session {
     int fri_fold(ext2 beta) {
         GLP_REQUIRE(stage == S_FRI && layer_open, "fri_fold: call after fri_commit");
         StageScope st(c, "fri_commit", 0.0);
-        const u32 ab = layers.back().ab;
-        u64 *nxt;
-        const size_t nnew = ((size_t)1 << lgcur) >> ab;
-        GLP_TRY(tmp.get(&nxt, 2 * nnew));
-        hipLaunchKernelGGL(k_fri_fold, dim3(nblk(nnew)), dim3(256), 0, c->stream, cur, nxt, beta, (u32)lgcur, ab, (const u64 *)nullptr);
-        GLP_HIP(hipGetLastError());
-        cur = nxt; lgcur -= (int)ab;
-        shift = pow(shift, (u64)1 << ab);
+        GLP_TRY(stage_fri_fold(c, g, tmp, fri, beta, nullptr));
         layer_open = false;
         return GLP_OK;
     }
     // final polynomial (natural coefficient order) -> proof
     int fri_final_poly() {
-        GLP_REQUIRE(stage == S_FRI && !layer_open && layers.size() == d.num_reductions, "fri_final_poly: reductions not finished");
-        const size_t fl = (size_t)1 << lgcur;
+        GLP_REQUIRE(stage == S_FRI && !layer_open && fri.layers.size() == d.num_reductions, "fri_final_poly: reductions not finished");
+        const size_t fl = (size_t)1 << fri.lgcur;
         if (fl != L.final_len) return set_error(GLP_ERR_ARG, "reduction_arity_bits inconsistent with degree_bits");
         std::vector<u64> h(2 * fl);
-        GLP_TRY(d2h(c, h.data(), cur, h.size() * 8));
+        GLP_TRY(d2h(c, h.data(), fri.cur, h.size() * 8));
         for (size_t p = 0; p < fl; p++) {
-            const size_t k = bitrev32((u32)p, lgcur);
+            const size_t k = bitrev32((u32)p, fri.lgcur);
             proof()[L.final_poly + 2 * k] = h[p];
             proof()[L.final_poly + 2 * k + 1] = h[fl + p];
         }
@@ -1909,36 +1700,15 @@ struct glp_session {
         proof()[L.pow] = pow_witness;
         StageScope st(c, "fri_queries", 0.0);
         std::vector<u64> xi(indices, indices + nq);
-        for (u32 q = 0; q < nq; q++) GLP_REQUIRE(xi[q] < (u64)N, "query index %llu outside the LDE domain", (unsigned long long)xi[q]);
+        for (u32 q = 0; q < nq; q++) GLP_REQUIRE(xi[q] < (u64)g.N, "query index %llu outside the LDE domain", (unsigned long long)xi[q]);
         // every gather writes straight into a device image of the proof's query section; one copy brings it back
         u64 *dev_idx, *dev_q;
-        const size_t stride = L.query_stride;
+        const size_t qsec = (size_t)nq * L.query_stride;
         GLP_TRY(tmp.get(&dev_idx, nq));
-        GLP_TRY(tmp.get(&dev_q, (size_t)nq * stride));
+        GLP_TRY(tmp.get(&dev_q, qsec));
         GLP_TRY(h2d(c, dev_idx, xi.data(), nq * 8));
-        size_t off = 0;   // word offset inside one query record
-        for (int k = 0; k < 4; k++) {
-            const u32 ncol = ob[k]->ncols + ob[k]->salt;     // the whole leaf: salts ride after the polynomial values
-            GLP_TRY(merkle_gather_lde_rows(c, ob[k]->lde, ncol, lg, rb, dev_idx, nq, dev_q + off, stride));
-            off += ncol;
-            GLP_TRY(merkle_gather_paths(c, ob[k]->digests, N, (int)d.cap_height, dev_idx, nq, dev_q + off, stride, 0));
-            off += 4 * (size_t)L.depth0;
-        }
-        u32 shift_bits = 0;
-        for (size_t r = 0; r < layers.size(); r++) {
-            const Layer &ly = layers[r];
-            const u32 arity = 1u << ly.ab;
-            const size_t nleaves = ((size_t)1 << ly.lgL) >> ly.ab;
-            shift_bits += ly.ab;
-            hipLaunchKernelGGL(k_fri_gather_leaf, dim3(nblk((size_t)nq * arity)), dim3(256), 0, c->stream, ly.vals, ly.lgL, (u32)rb,
-                               ly.ab, dev_idx, shift_bits, nq, dev_q + off, stride, (size_t)0, (size_t)0);
-            GLP_HIP(hipGetLastError());
-            off += 2 * (size_t)arity;
-            GLP_TRY(merkle_gather_paths(c, ly.dig, nleaves, (int)d.cap_height, dev_idx, nq, dev_q + off, stride, shift_bits));
-            off += 4 * (size_t)L.step_depth[r];
-        }
-        if (off != stride) return set_error(GLP_ERR_ARG, "internal: query record layout mismatch");
-        GLP_TRY(d2h(c, proof() + L.queries, dev_q, (size_t)nq * stride * 8));
+        GLP_TRY(stage_queries(c, g, ob, fri.layers, dev_idx, dev_q, L.query_stride, qsec));
+        GLP_TRY(d2h(c, proof() + L.queries, dev_q, qsec * 8));
         stage = S_DONE;
         return GLP_OK;
     }
@@ -1983,7 +1753,7 @@ static int prove_impl(glp_ctx *c, const glp_circuit *cc, const u64 *dev_wires, c
     glp_session s(c, cc);
     const glp_circuit_desc &d = cc->d;
     const Layout &L = cc->L;
-    const u32 nch = s.nch, nr = s.nr, nw = s.nw, nc = s.nc, qdf = s.qdf, npp = s.npp, capn = s.capn;
+    const u32 nch = s.g.nch, capn = s.g.capn;
     GLP_TRY(s.begin(dev_wires, public_inputs, host_wires));
     Challenger ch((int)d.hasher);
     ch.observe_hashes(cc->digest, 1);
@@ -1998,13 +1768,7 @@ static int prove_impl(glp_ctx *c, const glp_circuit *cc, const u64 *dev_wires, c
     GLP_TRY(s.quotient(alphas));
     ch.observe_hashes(s.cap.data(), capn);
     GLP_TRY(s.open_at(ch.get_ext()));
-    {
-        const u64 *op = s.proof() + L.openings;
-        const u64 *p_cs = op, *p_w = op + 2 * (nc + nr), *p_zs = p_w + 2 * nw, *p_zn = p_zs + 2 * nch;
-        const u64 *p_pp = p_zn + 2 * nch, *p_q = p_pp + 2 * nch * npp;
-        ch.observe(p_cs, 2 * (nc + nr)); ch.observe(p_w, 2 * nw); ch.observe(p_zs, 2 * nch);
-        ch.observe(p_pp, 2 * (size_t)nch * npp); ch.observe(p_q, 2 * (size_t)nch * qdf); ch.observe(p_zn, 2 * nch);
-    }
+    observe_openings(ch, s.g, s.proof() + L.openings);
     GLP_TRY(s.fri_combine(ch.get_ext()));
     for (u32 r = 0; r < d.num_reductions; r++) {
         GLP_TRY(s.fri_commit_layer());
@@ -2020,7 +1784,7 @@ static int prove_impl(glp_ctx *c, const glp_circuit *cc, const u64 *dev_wires, c
     if (d.proof_of_work_bits && (resp >> (64 - d.proof_of_work_bits)) != 0)
         return set_error(GLP_ERR_PROVE, "proof-of-work response check failed");
     std::vector<u64> xi(d.num_query_rounds);
-    for (u32 q = 0; q < d.num_query_rounds; q++) xi[q] = ch.get() % (u64)s.N;
+    for (u32 q = 0; q < d.num_query_rounds; q++) xi[q] = ch.get() % (u64)s.g.N;
     GLP_TRY(s.queries(found, xi.data(), d.num_query_rounds));
     memcpy(proof, s.proof(), L.total * 8);
     return GLP_OK;
@@ -2432,7 +2196,7 @@ int glp_session_begin(glp_ctx *c, const glp_circuit *cc, const uint64_t *wires, 
         dw = s->owned_wires;
     }
     GLP_TRY(s->begin(dw, public_inputs, wires_on_device ? nullptr : wires));
-    memcpy(wires_cap_out, s->cap.data(), (size_t)s->capn * 32);
+    memcpy(wires_cap_out, s->cap.data(), (size_t)s->g.capn * 32);
     memcpy(public_inputs_hash_out, s->pih, 32);
     *out = s.release();
     return GLP_OK;
@@ -2443,17 +2207,17 @@ int glp_session_begin(glp_ctx *c, const glp_circuit *cc, const uint64_t *wires, 
 int glp_session_partial_products(glp_session *s, const uint64_t *betas, const uint64_t *gammas, uint64_t *zs_cap_out) {
     GLP_SESSION_ENTER(s);
     GLP_REQUIRE(betas && gammas && zs_cap_out, "null argument");
-    for (u32 i = 0; i < s->nch; i++) GLP_REQUIRE(betas[i] < P && gammas[i] < P, "challenge %u is not a canonical field element", i);
+    for (u32 i = 0; i < s->g.nch; i++) GLP_REQUIRE(betas[i] < P && gammas[i] < P, "challenge %u is not a canonical field element", i);
     GLP_TRY(s->partial_products(betas, gammas));
-    memcpy(zs_cap_out, s->cap.data(), (size_t)s->capn * 32);
+    memcpy(zs_cap_out, s->cap.data(), (size_t)s->g.capn * 32);
     return GLP_OK;
 }
 int glp_session_quotient(glp_session *s, const uint64_t *alphas, uint64_t *quotient_cap_out) {
     GLP_SESSION_ENTER(s);
     GLP_REQUIRE(alphas && quotient_cap_out, "null argument");
-    for (u32 i = 0; i < s->nch; i++) GLP_REQUIRE(alphas[i] < P, "challenge %u is not a canonical field element", i);
+    for (u32 i = 0; i < s->g.nch; i++) GLP_REQUIRE(alphas[i] < P, "challenge %u is not a canonical field element", i);
     GLP_TRY(s->quotient(alphas));
-    memcpy(quotient_cap_out, s->cap.data(), (size_t)s->capn * 32);
+    memcpy(quotient_cap_out, s->cap.data(), (size_t)s->g.capn * 32);
     return GLP_OK;
 }
 size_t glp_num_openings(const glp_circuit *cc) { return cc ? cc->L.nopen : 0; }
@@ -2475,7 +2239,7 @@ int glp_session_fri_commit(glp_session *s, uint64_t *cap_out) {
     GLP_SESSION_ENTER(s);
     GLP_REQUIRE(cap_out, "null argument");
     GLP_TRY(s->fri_commit_layer());
-    memcpy(cap_out, s->cap.data(), (size_t)s->capn * 32);
+    memcpy(cap_out, s->cap.data(), (size_t)s->g.capn * 32);
     return GLP_OK;
 }
 int glp_session_fri_fold(glp_session *s, const uint64_t beta[2]) {
@@ -2614,6 +2378,5 @@ int glp_prove_staged(glp_ctx *c, const glp_circuit *cc, glp_witness *w, const ui
 }
 }  // extern "C"
 
-#include <stdlib.h>
 #include "prover_batch.inc"
 #include "prover_batch_dev.inc"

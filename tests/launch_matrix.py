@@ -12,7 +12,7 @@ import plonky2_lib_amd.synth as synth
 
 LIMB_SLOTS, LIMB_GROUPS = 5, 4            # prover.hip: constexpr int LIMB_SLOTS = 5, LIMB_GROUPS = 4
 LIGHT_MAX, EXTRA_MAX = 8, 4               # prover.hip: LightArgs::gi[8], LimbArgs::extra_gi[4]
-PP_SMALL_LDS = 64 * 1024                  # prover.hip partial_products(): small_lds <= 64 KiB
+PP_SMALL_LDS = 64 * 1024                  # prover_stages.inc stage_partial_products(): small_lds <= 64 KiB
 MERKLE_COOP_MAX, MERKLE_QUAD_MAX = 4096, 32768   # common.h: glp_ctx::merkle_coop_max / merkle_quad_max (GLP_MERKLE_COOP_MAX / _QUAD_MAX)
 
 # context thresholds that force one FRI leaf-hash form (the values test_gpu_commit.py::test_leaf_hash_forms uses)
@@ -60,21 +60,21 @@ def quotient_plan(desc):
 
 
 def launch_plan(desc, K=1, coop_max=MERKLE_COOP_MAX, quad_max=MERKLE_QUAD_MAX):
-    """The set of launch-path names one glp_prove (K = 1) or one device-transcript glp_prove_batch of K proofs takes."""
+    """The set of launch-path names one glp_prove (K = 1) or one glp_prove_batch of K proofs takes (prover_stages.inc)."""
     nch, lg, rb, qdf = desc.num_challenges, desc.degree_bits, desc.rate_bits, desc.quotient_degree_factor
     if K > 1 and nch != 2:
-        raise ValueError("glp_prove_batch takes two challenges only (prover_batch.inc)")
+        raise ValueError("glp_prove_batch takes two challenges only (prover_stages.inc batch_check())")
     out = set()
-    # quotient: Rq = qdf cosets evaluated, every 2^rb / qdf-th LDE plane (prover.hip quotient(), ~l.1604)
+    # quotient: Rq = qdf cosets evaluated, every 2^rb / qdf-th LDE plane (prover_stages.inc prove_geo())
     out.add("quotient_rq%d_step%d" % (qdf, (1 << rb) // qdf))
     types = {g["type"] for g in desc.gates} - {synth.GATE_NOOP}
     if nch != 2:
-        # prover.hip quotient(): gate_mode 0, k_quotient<NCH, 1>: every gate through gate_contrib<NCH, -1>
+        # stage_quotient_eval(): gate_mode 0, k_quotient<NCH, 1>: every gate through gate_contrib<NCH, -1>
         out.add("quotient_monolithic_nch%d" % nch)
         out |= {"monolithic_" + GATE_NAMES[t] for t in types}
     else:
-        # prover.hip quotient() ~l.1655 / prover_batch_dev.inc ~l.132: k_quotient<2, 2> (light gates, fused ArithmeticGate) or <2, 0>;
-        # then k_quotient_limbs<2> and one k_quotient_gate<2, T> per gate in single_gates (plan: build_quotient_plan, ~l.2016)
+        # stage_quotient_eval(): k_quotient<2, 2> (light gates, fused ArithmeticGate) or <2, 0>;
+        # then k_quotient_limbs<2> and one k_quotient_gate<2, T> per gate in single_gates (plan: prover.hip build_quotient_plan())
         qp = quotient_plan(desc)
         gt = lambda gi: desc.gates[gi]["type"]
         out.add("quotient_perm_light" if qp["light"] or qp["arith"] is not None else "quotient_perm_only")
@@ -101,19 +101,19 @@ def launch_plan(desc, K=1, coop_max=MERKLE_COOP_MAX, quad_max=MERKLE_QUAD_MAX):
             out.add("single_poseidon")
         if any(gt(gi) in _INTERLEAVE for gi in qp["single"]):
             out.add("single_interleave")
-    # partial products: prover.hip partial_products() ~l.1575, prover_batch_dev.inc ~l.76
+    # partial products: stage_partial_products()
     npp = desc.num_partial_products
     small_lds = 2 * nch * (npp + 2) * (1 << lg) * 8
     if lg <= 7 and small_lds <= PP_SMALL_LDS:
         out.add("pp_small_lg%d" % lg)
     else:
         out.add("pp_large_lds_fallback" if lg <= 7 else "pp_large")
-    # final values (FRI combination): prover.hip ~l.1785, prover_batch_dev.inc ~l.229; 256 / n lanes per point
+    # final values (FRI combination): stage_fri_values(); 256 / n lanes per point
     if 2 <= lg <= 7:
         out.add("fv_small_lg%d_nch%d" % (lg, nch) if lg in (2, 3, 7) else "fv_small_nch%d" % nch)
     else:
         out.add("fv_large_nch%d" % nch)
-    # FRI leaf hash of each reduction: prover.hip fri_commit_layer() ~l.1813, prover_batch_dev.inc ~l.251 (nleaves * K)
+    # FRI leaf hash of each reduction: stage_fri_commit() (nleaves * K)
     lgcur = lg
     for ab in desc.reduction_arity_bits:
         nleaves = 1 << (lgcur + rb - ab)
