@@ -169,8 +169,8 @@ GLP_API int glp_batch_digests(const glp_batch *b, uint64_t *out);
  * `builder.build::<C>()` returns at [REF src/ecdsa/gadgets/ecdsa.rs:298].  Scope of this build:
  * no lookup tables, zero_knowledge = false unless asked for (glp_circuit_create_ex), quotient_degree_factor a power of two <= 2^rate_bits,
  * D = 2, Poseidon hashing (PoseidonGoldilocksConfig, the `type C` of every reference driver but
- * one [REF src/hash/keccak256.rs:281]).  Gate types a circuit may contain: see GLP_GATE_* (0..18; a larger type is
- * GLP_ERR_UNSUPPORTED: CosetInterpolationGate, ExponentiationGate, PoseidonMdsGate, the lookup gates). */
+ * one [REF src/hash/keccak256.rs:281]).  Gate types a circuit may contain: see GLP_GATE_* (0..18 and 20..22; any other
+ * type is GLP_ERR_UNSUPPORTED: the lookup gates, Poseidon2Gate). */
 enum {
     GLP_GATE_NOOP = 0,             /* plonky2 gates/noop.rs */
     GLP_GATE_CONSTANT = 1,         /* gates/constant.rs, p0 = num_consts */
@@ -194,7 +194,12 @@ enum {
     GLP_GATE_ARITHMETIC_EXTENSION = 15, /* gates/arithmetic_extension.rs, p0 = num_ops (>= 1) */
     GLP_GATE_MUL_EXTENSION = 16,        /* gates/multiplication_extension.rs, p0 = num_ops (>= 1) */
     GLP_GATE_REDUCING = 17,             /* gates/reducing.rs, p0 = num_coeffs (>= 1, 6 + num_coeffs <= num_routed_wires) */
-    GLP_GATE_REDUCING_EXTENSION = 18    /* gates/reducing_extension.rs, p0 = num_coeffs (>= 1, 6 + 2 num_coeffs <= num_routed_wires) */
+    GLP_GATE_REDUCING_EXTENSION = 18,   /* gates/reducing_extension.rs, p0 = num_coeffs (>= 1, 6 + 2 num_coeffs <= num_routed_wires) */
+    /* 19 is unassigned and stays GLP_ERR_UNSUPPORTED (callers probe it as "a type this build does not know") */
+    /* the rest of the recursive verifier's gate set: exp_from_bits, the FRI fold step, Poseidon's linear layer on ext targets */
+    GLP_GATE_EXPONENTIATION = 20,       /* gates/exponentiation.rs, p0 = num_power_bits (>= 1, p0 + 2 <= num_routed_wires) */
+    GLP_GATE_COSET_INTERPOLATION = 21,  /* gates/coset_interpolation.rs, p0 = subgroup_bits (1..5), p1 = degree (2 <= p1 <= 2^p0) */
+    GLP_GATE_POSEIDON_MDS = 22          /* gates/poseidon_mds.rs, no parameters (48 wires, all routed) */
 };
 
 typedef struct {
@@ -340,7 +345,8 @@ GLP_API int glp_prove_batch(glp_ctx *ctx, const glp_circuit *circuit, uint32_t n
  *   plonky2_u32 (recalled) U32Arithmetic / U32AddMany / U32Subtraction / U32RangeCheck / Comparison generators;
  *   plonky2 (recalled)     BaseSplitGenerator, ArithmeticBaseGenerator, RandomAccessGenerator, PoseidonGenerator,
  *                          ConstantGenerator, ArithmeticExtensionGenerator, MulExtensionGenerator, ReducingGenerator,
- *                          ReducingExtensionGenerator.
+ *                          ReducingExtensionGenerator, ExponentiationGenerator, InterpolationGenerator (CosetInterpolationGate),
+ *                          PoseidonMdsGenerator.
  * Each generator reads its dependencies (glp_witness_columns role 2) from the row and writes its outputs (role 1):
  * bits, base-4 limbs, inverses, S-box traces, u32 results.  only_advice != 0: only non-routed columns
  * (index >= num_routed_wires) are written, for a caller whose CPU pass already resolved every routed wire -- then the

@@ -742,6 +742,71 @@ __device__ __forceinline__ void gate_terms(const QArgs &a, const QProof &p, cons
             }
             break;
         }
+        // The rest of the recursive verifier's gate set (D = 2).  Exponentiation and CosetInterpolation are recalled, unpinned
+        // (DESIGN.md); PoseidonMds is pinned through the Poseidon MDS constants.
+        case GLP_GATE_EXPONENTIATION: {              // base 0, bits 1..n (little-endian), output n+1, intermediates n+2..2n+1
+            // constraint i: prev (bit base + 1 - bit) - intermediate_i, prev = 1 resp. intermediate_{i-1}^2, bit = bits[n-1-i]
+            const u32 nb = g.p0;
+            const u64 bm1 = sub(W[0], 1);            // bit base + 1 - bit = bit (base - 1) + 1
+            u64 last = 0;
+            for (u32 i0 = 0; i0 < nb; i0 += 8) {     // eight bit planes and eight intermediate planes in flight
+                u64 bt[8], im[8];
+                _Pragma("unroll") for (u32 t = 0; t < 8; t++) if (i0 + t < nb) { bt[t] = W[(size_t)(nb - (i0 + t)) * N]; im[t] = W[(size_t)(nb + 2 + i0 + t) * N]; }
+                _Pragma("unroll") for (u32 t = 0; t < 8; t++) if (i0 + t < nb) {
+                    const u64 f = add(mul(bt[t], bm1), 1);
+                    EMIT(i0 + t, sub(i0 + t == 0 ? f : mul(mul(last, last), f), im[t]));
+                    last = im[t];
+                }
+            }
+            EMIT(nb, sub(W[(size_t)(nb + 1) * N], last));
+            break;
+        }
+        case GLP_GATE_COSET_INTERPOLATION: {
+            // shift 0, values from 1 (N pairs), evaluation point, evaluation value, I intermediate evals, I intermediate prods,
+            // shifted point x.  Barycentric chain over the unshifted subgroup {x_i} with weights w_i = x_i / N (coset_table):
+            // (eval, prod) <- (eval (x - x_i) + w_i value_i prod, prod (x - x_i)), checkpointed into the intermediates after the
+            // first d points and then after every d - 1.
+            const u32 np = 1u << g.p0, d = g.p1, ni = (np - 2) / (d - 1);
+            const u32 o_pt = 1 + 2 * np, o_ie = o_pt + 4, o_ip = o_ie + 2 * ni, o_sp = o_ip + 2 * ni;
+            const u64 *tab = coset_table(a.gates, a.num_gates, g.p0);
+            const u64 shift = W[0];
+            const ext2 x = e_make(W[(size_t)o_sp * N], W[(size_t)(o_sp + 1) * N]);
+            EMIT(0, sub(mul(x.a, shift), W[(size_t)o_pt * N])); EMIT(1, sub(mul(x.b, shift), W[(size_t)(o_pt + 1) * N]));
+            ext2 ev = e_from(0), pr = e_from(1);
+            u32 start = 0;
+            for (u32 c = 0; c <= ni; c++) {
+                const u32 end = min(np, d + c * (d - 1));
+                for (u32 j0 = start; j0 < end; j0 += 8) {      // a chunk's value planes (eight points at a time) before their use
+                    u64 va[8], vb[8];
+                    _Pragma("unroll") for (u32 t = 0; t < 8; t++) if (j0 + t < end) { va[t] = W[(size_t)(1 + 2 * (j0 + t)) * N]; vb[t] = W[(size_t)(2 + 2 * (j0 + t)) * N]; }
+                    _Pragma("unroll") for (u32 t = 0; t < 8; t++) if (j0 + t < end) {
+                        const ext2 dx = e_make(sub(x.a, tab[2 * (j0 + t)]), x.b);
+                        ev = e_add(e_mul(ev, dx), e_scale(e_mul(e_make(va[t], vb[t]), pr), tab[2 * (j0 + t) + 1]));
+                        pr = e_mul(pr, dx);
+                    }
+                }
+                start = end;
+                if (c < ni) {
+                    const u64 *ie = W + (size_t)(o_ie + 2 * c) * N, *ip = W + (size_t)(o_ip + 2 * c) * N;
+                    const u64 e0 = ie[0], e1 = ie[N], q0 = ip[0], q1 = ip[N];
+                    EMIT(2 + 4 * c, sub(e0, ev.a)); EMIT(3 + 4 * c, sub(e1, ev.b)); EMIT(4 + 4 * c, sub(q0, pr.a)); EMIT(5 + 4 * c, sub(q1, pr.b));
+                    ev = e_make(e0, e1); pr = e_make(q0, q1);
+                }
+            }
+            EMIT(2 + 4 * ni, sub(W[(size_t)(o_pt + 2) * N], ev.a)); EMIT(3 + 4 * ni, sub(W[(size_t)(o_pt + 3) * N], ev.b));
+            break;
+        }
+        case GLP_GATE_POSEIDON_MDS: {                // input i at [2i, 2i+2), output i at [24+2i, 24+2i+2): out - MDS in, per component
+#if defined(__HIP_DEVICE_COMPILE__)
+            for (u32 cmp = 0; cmp < 2; cmp++) {      // one component at a time: 12 input planes, the unreduced limb rows of poseidon.h
+                u64 st[12], ov[12];
+                _Pragma("unroll") for (u32 i = 0; i < 12; i++) { st[i] = W[(size_t)(2 * i + cmp) * N]; ov[i] = W[(size_t)(24 + 2 * i + cmp) * N]; }
+                pos::mds_add_nc(st, pos::RC_ZERO);
+                _Pragma("unroll") for (u32 i = 0; i < 12; i++) EMIT(2 * i + cmp, sub(ov[i], canon(st[i])));
+            }
+#endif
+            break;
+        }
         default: break;   // NOOP
         }
 #undef LIMBS4_DESC
@@ -1995,6 +2060,16 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
         case GLP_GATE_MUL_EXTENSION: wires = 6 * p0; consts = 1; constraints = 2 * p0; return p0 >= 1 && p0 <= 4096;
         case GLP_GATE_REDUCING: wires = 3 * p0 + 4; constraints = 2 * p0; return p0 >= 1 && p0 <= 4096;
         case GLP_GATE_REDUCING_EXTENSION: wires = 4 * p0 + 4; constraints = 2 * p0; return p0 >= 1 && p0 <= 4096;
+        // the recursion gates.  Exponentiation: base, p0 bits, output, p0 intermediates.  CosetInterpolation: shift, 2^p0 values, point,
+        // value, I evals, I prods, shifted point (pairs), I = (2^p0 - 2) div (p1 - 1); at most 2 (2 + 2 * 30) = 124 constraints
+        case GLP_GATE_EXPONENTIATION: wires = 2 * p0 + 2; constraints = p0 + 1; return p0 >= 1 && p0 <= 4096;
+        case GLP_GATE_COSET_INTERPOLATION: {
+            if (p0 < 1 || p0 > COSET_MAX_BITS || p1 < 2 || p1 > (1u << p0)) return false;
+            const u32 ni = ((1u << p0) - 2) / (p1 - 1);
+            wires = 7 + (2u << p0) + 4 * ni; constraints = 2 * (2 + 2 * ni);
+            return true;
+        }
+        case GLP_GATE_POSEIDON_MDS: wires = 48; constraints = 24; return p0 == 0 && p1 == 0;
         default: return false;
         }
     };
@@ -2004,7 +2079,7 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
         {
             u32 gw = 0, gcn = 0, gk = 0;
             if (!gate_shape(g, gw, gcn, gk))
-                return set_error(g.type > GLP_GATE_REDUCING_EXTENSION ? GLP_ERR_UNSUPPORTED : GLP_ERR_ARG,
+                return set_error(g.type > GLP_GATE_POSEIDON_MDS || g.type == 19 ? GLP_ERR_UNSUPPORTED : GLP_ERR_ARG,      // 19 is unassigned
                                  "gate %u: type %u with parameters (%u, %u) is not supported", i, g.type, g.p0, g.p1);
             GLP_REQUIRE(gw <= d.num_wires, "gate %u (type %u) needs %u wires, circuit has %u", i, g.type, gw, d.num_wires);
             GLP_REQUIRE(d.num_selectors + gcn <= d.num_constants, "gate %u (type %u) needs %u constants", i, g.type, gcn);
@@ -2024,6 +2099,20 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
             const u32 routed = 6 + (g.type == GLP_GATE_REDUCING ? 1 : 2) * g.p0;     // output, alpha, old_acc, coefficients
             GLP_REQUIRE(routed <= d.num_routed_wires, "gate %u (type %u): %u routed inputs, circuit has %u routed wires", i, g.type, routed,
                         d.num_routed_wires);
+            break;
+        }
+        case GLP_GATE_EXPONENTIATION: case GLP_GATE_COSET_INTERPOLATION: case GLP_GATE_POSEIDON_MDS: {
+            // routed: base, bits, output / shift, values, evaluation point and value / every wire
+            const u32 routed = g.type == GLP_GATE_EXPONENTIATION ? g.p0 + 2 : g.type == GLP_GATE_COSET_INTERPOLATION ? 5 + (2u << g.p0) : 48;
+            GLP_REQUIRE(routed <= d.num_routed_wires, "gate %u (type %u): %u routed inputs, circuit has %u routed wires", i, g.type, routed,
+                        d.num_routed_wires);
+            // The quotient is evaluated on quotient_degree_factor cosets, so filter x constraint may have degree quotient_degree_factor + 1
+            // at most (what plonky2's selector grouping guarantees for every gate it places): the filter has one factor per other gate of
+            // the group, and the UNUSED factor when there are several selectors.
+            const u32 deg = g.type == GLP_GATE_EXPONENTIATION ? 4 : g.type == GLP_GATE_COSET_INTERPOLATION ? g.p1 : 1;
+            const u32 filt = g.group_end - g.group_start - 1 + (d.num_selectors > 1 ? 1 : 0);
+            GLP_REQUIRE(g.group_start < g.group_end && deg + filt <= qdf + 1, "gate %u (type %u): degree %u with a selector filter of degree %u exceeds "
+                        "quotient_degree_factor %u + 1", i, g.type, deg, g.group_start < g.group_end ? filt : 0, qdf);
             break;
         }
         default: break;
@@ -2060,11 +2149,16 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
     make_layout(cc->d, cc->L, cc->zk);
     const size_t n = (size_t)1 << d.degree_bits;
     const u32 nc = d.num_constants, nr = d.num_routed_wires;
-    GLP_TRY(c->alloc((void **)&cc->dev_gates, sizeof(DevGate) * std::max<u32>(d.num_gates, 1)));
+    GLP_TRY(c->alloc((void **)&cc->dev_gates, sizeof(DevGate) * d.num_gates + 8 * COSET_TABLE_WORDS));      // gate table ++ coset_table
     GLP_TRY(c->alloc((void **)&cc->dev_k_is, (size_t)nr * 8));
     GLP_TRY(c->alloc((void **)&cc->dev_sigmas, (size_t)nr * n * 8));
     static_assert(sizeof(DevGate) == sizeof(glp_gate), "gate layout");
     GLP_TRY(h2d(c, cc->dev_gates, cc->gates.data(), sizeof(DevGate) * d.num_gates));
+    {
+        u64 tab[COSET_TABLE_WORDS];
+        coset_table_fill(tab);
+        GLP_TRY(h2d(c, cc->dev_gates + d.num_gates, tab, sizeof(tab)));
+    }
     GLP_TRY(h2d(c, cc->dev_k_is, cc->k_is.data(), (size_t)nr * 8));
     GLP_TRY(h2d(c, cc->dev_sigmas, d.sigmas, (size_t)nr * n * 8));
     GLP_TRY(c->alloc((void **)&cc->dev_consts, (size_t)nc * n * 8));

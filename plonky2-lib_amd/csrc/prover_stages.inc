@@ -150,6 +150,7 @@ int stage_quotient_eval(glp_ctx *c, const ProveGeo &g, const QProof &qp, const Q
             GLP_GATE_LAUNCH(GLP_GATE_BASE_SUM) GLP_GATE_LAUNCH(GLP_GATE_RANDOM_ACCESS)
             GLP_GATE_LAUNCH(GLP_GATE_ARITHMETIC_EXTENSION) GLP_GATE_LAUNCH(GLP_GATE_MUL_EXTENSION)
             GLP_GATE_LAUNCH(GLP_GATE_REDUCING) GLP_GATE_LAUNCH(GLP_GATE_REDUCING_EXTENSION)
+            GLP_GATE_LAUNCH(GLP_GATE_EXPONENTIATION) GLP_GATE_LAUNCH(GLP_GATE_COSET_INTERPOLATION) GLP_GATE_LAUNCH(GLP_GATE_POSEIDON_MDS)
         default: break;   // NoopGate: no constraints
         }
 #undef GLP_GATE_LAUNCH

@@ -17,6 +17,18 @@ constexpr int MAXR = 16;      // 2^rate_bits supported
 constexpr u32 APL_WORDS = 4;  // table words per alpha power in the quotient kernels' limb form (prover.hip AccHL): m0 | m1 << 32, m2, m0' | m1' << 32, m2'
 
 struct DevGate { u32 type, selector_index, group_start, group_end, row, num_constraints, p0, p1; };
+// CosetInterpolationGate's interpolation domain and barycentric weights, built once in glp_circuit_create and stored behind the
+// device gate table (so no kernel argument changes): for subgroup_bits b = 1 .. COSET_MAX_BITS the 2^b pairs
+// {x_i = g^i, w_i = x_i / 2^b}, g = the root of unity of order 2^b, from word 2 (2^b - 2) on.  At most 32 pairs per gate.
+constexpr u32 COSET_MAX_BITS = 5, COSET_TABLE_WORDS = 2 * ((2u << COSET_MAX_BITS) - 2);
+inline void coset_table_fill(u64 *t) {
+    for (u32 b = 1; b <= COSET_MAX_BITS; b++) {
+        const u64 g = root_of_unity((int)b), ninv = inv((u64)1 << b);
+        u64 x = 1;
+        for (u32 i = 0; i < (1u << b); i++, x = mul(x, g)) { t[2 * ((1u << b) - 2 + i)] = x; t[2 * ((1u << b) - 2 + i) + 1] = mul(x, ninv); }
+    }
+}
+GLF_HD const u64 *coset_table(const DevGate *gates, u32 num_gates, u32 bits) { return (const u64 *)(gates + num_gates) + 2 * ((1u << bits) - 2); }
 
 struct Layout {
     size_t caps, openings, fri_caps, queries, final_poly, pow, pis, total, nopen, query_stride;

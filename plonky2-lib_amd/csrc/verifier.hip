@@ -285,6 +285,61 @@ void gate_constraints(const glp_gate &g, const E *gc, const E *w, const u64 pih[
         }
         break;
     }
+    // The recursion gates at zeta.  ExponentiationGate's wires are base-field targets: plain F_p^2 arithmetic on the openings.
+    // CosetInterpolationGate's values, points and intermediates and PoseidonMdsGate's inputs / outputs are ext targets, i.e.
+    // algebra elements on wire pairs; the shift, the domain points x_i = g^i and the weights w_i = x_i / N are scalars.
+    // Exponentiation and CosetInterpolation: recalled, unpinned; PoseidonMds: pinned through the Poseidon MDS constants.
+    case GLP_GATE_EXPONENTIATION: {
+        const u32 nb = g.p0;
+        E prev = ONE;
+        for (u32 i = 0; i < nb; i++) {
+            const E bit = w[nb - i], cur = w[nb + 2 + i];
+            emit(prev * (bit * w[0] + ONE - bit) - cur);
+            prev = cur * cur;
+        }
+        emit(w[nb + 1] - w[2 * nb + 1]);
+        break;
+    }
+    case GLP_GATE_COSET_INTERPOLATION: {
+        const u32 np = 1u << g.p0, d = g.p1, ni = (np - 2) / (d - 1);
+        const u32 o_pt = 1 + 2 * np, o_ie = o_pt + 4, o_ip = o_ie + 2 * ni, o_sp = o_ip + 2 * ni;
+        const u64 gen = root_of_unity((int)g.p0), ninv = glf::inv((u64)np);
+        const E x0 = w[o_sp], x1 = w[o_sp + 1];
+        emit(x0 * w[0] - w[o_pt]);
+        emit(x1 * w[0] - w[o_pt + 1]);
+        E e0 = ZERO, e1 = ZERO, q0 = ONE, q1 = ZERO;
+        u64 xi = 1;
+        u32 j = 0;
+        for (u32 c = 0; c <= ni; c++) {
+            const u32 end = std::min(np, d + c * (d - 1));
+            for (; j < end; j++, xi = glf::mul(xi, gen)) {
+                const E d0 = x0 - E(xi);
+                E a0, a1, b0, b1;
+                alg_mul(e0, e1, d0, x1, a0, a1);                          // eval (x - x_i)
+                alg_mul(w[1 + 2 * j], w[2 + 2 * j], q0, q1, b0, b1);      // value_i prod
+                const u64 wi = glf::mul(xi, ninv);
+                e0 = a0 + b0 * wi; e1 = a1 + b1 * wi;
+                alg_mul(q0, q1, d0, x1, a0, a1);
+                q0 = a0; q1 = a1;
+            }
+            if (c < ni) {
+                emit(w[o_ie + 2 * c] - e0); emit(w[o_ie + 2 * c + 1] - e1);
+                emit(w[o_ip + 2 * c] - q0); emit(w[o_ip + 2 * c + 1] - q1);
+                e0 = w[o_ie + 2 * c]; e1 = w[o_ie + 2 * c + 1]; q0 = w[o_ip + 2 * c]; q1 = w[o_ip + 2 * c + 1];
+            }
+        }
+        emit(w[o_pt + 2] - e0);
+        emit(w[o_pt + 3] - e1);
+        break;
+    }
+    case GLP_GATE_POSEIDON_MDS: {
+        E c0[12], c1[12];
+        for (int i = 0; i < 12; i++) { c0[i] = w[2 * i]; c1[i] = w[2 * i + 1]; }
+        mds(c0);
+        mds(c1);
+        for (int i = 0; i < 12; i++) { emit(w[24 + 2 * i] - c0[i]); emit(w[24 + 2 * i + 1] - c1[i]); }
+        break;
+    }
     default: break;    // NoopGate
     }
 }

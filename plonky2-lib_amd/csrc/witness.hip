@@ -17,7 +17,8 @@
 //   plonky2 (crate absent, recalled)      BaseSplitGenerator (gates/base_sum.rs), ArithmeticBaseGenerator,
 //                           RandomAccessGenerator, PoseidonGenerator, ConstantGenerator (gates/constant.rs and the
 //                           extra constants of RandomAccessGate), ArithmeticExtensionGenerator, MulExtensionGenerator,
-//                           ReducingGenerator, ReducingExtensionGenerator (F_p^2 values on wire pairs)
+//                           ReducingGenerator, ReducingExtensionGenerator (F_p^2 values on wire pairs),
+//                           ExponentiationGenerator, InterpolationGenerator (CosetInterpolationGate), PoseidonMdsGenerator
 // Every value written is a canonical field element; inputs are read as canonical u64 exactly as
 // `to_canonical_u64()` hands them to the Rust generators.
 #include "common.h"
@@ -265,6 +266,55 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         }
         break;
     }
+    case GLP_GATE_EXPONENTIATION: {
+        // gates/exponentiation.rs ExponentiationGenerator: square-and-multiply from the most significant bit; intermediate_i
+        // at wire n + 2 + i, output = the last intermediate
+        const u32 nb = g.p0;
+        const u64 base = RD(0);
+        u64 cur = 1;
+        for (u32 i = 0; i < nb; i++) {
+            cur = mul(sqr(cur), add(mul(RD(nb - i), sub(base, 1)), 1));   // bit n-1-i sits at wire 1 + (n-1-i); bit base + 1 - bit
+            WR(nb + 2 + i, cur);
+        }
+        WR(nb + 1, cur);
+        break;
+    }
+    case GLP_GATE_COSET_INTERPOLATION: {
+        // gates/coset_interpolation.rs InterpolationGenerator: shifted point = evaluation point / shift, then the barycentric chain
+        // of prover.hip `gate_terms` with its checkpoints (the intermediates) and the evaluation value
+        const u32 np = 1u << g.p0, d = g.p1, ni = (np - 2) / (d - 1);
+        const u32 o_pt = 1 + 2 * np, o_ie = o_pt + 4, o_ip = o_ie + 2 * ni, o_sp = o_ip + 2 * ni;
+        const u64 *tab = coset_table(a.gates, a.num_gates, g.p0);
+        const u64 sh = RD(0);
+        const u64 shi = sh ? winv(sh) : 0;                         // a zero shift has no coset: the Rust generator panics there
+        const ext2 x = e_scale(e_make(RD(o_pt), RD(o_pt + 1)), shi);
+        WR(o_sp, x.a);
+        WR(o_sp + 1, x.b);
+        ext2 ev = e_from(0), pr = e_from(1);
+        u32 j = 0;
+        for (u32 c = 0; c <= ni; c++) {
+            const u32 end = min(np, d + c * (d - 1));
+            for (; j < end; j++) {
+                const ext2 dx = e_make(sub(x.a, tab[2 * j]), x.b);
+                ev = e_add(e_mul(ev, dx), e_scale(e_mul(e_make(RD(1 + 2 * j), RD(2 + 2 * j)), pr), tab[2 * j + 1]));
+                pr = e_mul(pr, dx);
+            }
+            if (c < ni) { WR(o_ie + 2 * c, ev.a); WR(o_ie + 2 * c + 1, ev.b); WR(o_ip + 2 * c, pr.a); WR(o_ip + 2 * c + 1, pr.b); }
+        }
+        WR(o_pt + 2, ev.a);
+        WR(o_pt + 3, ev.b);
+        break;
+    }
+    case GLP_GATE_POSEIDON_MDS: {
+        // gates/poseidon_mds.rs PoseidonMdsGenerator: the MDS layer on each F_p^2 component of the 12 inputs
+        for (u32 cmp = 0; cmp < 2; cmp++) {
+            u64 st[12];
+            for (u32 i = 0; i < 12; i++) st[i] = RD(2 * i + cmp);
+            pos::mds_layer(st);
+            for (u32 i = 0; i < 12; i++) WR(24 + 2 * i + cmp, st[i]);
+        }
+        break;
+    }
     default: break;     // NoopGate; PublicInputGate (its wires are set from the public-input hash through copy constraints)
     }
 #undef WR
@@ -329,6 +379,13 @@ extern "C" int glp_witness_columns(const glp_circuit *cc, uint32_t gate_index, u
         out(0, 2); in(2, 4 + cw * g.p0); out(6 + cw * g.p0, 2 * (g.p0 - 1));
         break;
     }
+    case GLP_GATE_EXPONENTIATION: in(0, 1 + g.p0); out(g.p0 + 1, 1 + g.p0); break;
+    case GLP_GATE_COSET_INTERPOLATION: {
+        const u32 np = 1u << g.p0, ni = (np - 2) / (g.p1 - 1);
+        in(0, 3 + 2 * np); out(3 + 2 * np, 2 + 4 * ni + 2);      // shift, values, point | value, intermediates, shifted point
+        break;
+    }
+    case GLP_GATE_POSEIDON_MDS: in(0, 24); out(24, 24); break;
     default: break;
     }
     return GLP_OK;

@@ -26,6 +26,9 @@ GATE_COMPARISON, GATE_BASE_SUM, GATE_RANDOM_ACCESS = 12, 13, 14
 # plonky2's extension-field arithmetic (D = 2: an F_p^2 value a + b X, X^2 = 7, on two consecutive wires)
 GATE_ARITHMETIC_EXTENSION, GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING_EXTENSION = 15, 16, 17, 18
 EXT_GATES = (GATE_ARITHMETIC_EXTENSION, GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING_EXTENSION)
+# the rest of the recursive verifier's gate set (19 is unassigned): exp_from_bits, the FRI fold step, Poseidon's MDS on ext targets
+GATE_EXPONENTIATION, GATE_COSET_INTERPOLATION, GATE_POSEIDON_MDS = 20, 21, 22
+RECURSION_GATES = (GATE_EXPONENTIATION, GATE_COSET_INTERPOLATION, GATE_POSEIDON_MDS)
 
 # (degree, id string as plonky2's `Gate::id` prints it) -- the build() sort key
 _GATE_META = {
@@ -48,6 +51,10 @@ _GATE_META = {
     GATE_MUL_EXTENSION: (3, "MulExtensionGate {{ num_ops: {p0} }}"),
     GATE_REDUCING: (2, "ReducingGate {{ num_coeffs: {p0} }}"),
     GATE_REDUCING_EXTENSION: (2, "ReducingExtensionGate {{ num_coeffs: {p0} }}"),
+    # id strings recalled; CosetInterpolationGate's degree is its p1 (gate_degree)
+    GATE_EXPONENTIATION: (4, "ExponentiationGate {{ num_power_bits: {p0} }}"),
+    GATE_COSET_INTERPOLATION: (None, "CosetInterpolationGate {{ subgroup_bits: {p0}, degree: {p1} }}"),
+    GATE_POSEIDON_MDS: (1, "PoseidonMdsGate"),
 }
 
 
@@ -56,7 +63,7 @@ def gate_degree(t, p0=0, p1=0):
     range product of a chunk has 2^chunk_bits factors)."""
     if t == GATE_COMPARISON:
         return 1 << -(-p0 // p1)
-    return p1 if t == GATE_BASE_SUM else _GATE_META[t][0]
+    return p1 if t in (GATE_BASE_SUM, GATE_COSET_INTERPOLATION) else _GATE_META[t][0]
 
 
 def gate_num_constraints(t, p0, p1=0):
@@ -71,6 +78,12 @@ def gate_num_constraints(t, p0, p1=0):
         return (p1 & 0xFFFF) * (p0 + 2) + (p1 >> 16)
     if t in EXT_GATES:
         return 2 * p0
+    if t == GATE_EXPONENTIATION:
+        return p0 + 1
+    if t == GATE_COSET_INTERPOLATION:
+        return 2 * (2 + 2 * coset_num_intermediates(p0, p1))
+    if t == GATE_POSEIDON_MDS:
+        return 24
     return {GATE_NOOP: 0, GATE_CONSTANT: p0, GATE_PUBLIC_INPUT: 4, GATE_ARITHMETIC: p0, GATE_POSEIDON: 123,
             GATE_U32_INTERLEAVE: p0 * 34, GATE_UNINTERLEAVE_U32: p0 * 67, GATE_UNINTERLEAVE_B32: p0 * 67,
             GATE_U32_ARITHMETIC: p0 * 36, GATE_U32_SUBTRACTION: p0 * 19, GATE_U32_RANGE_CHECK: p0 * 17}[t]
@@ -517,6 +530,209 @@ def ext_gates_circuit(log_n, config=None, seed=11, num_challenges=2, public_inpu
         for src, dst in ((2, 2), (3, 3), (0, 4), (1, 5)):
             b.connect_pairs(r1, src, r2, dst)
         _fill_ext_rows(b, r2, t, par[t])
+    if zk:
+        b.blind(n, pi_row=0, seed=blinding_seed)
+    return b.build()
+
+
+def coset_num_intermediates(subgroup_bits, degree):
+    """Checkpoints of CosetInterpolationGate's barycentric chain: the first chunk takes `degree` points, each later one degree - 1."""
+    return ((1 << subgroup_bits) - 2) // (degree - 1)
+
+
+def coset_degree(subgroup_bits, max_degree):
+    """CosetInterpolationGate::with_max_degree (recalled): the smallest degree that needs no more intermediates than max_degree does."""
+    n_points = 1 << subgroup_bits
+    return (n_points - 2) // ((n_points - 2) // (max_degree - 1) + 1) + 2
+
+
+def recursion_gate_params(cfg, subgroup_bits=4):
+    """(p0, p1) of each recursion gate as plonky2 picks them under a config (recalled): ExponentiationGate::new_from_config takes
+    min(routed - 3, (wires - 2) / 2) power bits; the FRI fold interpolates 2^arity_bits = 16 points at the degree
+    max_quotient_degree_factor admits."""
+    return {GATE_EXPONENTIATION: (min(cfg.num_routed_wires - 3, (cfg.num_wires - 2) // 2), 0),
+            GATE_COSET_INTERPOLATION: (subgroup_bits, coset_degree(subgroup_bits, cfg.max_quotient_degree_factor)),
+            GATE_POSEIDON_MDS: (0, 0)}
+
+
+def recursion_gate_wires(t, p0=0, p1=0):
+    """(wire columns, routed wire columns) of a row of recursion gate (t, p0, p1)."""
+    if t == GATE_EXPONENTIATION:
+        return 2 * p0 + 2, p0 + 2
+    if t == GATE_COSET_INTERPOLATION:
+        return 7 + (2 << p0) + 4 * coset_num_intermediates(p0, p1), 5 + (2 << p0)
+    return 48, 48
+
+
+def _fill_exponentiation_rows(b, rows, nb):
+    """intermediate_i = intermediate_{i-1}^2 (base if bit n-1-i else 1) from 1; output = the last one.  Base (wire 0) and bits
+    (wires 1..n, little-endian) are already in the wires."""
+    w = b.wires
+    b.set_rows(rows, GATE_EXPONENTIATION, nb)
+    base, cur = w[0, rows], np.ones(len(rows), np.uint64)
+    for i in range(nb):
+        cur = gl.mul(gl.mul(cur, cur), np.where(w[nb - i, rows] != 0, base, np.uint64(1)))
+        w[nb + 2 + i, rows] = cur
+    w[nb + 1, rows] = cur
+
+
+def _fill_coset_rows(b, rows, bits, d):
+    """shifted point = evaluation point / shift, then the barycentric chain over the subgroup x_i = g^i with weights x_i / N:
+    (eval, prod) <- (eval (x - x_i) + w_i value_i prod, prod (x - x_i)), stored into the intermediates after the first d points and
+    then after every d - 1; the final eval is the evaluation value.  Shift, values and evaluation point are already in the wires."""
+    w = b.wires
+    b.set_rows(rows, GATE_COSET_INTERPOLATION, bits, d)
+    if len(rows) == 0:
+        return
+    n_pts, ni = 1 << bits, coset_num_intermediates(bits, d)
+    o_pt = 1 + 2 * n_pts
+    o_ie, o_ip, o_sp = o_pt + 4, o_pt + 4 + 2 * ni, o_pt + 4 + 4 * ni
+    sh_inv = np.array([gl.inv_scalar(int(v)) for v in w[0, rows]], dtype=np.uint64)
+    x0, x1 = gl.mul(w[o_pt, rows], sh_inv), gl.mul(w[o_pt + 1, rows], sh_inv)
+    w[o_sp, rows], w[o_sp + 1, rows] = x0, x1
+    xs = gl.powers(gl.root_of_unity(bits), n_pts)
+    n_inv = np.uint64(gl.inv_scalar(n_pts))
+    e0 = e1 = q1 = np.zeros(len(rows), np.uint64)
+    q0 = np.ones(len(rows), np.uint64)
+    j = 0
+    for c in range(ni + 1):
+        end = min(n_pts, d + c * (d - 1))
+        while j < end:
+            d0 = gl.sub(x0, xs[j])
+            wi = gl.mul(xs[j], n_inv)
+            a0, a1 = ext_mul(e0, e1, d0, x1)
+            v0, v1 = ext_mul(w[1 + 2 * j, rows], w[2 + 2 * j, rows], q0, q1)
+            e0, e1 = gl.add(a0, gl.mul(v0, wi)), gl.add(a1, gl.mul(v1, wi))
+            q0, q1 = ext_mul(q0, q1, d0, x1)
+            j += 1
+        if c < ni:
+            w[o_ie + 2 * c, rows], w[o_ie + 2 * c + 1, rows] = e0, e1
+            w[o_ip + 2 * c, rows], w[o_ip + 2 * c + 1, rows] = q0, q1
+    w[o_pt + 2, rows], w[o_pt + 3, rows] = e0, e1
+
+
+def _fill_poseidon_mds_rows(b, rows):
+    """output_r = sum_i CIRC[i] input[(i + r) mod 12] + DIAG[r] input[r] on each F_p^2 component (DIAG = 8 at r = 0)."""
+    from .poseidon_py import CIRC
+    w = b.wires
+    b.set_rows(rows, GATE_POSEIDON_MDS, 0)
+    for cmp in range(2):
+        for r in range(12):
+            acc = gl.mul(w[cmp, rows], np.uint64(8)) if r == 0 else np.zeros(len(rows), np.uint64)
+            for i in range(12):
+                acc = gl.add(acc, gl.mul(w[2 * ((i + r) % 12) + cmp, rows], np.uint64(CIRC[i])))
+            w[24 + 2 * r + cmp, rows] = acc
+
+
+def recursion_gates_circuit(log_n, config=None, seed=13, num_challenges=2, public_inputs=(), pi_hash=None, gates=RECURSION_GATES,
+                            params=None, mix_ext=False, witness_seed=None, blinding_seed=None):
+    """A circuit of the recursive verifier's remaining gates -- Exponentiation, CosetInterpolation, PoseidonMds (restricted to
+    `gates`) -- with satisfying witnesses, wired the way the verifier circuit uses them:
+    [PublicInput][Constant x2][unit ...][Noop ...], a unit being
+      BaseSum<2>, Exponentiation      the power bits are the limbs of the BaseSum row (its 63 limbs; further bits are free 0 / 1 wires),
+      ArithmeticExtension, CosetInterpolation
+                                      the evaluation point and the first values are ArithmeticExtension outputs (one row of them:
+                                      the remaining values are free wires); the shift is the Exponentiation output,
+      PoseidonMds                     input 0 is the CosetInterpolation result,
+    and with mix_ext one row each of MulExtension, Reducing, ReducingExtension.  The two helper rows come with their gate.
+    params: {gate: (p0, p1)} overrides recursion_gate_params (what plonky2 picks under the config: 66 power bits, 16 points at degree 6
+    for standard_recursion_config).  2^3 .. 2^20 rows; 2^4 at least with mix_ext.  witness_seed, blinding_seed and
+    config.zero_knowledge as in ext_gates_circuit."""
+    import copy
+    cfg = copy.copy(config or Config.standard_recursion_config())
+    cfg.num_challenges = num_challenges
+    zk = bool(getattr(cfg, "zero_knowledge", False))
+    b = Builder(cfg, zk_degree_bits(cfg, 1 << log_n, log_n) if zk else log_n, seed)
+    n = 1 << log_n
+    if witness_seed is not None:
+        b.wires = gl.rand(np.random.default_rng(witness_seed), b.wires.shape)
+    gates = tuple(gates)
+    if not gates or any(t not in RECURSION_GATES for t in gates):
+        raise ValueError("gates must be a non-empty subset of RECURSION_GATES")
+    par = recursion_gate_params(cfg)
+    par.update(params or {})
+    nw, nr = cfg.num_wires, cfg.num_routed_wires
+    for t in gates:
+        need = recursion_gate_wires(t, *par[t])
+        if need[0] > nw or need[1] > nr:
+            raise ValueError("gate %d with parameters %r needs %d wires / %d routed" % (t, par[t], need[0], need[1]))
+    pi = np.asarray(public_inputs, dtype=np.uint64)
+    b.public_inputs = pi
+    if pi_hash is None:
+        if len(pi):
+            raise ValueError("pass pi_hash = hash_no_pad(public_inputs) when public inputs are non-empty")
+        pi_hash = np.zeros(4, np.uint64)
+    ext_par = ext_gate_params(cfg)
+    unit = []
+    if GATE_EXPONENTIATION in gates:
+        unit += [GATE_BASE_SUM, GATE_EXPONENTIATION]
+    if GATE_COSET_INTERPOLATION in gates:
+        unit += [GATE_ARITHMETIC_EXTENSION, GATE_COSET_INTERPOLATION]
+    if GATE_POSEIDON_MDS in gates:
+        unit += [GATE_POSEIDON_MDS]
+    if mix_ext:
+        unit += [GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING_EXTENSION]
+    num_noop = 3 if n >= 16 else 0
+    rows_c = np.array([1, 2])
+    units = (n - num_noop - 3) // len(unit)
+    if units < 1:
+        raise ValueError("log_n too small")
+    b.set_rows(np.array([0]), GATE_PUBLIC_INPUT, 0)
+    b.set_rows(rows_c, GATE_CONSTANT, cfg.num_constants)
+    cvals = gl.rand(b.rng, (cfg.num_constants, 2))
+    cvals[0, 0], cvals[1, 0], cvals[0, 1], cvals[1, 1] = pi_hash[0], pi_hash[1], pi_hash[2], pi_hash[3]
+    b.gate_consts[:, rows_c] = cvals
+    b.wires[:cfg.num_constants, rows_c] = cvals
+    b.wires[:4, 0] = pi_hash
+    for k in range(4):
+        b.connect_pairs(np.array([0]), k, np.array([rows_c[k // 2]]), k % 2)
+    b.set_rows(np.arange(3 + units * len(unit), n), GATE_NOOP, 0)
+
+    def rows_of(t):
+        return 3 + unit.index(t) + len(unit) * np.arange(units, dtype=np.int64)
+    w = b.wires
+    if GATE_EXPONENTIATION in gates:
+        nb = par[GATE_EXPONENTIATION][0]
+        r_bs, r_ex = rows_of(GATE_BASE_SUM), rows_of(GATE_EXPONENTIATION)
+        nl = min(nr - 1, 63, nb)
+        b.set_rows(r_bs, GATE_BASE_SUM, nl, 2)
+        v = b.rng.integers(0, 1 << nl, size=units, dtype=np.uint64)
+        w[0, r_bs] = v
+        for j in range(nl):
+            w[1 + j, r_bs] = (v >> np.uint64(j)) & np.uint64(1)
+            w[1 + j, r_ex] = w[1 + j, r_bs]
+            b.connect_pairs(r_bs, 1 + j, r_ex, 1 + j)
+        if nb > nl:
+            w[1 + nl:1 + nb, r_ex] = b.rng.integers(0, 2, size=(nb - nl, units), dtype=np.uint64)
+        _fill_exponentiation_rows(b, r_ex, nb)
+    if GATE_COSET_INTERPOLATION in gates:
+        bits, d = par[GATE_COSET_INTERPOLATION]
+        r_ae, r_co = rows_of(GATE_ARITHMETIC_EXTENSION), rows_of(GATE_COSET_INTERPOLATION)
+        ops = ext_par[GATE_ARITHMETIC_EXTENSION]
+        _fill_ext_rows(b, r_ae, GATE_ARITHMETIC_EXTENSION, ops, chain=False)
+        n_pts = 1 << bits
+        # ArithmeticExtension output 0 -> the evaluation point, outputs 1.. -> values 0..
+        dst = [1 + 2 * n_pts] + [1 + 2 * i for i in range(min(n_pts, ops - 1))]
+        for i, col in enumerate(dst):
+            for k in range(2):
+                w[col + k, r_co] = w[8 * i + 6 + k, r_ae]
+                b.connect_pairs(r_ae, 8 * i + 6 + k, r_co, col + k)
+        if GATE_EXPONENTIATION in gates:
+            w[0, r_co] = w[par[GATE_EXPONENTIATION][0] + 1, r_ex]
+            b.connect_pairs(r_ex, par[GATE_EXPONENTIATION][0] + 1, r_co, 0)
+        w[0, r_co] = np.where(w[0, r_co] == 0, np.uint64(1), w[0, r_co])     # a coset needs a non-zero shift (never hit by random wires)
+        _fill_coset_rows(b, r_co, bits, d)
+    if GATE_POSEIDON_MDS in gates:
+        r_md = rows_of(GATE_POSEIDON_MDS)
+        if GATE_COSET_INTERPOLATION in gates:
+            o_val = 3 + 2 * n_pts
+            for k in range(2):
+                w[k, r_md] = w[o_val + k, r_co]
+                b.connect_pairs(r_co, o_val + k, r_md, k)
+        _fill_poseidon_mds_rows(b, r_md)
+    if mix_ext:
+        for t in (GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING_EXTENSION):
+            _fill_ext_rows(b, rows_of(t), t, ext_par[t])
     if zk:
         b.blind(n, pi_row=0, seed=blinding_seed)
     return b.build()
