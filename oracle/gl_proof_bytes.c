@@ -5,7 +5,7 @@
  * its gate / generator serializers on it [REF src/ecdsa/serialization.rs:7-46]).  RECALLED, UNPINNED: the reference holds no
  * proof bytes, so this restatement and the product's glp_proof_to_bytes can only be checked against each other -- which is the
  * point of keeping them structurally independent: the product walks a flat list of (offset, count, kind) pieces
- * (csrc/prover.hip walk_proof), this file follows the Rust writer's call tree, one function per `Write` method:
+ * (csrc/proof_bytes.inc walk_proof), this file follows the Rust writer's call tree, one function per `Write` method:
  *
  *   write_proof_with_public_inputs = write_proof ; write_field_vec(public_inputs)            (no length prefix: `read_field_vec(len)`)
  *   write_proof           = write_merkle_cap x3 (wires, plonk_zs_partial_products, quotient_polys) ; write_opening_set ; write_fri_proof

@@ -143,14 +143,7 @@ int stage_quotient_eval(glp_ctx *c, const ProveGeo &g, const QProof &qp, const Q
     for (u32 gi : cc->single_gates) {
 #define GLP_GATE_LAUNCH(T) case T: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient_gate<2, T>), grid, dim3(256), 0, c->stream, a, qp, qbt, gi); break;
         switch (cc->gates[gi].type) {
-            GLP_GATE_LAUNCH(GLP_GATE_CONSTANT) GLP_GATE_LAUNCH(GLP_GATE_PUBLIC_INPUT) GLP_GATE_LAUNCH(GLP_GATE_ARITHMETIC)
-            GLP_GATE_LAUNCH(GLP_GATE_POSEIDON) GLP_GATE_LAUNCH(GLP_GATE_U32_INTERLEAVE) GLP_GATE_LAUNCH(GLP_GATE_UNINTERLEAVE_U32)
-            GLP_GATE_LAUNCH(GLP_GATE_UNINTERLEAVE_B32) GLP_GATE_LAUNCH(GLP_GATE_U32_ARITHMETIC) GLP_GATE_LAUNCH(GLP_GATE_U32_ADD_MANY)
-            GLP_GATE_LAUNCH(GLP_GATE_U32_SUBTRACTION) GLP_GATE_LAUNCH(GLP_GATE_U32_RANGE_CHECK) GLP_GATE_LAUNCH(GLP_GATE_COMPARISON)
-            GLP_GATE_LAUNCH(GLP_GATE_BASE_SUM) GLP_GATE_LAUNCH(GLP_GATE_RANDOM_ACCESS)
-            GLP_GATE_LAUNCH(GLP_GATE_ARITHMETIC_EXTENSION) GLP_GATE_LAUNCH(GLP_GATE_MUL_EXTENSION)
-            GLP_GATE_LAUNCH(GLP_GATE_REDUCING) GLP_GATE_LAUNCH(GLP_GATE_REDUCING_EXTENSION)
-            GLP_GATE_LAUNCH(GLP_GATE_EXPONENTIATION) GLP_GATE_LAUNCH(GLP_GATE_COSET_INTERPOLATION) GLP_GATE_LAUNCH(GLP_GATE_POSEIDON_MDS)
+            GLP_CONSTRAINED_GATES(GLP_GATE_LAUNCH)      // gate_shapes.h: every type that has constraints
         default: break;   // NoopGate: no constraints
         }
 #undef GLP_GATE_LAUNCH

@@ -6,6 +6,7 @@
 #include <vector>
 #include "batch.h"
 #include "common.h"
+#include "gate_shapes.h"
 #include "keccak.h"
 #include "poseidon.h"
 
@@ -14,13 +15,13 @@ using namespace glf;
 
 constexpr int MAXCH = 4;      // num_challenges supported
 constexpr int MAXR = 16;      // 2^rate_bits supported
-constexpr u32 APL_WORDS = 4;  // table words per alpha power in the quotient kernels' limb form (prover.hip AccHL): m0 | m1 << 32, m2, m0' | m1' << 32, m2'
+constexpr u32 APL_WORDS = 4;  // table words per alpha power in the quotient kernels' limb form (quotient_kernels.inc AccHL): m0 | m1 << 32, m2, m0' | m1' << 32, m2'
 
 struct DevGate { u32 type, selector_index, group_start, group_end, row, num_constraints, p0, p1; };
 // CosetInterpolationGate's interpolation domain and barycentric weights, built once in glp_circuit_create and stored behind the
 // device gate table (so no kernel argument changes): for subgroup_bits b = 1 .. COSET_MAX_BITS the 2^b pairs
 // {x_i = g^i, w_i = x_i / 2^b}, g = the root of unity of order 2^b, from word 2 (2^b - 2) on.  At most 32 pairs per gate.
-constexpr u32 COSET_MAX_BITS = 5, COSET_TABLE_WORDS = 2 * ((2u << COSET_MAX_BITS) - 2);
+constexpr u32 COSET_TABLE_WORDS = 2 * ((2u << COSET_MAX_BITS) - 2);
 inline void coset_table_fill(u64 *t) {
     for (u32 b = 1; b <= COSET_MAX_BITS; b++) {
         const u64 g = root_of_unity((int)b), ninv = inv((u64)1 << b);

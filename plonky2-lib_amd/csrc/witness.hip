@@ -8,7 +8,7 @@
 // embarrassingly row-parallel: one thread per trace row here, written straight into the HBM witness that
 // glp_prove_device consumes, so those columns never cross PCIe.
 //
-// Generators restated (one `case` each below; wire layouts = the gate definitions in prover.hip `gate_terms`):
+// Generators restated (one `case` each below; wire layouts = the gate definitions in quotient_kernels.inc `gate_terms`):
 //   the reference's own     U32InterleaveGenerator      [REF src/u32/gates/interleave_u32.rs:289-318]
 //                           UninterleaveToU32Generator  [REF src/u32/gates/uninterleave_to_u32.rs:332-369]
 //                           UninterleaveToB32Generator  [REF src/u32/gates/uninterleave_to_b32.rs:335-372]
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
     }
     case GLP_GATE_COSET_INTERPOLATION: {
         // gates/coset_interpolation.rs InterpolationGenerator: shifted point = evaluation point / shift, then the barycentric chain
-        // of prover.hip `gate_terms` with its checkpoints (the intermediates) and the evaluation value
+        // of quotient_kernels.inc `gate_terms` with its checkpoints (the intermediates) and the evaluation value
         const u32 np = 1u << g.p0, d = g.p1, ni = (np - 2) / (d - 1);
         const u32 o_pt = 1 + 2 * np, o_ie = o_pt + 4, o_ip = o_ie + 2 * ni, o_sp = o_ip + 2 * ni;
         const u64 *tab = coset_table(a.gates, a.num_gates, g.p0);

@@ -1,5 +1,5 @@
 """Where the limb launch of the real secp256k1 circuit spends its time: the quotient stage with one component of k_quotient_limbs compiled
-out at a time (-DLIMB_NO_CMP / _NO_HEADS / _NO_RP / _NO_ACC builds of prover.hip; the proofs of those builds are of course invalid --
+out at a time (-DLIMB_NO_CMP / _NO_HEADS / _NO_RP / _NO_ACC builds of prover.hip, whose quotient_kernels.inc holds the kernel; the proofs of those builds are of course invalid --
 timing only).  The circuit is built once and handed over through a hand-off file."""
 import os, sys, time
 import numpy as np

@@ -10,8 +10,8 @@ import numpy as np
 
 import plonky2_lib_amd.synth as synth
 
-LIMB_SLOTS, LIMB_GROUPS = 5, 4            # prover.hip: constexpr int LIMB_SLOTS = 5, LIMB_GROUPS = 4
-LIGHT_MAX, EXTRA_MAX = 8, 4               # prover.hip: LightArgs::gi[8], LimbArgs::extra_gi[4]
+LIMB_SLOTS, LIMB_GROUPS = 5, 4            # quotient_kernels.inc: constexpr int LIMB_SLOTS = 5, LIMB_GROUPS = 4
+LIGHT_MAX, EXTRA_MAX = 8, 4               # quotient_kernels.inc: LightArgs::gi[8], LimbArgs::extra_gi[4]
 PP_SMALL_LDS = 64 * 1024                  # prover_stages.inc stage_partial_products(): small_lds <= 64 KiB
 MERKLE_COOP_MAX, MERKLE_QUAD_MAX = 4096, 32768   # common.h: glp_ctx::merkle_coop_max / merkle_quad_max (GLP_MERKLE_COOP_MAX / _QUAD_MAX)
 
@@ -30,7 +30,7 @@ GATE_NAMES = {synth.GATE_CONSTANT: "constant", synth.GATE_PUBLIC_INPUT: "public_
 
 
 def quotient_plan(desc):
-    """prover.hip build_quotient_plan(): which launch of the two-challenge quotient evaluates each gate (by index into desc.gates)."""
+    """circuit_create.inc build_quotient_plan(): which launch of the two-challenge quotient evaluates each gate (by index into desc.gates)."""
     limb, light, single, extra = [], [], [], []
     arith = None
     for gi, g in enumerate(desc.gates):
@@ -74,7 +74,7 @@ def launch_plan(desc, K=1, coop_max=MERKLE_COOP_MAX, quad_max=MERKLE_QUAD_MAX):
         out |= {"monolithic_" + GATE_NAMES[t] for t in types}
     else:
         # stage_quotient_eval(): k_quotient<2, 2> (light gates, fused ArithmeticGate) or <2, 0>;
-        # then k_quotient_limbs<2> and one k_quotient_gate<2, T> per gate in single_gates (plan: prover.hip build_quotient_plan())
+        # then k_quotient_limbs<2> and one k_quotient_gate<2, T> per gate in single_gates (plan: circuit_create.inc build_quotient_plan())
         qp = quotient_plan(desc)
         gt = lambda gi: desc.gates[gi]["type"]
         out.add("quotient_perm_light" if qp["light"] or qp["arith"] is not None else "quotient_perm_only")
