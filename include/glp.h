@@ -163,6 +163,70 @@ GLP_API int glp_batch_merkle_proof(const glp_batch *b, uint64_t leaf_index, uint
 GLP_API size_t glp_batch_num_digests(const glp_batch *b);
 GLP_API int glp_batch_digests(const glp_batch *b, uint64_t *out);
 
+/* ---- openings and FRI of caller-held batches (fri/oracle.rs `PolynomialBatch::prove_openings`) ----------------------------------
+ * For an integrator that keeps its own quotient (circuits with lookup tables, Poseidon2Gate, custom gates, starky AIRs: anything
+ * glp_circuit_create answers with GLP_ERR_UNSUPPORTED): commit with glp_batch_from_values / _from_coeffs, evaluate the committed
+ * polynomials at the opening points and run FRI over them here.  glp_fri_desc is plonky2's `FriInstanceInfo` plus the `FriParams`
+ * the prover reads.  A point names its polynomials in the order of its ranges; that order is the order of the alpha powers and of
+ * the openings.  With F = 0, for each point b in order (plonky2's combination rule, the coefficient-form `divide_by_linear`):
+ *     F <- alpha^(len_b) F + (sum_j alpha^j p_{b,j}(X) - sum_j alpha^j p_{b,j}(z_b)) / (X - z_b),   j over that point's polynomials.
+ * Many-proof batches (glp_prove_batch's K > 1 oracles) are GLP_ERR_UNSUPPORTED here. */
+#define GLP_FRI_MAX_ORACLES 8
+#define GLP_FRI_MAX_POINTS 4
+#define GLP_FRI_MAX_RANGES 16     /* per point */
+typedef struct { uint32_t oracle, col_begin, num_cols; } glp_fri_range;      /* polynomials [col_begin, col_begin+num_cols) of oracles[oracle] */
+typedef struct { uint64_t point[2]; uint32_t num_ranges; const glp_fri_range *ranges; } glp_fri_point;   /* plonky2 FriBatchInfo */
+typedef struct {
+    uint32_t num_oracles;  const glp_batch *const *oracles;   /* FriInstanceInfo.oracles: same ctx, log_n, rate_bits, cap_height, hasher; salted or not, each */
+    uint32_t num_points;   const glp_fri_point *points;       /* FriInstanceInfo.batches, in order */
+    uint32_t num_reductions, reduction_arity_bits[16];
+    uint32_t proof_of_work_bits, num_query_rounds;
+} glp_fri_desc;
+typedef struct glp_fri glp_fri;
+/* Stepped form: mirrors glp_session_* from `open` onward (order enforced; GLP_ERR_ARG otherwise):
+ *
+ *   glp_fri_begin        validates and copies the description; the batches are borrowed and must outlive the handle
+ *   glp_fri_open         out: 2 words per (point, polynomial), points in order: `PolynomialCoeffs::to_extension().eval(point)`, what the
+ *                        Rust prover computes for its `OpeningSet`
+ *   glp_fri_combine      in: FRI alpha (ext)
+ *   num_reductions x { glp_fri_commit (out: layer cap [2^cap_height][4]) ; glp_fri_fold (in: beta, ext) }
+ *   glp_fri_final_poly   out: final polynomial coefficients (ext), glp_fri_final_poly_len of them
+ *   glp_pow_search_h     (stateless) the proof-of-work witness on the caller's sponge
+ *   glp_fri_queries      in: pow witness, num_query_rounds indices in [0, 2^(log_n + rate_bits))
+ *   glp_fri_proof        out: plonky2's `FriProof`, glp_fri_proof_words words, laid out as the tail of glp_prove's proof:
+ *                          commit_phase_merkle_caps [num_reductions][2^cap_height][4]
+ *                          query_round_proofs [num_query_rounds]: per oracle (leaf: glp_batch_leaf_len words, salts last; Merkle path),
+ *                                                                 then per reduction (evals, Merkle path)
+ *                          final_poly | pow_witness
+ *   glp_fri_end
+ *
+ * glp_fri_begin errors: GLP_ERR_ARG with a message naming the field for a null pointer or a count out of range (num_oracles,
+ * num_points, num_ranges, num_reductions); oracles that disagree in log_n, rate_bits, cap_height, hasher or ctx; a range past its
+ * oracle's ncols (the salts are not polynomials); a point with no polynomial; arity bits that sum above log_n or any arity bit
+ * outside 1..4; num_query_rounds = 0.  GLP_ERR_PROVE for a point that lies on the coset g H (b = 0 and a^n = g^n), as the session
+ * answers zeta in the subgroup. */
+GLP_API int glp_fri_begin(glp_ctx *ctx, const glp_fri_desc *desc, glp_fri **out);
+GLP_API size_t glp_fri_num_openings(const glp_fri *f);
+GLP_API int glp_fri_open(glp_fri *f, uint64_t *openings_out /* [2 * glp_fri_num_openings] */);
+GLP_API int glp_fri_combine(glp_fri *f, const uint64_t alpha[2]);
+GLP_API int glp_fri_commit(glp_fri *f, uint64_t *cap_out);
+GLP_API int glp_fri_fold(glp_fri *f, const uint64_t beta[2]);
+GLP_API size_t glp_fri_final_poly_len(const glp_fri *f);                /* ext coefficients */
+GLP_API int glp_fri_final_poly(glp_fri *f, uint64_t *coeffs_out /* [2 * glp_fri_final_poly_len] */);
+GLP_API int glp_fri_queries(glp_fri *f, uint64_t pow_witness, const uint64_t *indices, uint32_t num_indices);
+GLP_API size_t glp_fri_proof_words(const glp_fri *f);
+GLP_API int glp_fri_proof(glp_fri *f, uint64_t *proof_out /* [glp_fri_proof_words] */);
+GLP_API void glp_fri_end(glp_fri *f);
+/* One-call form: the same sequence driven by the library's transcript, resumed from a duplex-sponge state plus num_pending (< 8)
+ * buffered inputs (the convention of glp_pow_search_h).  The caller has just observed the openings, so its output buffer is empty --
+ * or, with num_pending = 0, holds the state's 8 rate words: the last observation filled the rate and permuted, and plonky2's
+ * `duplexing` refills the output buffer; the library resumes either way from (state, num_pending) alone.  The permutation is that of
+ * the batches' hasher.  Order (fri/prover.rs): alpha; per reduction observe the cap, draw beta; observe
+ * the final polynomial; the SMALLEST proof-of-work witness; num_query_rounds indices, get() % N.  openings_out
+ * [2 * sum of the points' polynomial counts] is filled for the caller's proof (they are computed inside the call anyway). */
+GLP_API int glp_fri_prove(glp_ctx *ctx, const glp_fri_desc *desc, const uint64_t sponge_state[12], const uint64_t *pending_inputs,
+                          uint32_t num_pending, uint64_t *openings_out, uint64_t *proof_out);
+
 /* ---- circuits and whole proofs ------------------------------------------------------------------
  * glp_circuit_desc carries the parts of plonky2's CommonCircuitData / ProverOnlyCircuitData /
  * VerifierOnlyCircuitData that `prove` reads (plonk/circuit_data.rs), i.e. what
@@ -401,6 +465,10 @@ GLP_API int glp_pow_search(glp_ctx *ctx, const uint64_t sponge_state[12], const 
 /* the same for a transcript whose permutation is that of `hasher` (GLP_HASH_KECCAK25: KeccakPermutation) */
 GLP_API int glp_pow_search_h(glp_ctx *ctx, uint32_t hasher, const uint64_t sponge_state[12], const uint64_t *pending_inputs,
                              uint32_t num_pending, uint32_t bits, uint64_t *witness_out);
+/* The session's committed oracles, index 0..3: constants_sigmas, wires, zs and partial products, quotient.  Valid once the stage that
+ * commits that oracle has run (0, 1: after begin; 2: partial_products; 3: quotient); GLP_ERR_ARG before that or for another index.
+ * The handle is borrowed until glp_session_end: read it (glp_batch_coeffs of Z or of the quotient) or hand it to glp_fri_*. */
+GLP_API int glp_session_oracle(glp_session *s, uint32_t index, const glp_batch **out);
 GLP_API int glp_session_queries(glp_session *s, uint64_t pow_witness, const uint64_t *indices, uint32_t num_indices);
 GLP_API int glp_session_proof(glp_session *s, uint64_t *proof_out /* glp_proof_words(circuit) */);
 GLP_API void glp_session_end(glp_session *s);

@@ -41,6 +41,20 @@ class _CircuitDesc(C.Structure):
                  ("constants", C.c_void_p), ("sigmas", C.c_void_p), ("hasher", C.c_uint32)])
 
 
+class _FriRange(C.Structure):
+    _fields_ = [("oracle", C.c_uint32), ("col_begin", C.c_uint32), ("num_cols", C.c_uint32)]
+
+
+class _FriPoint(C.Structure):
+    _fields_ = [("point", C.c_uint64 * 2), ("num_ranges", C.c_uint32), ("ranges", C.POINTER(_FriRange))]
+
+
+class _FriDesc(C.Structure):
+    _fields_ = [("num_oracles", C.c_uint32), ("oracles", C.POINTER(C.c_void_p)), ("num_points", C.c_uint32),
+                ("points", C.POINTER(_FriPoint)), ("num_reductions", C.c_uint32), ("reduction_arity_bits", C.c_uint32 * 16),
+                ("proof_of_work_bits", C.c_uint32), ("num_query_rounds", C.c_uint32)]
+
+
 def library_path():
     return _SO
 
@@ -134,6 +148,17 @@ def load_library():
         "glp_session_queries": [vp, C.c_uint64, vp, C.c_uint32],
         "glp_session_proof": [vp, vp],
         "glp_session_end": [vp],
+        "glp_session_oracle": [vp, u32, C.POINTER(vp)],
+        "glp_fri_begin": [vp, C.POINTER(_FriDesc), C.POINTER(vp)],
+        "glp_fri_open": [vp, vp],
+        "glp_fri_combine": [vp, vp],
+        "glp_fri_commit": [vp, vp],
+        "glp_fri_fold": [vp, vp],
+        "glp_fri_final_poly": [vp, vp],
+        "glp_fri_queries": [vp, C.c_uint64, vp, C.c_uint32],
+        "glp_fri_proof": [vp, vp],
+        "glp_fri_end": [vp],
+        "glp_fri_prove": [vp, C.POINTER(_FriDesc), vp, vp, u32, vp, vp],
         "glp_verify": [vp, vp],
         "glp_verify_n": [vp, vp, sz],
         "glp_prove_batch": [vp, vp, u32, vp, C.c_int, vp, vp],
@@ -163,8 +188,12 @@ def load_library():
     for name in ("glp_num_openings", "glp_final_poly_len"):
         getattr(L, name).restype = sz
         getattr(L, name).argtypes = [vp]
+    for name in ("glp_fri_num_openings", "glp_fri_final_poly_len", "glp_fri_proof_words"):
+        getattr(L, name).restype = sz
+        getattr(L, name).argtypes = [vp]
     for name, argtypes in sigs.items():
         getattr(L, name).argtypes = argtypes
+    L.glp_fri_end.restype = None
     L.glp_ctx_destroy.restype = None
     L.glp_batch_free.restype = None
     L.glp_circuit_free.restype = None
@@ -359,9 +388,10 @@ class Context:
 class Batch:
     """plonky2 `PolynomialBatch` resident on the GPU."""
 
-    def __init__(self, ctx, handle, ncols, log_n, rate_bits, cap_height):
+    def __init__(self, ctx, handle, ncols, log_n, rate_bits, cap_height, owner=None):
         self.ctx, self._h = ctx, handle
         self.ncols, self.log_n, self.rate_bits, self.cap_height = ncols, log_n, rate_bits, cap_height
+        self._owner = owner        # a borrowed handle (Session.oracle): the owner frees it, and is kept alive meanwhile
 
     @classmethod
     def _make(cls, ctx, fn, arr, rate_bits, cap_height, hasher=0):
@@ -383,7 +413,7 @@ class Batch:
 
     def free(self):
         if self._h:
-            if getattr(self.ctx, "_h", None):                # never touch a handle whose context is already gone
+            if self._owner is None and getattr(self.ctx, "_h", None):     # never touch a handle whose context is already gone
                 load_library().glp_batch_free(self._h)
             self._h = None
 
@@ -799,6 +829,16 @@ class Session:
         _chk(load_library().glp_session_proof(self._h, _p(out)))
         return out
 
+    def oracle(self, index):
+        """glp_session_oracle: committed oracle 0..3 (constants_sigmas, wires, zs and partial products, quotient) as a Batch borrowed
+        from this session: valid until end(), never freed by the Batch."""
+        L = load_library()
+        h = C.c_void_p()
+        _chk(L.glp_session_oracle(self._h, int(index), C.byref(h)))
+        nc, lg, rb, ch = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _chk(L.glp_batch_info(h, C.byref(nc), C.byref(lg), C.byref(rb), C.byref(ch)))
+        return Batch(self.circuit.ctx, h, nc.value, lg.value, rb.value, ch.value, owner=self)
+
     def end(self):
         if getattr(self, "_h", None):
             if getattr(self.circuit.ctx, "_h", None):        # a session must not outlive its context: then it is only dropped
@@ -810,3 +850,117 @@ class Session:
             self.end()
         except Exception:
             pass
+
+
+def _fri_desc_to_c(oracles, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds):
+    """(list of Batch, [(point (a, b), [(oracle, col_begin, num_cols), ...]), ...], FriParams) -> (glp_fri_desc, keep-alive objects)."""
+    if len(reduction_arity_bits) > 16:
+        raise GlpError(-1, "more than 16 FRI reductions")
+    d = _FriDesc()
+    handles = (C.c_void_p * max(1, len(oracles)))(*[b._h for b in oracles])
+    pts = (_FriPoint * max(1, len(points)))()
+    keep = [handles, pts, list(oracles)]
+    for i, (z, ranges) in enumerate(points):
+        rs = (_FriRange * max(1, len(ranges)))()
+        for j, (o, cb, ncol) in enumerate(ranges):
+            rs[j].oracle, rs[j].col_begin, rs[j].num_cols = int(o), int(cb), int(ncol)
+        pts[i].point[0], pts[i].point[1] = int(z[0]), int(z[1])
+        pts[i].num_ranges = len(ranges)
+        pts[i].ranges = C.cast(rs, C.POINTER(_FriRange))
+        keep.append(rs)
+    d.num_oracles, d.oracles = len(oracles), C.cast(handles, C.POINTER(C.c_void_p))
+    d.num_points, d.points = len(points), C.cast(pts, C.POINTER(_FriPoint))
+    d.num_reductions = len(reduction_arity_bits)
+    for i, ab in enumerate(reduction_arity_bits):
+        d.reduction_arity_bits[i] = int(ab)
+    d.proof_of_work_bits, d.num_query_rounds = int(proof_of_work_bits), int(num_query_rounds)
+    return d, keep
+
+
+class FriOpenings:
+    """plonky2 `PolynomialBatch::prove_openings` and the openings themselves for caller-held batches, stepped by the caller's
+    transcript (include/glp.h, glp_fri_*).  oracles: Batch objects of one context and shape; points: [((a, b), [(oracle, col_begin,
+    num_cols), ...]), ...] = `FriInstanceInfo.batches`.  The batches are borrowed and must outlive this object."""
+
+    def __init__(self, ctx, oracles, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds):
+        self.ctx = ctx
+        d, self._keep = _fri_desc_to_c(oracles, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds)
+        self._capn = 1 << oracles[0].cap_height if oracles else 1
+        self._h = C.c_void_p()
+        _chk(load_library().glp_fri_begin(ctx._h, C.byref(d), C.byref(self._h)))
+
+    @property
+    def num_openings(self):
+        return load_library().glp_fri_num_openings(self._h)
+
+    def open(self):
+        out = np.empty((self.num_openings, 2), np.uint64)
+        _chk(load_library().glp_fri_open(self._h, _p(out)))
+        return out
+
+    def combine(self, alpha):
+        _chk(load_library().glp_fri_combine(self._h, _p(_a(alpha))))
+
+    def commit(self):
+        out = np.empty((self._capn, 4), np.uint64)
+        _chk(load_library().glp_fri_commit(self._h, _p(out)))
+        return out
+
+    def fold(self, beta):
+        _chk(load_library().glp_fri_fold(self._h, _p(_a(beta))))
+
+    def final_poly(self):
+        L = load_library()
+        out = np.empty((L.glp_fri_final_poly_len(self._h), 2), np.uint64)
+        _chk(L.glp_fri_final_poly(self._h, _p(out)))
+        return out
+
+    def queries(self, pow_witness, indices):
+        idx = _a(indices)
+        _chk(load_library().glp_fri_queries(self._h, C.c_uint64(int(pow_witness)), _p(idx), idx.size))
+
+    def proof(self):
+        L = load_library()
+        out = np.zeros(L.glp_fri_proof_words(self._h), np.uint64)
+        _chk(L.glp_fri_proof(self._h, _p(out)))
+        return out
+
+    def end(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                load_library().glp_fri_end(self._h)
+            self._h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.end()
+        except Exception:
+            pass
+
+
+def fri_proof_words(oracles, reduction_arity_bits, num_query_rounds):
+    """words of the FriProof glp_fri_proof / glp_fri_prove write for these oracles (layout: include/glp.h)"""
+    b = oracles[0]
+    lg_n = b.log_n + b.rate_bits
+    q = sum(o.leaf_len + 4 * (lg_n - b.cap_height) for o in oracles)
+    lg = lg_n
+    for ab in reduction_arity_bits:
+        lg -= ab
+        q += (2 << ab) + 4 * (lg - b.cap_height)
+    return (4 << b.cap_height) * len(reduction_arity_bits) + q * num_query_rounds + (2 << (lg - b.rate_bits)) + 1
+
+
+def fri_prove(ctx, oracles, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds, sponge_state, pending_inputs=()):
+    """glp_fri_prove: the whole of FriOpenings driven by the library's transcript, resumed from the caller's duplex sponge
+    (12 state words + fewer than 8 buffered inputs) right after it observed the openings.  Returns (openings [count][2], proof words)."""
+    d, keep = _fri_desc_to_c(oracles, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds)
+    st, pend = _a(sponge_state), _a(list(pending_inputs))
+    if st.size != 12 or pend.size >= 8:
+        raise GlpError(-1, "the sponge state is 12 words with fewer than 8 pending inputs")
+    nopen = sum(int(nc) for _, ranges in points for _, _, nc in ranges)
+    openings = np.zeros((max(nopen, 1), 2), np.uint64)
+    proof = np.zeros(fri_proof_words(oracles, reduction_arity_bits, num_query_rounds) if oracles else 1, np.uint64)
+    _chk(load_library().glp_fri_prove(ctx._h, C.byref(d), _p(st), _p(pend) if pend.size else None, pend.size, _p(openings), _p(proof)))
+    del keep
+    return openings[:nopen], proof

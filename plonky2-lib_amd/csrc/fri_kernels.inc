@@ -155,6 +155,66 @@ __global__ __launch_bounds__(256) void k_final_values_small(FVArgs a) {
         a.out[q] = f.a; a.out[n + q] = f.b;
     }
 }
+// K8 for any FRI instance (fri_openings.inc): up to GLP_FRI_MAX_POINTS opening points, each naming its own list of columns:
+//   F <- alpha^(len_b) F + (sum_j alpha^j p_{b,j}(x) - red_b) / (x - z_b)     for b = 0 .. npoints - 1, F = 0 before the first
+// One pass over the union of the named columns: prog[e] is one column (its plane 0) and, per point, where that column's alpha
+// power sits in the table (FC_ABSENT: the point does not name it), so a column several points name is loaded once.  The
+// program and the powers are read uniformly (scalar loads, uniform branches), as coset_table is; one carry-free accumulator
+// pair per point, all flushed every ACC_MAX_TERMS columns.  Columns are loaded four at a time to keep four loads in flight:
+// the four pairs cost 96 of the kernel's 130 VGPRs (3 waves per SIMD; bounding it to 128 for a fourth wave spills).
+constexpr u32 FC_ABSENT = 0xFFFFFFFFu;
+struct FCCol { const u64 *plane; u32 ap[GLP_FRI_MAX_POINTS]; };
+struct FCArgs {
+    const FCCol *prog; u32 nprog, npoints;
+    const u64 *apow;            // ext alpha powers, indexed by FCCol::ap
+    u64 *out;                   // [2][n]
+    ext2 red[GLP_FRI_MAX_POINTS], z[GLP_FRI_MAX_POINTS], shift[GLP_FRI_MAX_POINTS];   // shift[b] = alpha^(len_b)
+    u64 w_n, g;
+    u32 lg;
+};
+__global__ __launch_bounds__(256) void k_fri_combine(FCArgs a) {
+    constexpr int NP = GLP_FRI_MAX_POINTS;
+    const size_t n = (size_t)1 << a.lg;
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    ext2 sum[NP];
+    AccLimb xa[NP], xb[NP];
+#pragma unroll
+    for (int b = 0; b < NP; b++) { sum[b] = e_from(0); acc2_zero(xa[b]); acc2_zero(xb[b]); }
+    u32 terms = 0;
+    for (u32 e0 = 0; e0 < a.nprog; e0 += 4) {
+        u64 v[4];
+#pragma unroll
+        for (u32 i = 0; i < 4; i++) v[i] = e0 + i < a.nprog ? a.prog[e0 + i].plane[q] : 0;
+#pragma unroll
+        for (u32 i = 0; i < 4; i++) {
+            if (e0 + i >= a.nprog) break;
+            const u32 v0 = (u32)v[i] & 0x3FFFFFu, v1 = (u32)(v[i] >> 22) & 0x3FFFFFu, v2 = (u32)(v[i] >> 44);
+#pragma unroll
+            for (int b = 0; b < NP; b++) {
+                const u32 j = a.prog[e0 + i].ap[b];
+                if (j != FC_ABSENT) { acc2_fma(xa[b], v0, v1, v2, a.apow[2 * (size_t)j]); acc2_fma(xb[b], v0, v1, v2, a.apow[2 * (size_t)j + 1]); }
+            }
+        }
+        if ((terms += 4) == ACC_MAX_TERMS) {
+#pragma unroll
+            for (int b = 0; b < NP; b++) {
+                sum[b] = e_add(sum[b], e_make(acc2_reduce(xa[b]), acc2_reduce(xb[b])));
+                acc2_zero(xa[b]); acc2_zero(xb[b]);
+            }
+            terms = 0;
+        }
+    }
+    const ext2 x = e_from(mul(a.g, dpow(a.w_n, q)));
+    ext2 f = e_from(0);
+#pragma unroll
+    for (int b = 0; b < NP; b++) {
+        if ((u32)b >= a.npoints) break;
+        const ext2 s = e_add(sum[b], e_make(acc2_reduce(xa[b]), acc2_reduce(xb[b])));
+        f = e_add(e_mul(f, a.shift[b]), e_mul(e_sub(s, a.red[b]), e_inv(e_sub(x, a.z[b]))));
+    }
+    a.out[q] = f.a; a.out[n + q] = f.b;
+}
 // data[c][p] *= base^bitrev(p)
 __global__ __launch_bounds__(256) void k_scale_bitrev_pow(u64 *data, u64 base, u32 lg) {
     const size_t n = (size_t)1 << lg;

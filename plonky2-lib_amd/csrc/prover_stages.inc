@@ -16,10 +16,12 @@ namespace {
 
 // what every stage needs of the circuit and the batch, computed once per prove call
 struct ProveGeo {
-    const glp_circuit *cc;
+    const glp_circuit *cc;                         // nullptr: no circuit (fri_openings.inc), only the FRI fields below are set
     int lg, rb, qdb, hasher, cap_height;           // qdb: log2 of the evaluated quotient planes
     size_t n, N;
     u32 nch, nr, nw, nc, qdf, npp, nzp, capn, Rq, step, nterms, K;
+    const u32 *arity_bits;                         // FRI: reduction_arity_bits of the owner (circuit description or glp_fri)
+    u32 nq;                                        // FRI: num_query_rounds
 };
 ProveGeo prove_geo(const glp_circuit *cc, u32 K) {
     const glp_circuit_desc &d = cc->d;
@@ -34,6 +36,7 @@ ProveGeo prove_geo(const glp_circuit *cc, u32 K) {
     while ((1u << g.qdb) < g.qdf) g.qdb++;
     g.Rq = 1u << g.qdb; g.step = 1u << (g.rb - g.qdb);
     g.nterms = g.nch + g.nch * (g.npp + 1) + d.num_gate_constraints;
+    g.arity_bits = d.reduction_arity_bits; g.nq = d.num_query_rounds;
     return g;
 }
 // the constants/sigmas oracle (oracle 0) is shared by all proofs of a batch, the other three advance per proof
@@ -247,6 +250,13 @@ void fri_alpha_powers(const ProveGeo &g, const glp_batch *const ob[4], const std
     pt[0] = red0; pt[1] = red1; pt[2] = zeta; pt[3] = zeta_next; pt[4] = e_pow(alpha, g.nch);
 }
 
+// the FRI batch polynomial's values on coset plane 0 (fv [K][2][n]) -> its coefficients (fcoef, bit-reversed order)
+int fri_values_to_coeffs(glp_ctx *c, const ProveGeo &g, const u64 *fv, u64 *fcoef) {
+    GLP_TRY(intt_values_to_coeffs(c, fv, fcoef, 2 * g.K, g.lg));
+    hipLaunchKernelGGL(k_scale_bitrev_pow, dim3(nblk(g.n), 2 * g.K), dim3(256), 0, c->stream, fcoef, inv(GEN), (u32)g.lg);
+    GLP_HIP(hipGetLastError());
+    return GLP_OK;
+}
 // K8: alpha-combination of all openings batches, quotient by (X - zeta) / (X - g zeta) -> fcoef [K][2][n], the FRI polynomial's
 // coefficients; fv: scratch of the same size.  dev_ap [K][2 oracle_cols]; pt != nullptr: one proof with the values of
 // fri_alpha_powers; else they come from dev_pp[K][10].
@@ -262,10 +272,7 @@ int stage_fri_values(glp_ctx *c, const ProveGeo &g, const glp_batch *const ob[4]
     if (g.lg >= 2 && g.lg <= 7) hipLaunchKernelGGL(k_final_values_small, dim3(1, g.K), dim3(256), 0, c->stream, a);      // 4..128 points: 256 / n lanes per point
     else hipLaunchKernelGGL(k_final_values, dim3(nblk(g.n), g.K), dim3(256), 0, c->stream, a);
     GLP_HIP(hipGetLastError());
-    GLP_TRY(intt_values_to_coeffs(c, fv, fcoef, 2 * g.K, g.lg));
-    hipLaunchKernelGGL(k_scale_bitrev_pow, dim3(nblk(g.n), 2 * g.K), dim3(256), 0, c->stream, fcoef, inv(GEN), (u32)g.lg);
-    GLP_HIP(hipGetLastError());
-    return GLP_OK;
+    return fri_values_to_coeffs(c, g, fv, fcoef);
 }
 
 // K9: the commit phase.  One layer per reduction: values on the coset and the tree over arity-sized leaves, [K] of each.
@@ -281,7 +288,7 @@ struct FriState {
 int stage_fri_commit(glp_ctx *c, const ProveGeo &g, Tmp &tmp, FriState &f) {
     const u32 K = g.K, rb = (u32)g.rb;
     FriLayer ly;
-    ly.ab = g.cc->d.reduction_arity_bits[f.layers.size()]; ly.lgL = (u32)(f.lgcur + g.rb);
+    ly.ab = g.arity_bits[f.layers.size()]; ly.lgL = (u32)(f.lgcur + g.rb);
     const u32 ab = ly.ab, lgL = ly.lgL;
     const size_t Lsz = (size_t)1 << lgL, nleaves = Lsz >> ab;
     ly.ndig = merkle_num_digests(nleaves, g.cap_height);
@@ -319,33 +326,41 @@ int stage_fri_fold(glp_ctx *c, const ProveGeo &g, Tmp &tmp, FriState &f, ext2 be
     return GLP_OK;
 }
 
-// query phase: leaves and Merkle paths of the four initial oracles and of every commit-phase layer, for the nq indices per proof in
-// dev_idx, written into dev_q: `stride` words per query record, `qsec` words from one proof's records to the next
-int stage_queries(glp_ctx *c, const ProveGeo &g, const glp_batch *const ob[4], const std::vector<FriLayer> &layers, const u64 *dev_idx,
-                  u64 *dev_q, size_t stride, size_t qsec) {
-    const Layout &L = g.cc->L;
-    const u32 nq = g.cc->d.num_query_rounds, K = g.K;
-    size_t off = 0;   // word offset inside one query record
-    for (int b = 0; b < 4; b++) {
-        const u32 ncol = ob[b]->ncols + ob[b]->salt;      // the whole leaf: salts ride after the polynomial values
-        GLP_TRY(merkle_gather_lde_rows(c, ob[b]->lde, ncol, g.lg, g.rb, dev_idx, nq, dev_q + off, stride, K, per_proof(b, ncol * g.N), qsec));
-        off += ncol;
-        GLP_TRY(merkle_gather_paths(c, ob[b]->digests, g.N, g.cap_height, dev_idx, nq, dev_q + off, stride, 0, K, per_proof(b, ob[b]->ndigests * 4), qsec));
-        off += 4 * (size_t)L.depth0;
-    }
+// query phase.  Every gather writes into dev_q: `stride` words per query record, `qsec` words from one proof's records to the next; `off` is
+// the word offset inside a record and advances by what was written.  The g.nq indices per proof are in dev_idx.
+// one initial oracle: the whole leaf (salts ride after the polynomial values), then its Merkle path.  shared: one oracle for all proofs of a batch
+int queries_oracle(glp_ctx *c, const ProveGeo &g, const glp_batch *b, bool shared, const u64 *dev_idx, u64 *dev_q, size_t stride, size_t qsec,
+                   size_t &off) {
+    const u32 ncol = b->ncols + b->salt;
+    GLP_TRY(merkle_gather_lde_rows(c, b->lde, ncol, g.lg, g.rb, dev_idx, g.nq, dev_q + off, stride, g.K, shared ? 0 : ncol * g.N, qsec));
+    off += ncol;
+    GLP_TRY(merkle_gather_paths(c, b->digests, g.N, g.cap_height, dev_idx, g.nq, dev_q + off, stride, 0, g.K, shared ? 0 : b->ndigests * 4, qsec));
+    off += 4 * (size_t)(g.lg + g.rb - g.cap_height);
+    return GLP_OK;
+}
+// every commit-phase layer: the evals of the leaf the index falls into, then its Merkle path
+int queries_layers(glp_ctx *c, const ProveGeo &g, const std::vector<FriLayer> &layers, const u64 *dev_idx, u64 *dev_q, size_t stride, size_t qsec,
+                   size_t &off) {
     u32 shift_bits = 0;
-    for (size_t r = 0; r < layers.size(); r++) {
-        const FriLayer &ly = layers[r];
+    for (const FriLayer &ly : layers) {
         const u32 arity = 1u << ly.ab;
         const size_t Lsz = (size_t)1 << ly.lgL, nleaves = Lsz >> ly.ab;
         shift_bits += ly.ab;
-        hipLaunchKernelGGL(k_fri_gather_leaf, dim3(nblk((size_t)nq * arity), K), dim3(256), 0, c->stream, ly.vals, ly.lgL, (u32)g.rb, ly.ab, dev_idx,
-                           shift_bits, nq, dev_q + off, stride, 2 * Lsz, qsec);
+        hipLaunchKernelGGL(k_fri_gather_leaf, dim3(nblk((size_t)g.nq * arity), g.K), dim3(256), 0, c->stream, ly.vals, ly.lgL, (u32)g.rb, ly.ab, dev_idx,
+                           shift_bits, g.nq, dev_q + off, stride, 2 * Lsz, qsec);
         GLP_HIP(hipGetLastError());
         off += 2 * (size_t)arity;
-        GLP_TRY(merkle_gather_paths(c, ly.dig, nleaves, g.cap_height, dev_idx, nq, dev_q + off, stride, shift_bits, K, ly.ndig * 4, qsec));
-        off += 4 * (size_t)L.step_depth[r];
+        GLP_TRY(merkle_gather_paths(c, ly.dig, nleaves, g.cap_height, dev_idx, g.nq, dev_q + off, stride, shift_bits, g.K, ly.ndig * 4, qsec));
+        off += 4 * (size_t)(ly.lgL - ly.ab - g.cap_height);
     }
+    return GLP_OK;
+}
+// the four initial oracles of a circuit's proof(s), then the layers
+int stage_queries(glp_ctx *c, const ProveGeo &g, const glp_batch *const ob[4], const std::vector<FriLayer> &layers, const u64 *dev_idx,
+                  u64 *dev_q, size_t stride, size_t qsec) {
+    size_t off = 0;
+    for (int b = 0; b < 4; b++) GLP_TRY(queries_oracle(c, g, ob[b], b == 0, dev_idx, dev_q, stride, qsec, off));
+    GLP_TRY(queries_layers(c, g, layers, dev_idx, dev_q, stride, qsec, off));
     if (off != stride) return set_error(GLP_ERR_ARG, "internal: query record layout mismatch");
     return GLP_OK;
 }
