@@ -163,6 +163,30 @@ GLP_API int glp_batch_merkle_proof(const glp_batch *b, uint64_t leaf_index, uint
 GLP_API size_t glp_batch_num_digests(const glp_batch *b);
 GLP_API int glp_batch_digests(const glp_batch *b, uint64_t *out);
 
+/* ---- many-proof batches: num_proofs PolynomialBatches of one shape, built and held as one object ---------------------------------
+ * The commitments of num_proofs proofs of one circuit that advance in lock step (glp_fri_begin_many below): one transform and one
+ * Merkle launch over all of them instead of num_proofs glp_batch_from_* calls.
+ *   values / coeffs  [num_proofs][ncols][n], natural order; host memory, or (*_on_device != 0) an HBM pointer on the ctx's GPU
+ *   seed             NULL: no blinding.  Else 4 words: member k is salted with (seed0, seed1, seed2, seed3 + k) and tag
+ *                    GLP_SALT_TAG_BATCH, the rule of glp_prove_batch: member k is word for word
+ *                    glp_batch_from_values_salted(member k's values, .., {seed0, seed1, seed2, seed3 + k})
+ *   num_proofs       1..4096, and num_proofs * ncols * 2^(log_n + rate_bits) words at most 64 GiB (the cap of glp_prove_batch)
+ * glp_batch_info and glp_batch_leaf_len describe one member.  The accessors that read ONE tree (glp_batch_cap, _coeffs, _leaf,
+ * _merkle_proof, _digests) answer GLP_ERR_ARG for a batch of more than one member: take a member first. */
+GLP_API int glp_batch_many_from_values(glp_ctx *ctx, const uint64_t *values, int values_on_device, uint32_t num_proofs, uint32_t ncols,
+                                       uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, uint32_t hasher, const uint64_t *seed,
+                                       glp_batch **out);
+GLP_API int glp_batch_many_from_coeffs(glp_ctx *ctx, const uint64_t *coeffs, int coeffs_on_device, uint32_t num_proofs, uint32_t ncols,
+                                       uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, uint32_t hasher, const uint64_t *seed,
+                                       glp_batch **out);
+/* members of the batch: 1 for every glp_batch_from_* batch (0 for NULL) */
+GLP_API uint32_t glp_batch_num_proofs(const glp_batch *b);
+/* Member k as a batch of its own: a BORROWED view whose device pointers point into b.  Valid until b is freed; released with
+ * glp_batch_free, which frees no device memory for a view.  Every accessor above and glp_fri_begin / glp_fri_prove take it. */
+GLP_API int glp_batch_member(const glp_batch *b, uint32_t k, glp_batch **view_out);
+/* every member's merkle_tree.cap in one copy: [num_proofs][2^cap_height][4] */
+GLP_API int glp_batch_caps(const glp_batch *b, uint64_t *caps_out);
+
 /* ---- openings and FRI of caller-held batches (fri/oracle.rs `PolynomialBatch::prove_openings`) ----------------------------------
  * For an integrator that keeps its own quotient (circuits with lookup tables, Poseidon2Gate, custom gates, starky AIRs: anything
  * glp_circuit_create answers with GLP_ERR_UNSUPPORTED): commit with glp_batch_from_values / _from_coeffs, evaluate the committed
@@ -170,7 +194,8 @@ GLP_API int glp_batch_digests(const glp_batch *b, uint64_t *out);
  * the prover reads.  A point names its polynomials in the order of its ranges; that order is the order of the alpha powers and of
  * the openings.  With F = 0, for each point b in order (plonky2's combination rule, the coefficient-form `divide_by_linear`):
  *     F <- alpha^(len_b) F + (sum_j alpha^j p_{b,j}(X) - sum_j alpha^j p_{b,j}(z_b)) / (X - z_b),   j over that point's polynomials.
- * Many-proof batches (glp_prove_batch's K > 1 oracles) are GLP_ERR_UNSUPPORTED here. */
+ * Many proofs of one instance in lock step, over many-proof batches: glp_fri_begin_many / glp_fri_prove_many below; glp_fri_begin and
+ * glp_fri_prove answer GLP_ERR_UNSUPPORTED for a batch of more than one member (a glp_batch_member view is a batch of one). */
 #define GLP_FRI_MAX_ORACLES 8
 #define GLP_FRI_MAX_POINTS 4
 #define GLP_FRI_MAX_RANGES 16     /* per point */
@@ -226,6 +251,39 @@ GLP_API void glp_fri_end(glp_fri *f);
  * [2 * sum of the points' polynomial counts] is filled for the caller's proof (they are computed inside the call anyway). */
 GLP_API int glp_fri_prove(glp_ctx *ctx, const glp_fri_desc *desc, const uint64_t sponge_state[12], const uint64_t *pending_inputs,
                           uint32_t num_pending, uint64_t *openings_out, uint64_t *proof_out);
+
+/* ---- the same for num_proofs proofs of ONE instance in lock step ------------------------------------------------------------------
+ * What glp_prove_batch is to glp_prove, for circuits whose quotient stays with the caller: small proofs are bound by launch and host
+ * round-trip latency when proved one by one; here every step is a fixed number of launches over all proofs and one copy to or from
+ * the host.  desc is the description of one proof: ranges, arities, proof-of-work bits and query count are shared; desc->points[].point
+ * is ignored, proof k opens at points[k][0 .. num_points) (every proof has its own zeta).  Each oracle is either per proof
+ * (glp_batch_num_proofs == num_proofs: glp_batch_many_from_*) or shared by all proofs (a batch of one: preprocessed columns, as
+ * constants_sigmas is in glp_prove_batch); for num_proofs > 1 at least one is per proof.
+ * Errors beyond those of glp_fri_begin, all GLP_ERR_ARG naming the field unless said: num_proofs outside 1..4096; points null; an
+ * oracle whose member count is neither 1 nor num_proofs; only shared oracles; points[k][p] not canonical; points[k][p] on the coset
+ * g H is GLP_ERR_PROVE and names proof k.
+ * The handle takes the step functions above with a leading [num_proofs] on every array:
+ *   glp_fri_open         out: [num_proofs][glp_fri_num_openings][2]
+ *   glp_fri_combine      in:  alphas [num_proofs][2]
+ *   glp_fri_commit       out: [num_proofs][2^cap_height][4]          glp_fri_fold   in: betas [num_proofs][2]
+ *   glp_fri_final_poly   out: [num_proofs][glp_fri_final_poly_len][2]
+ *   glp_pow_search_many  (stateless) the num_proofs witnesses in one launch
+ *   glp_fri_queries_many in:  pow_witnesses [num_proofs], indices [num_proofs][num_query_rounds]  (glp_fri_queries is GLP_ERR_ARG here)
+ *   glp_fri_proof        out: [num_proofs][glp_fri_proof_words]
+ * Proof k is word for word what glp_fri_prove returns for member k of every per-proof oracle (tests/test_gpu_fri_many.py). */
+GLP_API int glp_fri_begin_many(glp_ctx *ctx, const glp_fri_desc *desc, uint32_t num_proofs, const uint64_t *points /* [num_proofs][num_points][2] */,
+                               glp_fri **out);
+GLP_API uint32_t glp_fri_num_proofs(const glp_fri *f);                  /* 1 for a glp_fri_begin handle */
+GLP_API int glp_fri_queries_many(glp_fri *f, const uint64_t *pow_witnesses, const uint64_t *indices);
+/* glp_pow_search_h for num_proofs sponges with num_pending (< 8) buffered inputs each: sponge_states [num_proofs][12], pending_inputs
+ * [num_proofs][num_pending], witnesses_out [num_proofs], the smallest witness of each */
+GLP_API int glp_pow_search_many(glp_ctx *ctx, uint32_t hasher, uint32_t num_proofs, const uint64_t *sponge_states, const uint64_t *pending_inputs,
+                                uint32_t num_pending, uint32_t bits, uint64_t *witnesses_out);
+/* One-call form: glp_fri_prove's transcript order for each proof, the num_proofs transcripts on the context's host threads
+ * (GLP_HOST_THREADS, as glp_prove_batch).  sponge_states [num_proofs][12], pending_inputs [num_proofs][num_pending], openings_out
+ * [num_proofs][openings][2], proofs_out [num_proofs][FriProof words]. */
+GLP_API int glp_fri_prove_many(glp_ctx *ctx, const glp_fri_desc *desc, uint32_t num_proofs, const uint64_t *points, const uint64_t *sponge_states,
+                               const uint64_t *pending_inputs, uint32_t num_pending, uint64_t *openings_out, uint64_t *proofs_out);
 
 /* ---- circuits and whole proofs ------------------------------------------------------------------
  * glp_circuit_desc carries the parts of plonky2's CommonCircuitData / ProverOnlyCircuitData /

@@ -10,6 +10,7 @@ import ctypes as C
 import os
 import re
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -120,6 +121,9 @@ def load_library():
     }
     L.glp_batch_leaf_len.restype = u32
     L.glp_batch_leaf_len.argtypes = [vp]
+    for name in ("glp_batch_num_proofs", "glp_fri_num_proofs"):
+        getattr(L, name).restype = u32
+        getattr(L, name).argtypes = [vp]
     L.glp_proof_words.restype = sz
     L.glp_proof_words.argtypes = [vp]
     L.glp_proof_bytes_len.restype = sz
@@ -159,6 +163,14 @@ def load_library():
         "glp_fri_proof": [vp, vp],
         "glp_fri_end": [vp],
         "glp_fri_prove": [vp, C.POINTER(_FriDesc), vp, vp, u32, vp, vp],
+        "glp_batch_many_from_values": [vp, vp, C.c_int, u32, u32, u32, u32, u32, u32, vp, C.POINTER(vp)],
+        "glp_batch_many_from_coeffs": [vp, vp, C.c_int, u32, u32, u32, u32, u32, u32, vp, C.POINTER(vp)],
+        "glp_batch_member": [vp, u32, C.POINTER(vp)],
+        "glp_batch_caps": [vp, vp],
+        "glp_fri_begin_many": [vp, C.POINTER(_FriDesc), u32, vp, C.POINTER(vp)],
+        "glp_fri_queries_many": [vp, vp, vp],
+        "glp_pow_search_many": [vp, u32, u32, vp, vp, u32, u32, vp],
+        "glp_fri_prove_many": [vp, C.POINTER(_FriDesc), u32, vp, vp, vp, u32, vp, vp],
         "glp_verify": [vp, vp],
         "glp_verify_n": [vp, vp, sz],
         "glp_prove_batch": [vp, vp, u32, vp, C.c_int, vp, vp],
@@ -365,6 +377,24 @@ class Context:
     def batch_from_coeffs(self, coeffs, rate_bits=3, cap_height=4, hasher=0):
         return Batch._make(self, "glp_batch_from_coeffs_h", coeffs, rate_bits, cap_height, hasher)
 
+    def batch_many_from_values(self, values, rate_bits=3, cap_height=4, hasher=0, seed=None):
+        """glp_batch_many_from_values: values [num_proofs][ncols][n] -> one Batch of num_proofs members; seed (4 words): member k is
+        salted with seed3 + k"""
+        return Batch._make_many(self, "glp_batch_many_from_values", values, rate_bits, cap_height, hasher, seed)
+
+    def batch_many_from_coeffs(self, coeffs, rate_bits=3, cap_height=4, hasher=0, seed=None):
+        return Batch._make_many(self, "glp_batch_many_from_coeffs", coeffs, rate_bits, cap_height, hasher, seed)
+
+    def pow_search_many(self, hasher, sponge_states, pending_inputs, bits):
+        """glp_pow_search_many: sponge_states [K][12], pending_inputs [K][num_pending] (num_pending < 8) -> the K smallest witnesses"""
+        st = _a(sponge_states).reshape(-1, 12)
+        pend = _a(pending_inputs)
+        pend = pend.reshape(st.shape[0], pend.size // max(st.shape[0], 1))
+        out = np.zeros(st.shape[0], np.uint64)
+        _chk(load_library().glp_pow_search_many(self._h, int(hasher), st.shape[0], _p(st), _p(pend) if pend.size else None, pend.shape[1],
+                                                int(bits), _p(out)))
+        return out
+
     def keccak256(self, msgs):
         """Keccak-256 of equal-length byte strings on the GPU (glp_keccak256): list of bytes -> list of 32-byte digests."""
         msgs = [bytes(m) for m in msgs]
@@ -388,10 +418,46 @@ class Context:
 class Batch:
     """plonky2 `PolynomialBatch` resident on the GPU."""
 
-    def __init__(self, ctx, handle, ncols, log_n, rate_bits, cap_height, owner=None):
+    def __init__(self, ctx, handle, ncols, log_n, rate_bits, cap_height, owner=None, parent=None):
         self.ctx, self._h = ctx, handle
         self.ncols, self.log_n, self.rate_bits, self.cap_height = ncols, log_n, rate_bits, cap_height
         self._owner = owner        # a borrowed handle (Session.oracle): the owner frees it, and is kept alive meanwhile
+        self._parent = parent      # a member view (Batch.member): freed like any batch, its device memory is the parent's
+        self._views = weakref.WeakSet()    # views handed out by member(): they end with this batch
+
+    @classmethod
+    def _make_many(cls, ctx, fn, arr, rate_bits, cap_height, hasher, seed):
+        a = _a(arr)
+        if a.ndim != 3 or a.shape[2] & (a.shape[2] - 1) or a.shape[2] == 0:
+            raise GlpError(-1, "expected a [num_proofs][ncols][n] array, n a power of two")
+        sd = None if seed is None else _a(seed)
+        if sd is not None and sd.size != 4:
+            raise GlpError(-1, "the salt seed is 4 words")
+        K, ncols, n = a.shape
+        h = C.c_void_p()
+        _chk(getattr(load_library(), fn)(ctx._h, _p(a), 0, K, ncols, n.bit_length() - 1, rate_bits, cap_height, int(hasher),
+                                         None if sd is None else _p(sd), C.byref(h)))
+        return cls(ctx, h, ncols, n.bit_length() - 1, rate_bits, cap_height)
+
+    @property
+    def num_proofs(self):
+        """members of a many-proof batch (1 for every other batch)"""
+        return int(load_library().glp_batch_num_proofs(self._h))
+
+    def member(self, k):
+        """glp_batch_member: member k as a Batch of its own, a view into this one.  The view keeps this batch alive; free() of this
+        batch ends its views first (their handles become None, so a later use is a GlpError, not a stale pointer)"""
+        h = C.c_void_p()
+        _chk(load_library().glp_batch_member(self._h, int(k), C.byref(h)))
+        v = Batch(self.ctx, h, self.ncols, self.log_n, self.rate_bits, self.cap_height, parent=self)
+        self._views.add(v)
+        return v
+
+    def caps(self):
+        """every member's cap: [num_proofs][2^cap_height][4]"""
+        out = np.empty((self.num_proofs, 1 << self.cap_height, 4), np.uint64)
+        _chk(load_library().glp_batch_caps(self._h, _p(out)))
+        return out
 
     @classmethod
     def _make(cls, ctx, fn, arr, rate_bits, cap_height, hasher=0):
@@ -413,7 +479,11 @@ class Batch:
 
     def free(self):
         if self._h:
-            if self._owner is None and getattr(self.ctx, "_h", None):     # never touch a handle whose context is already gone
+            for v in list(self._views):
+                v.free()
+            if self._parent is not None:                                  # a view: only its host struct, no context needed
+                load_library().glp_batch_free(self._h)
+            elif self._owner is None and getattr(self.ctx, "_h", None):   # never touch a handle whose context is already gone
                 load_library().glp_batch_free(self._h)
             self._h = None
 
@@ -964,3 +1034,102 @@ def fri_prove(ctx, oracles, points, reduction_arity_bits, proof_of_work_bits, nu
     _chk(load_library().glp_fri_prove(ctx._h, C.byref(d), _p(st), _p(pend) if pend.size else None, pend.size, _p(openings), _p(proof)))
     del keep
     return openings[:nopen], proof
+
+
+class FriOpeningsMany:
+    """FriOpenings for num_proofs proofs of one instance in lock step (glp_fri_begin_many).  oracles: Batch objects, each with
+    num_proofs members (Context.batch_many_from_*) or with one (shared by all proofs); points: the ranges as for FriOpenings, their
+    (a, b) ignored; zs [num_proofs][len(points)][2]: every proof's own points.  Every step takes and returns arrays with a leading
+    [num_proofs]."""
+
+    def __init__(self, ctx, oracles, points, zs, reduction_arity_bits, proof_of_work_bits, num_query_rounds):
+        self.ctx = ctx
+        d, self._keep = _fri_desc_to_c(oracles, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds)
+        z = None if zs is None else _a(zs)
+        self.num_proofs = 0 if z is None else (z.shape[0] if z.ndim == 3 else -1)
+        if z is not None and (z.ndim != 3 or z.shape[1:] != (len(points), 2)):
+            raise GlpError(-1, "zs is [num_proofs][%d][2]" % len(points))
+        self._capn = 1 << oracles[0].cap_height if oracles else 1
+        self._h = C.c_void_p()
+        _chk(load_library().glp_fri_begin_many(ctx._h, C.byref(d), self.num_proofs, None if z is None or z.size == 0 else _p(z), C.byref(self._h)))
+        self._nq = int(num_query_rounds)
+
+    @property
+    def num_openings(self):
+        return load_library().glp_fri_num_openings(self._h)
+
+    def open(self):
+        out = np.empty((self.num_proofs, self.num_openings, 2), np.uint64)
+        _chk(load_library().glp_fri_open(self._h, _p(out)))
+        return out
+
+    def _ext(self, x, what):
+        a = _a(x)
+        if a.shape != (self.num_proofs, 2):
+            raise GlpError(-1, "%s is [num_proofs][2]" % what)
+        return a
+
+    def combine(self, alphas):
+        _chk(load_library().glp_fri_combine(self._h, _p(self._ext(alphas, "alphas"))))
+
+    def commit(self):
+        out = np.empty((self.num_proofs, self._capn, 4), np.uint64)
+        _chk(load_library().glp_fri_commit(self._h, _p(out)))
+        return out
+
+    def fold(self, betas):
+        _chk(load_library().glp_fri_fold(self._h, _p(self._ext(betas, "betas"))))
+
+    def final_poly(self):
+        L = load_library()
+        out = np.empty((self.num_proofs, L.glp_fri_final_poly_len(self._h), 2), np.uint64)
+        _chk(L.glp_fri_final_poly(self._h, _p(out)))
+        return out
+
+    def queries(self, pow_witnesses, indices):
+        w, idx = _a(pow_witnesses), _a(indices)
+        if w.shape != (self.num_proofs,) or idx.shape != (self.num_proofs, self._nq):
+            raise GlpError(-1, "pow_witnesses is [num_proofs], indices [num_proofs][num_query_rounds]")
+        _chk(load_library().glp_fri_queries_many(self._h, _p(w), _p(idx)))
+
+    def proof(self):
+        L = load_library()
+        out = np.zeros((self.num_proofs, L.glp_fri_proof_words(self._h)), np.uint64)
+        _chk(L.glp_fri_proof(self._h, _p(out)))
+        return out
+
+    def end(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                load_library().glp_fri_end(self._h)
+            self._h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.end()
+        except Exception:
+            pass
+
+
+def fri_prove_many(ctx, oracles, points, zs, reduction_arity_bits, proof_of_work_bits, num_query_rounds, sponge_states, pending_inputs=None):
+    """glp_fri_prove_many: num_proofs proofs of one instance in lock step, each resumed from its own duplex sponge (sponge_states
+    [num_proofs][12], pending_inputs [num_proofs][num_pending], num_pending < 8).  Returns (openings [num_proofs][count][2], FriProof
+    words [num_proofs][words])."""
+    d, keep = _fri_desc_to_c(oracles, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds)
+    z = _a(zs)
+    if z.ndim != 3 or z.shape[1:] != (len(points), 2):
+        raise GlpError(-1, "zs is [num_proofs][%d][2]" % len(points))
+    K = z.shape[0]
+    st = _a(sponge_states)
+    pend = np.zeros((K, 0), np.uint64) if pending_inputs is None else _a(pending_inputs)
+    pend = pend.reshape(K, pend.size // max(K, 1))
+    if st.shape != (K, 12) or pend.shape[1] >= 8:
+        raise GlpError(-1, "sponge_states is [num_proofs][12], with fewer than 8 pending inputs per proof")
+    nopen = sum(int(nc) for _, ranges in points for _, _, nc in ranges)
+    openings = np.zeros((K, max(nopen, 1), 2), np.uint64)
+    proofs = np.zeros((K, fri_proof_words(oracles, reduction_arity_bits, num_query_rounds) if oracles else 1), np.uint64)
+    _chk(load_library().glp_fri_prove_many(ctx._h, C.byref(d), K, _p(z) if z.size else None, _p(st), _p(pend) if pend.size else None,
+                                           pend.shape[1], _p(openings), _p(proofs)))
+    del keep
+    return openings[:, :nopen], proofs

@@ -385,6 +385,7 @@ namespace glp {
 
 void batch_destroy(glp_batch *b) {
     if (!b) return;
+    if (b->view) { delete b; return; }
     glp_ctx *c = b->ctx;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
@@ -418,8 +419,10 @@ int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg
         GLP_TRY(c->alloc((void **)&b->lde, (size_t)K * leaf_len * N * 8));
         GLP_TRY(c->alloc((void **)&b->digests, (size_t)K * b->ndigests * 32));
         if (input_kind == BATCH_VALUES) GLP_TRY(intt_values_to_coeffs(c, dev_in, b->coeffs, (u32)tot, lg));
-        else if (input_kind == BATCH_COEFFS_NATURAL) GLP_TRY(bitrev_copy(c, dev_in, b->coeffs, (u32)tot, lg));
-        else GLP_HIP(hipMemcpyAsync(b->coeffs, dev_in, tot * n * 8, hipMemcpyDeviceToDevice, c->stream));
+        else if (input_kind == BATCH_COEFFS_NATURAL) {
+            for (size_t c0 = 0; c0 < tot; c0 += 65535)        // bitrev_copy keeps the column in grid.y
+                GLP_TRY(bitrev_copy(c, dev_in + c0 * n, b->coeffs + c0 * n, (u32)std::min<size_t>(65535, tot - c0), lg));
+        } else GLP_HIP(hipMemcpyAsync(b->coeffs, dev_in, tot * n * 8, hipMemcpyDeviceToDevice, c->stream));
         if (!b->salt) {
             GLP_TRY(lde_coeffs(c, b->coeffs, b->lde, (u32)tot, lg, rate_bits, glf::GEN));
         } else {
@@ -528,9 +531,78 @@ static int batch_from_host(glp_ctx *c, const u64 *host, bool from_values, u32 nc
     return rc;
 }
 
+// glp_batch_many_from_*: K batches of one shape from [K][ncols][n], host or device memory
+static int batch_many(glp_ctx *c, const u64 *in, int on_device, bool from_values, u32 K, u32 ncols, u32 log_n, u32 rate_bits, u32 cap_height,
+                      u32 hasher, const u64 *seed, glp_batch **out) {
+    GLP_REQUIRE(c && in && out, "null argument");
+    *out = nullptr;
+    GLP_REQUIRE(K >= 1 && K <= 4096, "num_proofs = %u outside 1..4096", K);
+    if (log_n > (u32)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
+    GLP_REQUIRE(rate_bits <= 4, "rate_bits=%u outside 0..4", rate_bits);
+    GLP_REQUIRE(cap_height <= log_n + rate_bits, "cap_height=%u should be at most log2(leaves)=%u", cap_height, log_n + rate_bits);
+    GLP_REQUIRE(ncols > 0, "ncols must be positive");
+    GLP_REQUIRE((size_t)K * ncols * ((size_t)8 << (log_n + rate_bits)) <= ((size_t)64 << 30),
+                "batch too large (num_proofs * ncols * 2^(log_n + rate_bits) words)");
+    GLP_TRY(bind(c));
+    u64 s[4];
+    if (seed) for (int i = 0; i < 4; i++) s[i] = glf::canon(seed[i]);
+    const int kind = from_values ? BATCH_VALUES : BATCH_COEFFS_NATURAL;
+    const u64 *salt = seed ? s : nullptr;
+    if (on_device)
+        return batch_build(c, in, kind, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, nullptr, K, (int)hasher, salt, GLP_SALT_TAG_BATCH);
+    const size_t tot = ((size_t)K * ncols) << log_n;
+    void *d = nullptr;
+    GLP_TRY(c->alloc(&d, tot * 8));
+    int rc = GLP_OK;
+    const hipError_t e = hipMemcpyAsync(d, in, tot * 8, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
+    if (rc == GLP_OK)
+        rc = batch_build(c, (const u64 *)d, kind, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, nullptr, K, (int)hasher, salt, GLP_SALT_TAG_BATCH);
+    (void)hipStreamSynchronize(c->stream);
+    c->release(d);
+    return rc;
+}
+
 }  // namespace glp
 
+// the single-batch accessors read one tree: a many-proofs batch is taken apart with glp_batch_member first
+#define GLP_BATCH_SINGLE(B) \
+    GLP_REQUIRE((B)->K == 1, "a many-proof batch (K = %u): take one member with glp_batch_member, or all caps with glp_batch_caps", (B)->K)
+
 extern "C" {
+
+int glp_batch_many_from_values(glp_ctx *c, const uint64_t *values, int values_on_device, uint32_t num_proofs, uint32_t ncols, uint32_t log_n,
+                               uint32_t rate_bits, uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out) {
+    return batch_many(c, values, values_on_device, true, num_proofs, ncols, log_n, rate_bits, cap_height, hasher, seed, out);
+}
+int glp_batch_many_from_coeffs(glp_ctx *c, const uint64_t *coeffs, int coeffs_on_device, uint32_t num_proofs, uint32_t ncols, uint32_t log_n,
+                               uint32_t rate_bits, uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out) {
+    return batch_many(c, coeffs, coeffs_on_device, false, num_proofs, ncols, log_n, rate_bits, cap_height, hasher, seed, out);
+}
+uint32_t glp_batch_num_proofs(const glp_batch *b) { return b ? b->K : 0; }
+int glp_batch_member(const glp_batch *b, uint32_t k, glp_batch **view_out) {
+    GLP_REQUIRE(b && view_out, "null argument");
+    *view_out = nullptr;
+    GLP_REQUIRE(k < b->K, "glp_batch_member: k = %u, the batch has %u members", k, b->K);
+    const size_t n = (size_t)1 << b->lg, N = n << b->rate_bits;
+    glp_batch *v = new glp_batch(*b);
+    v->K = 1; v->view = true;
+    v->coeffs = b->coeffs + (size_t)k * b->ncols * n;
+    v->lde = b->lde + (size_t)k * (b->ncols + b->salt) * N;
+    v->digests = b->digests + (size_t)k * b->ndigests * 4;
+    *view_out = v;
+    return GLP_OK;
+}
+int glp_batch_caps(const glp_batch *b, uint64_t *caps_out) {
+    GLP_REQUIRE(b && caps_out, "null argument");
+    glp_ctx *c = b->ctx;
+    GLP_TRY(bind(c));
+    const size_t N = (size_t)1 << (b->lg + b->rate_bits), capb = (size_t)32 << b->cap_height;
+    GLP_HIP(hipMemcpy2DAsync(caps_out, capb, b->digests + 4 * merkle_cap_offset(N, b->cap_height), b->ndigests * 32, capb, b->K,
+                             hipMemcpyDeviceToHost, c->stream));
+    GLP_HIP(hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
 
 int glp_batch_from_values(glp_ctx *c, const uint64_t *values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
                           uint32_t cap_height, glp_batch **out) {
@@ -583,6 +655,7 @@ uint32_t glp_batch_leaf_len(const glp_batch *b) { return b ? b->ncols + b->salt 
 
 int glp_batch_cap(const glp_batch *b, uint64_t *cap_out) {
     GLP_REQUIRE(b && cap_out, "null argument");
+    GLP_BATCH_SINGLE(b);
     glp_ctx *c = b->ctx;
     GLP_TRY(bind(c));
     const size_t N = (size_t)1 << (b->lg + b->rate_bits);
@@ -594,6 +667,7 @@ int glp_batch_cap(const glp_batch *b, uint64_t *cap_out) {
 
 int glp_batch_coeffs(const glp_batch *b, uint32_t col_begin, uint32_t ncols, uint64_t *out) {
     GLP_REQUIRE(b && (out || !ncols), "null argument");
+    GLP_BATCH_SINGLE(b);
     GLP_REQUIRE((u64)col_begin + ncols <= b->ncols, "column range out of bounds");
     if (!ncols) return GLP_OK;
     glp_ctx *c = b->ctx;
@@ -610,6 +684,7 @@ int glp_batch_coeffs(const glp_batch *b, uint32_t col_begin, uint32_t ncols, uin
 
 int glp_batch_leaf(const glp_batch *b, uint64_t leaf_index, uint64_t *out) {
     GLP_REQUIRE(b && out, "null argument");
+    GLP_BATCH_SINGLE(b);
     const size_t N = (size_t)1 << (b->lg + b->rate_bits);
     GLP_REQUIRE(leaf_index < N, "leaf_index out of range");
     glp_ctx *c = b->ctx;
@@ -628,6 +703,7 @@ int glp_batch_leaf(const glp_batch *b, uint64_t leaf_index, uint64_t *out) {
 
 int glp_batch_merkle_proof(const glp_batch *b, uint64_t leaf_index, uint64_t *siblings_out) {
     GLP_REQUIRE(b, "null argument");
+    GLP_BATCH_SINGLE(b);
     const size_t N = (size_t)1 << (b->lg + b->rate_bits);
     GLP_REQUIRE(leaf_index < N, "leaf_index out of range");
     const int depth = b->lg + b->rate_bits - b->cap_height;
@@ -650,6 +726,7 @@ size_t glp_batch_num_digests(const glp_batch *b) { return b ? b->ndigests : 0; }
 
 int glp_batch_digests(const glp_batch *b, uint64_t *out) {
     GLP_REQUIRE(b && out, "null argument");
+    GLP_BATCH_SINGLE(b);
     glp_ctx *c = b->ctx;
     GLP_TRY(bind(c));
     GLP_HIP(hipMemcpyAsync(out, b->digests, b->ndigests * 32, hipMemcpyDeviceToHost, c->stream));

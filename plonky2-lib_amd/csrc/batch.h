@@ -12,7 +12,8 @@ struct glp_batch {
     u64 *digests = nullptr;   // [ndigests][4]  level 0 (leaf j at slot j) ... cap level
     size_t ndigests = 0;
     int hasher = GLP_HASH_POSEIDON;   // GenericConfig::Hasher of the tree
-    u32 K = 1;                // many-proofs batches (glp_prove_batch): K independent oracles of identical shape, arrays [K][...]
+    u32 K = 1;                // many-proofs batches (glp_prove_batch, glp_batch_many_from_*): K independent oracles of identical shape, arrays [K][...]
+    bool view = false;        // glp_batch_member: a K = 1 window into a many-proofs batch; the pointers belong to the parent
 };
 
 namespace glp {

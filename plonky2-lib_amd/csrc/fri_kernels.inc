@@ -215,6 +215,182 @@ __global__ __launch_bounds__(256) void k_fri_combine(FCArgs a) {
     }
     a.out[q] = f.a; a.out[n + q] = f.b;
 }
+
+// ---- the many-proof form of K8 (glp_fri_begin_many): K proofs of one instance in lock step, blockIdx.y = proof.
+// The column program is shared by all proofs; a column's plane advances by `stride` words per proof (0: an oracle all proofs
+// share, else (ncols + salt) N of its oracle).  What k_fri_combine takes as kernel arguments comes per proof from device tables
+// that k_fri_table fills: apow [K][nopen] ext, pp [K][FCM_PP_WORDS] = red[NP], z[NP], shift[NP] (ext each).  Every table address
+// is made of kernel arguments and blockIdx.y only, so the reads stay scalar.
+struct FCColM { const u64 *plane; size_t stride; u32 ap[GLP_FRI_MAX_POINTS]; };
+constexpr u32 FCM_PP_WORDS = 6 * GLP_FRI_MAX_POINTS;
+struct FCMArgs {
+    const FCColM *prog; u32 nprog, npoints;
+    const u64 *apow;            // [K][nopen] ext alpha powers of proof k, indexed by FCColM::ap
+    const u64 *pp;              // [K][FCM_PP_WORDS]
+    u64 *out;                   // [K][2][n]
+    size_t nopen;
+    u64 w_n, g;
+    u32 lg;
+};
+// pp of one proof: part 0 = red_b, 1 = z_b, 2 = shift_b
+__device__ __forceinline__ ext2 fcm_pp(const u64 *pp, int part, int b) {
+    return e_make(pp[2 * (part * GLP_FRI_MAX_POINTS + b)], pp[2 * (part * GLP_FRI_MAX_POINTS + b) + 1]);
+}
+// 2^8 points per proof and more: k_fri_combine with the proof in blockIdx.y
+__global__ __launch_bounds__(256) void k_fri_combine_many(FCMArgs a) {
+    constexpr int NP = GLP_FRI_MAX_POINTS;
+    const size_t n = (size_t)1 << a.lg, pk = blockIdx.y;
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const u64 *apow = a.apow + pk * 2 * a.nopen, *pp = a.pp + pk * FCM_PP_WORDS;
+    ext2 sum[NP];
+    AccLimb xa[NP], xb[NP];
+#pragma unroll
+    for (int b = 0; b < NP; b++) { sum[b] = e_from(0); acc2_zero(xa[b]); acc2_zero(xb[b]); }
+    u32 terms = 0;
+    for (u32 e0 = 0; e0 < a.nprog; e0 += 4) {
+        u64 v[4];
+#pragma unroll
+        for (u32 i = 0; i < 4; i++) v[i] = e0 + i < a.nprog ? a.prog[e0 + i].plane[pk * a.prog[e0 + i].stride + q] : 0;
+#pragma unroll
+        for (u32 i = 0; i < 4; i++) {
+            if (e0 + i >= a.nprog) break;
+            const u32 v0 = (u32)v[i] & 0x3FFFFFu, v1 = (u32)(v[i] >> 22) & 0x3FFFFFu, v2 = (u32)(v[i] >> 44);
+#pragma unroll
+            for (int b = 0; b < NP; b++) {
+                const u32 j = a.prog[e0 + i].ap[b];
+                if (j != FC_ABSENT) { acc2_fma(xa[b], v0, v1, v2, apow[2 * (size_t)j]); acc2_fma(xb[b], v0, v1, v2, apow[2 * (size_t)j + 1]); }
+            }
+        }
+        if ((terms += 4) == ACC_MAX_TERMS) {
+#pragma unroll
+            for (int b = 0; b < NP; b++) {
+                sum[b] = e_add(sum[b], e_make(acc2_reduce(xa[b]), acc2_reduce(xb[b])));
+                acc2_zero(xa[b]); acc2_zero(xb[b]);
+            }
+            terms = 0;
+        }
+    }
+    const ext2 x = e_from(mul(a.g, dpow(a.w_n, q)));
+    ext2 f = e_from(0);
+#pragma unroll
+    for (int b = 0; b < NP; b++) {
+        if ((u32)b >= a.npoints) break;
+        const ext2 s = e_add(sum[b], e_make(acc2_reduce(xa[b]), acc2_reduce(xb[b])));
+        f = e_add(e_mul(f, fcm_pp(pp, 2, b)), e_mul(e_sub(s, fcm_pp(pp, 0, b)), e_inv(e_sub(x, fcm_pp(pp, 1, b)))));
+    }
+    u64 *out = a.out + pk * 2 * n;
+    out[q] = f.a; out[n + q] = f.b;
+}
+// 4 .. 128 points per proof (where batches of small proofs live): one workgroup per proof, lpp = 256 / n lanes share a point.  Lane t
+// of a point takes the program entries t, t + lpp, ..; an xor-butterfly inside the group (lpp <= 64: one wavefront) adds the partial
+// sums of every point up, lane b % lpp of the group inverts x - z_b, and lane 0 finishes.  A lane's slice of the program is its own,
+// so the program and the powers are vector loads here; the per-proof table stays scalar.  Unlike k_final_values_small a lane
+// flushes its carry-free accumulators every ACC_MAX_TERMS entries: an instance may name any number of columns.
+__global__ __launch_bounds__(256) void k_fri_combine_many_small(FCMArgs a) {
+    constexpr int NP = GLP_FRI_MAX_POINTS;
+    const u32 n = 1u << a.lg, lpp = 256u >> a.lg;            // lanes per point: 2 .. 64
+    const size_t pk = blockIdx.y;
+    const u32 q = threadIdx.x / lpp, t = threadIdx.x % lpp;
+    const u64 *apow = a.apow + pk * 2 * a.nopen, *pp = a.pp + pk * FCM_PP_WORDS;
+    ext2 sum[NP];
+    AccLimb xa[NP], xb[NP];
+#pragma unroll
+    for (int b = 0; b < NP; b++) { sum[b] = e_from(0); acc2_zero(xa[b]); acc2_zero(xb[b]); }
+    u32 terms = 0;
+    for (u32 e = t; e < a.nprog; e += lpp) {
+        const FCColM col = a.prog[e];
+        const u64 v = col.plane[pk * col.stride + q];
+        const u32 v0 = (u32)v & 0x3FFFFFu, v1 = (u32)(v >> 22) & 0x3FFFFFu, v2 = (u32)(v >> 44);
+#pragma unroll
+        for (int b = 0; b < NP; b++) {
+            const u32 j = col.ap[b];
+            if (j != FC_ABSENT) { acc2_fma(xa[b], v0, v1, v2, apow[2 * (size_t)j]); acc2_fma(xb[b], v0, v1, v2, apow[2 * (size_t)j + 1]); }
+        }
+        if (++terms == ACC_MAX_TERMS) {
+#pragma unroll
+            for (int b = 0; b < NP; b++) {
+                sum[b] = e_add(sum[b], e_make(acc2_reduce(xa[b]), acc2_reduce(xb[b])));
+                acc2_zero(xa[b]); acc2_zero(xb[b]);
+            }
+            terms = 0;
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NP; b++) {
+        sum[b] = e_add(sum[b], e_make(acc2_reduce(xa[b]), acc2_reduce(xb[b])));
+        for (u32 m = lpp >> 1; m >= 1; m >>= 1)
+            sum[b] = e_add(sum[b], e_make(pos::shfl_xor64(sum[b].a, (int)m), pos::shfl_xor64(sum[b].b, (int)m)));
+    }
+    // 1 / (x - z_b) on lane b % lpp, slot b / lpp (two slots only when two lanes share a point: n = 128)
+    const ext2 x = e_from(mul(a.g, dpow(a.w_n, q)));
+    ext2 dinv[2];
+#pragma unroll
+    for (u32 s = 0; s < 2; s++) {
+        const u32 b = t + s * lpp;
+        dinv[s] = b < a.npoints ? e_inv(e_sub(x, e_make(pp[2 * (NP + b)], pp[2 * (NP + b) + 1]))) : e_from(0);
+    }
+    const int lane0 = (int)((threadIdx.x & 63u) - t);
+    ext2 f = e_from(0);
+#pragma unroll
+    for (int b = 0; b < NP; b++) {
+        if ((u32)b >= a.npoints) break;
+        const ext2 mine = (u32)b / lpp ? dinv[1] : dinv[0];
+        const int src = lane0 + (int)((u32)b % lpp);
+        const ext2 d = e_make(pos::shfl64(mine.a, src), pos::shfl64(mine.b, src));
+        f = e_add(e_mul(f, fcm_pp(pp, 2, b)), e_mul(e_sub(sum[b], fcm_pp(pp, 0, b)), d));
+    }
+    if (t == 0) {
+        u64 *out = a.out + pk * 2 * n;
+        out[q] = f.a; out[n + q] = f.b;
+    }
+}
+// the openings of all proofs from k_open_dot's partial sums (open_batch_finish on the device): partial [count][nob] ext -> open [count] ext
+__global__ __launch_bounds__(256) void k_fri_open_finish(const u64 *partial, u64 *open, size_t count, u32 nob) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    u64 sa = 0, sb = 0;
+    for (u32 k = 0; k < nob; k++) { sa = add(sa, partial[2 * (i * nob + k)]); sb = add(sb, partial[2 * (i * nob + k) + 1]); }
+    open[2 * i] = sa; open[2 * i + 1] = sb;
+}
+// the per-proof tables of k_fri_combine_many* (the host loop of glp_fri::combine_into, on the device): workgroup (b, k) walks the
+// len_b polynomials of point b for proof k, 256 lanes a chunk each from alpha_k^(chunk start): apow[k][first_b + j] = alpha_k^j,
+// red_b = sum_j alpha_k^j open[k][first_b + j], shift_b = alpha_k^(len_b), z_b copied next to them.
+struct FTArgs {
+    const u64 *alpha;           // [K] ext
+    const u64 *open;            // [K][nopen] ext
+    const u64 *z;               // [K][npoints] ext
+    u64 *apow, *pp;             // [K][nopen] ext, [K][FCM_PP_WORDS]
+    size_t nopen;
+    u32 first[GLP_FRI_MAX_POINTS], len[GLP_FRI_MAX_POINTS];
+};
+__global__ __launch_bounds__(256) void k_fri_table(FTArgs a) {
+    constexpr int NP = GLP_FRI_MAX_POINTS;
+    __shared__ u64 sa[256], sb[256];
+    const u32 b = blockIdx.x, t = threadIdx.x, npoints = gridDim.x;
+    const size_t pk = blockIdx.y;
+    const ext2 alpha = e_make(a.alpha[2 * pk], a.alpha[2 * pk + 1]);
+    const u32 first = a.first[b], len = a.len[b], chunk = (len + 255) / 256;
+    const u64 *open = a.open + 2 * (pk * a.nopen + first);
+    u64 *apow = a.apow + 2 * (pk * a.nopen + first);
+    const u32 j0 = t * chunk < len ? t * chunk : len, j1 = j0 + chunk < len ? j0 + chunk : len;
+    ext2 x = e_pow(alpha, j0), red = e_from(0);
+    for (u32 j = j0; j < j1; j++) {
+        apow[2 * j] = x.a; apow[2 * j + 1] = x.b;
+        red = e_add(red, e_mul(x, e_make(open[2 * j], open[2 * j + 1])));
+        x = e_mul(x, alpha);
+    }
+    sa[t] = red.a; sb[t] = red.b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if ((int)t < s) { sa[t] = add(sa[t], sa[t + s]); sb[t] = add(sb[t], sb[t + s]); } __syncthreads(); }
+    if (t == 0) {
+        u64 *pp = a.pp + pk * FCM_PP_WORDS;
+        const ext2 shift = e_pow(alpha, len);
+        pp[2 * b] = sa[0]; pp[2 * b + 1] = sb[0];
+        pp[2 * (NP + b)] = a.z[2 * (pk * npoints + b)]; pp[2 * (NP + b) + 1] = a.z[2 * (pk * npoints + b) + 1];
+        pp[2 * (2 * NP + b)] = shift.a; pp[2 * (2 * NP + b) + 1] = shift.b;
+    }
+}
 // data[c][p] *= base^bitrev(p)
 __global__ __launch_bounds__(256) void k_scale_bitrev_pow(u64 *data, u64 base, u32 lg) {
     const size_t n = (size_t)1 << lg;

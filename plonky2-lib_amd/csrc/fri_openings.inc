@@ -6,6 +6,8 @@
 // else is the session's: k_zeta_table / k_open_dot on a coefficient pointer advanced to the range, fri_values_to_coeffs,
 // stage_fri_commit / stage_fri_fold, queries_oracle / queries_layers, pow_search.  The geometry those read comes from fri_geo
 // instead of a circuit.
+// The many-proof form (glp_fri_begin_many: K proofs of one instance in lock step) shares the handle, the checks and the step entry
+// points; its steps are the functions of fri_many.inc.
 #include <map>
 
 namespace {
@@ -45,20 +47,36 @@ struct glp_fri {
     std::vector<u64> words;            // the FriProof being assembled
     std::vector<u64> cap;
     enum Stage { S_NEW, S_OPEN, S_FRI, S_FINAL, S_DONE } stage = S_NEW;
+    // the many-proof form (fri_many.inc): g.K proofs, `words` and `cap` hold [K] of what they hold for one proof
+    bool many = false;
+    std::vector<u64> zs;               // [K][points][2]: every proof's own points (FriPointPlan::z is proof 0's)
+    u64 *dev_zs = nullptr, *dev_open = nullptr;        // zs on the device; the finished openings [K][nopen][2]
 
-    glp_fri(glp_ctx *ctx, const glp_fri_desc &d) : c(ctx), tmp(ctx) {
+    // points_many == nullptr: one proof at the description's points; else K proofs, proof k at points_many[k][num_points][2]
+    glp_fri(glp_ctx *ctx, const glp_fri_desc &d, u32 K = 1, const u64 *points_many = nullptr) : c(ctx), tmp(ctx), many(points_many != nullptr) {
         ob.assign(d.oracles, d.oracles + d.num_oracles);
         nred = d.num_reductions; pow_bits = d.proof_of_work_bits;
         for (u32 i = 0; i < nred; i++) arity_bits[i] = d.reduction_arity_bits[i];
         g = fri_geo(ob[0], arity_bits, d.num_query_rounds);
+        g.K = K;
+        if (many) zs.assign(points_many, points_many + (size_t)K * d.num_points * 2);
+        // two points share a zeta table when they are equal for every proof
+        auto same_point = [&](u32 e, u32 b) {
+            if (!many) return e_eq(pts[e].z, e_make(d.points[b].point[0], d.points[b].point[1]));
+            for (u32 k = 0; k < K; k++) {
+                const u64 *ze = &zs[((size_t)k * d.num_points + e) * 2], *zb = &zs[((size_t)k * d.num_points + b) * 2];
+                if (ze[0] != zb[0] || ze[1] != zb[1]) return false;
+            }
+            return true;
+        };
         for (u32 b = 0; b < d.num_points; b++) {
             FriPointPlan p;
-            p.z = e_make(d.points[b].point[0], d.points[b].point[1]);
+            p.z = many ? e_make(zs[2 * b], zs[2 * b + 1]) : e_make(d.points[b].point[0], d.points[b].point[1]);
             p.ranges.assign(d.points[b].ranges, d.points[b].ranges + d.points[b].num_ranges);
             for (const glp_fri_range &r : p.ranges) p.len += r.num_cols;
             p.first = nopen; nopen += p.len;
             p.table = b;
-            for (u32 e = 0; e < b; e++) if (e_eq(pts[e].z, p.z)) { p.table = e; break; }
+            for (u32 e = 0; e < b; e++) if (same_point(e, b)) { p.table = e; break; }
             pts.push_back(p);
         }
         const u32 lgN = (u32)(g.lg + g.rb), depth0 = lgN - (u32)g.cap_height;
@@ -72,7 +90,7 @@ struct glp_fri {
         o_final = o_queries + q * g.nq;
         o_pow = o_final + 2 * (size_t)final_len;
         total = o_pow + 1;
-        words.assign(total, 0);
+        words.assign((size_t)K * total, 0);
     }
     glp_fri(const glp_fri &) = delete;
 
@@ -224,7 +242,8 @@ struct glp_fri {
 };
 
 namespace {
-int fri_check(glp_ctx *c, const glp_fri_desc *d) {
+// num_proofs == 0: glp_fri_begin / glp_fri_prove (one proof at the description's points); else the many form at points_many[num_proofs][num_points][2]
+int fri_check(glp_ctx *c, const glp_fri_desc *d, u32 num_proofs = 0, const u64 *points_many = nullptr) {
     GLP_REQUIRE(d->num_oracles >= 1 && d->num_oracles <= GLP_FRI_MAX_ORACLES, "num_oracles = %u outside 1..%d", d->num_oracles, GLP_FRI_MAX_ORACLES);
     GLP_REQUIRE(d->oracles, "oracles is null");
     GLP_REQUIRE(d->num_points >= 1 && d->num_points <= GLP_FRI_MAX_POINTS, "num_points = %u outside 1..%d", d->num_points, GLP_FRI_MAX_POINTS);
@@ -233,12 +252,20 @@ int fri_check(glp_ctx *c, const glp_fri_desc *d) {
     for (u32 i = 0; i < d->num_oracles; i++) {
         const glp_batch *b = d->oracles[i];
         GLP_REQUIRE(b, "oracles[%u] is null", i);
-        if (b->K != 1) return set_error(GLP_ERR_UNSUPPORTED, "oracles[%u] is a many-proof batch (K = %u)", i, b->K);
+        if (!num_proofs && b->K != 1)
+            return set_error(GLP_ERR_UNSUPPORTED, "oracles[%u] is a many-proof batch (K = %u): glp_fri_begin_many proves those", i, b->K);
+        GLP_REQUIRE(!num_proofs || b->K == 1 || b->K == num_proofs,
+                    "oracles[%u]: K = %u, neither num_proofs = %u (an oracle per proof) nor 1 (one oracle shared by all proofs)", i, b->K, num_proofs);
         GLP_REQUIRE(b->ctx == c, "oracles[%u] belongs to another ctx", i);
         GLP_REQUIRE(b->lg == b0->lg, "oracles[%u]: log_n = %d, oracles[0] has %d", i, b->lg, b0->lg);
         GLP_REQUIRE(b->rate_bits == b0->rate_bits, "oracles[%u]: rate_bits = %d, oracles[0] has %d", i, b->rate_bits, b0->rate_bits);
         GLP_REQUIRE(b->cap_height == b0->cap_height, "oracles[%u]: cap_height = %d, oracles[0] has %d", i, b->cap_height, b0->cap_height);
         GLP_REQUIRE(b->hasher == b0->hasher, "oracles[%u]: hasher = %d, oracles[0] has %d", i, b->hasher, b0->hasher);
+    }
+    if (num_proofs > 1) {
+        bool per_proof = false;
+        for (u32 i = 0; i < d->num_oracles; i++) per_proof |= d->oracles[i]->K == num_proofs;
+        GLP_REQUIRE(per_proof, "oracles: every one is shared (K = 1), none has K = num_proofs = %u", num_proofs);
     }
     const u32 lg = (u32)b0->lg, lgN = lg + (u32)b0->rate_bits;
     const u64 gn = pow(GEN, (u64)1 << lg);
@@ -247,7 +274,7 @@ int fri_check(glp_ctx *c, const glp_fri_desc *d) {
         const glp_fri_point &pt = d->points[p];
         GLP_REQUIRE(pt.num_ranges <= GLP_FRI_MAX_RANGES, "points[%u].num_ranges = %u above %d", p, pt.num_ranges, GLP_FRI_MAX_RANGES);
         GLP_REQUIRE(pt.ranges || pt.num_ranges == 0, "points[%u].ranges is null", p);
-        GLP_REQUIRE(pt.point[0] < P && pt.point[1] < P, "points[%u].point is not canonical", p);
+        GLP_REQUIRE(num_proofs || (pt.point[0] < P && pt.point[1] < P), "points[%u].point is not canonical", p);
         size_t len = 0;
         for (u32 r = 0; r < pt.num_ranges; r++) {
             const glp_fri_range &rg = pt.ranges[r];
@@ -273,12 +300,20 @@ int fri_check(glp_ctx *c, const glp_fri_desc *d) {
                 d->proof_of_work_bits, POW_MAX_BITS);
     GLP_REQUIRE(d->num_query_rounds >= 1, "num_query_rounds = 0");
     // x - z must be invertible on coset plane 0 = g H: z = a + 0 X with (a / g)^n = 1 is a point of it
-    for (u32 p = 0; p < d->num_points; p++)
+    for (u32 p = 0; p < d->num_points && !num_proofs; p++)
         if (d->points[p].point[1] == 0 && pow(d->points[p].point[0], (u64)1 << lg) == gn)
             return set_error(GLP_ERR_PROVE, "points[%u] lies on the coset g H of the commitments", p);
+    for (u32 k = 0; k < num_proofs; k++)
+        for (u32 p = 0; p < d->num_points; p++) {
+            const u64 *z = points_many + ((size_t)k * d->num_points + p) * 2;
+            GLP_REQUIRE(z[0] < P && z[1] < P, "points[%u][%u] (proof %u) is not canonical", k, p, k);
+            if (z[1] == 0 && pow(z[0], (u64)1 << lg) == gn)
+                return set_error(GLP_ERR_PROVE, "points[%u][%u] (proof %u) lies on the coset g H of the commitments", k, p, k);
+        }
     return GLP_OK;
 }
 }  // namespace
+#include "fri_many.inc"
 
 extern "C" {
 int glp_session_oracle(glp_session *s, uint32_t index, const glp_batch **out) {
@@ -308,30 +343,34 @@ size_t glp_fri_proof_words(const glp_fri *f) { return f ? f->total : 0; }
 int glp_fri_open(glp_fri *f, uint64_t *openings_out) {
     GLP_FRI_ENTER(f);
     GLP_REQUIRE(openings_out, "null argument");
+    if (f->many) return fri_many_open(*f, openings_out);
     GLP_TRY(f->open_all());
     for (size_t k = 0; k < f->nopen; k++) { openings_out[2 * k] = f->open[k].a; openings_out[2 * k + 1] = f->open[k].b; }
     return GLP_OK;
 }
 int glp_fri_combine(glp_fri *f, const uint64_t alpha[2]) {
     GLP_FRI_ENTER(f);
+    if (f->many) return fri_many_combine(*f, alpha);
     GLP_REQUIRE(alpha && alpha[0] < P && alpha[1] < P, "alpha is null or not canonical");
     return f->combine(e_make(alpha[0], alpha[1]));
 }
 int glp_fri_commit(glp_fri *f, uint64_t *cap_out) {
     GLP_FRI_ENTER(f);
     GLP_REQUIRE(cap_out, "null argument");
-    GLP_TRY(f->commit_layer());
-    memcpy(cap_out, f->cap.data(), (size_t)f->g.capn * 32);
+    GLP_TRY(f->many ? fri_many_commit(*f) : f->commit_layer());
+    memcpy(cap_out, f->cap.data(), (size_t)f->g.K * f->g.capn * 32);
     return GLP_OK;
 }
 int glp_fri_fold(glp_fri *f, const uint64_t beta[2]) {
     GLP_FRI_ENTER(f);
+    if (f->many) return fri_many_fold(*f, beta);
     GLP_REQUIRE(beta && beta[0] < P && beta[1] < P, "beta is null or not canonical");
     return f->fold(e_make(beta[0], beta[1]));
 }
 int glp_fri_final_poly(glp_fri *f, uint64_t *coeffs_out) {
     GLP_FRI_ENTER(f);
     GLP_REQUIRE(coeffs_out, "null argument");
+    if (f->many) return fri_many_final_poly(*f, coeffs_out);
     GLP_TRY(f->final_poly());
     memcpy(coeffs_out, f->words.data() + f->o_final, (size_t)f->final_len * 16);
     return GLP_OK;
@@ -339,13 +378,14 @@ int glp_fri_final_poly(glp_fri *f, uint64_t *coeffs_out) {
 int glp_fri_queries(glp_fri *f, uint64_t pow_witness, const uint64_t *indices, uint32_t num_indices) {
     GLP_FRI_ENTER(f);
     GLP_REQUIRE(indices, "null argument");
+    GLP_REQUIRE(!f->many, "glp_fri_queries: a many-proof handle takes one witness per proof: glp_fri_queries_many");
     return f->queries(pow_witness, indices, num_indices);
 }
 int glp_fri_proof(glp_fri *f, uint64_t *proof_out) {
     GLP_FRI_ENTER(f);
     GLP_REQUIRE(proof_out, "null argument");
     GLP_REQUIRE(f->stage == glp_fri::S_DONE, "the proof is not finished (call glp_fri_queries first)");
-    memcpy(proof_out, f->words.data(), f->total * 8);
+    memcpy(proof_out, f->words.data(), (size_t)f->g.K * f->total * 8);
     return GLP_OK;
 }
 void glp_fri_end(glp_fri *f) {

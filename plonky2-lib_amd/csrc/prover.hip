@@ -603,6 +603,6 @@ int glp_prove_staged(glp_ctx *c, const glp_circuit *cc, glp_witness *w, const ui
 }
 }  // extern "C"
 
-#include "fri_openings.inc"
 #include "prover_batch.inc"
+#include "fri_openings.inc"
 #include "prover_batch_dev.inc"

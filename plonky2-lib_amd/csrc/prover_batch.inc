@@ -22,6 +22,30 @@ int caps_to_host(glp_ctx *c, const u64 *dev_digests, size_t dig_stride_words, si
     return GLP_OK;
 }
 
+// K10 for K sponges at once: pst [K][12] (the pending inputs already in place), ppos [K] where the witness goes -> best [K], the smallest
+// witness of each (~0: none below 2^40).  One launch (Poseidon: k_pow_prepare + k_pow_batch2), one copy back.
+int pow_search_batch(glp_ctx *c, Tmp &tmp, int hasher, const std::vector<u64> &pst, const std::vector<u32> &ppos, u32 bits, std::vector<u64> &best) {
+    const u32 K = (u32)ppos.size();
+    u64 *dev_pst, *dev_best, *dev_ppos, *dev_next;
+    GLP_TRY(tmp.get(&dev_pst, pst.size()));
+    GLP_TRY(tmp.get(&dev_best, K));
+    GLP_TRY(tmp.get(&dev_next, K));
+    GLP_HIP(hipMemsetAsync(dev_next, 0, (size_t)K * 8, c->stream));
+    GLP_TRY(tmp.get(&dev_ppos, (K + 1) / 2));
+    GLP_TRY(h2d(c, dev_pst, pst.data(), pst.size() * 8));
+    GLP_TRY(h2d(c, dev_ppos, ppos.data(), (size_t)K * 4));
+    best.assign(K, ~0ull);
+    GLP_TRY(h2d(c, dev_best, best.data(), (size_t)K * 8));
+    // persistent workgroups, a few per CU; each walks the proofs until none has candidates left below its witness
+    if (hasher == GLP_HASH_KECCAK25)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pow_batch<GLP_HASH_KECCAK25>), dim3((unsigned)c->num_cus * 8), dim3(256), 0, c->stream, dev_pst,
+                           (const u32 *)dev_ppos, bits, (unsigned long long *)dev_best, (unsigned long long *)dev_next, K);
+    else
+        GLP_TRY(pow_batch_launch(c, tmp, dev_pst, (const u32 *)dev_ppos, bits, dev_best, dev_next, K));
+    GLP_HIP(hipGetLastError());
+    return d2h(c, best.data(), dev_best, (size_t)K * 8);
+}
+
 int prove_batch_impl(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *dev_wires, const u64 *public_inputs, u64 *proofs_out) {
     const glp_circuit_desc &d = cc->d;
     const Layout &L = cc->L;
@@ -203,26 +227,8 @@ int prove_batch_impl(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *dev_wi
     });
     for (u32 k = 0; k < K; k++) GLP_REQUIRE(ppos[k] < 8, "proof of work: %u pending inputs (the rate is 8)", ppos[k]);
     mark("final poly + transcript 5 (host)");
-    u64 *dev_pst, *dev_best, *dev_ppos, *dev_next;
-    GLP_TRY(tmp.get(&dev_pst, pst.size()));
-    GLP_TRY(tmp.get(&dev_best, K));
-    GLP_TRY(tmp.get(&dev_next, K));
-    GLP_HIP(hipMemsetAsync(dev_next, 0, (size_t)K * 8, c->stream));
-    GLP_TRY(tmp.get(&dev_ppos, (K + 1) / 2));
-    GLP_TRY(h2d(c, dev_pst, pst.data(), pst.size() * 8));
-    GLP_TRY(h2d(c, dev_ppos, ppos.data(), (size_t)K * 4));
-    std::vector<u64> best(K, ~0ull);
-    GLP_TRY(h2d(c, dev_best, best.data(), (size_t)K * 8));
-    {
-        // persistent workgroups, a few per CU; each walks the proofs until none has candidates left below its witness
-        if (hasher == GLP_HASH_KECCAK25)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pow_batch<GLP_HASH_KECCAK25>), dim3((unsigned)c->num_cus * 8), dim3(256), 0, c->stream, dev_pst,
-                               (const u32 *)dev_ppos, d.proof_of_work_bits, (unsigned long long *)dev_best, (unsigned long long *)dev_next, K);
-        else
-            GLP_TRY(pow_batch_launch(c, tmp, dev_pst, (const u32 *)dev_ppos, d.proof_of_work_bits, dev_best, dev_next, K));
-        GLP_HIP(hipGetLastError());
-    }
-    GLP_TRY(d2h(c, best.data(), dev_best, (size_t)K * 8));
+    std::vector<u64> best;
+    GLP_TRY(pow_search_batch(c, tmp, hasher, pst, ppos, d.proof_of_work_bits, best));
     mark("proof of work");
     std::vector<u64> xi((size_t)K * nq);
     std::fill(err.begin(), err.end(), 0);

@@ -1,0 +1,375 @@
+"""glp_fri_begin_many / glp_fri_prove_many over many-proof batches: K proofs of one FRI instance in lock step (include/glp.h).
+Expected values never come from the code under test alone: the Python restatement tests/fri_restate.py (whose verifier must accept)
+and the K = 1 glp_fri_prove, on separately built single batches and on glp_batch_member views.
+A. members equal singles and the restatement   B. stepped equals one-call   C. accumulator flushes   D. views and batches   E. refusals"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import plonky2_lib_amd as glp
+from plonky2_lib_amd import binding
+import fri_restate as fr
+import zk_restate as zr
+from test_fri_openings import shape_b
+
+pytestmark = pytest.mark.gpu
+
+SEED = [11, 22, 33, 44]
+ACC_MAX_TERMS = 1024          # csrc/quotient_kernels.inc: the carry-free accumulators are flushed every so many terms
+K3 = 3                        # odd: no power-of-two stride hides an indexing error
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = glp.Context(0)
+    yield c
+    c.close()
+
+
+def _seed(k):
+    return SEED[:3] + [SEED[3] + k]
+
+
+_SALTS = {}
+
+
+def _salts(oracle, nleaves, k):
+    """salt columns of member k of a batch salted with SEED (computed once per size and member)"""
+    if (nleaves, k) not in _SALTS:
+        _SALTS[nleaves, k] = zr.salt_columns(oracle, SEED, zr.TAG_BATCH, nleaves, k)
+    return _SALTS[nleaves, k]
+
+
+class Many:
+    """K proofs of shape_b's instance: oracle 0 (5 columns) shared, oracle 1 (3, salted) and oracle 2 (41) per proof, every proof at
+    its own three points.  Holds the coefficients, the per-proof restated instances and the GPU batches (many and single)."""
+
+    def __init__(self, ctx, oracle, rng, K, log_n, arity_bits, cap_height, hasher=0, singles=True):
+        inst0, co, _ = shape_b(rng, oracle, log_n, arity_bits, cap_height, hasher=hasher)
+        self.K, self.ranges = K, [(z, r) for z, r in inst0.points]
+        n = 1 << log_n
+        self.co = [co[0], oracle.rand_field(rng, (K, 3, n)), oracle.rand_field(rng, (K, 41, n))]
+        self.zs = oracle.rand_field(rng, (K, 3, 2))
+        self.insts = [fr.Instance(log_n, inst0.rate_bits, cap_height, hasher, inst0.ncols, inst0.salted,
+                                  [(tuple(int(v) for v in self.zs[k][b]), r) for b, (_, r) in enumerate(inst0.points)], arity_bits,
+                                  inst0.pow_bits, inst0.nq) for k in range(K)]
+        i0 = self.insts[0]
+        self.params = (i0.arity_bits, i0.pow_bits, i0.nq)
+        rb = i0.rate_bits
+        vals1 = np.stack([np.stack([oracle.fft(c) for c in self.co[1][k]]) for k in range(K)])
+        self.shared = ctx.batch_from_coeffs(self.co[0], rb, cap_height, hasher)
+        self.many = [self.shared, ctx.batch_many_from_values(vals1, rb, cap_height, hasher, seed=SEED),
+                     ctx.batch_many_from_coeffs(self.co[2], rb, cap_height, hasher)]
+        self.single = [[self.shared, ctx.batch_from_values_salted(vals1[k], _seed(k), rb, cap_height, hasher),
+                        ctx.batch_from_coeffs(self.co[2][k], rb, cap_height, hasher)] for k in range(K)] if singles else []
+        self.ref = [[fr.commit(oracle, self.co[0], rb, cap_height, hasher),
+                     fr.commit(oracle, self.co[1][k], rb, cap_height, hasher, _salts(oracle, 1 << i0.lgN, k)),
+                     fr.commit(oracle, self.co[2][k], rb, cap_height, hasher)] for k in range(K)]
+
+    def views(self, k):
+        return [self.shared, self.many[1].member(k), self.many[2].member(k)]
+
+    def transcripts(self, oracle, rng, pending):
+        """one Challenger per proof, left with `pending` buffered inputs"""
+        out = []
+        for k in range(self.K):
+            ch = oracle.Challenger(self.insts[0].hasher)
+            if pending:
+                for o in self.ref[k]:
+                    ch.observe_hashes(o.cap)
+                have = fr.challenger_state(ch)[1].size
+                ch.observe(oracle.rand_field(rng, (pending - have) % 8 or 8))
+            else:
+                ch.observe(oracle.rand_field(rng, 16))       # fills the rate twice: nothing pending, the output buffer refilled
+            assert fr.challenger_state(ch)[1].size == pending
+            out.append(ch)
+        return out
+
+    def restated(self, oracle, chs):
+        """[(openings, FriProof words)] per proof from tests/fri_restate.py, accepted by its verifier"""
+        out = []
+        for k in range(self.K):
+            op, words = fr.prove_openings(oracle, self.insts[k], self.ref[k], fr.challenger_clone(oracle, chs[k]))
+            op = np.array(op, np.uint64)
+            assert fr.verify_fri_proof(oracle, self.insts[k], [o.cap for o in self.ref[k]], op, words, fr.challenger_clone(oracle, chs[k])) == 0
+            out.append((op, words))
+        return out
+
+    def free(self):
+        for b in self.many + [x for s in self.single for x in s[1:]]:
+            b.free()
+
+
+def _states(chs):
+    sp = [fr.challenger_state(ch) for ch in chs]
+    return np.stack([s for s, _ in sp]), np.stack([p for _, p in sp])
+
+
+def _same(got, want, what):
+    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
+    assert got.size == want.size, what
+    assert (got == want).all(), "%s: first mismatch at word %d" % (what, int(np.argmax(got != want)))
+
+
+# ------------------------------------------------------------------ A. members equal singles and the restatement
+# 2^3: the small-domain kernel; 2^5: one partly idle workgroup; 2^8: exactly one; 2^9: two.  The kernels switch between 2^7 and 2^8, so
+# 2^7 (two lanes per point: both inversion slots) and 2^2 (64 lanes per point) ride along.  [4] needs log_n >= 4.
+CASES_A = [(lg, ab, ch, 3) for lg in (3, 5, 8, 9) for ab in ([1, 2], [4]) for ch in (0, 2) if sum(ab) <= lg and (lg, ab, ch) != (5, [1, 2], 0)]
+CASES_A += [(5, [1, 2], 0, 0), (7, [1, 2], 0, 5), (2, [2], 0, 7)]
+
+
+@pytest.mark.parametrize("log_n,arity_bits,cap_height,pending", CASES_A)
+def test_members_equal_singles_and_restatement(ctx, oracle, log_n, arity_bits, cap_height, pending):
+    rng = np.random.default_rng(7000 + 100 * log_n + 10 * len(arity_bits) + cap_height)
+    m = Many(ctx, oracle, rng, K3, log_n, arity_bits, cap_height)
+    assert (m.many[1].caps() == np.stack([r[1].cap for r in m.ref])).all() and (m.many[2].caps() == np.stack([r[2].cap for r in m.ref])).all()
+    chs = m.transcripts(oracle, rng, pending)
+    want = m.restated(oracle, chs)
+    st, pend = _states(chs)
+    ops, proofs = glp.fri_prove_many(ctx, m.many, m.ranges, m.zs, *m.params, st, pend)
+    for k in range(K3):
+        _same(ops[k], want[k][0], "openings of proof %d against the restatement" % k)
+        _same(proofs[k], want[k][1], "FriProof of proof %d against the restatement" % k)
+        for name, obs in (("single batches", m.single[k]), ("member views", m.views(k))):
+            op1, proof1 = glp.fri_prove(ctx, obs, m.insts[k].points, *m.params, st[k], pend[k])
+            _same(ops[k], op1, "openings of proof %d against glp_fri_prove on %s" % (k, name))
+            _same(proofs[k], proof1, "FriProof of proof %d against glp_fri_prove on %s" % (k, name))
+    m.free()
+
+
+# ------------------------------------------------------------------ B. stepped equals one-call
+@pytest.mark.parametrize("hasher", [0, 1])
+def test_stepped_equals_one_call(ctx, oracle, hasher):
+    rng = np.random.default_rng(81 + hasher)
+    m = Many(ctx, oracle, rng, K3, 3, [1, 2], 0, hasher=hasher, singles=False)
+    chs = m.transcripts(oracle, rng, 3)
+    st, pend = _states(chs)
+    ops, proofs = glp.fri_prove_many(ctx, m.many, m.ranges, m.zs, *m.params, st, pend)
+    arity_bits, pow_bits, nq = m.params
+    if hasher == 1:                                          # part A runs under Poseidon only
+        for k, (op, words) in enumerate(m.restated(oracle, chs)):
+            _same(ops[k], op, "keccak openings %d" % k); _same(proofs[k], words, "keccak FriProof %d" % k)
+    f = glp.FriOpeningsMany(ctx, m.many, m.ranges, m.zs, arity_bits, pow_bits, nq)
+    _same(f.open(), ops, "stepped openings")
+    ch2 = [fr.challenger_clone(oracle, ch) for ch in chs]
+    f.combine([ch.get_ext() for ch in ch2])
+    capw = 4 << m.insts[0].cap_height
+    for r in range(len(arity_bits)):
+        caps = f.commit()
+        for k in range(K3):
+            _same(caps[k], proofs[k][r * capw:(r + 1) * capw], "layer %d cap of proof %d" % (r, k))
+            ch2[k].observe_hashes(caps[k])
+        f.fold([ch.get_ext() for ch in ch2])
+    fin = f.final_poly()
+    for k in range(K3):
+        ch2[k].observe(fin[k])
+    st2, pend2 = _states(ch2)
+    wit = ctx.pow_search_many(hasher, st2, pend2, pow_bits)
+    idx = []
+    for k in range(K3):
+        ch2[k].observe([int(wit[k])])
+        assert ch2[k].get() >> (64 - pow_bits) == 0
+        idx.append([ch2[k].get() % (1 << m.insts[0].lgN) for _ in range(nq)])
+    f.queries(wit, idx)
+    _same(f.proof(), proofs, "stepped FriProofs")
+    f.end()
+    m.free()
+
+
+# ------------------------------------------------------------------ C. accumulator flushes
+def _flush_case(ctx, oracle, rng, K, log_n, ncols, second, arity_bits, cap_height):
+    """one per-proof oracle of ncols columns; point 0 names all of them, point 1 the range `second` across a flush boundary"""
+    n = 1 << log_n
+    co = oracle.rand_field(rng, (K, ncols, n))
+    zs = oracle.rand_field(rng, (K, 2, 2))
+    ranges = [[(0, 0, ncols)], [second]]
+    insts = [fr.Instance(log_n, 3, cap_height, 0, [ncols], [False], [(tuple(int(v) for v in zs[k][b]), ranges[b]) for b in range(2)],
+                         arity_bits, 6, 2) for k in range(K)]
+    b = ctx.batch_many_from_coeffs(co, 3, cap_height)
+    chs, want = [], []
+    for k in range(K):
+        ref = [fr.commit(oracle, co[k], 3, cap_height)]
+        assert (b.member(k).cap() == ref[0].cap).all()
+        ch = oracle.Challenger(0)
+        ch.observe_hashes(ref[0].cap)
+        ch.observe(oracle.rand_field(rng, 3))
+        chs.append(ch)
+        op, words = fr.prove_openings(oracle, insts[k], ref, fr.challenger_clone(oracle, ch))
+        want.append((np.array(op, np.uint64), words))
+    st, pend = _states(chs)
+    ops, proofs = glp.fri_prove_many(ctx, [b], [((0, 0), r) for r in ranges], zs, arity_bits, 6, 2, st, pend)
+    for k in range(K):
+        _same(ops[k], want[k][0], "openings of proof %d" % k)
+        _same(proofs[k], want[k][1], "FriProof of proof %d" % k)
+    b.free()
+
+
+def test_flush_large_form(ctx, oracle):
+    """k_fri_combine_many (2^8 points and more; 2^8 here): ACC_MAX_TERMS + 8 columns, every lane walks all of them and crosses the flush"""
+    ncols = ACC_MAX_TERMS + 8
+    _flush_case(ctx, oracle, np.random.default_rng(5), 2, 8, ncols, (0, ACC_MAX_TERMS - 4, 12), [2, 1], 1)
+
+
+def test_flush_shape_of_the_single_form_test(ctx, oracle):
+    """K = 2 of test_more_columns_than_one_accumulator_flush's shape: 2^5 points, ACC_MAX_TERMS + 8 columns and its two points.  The
+    many form takes 2^5 points through the small kernel (8 lanes per point, 129 columns each), so this case pins the wide program
+    there; the flush of the large kernel is the case above, that of the small kernel the case below."""
+    ncols = ACC_MAX_TERMS + 8
+    _flush_case(ctx, oracle, np.random.default_rng(6), 2, 5, ncols, (0, ACC_MAX_TERMS - 4, 12), [2, 1], 1)
+
+
+def test_flush_small_form(ctx, oracle):
+    """k_fri_combine_many_small at 2^3 points: 256 / 8 = 32 lanes share a point and lane t takes the program entries t, t + 32, ..;
+    the program has one entry per column here, so 32 * ACC_MAX_TERMS + 40 columns give every lane 1025 or 1026 terms: each crosses
+    the flush.  The second point names 12 columns around column 32 * ACC_MAX_TERMS, the entries the flush falls on."""
+    lanes = 256 >> 3
+    ncols = lanes * ACC_MAX_TERMS + 40
+    assert ncols // lanes > ACC_MAX_TERMS
+    _flush_case(ctx, oracle, np.random.default_rng(8), 2, 3, ncols, (0, lanes * ACC_MAX_TERMS - 4, 12), [1, 2], 0)
+
+
+# ------------------------------------------------------------------ D. views and batches
+def test_views_and_batches(ctx, oracle):
+    rng = np.random.default_rng(9)
+    vals = oracle.rand_field(rng, (K3, 6, 16))
+    many = ctx.batch_many_from_values(vals, 3, 1, seed=SEED)
+    assert many.num_proofs == K3 and many.leaf_len == 10
+    caps = many.caps()
+    for k in range(K3):
+        single = ctx.batch_from_values_salted(vals[k], _seed(k), 3, 1)
+        v = many.member(k)
+        assert v.num_proofs == 1 and single.num_proofs == 1
+        assert (v.cap() == single.cap()).all() and (caps[k] == single.cap()).all()
+        assert (v.coeffs() == single.coeffs()).all() and (v.coeffs(2, 3) == single.coeffs(2, 3)).all()
+        assert (v.digests() == single.digests()).all()
+        for i in (0, 1, 77, 127):
+            assert (v.leaf(i) == single.leaf(i)).all() and (v.prove(i) == single.prove(i)).all()
+        v.free()                                             # a view: the parent's memory stays
+        single.free()
+    assert (many.caps() == caps).all() and (many.member(1).cap() == caps[1]).all()
+    for call in (many.cap, many.coeffs, lambda: many.leaf(0), lambda: many.prove(0), many.digests):
+        with pytest.raises(glp.GlpError) as e:
+            call()
+        assert e.value.code == -1 and "glp_batch_member" in str(e.value)
+    with pytest.raises(glp.GlpError) as e:
+        many.member(K3)
+    assert e.value.code == -1
+    plain = ctx.batch_many_from_coeffs(vals, 3, 1)           # unsalted, from coefficients
+    for k in range(K3):
+        single = ctx.batch_from_coeffs(vals[k], 3, 1)
+        assert (plain.member(k).digests() == single.digests()).all() and plain.leaf_len == 6
+        single.free()
+    one = ctx.batch_many_from_values(vals[:1], 3, 1, seed=SEED)      # one member: an ordinary batch
+    assert one.num_proofs == 1 and (one.cap() == caps[0]).all()
+    late = plain.member(2)
+    for b in (many, plain, one):
+        b.free()
+    with pytest.raises(glp.GlpError):                        # the parent's free() ended its views: an error, not a stale pointer
+        late.cap()
+
+
+@pytest.mark.parametrize("hasher", [0, 1])
+@pytest.mark.parametrize("bits", [0, 6])
+def test_pow_search_many_equals_singles(ctx, oracle, bits, hasher):
+    rng = np.random.default_rng(10 + bits)
+    K, L = 5, glp.load_library()
+    st, pend = oracle.rand_field(rng, (K, 12)), oracle.rand_field(rng, (K, 3))
+    got = ctx.pow_search_many(hasher, st, pend, bits)
+    for k in range(K):
+        w = C.c_uint64()
+        binding._chk(L.glp_pow_search_h(ctx._h, hasher, binding._p(st[k]), binding._p(pend[k]), 3, bits, C.byref(w)))
+        assert int(got[k]) == int(w.value)
+    assert (ctx.pow_search_many(hasher, st, np.zeros((K, 0), np.uint64), bits) >= 0).all()      # nothing pending
+
+
+# ------------------------------------------------------------------ E. refusals (all decided on the host, before any launch)
+def _refused(fn):
+    with pytest.raises(glp.GlpError) as e:
+        fn()
+    return e.value.code, str(e.value)
+
+
+def test_refusals(ctx, oracle):
+    rng = np.random.default_rng(12)
+    co = oracle.rand_field(rng, (3, 3, 32))
+    shared, m2, m3 = ctx.batch_from_coeffs(co[0], 3, 2), ctx.batch_many_from_coeffs(co[:2], 3, 2), ctx.batch_many_from_coeffs(co, 3, 2)
+    ranges = [((0, 0), [(0, 0, 3)]), ((0, 0), [(0, 1, 2)])]
+    zs = oracle.rand_field(rng, (3, 2, 2))
+
+    def begin(oracles, z, pts=ranges, arity=(2,)):
+        return _refused(lambda: glp.FriOpeningsMany(ctx, oracles, pts, z, list(arity), 4, 2))
+
+    glp.FriOpeningsMany(ctx, [m3], ranges, zs, [2], 4, 2).end()
+    glp.FriOpeningsMany(ctx, [shared], ranges, zs[:1], [2], 4, 2).end()      # one proof: its oracles are batches of one
+    for (oracles, z), code, fragment in [
+            (([m3], zs[:0]), -1, "num_proofs"), (([m3], np.zeros((4097, 2, 2), np.uint64)), -1, "num_proofs"),
+            (([m2, m3], zs), -1, "oracles[0]: K = 2"), (([m3, m2], zs), -1, "oracles[1]: K = 2"),
+            (([shared, shared], zs), -1, "shared"),
+            (([m3], zs[:2]), -1, "oracles[0]: K = 3"), (([shared, m2], zs), -1, "oracles[1]: K = 2")]:
+        got, msg = begin(oracles, z)
+        assert got == code and fragment in msg, (fragment, msg)
+    L, h = glp.load_library(), C.c_void_p()
+    d, keep = binding._fri_desc_to_c([m3], ranges, [2], 4, 2)
+    assert L.glp_fri_begin_many(ctx._h, C.byref(d), 3, None, C.byref(h)) == -1 and b"points" in L.glp_last_error() and not h.value
+    bad = zs.copy()
+    bad[1, 1, 0] = glp.P
+    code, msg = begin([m3], bad)
+    assert code == -1 and "canonical" in msg and "points[1][1]" in msg
+    bad = zs.copy()
+    bad[2, 0] = (7 * pow(oracle.root_of_unity(5), 3, glp.P) % glp.P, 0)
+    code, msg = begin([m3], bad)
+    assert code == -5 and "coset" in msg and "proof 2" in msg
+    bad[2, 0, 1] = 1                                         # the same a with b != 0 is a fine point
+    glp.FriOpeningsMany(ctx, [m3], ranges, bad, [2], 4, 2).end()
+    code, msg = begin([m3], zs, pts=[((0, 0), [(0, 2, 2)])] * 2)       # the checks of glp_fri_begin still hold
+    assert code == -1 and "ncols" in msg
+    code, msg = _refused(lambda: glp.FriOpenings(ctx, [m3], ranges, [2], 4, 2))
+    assert code == -3 and "glp_fri_begin_many" in msg
+    code, msg = _refused(lambda: glp.fri_prove(ctx, [shared, m3], ranges, [2], 4, 2, np.zeros(12, np.uint64)))
+    assert code == -3 and "oracles[1]" in msg
+    code, msg = _refused(lambda: glp.fri_prove_many(ctx, [m2, m3], ranges, zs, [2], 4, 2, np.zeros((3, 12), np.uint64)))
+    assert code == -1 and "K = 2" in msg
+    for b in (shared, m2, m3):
+        b.free()
+
+
+def test_steps_out_of_order_on_a_many_handle(ctx, oracle):
+    rng = np.random.default_rng(13)
+    K = 2
+    b = ctx.batch_many_from_coeffs(oracle.rand_field(rng, (K, 3, 32)), 3, 2)
+    f = glp.FriOpeningsMany(ctx, [b], [((0, 0), [(0, 0, 3)])], oracle.rand_field(rng, (K, 1, 2)), [2, 1], 0, 2)
+    ext = [[1, 2], [3, 4]]
+    L = glp.load_library()
+
+    def single_queries():
+        idx = np.array([1, 2], np.uint64)
+        binding._chk(L.glp_fri_queries(f._h, C.c_uint64(0), binding._p(idx), 2))
+
+    for early in (lambda: f.combine(ext), f.commit, lambda: f.fold(ext), f.final_poly, lambda: f.queries([0, 0], [[1, 2], [3, 4]]), f.proof):
+        assert _refused(early)[0] == -1
+    assert f.open().shape == (K, 3, 2)
+    for wrong in (f.open, f.commit, lambda: f.combine([[glp.P, 0], [1, 2]])):
+        assert _refused(wrong)[0] == -1
+    f.combine(ext)
+    assert _refused(lambda: f.fold(ext))[0] == -1            # no layer committed
+    assert f.commit().shape == (K, 4, 4)
+    for wrong in (f.commit, f.final_poly, lambda: f.fold([[1, 2], [0, glp.P]])):
+        assert _refused(wrong)[0] == -1
+    f.fold(ext); f.commit(); f.fold(ext)
+    for wrong in (f.commit, lambda: f.queries([0, 0], [[1, 2], [3, 4]])):
+        assert _refused(wrong)[0] == -1
+    assert f.final_poly().shape == (K, 4, 2)
+    code, msg = _refused(single_queries)
+    assert code == -1 and "glp_fri_queries_many" in msg
+    code, msg = _refused(lambda: f.queries([0, 0], [[1, 2], [3, 1 << 8]]))       # outside the LDE domain, for proof 1 only
+    assert code == -1 and "indices[1][1]" in msg
+    assert _refused(f.proof)[0] == -1
+    f.queries([0, 0], [[1, 255], [0, 7]])
+    assert f.proof().shape == (K, glp.fri_proof_words([b], [2, 1], 2))
+    f.end()
+    single = glp.FriOpenings(ctx, [b.member(0)], [((5, 9), [(0, 0, 3)])], [2, 1], 0, 2)
+    w, idx = np.zeros(1, np.uint64), np.zeros((1, 2), np.uint64)
+    assert L.glp_fri_queries_many(single._h, binding._p(w), binding._p(idx)) == -1 and b"glp_fri_queries" in L.glp_last_error()
+    single.end()
+    b.free()
