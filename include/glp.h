@@ -197,6 +197,7 @@ GLP_API int glp_batch_caps(const glp_batch *b, uint64_t *caps_out);
  * Many proofs of one instance in lock step, over many-proof batches: glp_fri_begin_many / glp_fri_prove_many below; glp_fri_begin and
  * glp_fri_prove answer GLP_ERR_UNSUPPORTED for a batch of more than one member (a glp_batch_member view is a batch of one). */
 #define GLP_FRI_MAX_ORACLES 8
+#define GLP_REASON_LEN 160     /* chars of one rejection reason (glp_verify_batch, glp_fri_verify*) */
 #define GLP_FRI_MAX_POINTS 4
 #define GLP_FRI_MAX_RANGES 16     /* per point */
 typedef struct { uint32_t oracle, col_begin, num_cols; } glp_fri_range;      /* polynomials [col_begin, col_begin+num_cols) of oracles[oracle] */
@@ -284,6 +285,60 @@ GLP_API int glp_pow_search_many(glp_ctx *ctx, uint32_t hasher, uint32_t num_proo
  * [num_proofs][openings][2], proofs_out [num_proofs][FriProof words]. */
 GLP_API int glp_fri_prove_many(glp_ctx *ctx, const glp_fri_desc *desc, uint32_t num_proofs, const uint64_t *points, const uint64_t *sponge_states,
                                const uint64_t *pending_inputs, uint32_t num_pending, uint64_t *openings_out, uint64_t *proofs_out);
+
+/* ---- verifying FRI proofs of caller-held instances (fri/verifier.rs `verify_fri_proof`) --------------------------------------------
+ * The other half of glp_fri_*: num_proofs FriProofs of ONE instance checked in one device launch, for the circuits whose quotient stays
+ * with the caller (no glp_circuit exists for them, so glp_verify_batch cannot take them).  The verifier holds no glp_batch, only caps,
+ * so it has a description of its own; it mirrors glp_fri_desc field for field where the two overlap and obeys the same shape rules.
+ *   glp_fri_oracle_shape  num_cols: polynomials of the oracle; salted != 0: a leaf carries GLP_SALT_SIZE salts after them (never
+ *                         named by a range); shared != 0: one cap for all proofs, else one per proof
+ *   points[].ranges       as in glp_fri_desc; points[].point is read only by glp_fri_verify
+ * Arrays (host memory), K = num_proofs:
+ *   points         [K][num_points][2]               proof k's opening points
+ *   caps           [num_oracles] pointers: [2^cap_height][4] for a shared oracle, else [K][2^cap_height][4] (glp_batch_caps)
+ *   openings       [K][glp_fri_verify_num_openings][2]   the claimed openings, order of glp_fri_open
+ *   proofs         [K][glp_fri_verify_proof_words]  layout of glp_fri_proof
+ *   status_out     [K]: GLP_OK = accepted, GLP_ERR_PROVE = rejected;   reasons_out  NULL or [K][GLP_REASON_LEN] (empty if accepted)
+ * The return value is that of glp_verify_batch: GLP_OK whenever every proof could be judged, whatever the verdicts.  A reason names the
+ * query round and the failed check and ends in "[check N]", N the stable number of the check (the return value of
+ * tests/fri_restate.py::verify_fri_proof); the reported failure is the first failing check of the first failing query:
+ *   1  a word that is not canonical (>= p; a KeccakHash<25> digest longer than 25 bytes) in proof, openings, caps or points
+ *   2  proof of work                          3  a query point equal to an opening point (rejected, never divided by zero)
+ *   4  an initial Merkle path                 5  a layer's evaluation disagrees with the previous fold
+ *   6  a layer's Merkle path                  7  final polynomial
+ * Per proof the canonical-form scan and the transcript run on the context's host threads (GLP_HOST_THREADS) beside the upload; every
+ * query round of every proof is one launch over K x num_query_rounds 16-lane groups, as in glp_verify_batch.
+ * GLP_ERR_ARG, naming the field: a count outside GLP_FRI_MAX_*; a range past num_cols; a point with no polynomial; arity bits outside
+ * 1..4 or summing above log_n; num_query_rounds = 0; num_proofs outside 1..65536; a null pointer; num_pending >= 8; an unknown hasher;
+ * (stepped form) an index >= 2^(log_n + rate_bits) or a challenge that is not canonical. */
+typedef struct { uint32_t num_cols, salted, shared; } glp_fri_oracle_shape;
+typedef struct {
+    uint32_t num_oracles;  const glp_fri_oracle_shape *oracles;
+    uint32_t log_n, rate_bits, cap_height, hasher;            /* what the prover's batches carry; hasher: GLP_HASH_* */
+    uint32_t num_points;   const glp_fri_point *points;
+    uint32_t num_reductions, reduction_arity_bits[16];
+    uint32_t proof_of_work_bits, num_query_rounds;
+} glp_fri_verify_desc;
+/* == glp_fri_proof_words / glp_fri_num_openings of the matching prover handle; 0 for a description the verifier refuses */
+GLP_API size_t glp_fri_verify_proof_words(const glp_fri_verify_desc *desc);
+GLP_API size_t glp_fri_verify_num_openings(const glp_fri_verify_desc *desc);
+/* One-call form: each proof's transcript resumes from (sponge_states[k], pending_inputs[k][num_pending]) exactly as glp_fri_prove's does
+ * (with num_pending = 0 the output buffer is refilled from the state).  Order: alpha; per reduction observe the cap, draw beta; observe
+ * the final polynomial; observe the witness; draw the response and check it against proof_of_work_bits; num_query_rounds indices,
+ * get() % N.  sponge_states [K][12], pending_inputs [K][num_pending]. */
+GLP_API int glp_fri_verify_many(glp_ctx *ctx, const glp_fri_verify_desc *desc, uint32_t num_proofs, const uint64_t *points,
+                                const uint64_t *const *caps, const uint64_t *openings, const uint64_t *proofs, const uint64_t *sponge_states,
+                                const uint64_t *pending_inputs, uint32_t num_pending, int32_t *status_out, char *reasons_out);
+/* Stepped form, for a caller that keeps its own Fiat-Shamir: it drew alphas [K][2], betas [K][num_reductions][2] and indices
+ * [K][num_query_rounds] and has checked the proof of work itself; the library does the canonical-form scan and every query check
+ * (checks 1 and 3..7).  The reduced openings are computed on the device from the uploaded openings. */
+GLP_API int glp_fri_verify_queries_many(glp_ctx *ctx, const glp_fri_verify_desc *desc, uint32_t num_proofs, const uint64_t *points,
+                                        const uint64_t *const *caps, const uint64_t *openings, const uint64_t *proofs, const uint64_t *alphas,
+                                        const uint64_t *betas, const uint64_t *indices, int32_t *status_out, char *reasons_out);
+/* One proof at desc->points[].point (caps [num_oracles] pointers to [2^cap_height][4] whatever `shared` says): GLP_OK = accepted,
+ * GLP_ERR_PROVE with the reason in glp_last_error() = rejected. */
+GLP_API int glp_fri_verify(glp_ctx *ctx, const glp_fri_verify_desc *desc, const uint64_t *const *caps, const uint64_t *openings,
+                           const uint64_t *proof, const uint64_t sponge_state[12], const uint64_t *pending_inputs, uint32_t num_pending);
 
 /* ---- circuits and whole proofs ------------------------------------------------------------------
  * glp_circuit_desc carries the parts of plonky2's CommonCircuitData / ProverOnlyCircuitData /
@@ -554,7 +609,6 @@ GLP_API int glp_verify_n(const glp_circuit *circuit, const uint64_t *proof_words
  * the canonical-form scan and the identity at zeta.  Environment variable GLP_VERIFY_HOST_TRANSCRIPT=1 (read per call): transcripts on host
  * threads, as under KeccakGoldilocksConfig.
  * Returns GLP_OK when the batch was checked (whatever the verdicts), an error code for bad arguments / HIP failures. */
-#define GLP_REASON_LEN 160
 GLP_API int glp_verify_batch(glp_ctx *ctx, const glp_circuit *circuit, uint32_t num_proofs, const uint64_t *proofs, int32_t *status_out,
                              char *reasons_out);
 

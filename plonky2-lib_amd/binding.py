@@ -56,6 +56,17 @@ class _FriDesc(C.Structure):
                 ("proof_of_work_bits", C.c_uint32), ("num_query_rounds", C.c_uint32)]
 
 
+class _FriOracleShape(C.Structure):
+    _fields_ = [("num_cols", C.c_uint32), ("salted", C.c_uint32), ("shared", C.c_uint32)]
+
+
+class _FriVerifyDesc(C.Structure):
+    _fields_ = [("num_oracles", C.c_uint32), ("oracles", C.POINTER(_FriOracleShape)), ("log_n", C.c_uint32), ("rate_bits", C.c_uint32),
+                ("cap_height", C.c_uint32), ("hasher", C.c_uint32), ("num_points", C.c_uint32), ("points", C.POINTER(_FriPoint)),
+                ("num_reductions", C.c_uint32), ("reduction_arity_bits", C.c_uint32 * 16), ("proof_of_work_bits", C.c_uint32),
+                ("num_query_rounds", C.c_uint32)]
+
+
 def library_path():
     return _SO
 
@@ -171,6 +182,9 @@ def load_library():
         "glp_fri_queries_many": [vp, vp, vp],
         "glp_pow_search_many": [vp, u32, u32, vp, vp, u32, u32, vp],
         "glp_fri_prove_many": [vp, C.POINTER(_FriDesc), u32, vp, vp, vp, u32, vp, vp],
+        "glp_fri_verify_many": [vp, C.POINTER(_FriVerifyDesc), u32, vp, C.POINTER(vp), vp, vp, vp, vp, u32, vp, vp],
+        "glp_fri_verify_queries_many": [vp, C.POINTER(_FriVerifyDesc), u32, vp, C.POINTER(vp), vp, vp, vp, vp, vp, vp, vp],
+        "glp_fri_verify": [vp, C.POINTER(_FriVerifyDesc), C.POINTER(vp), vp, vp, vp, vp, u32],
         "glp_verify": [vp, vp],
         "glp_verify_n": [vp, vp, sz],
         "glp_prove_batch": [vp, vp, u32, vp, C.c_int, vp, vp],
@@ -203,6 +217,9 @@ def load_library():
     for name in ("glp_fri_num_openings", "glp_fri_final_poly_len", "glp_fri_proof_words"):
         getattr(L, name).restype = sz
         getattr(L, name).argtypes = [vp]
+    for name in ("glp_fri_verify_proof_words", "glp_fri_verify_num_openings"):
+        getattr(L, name).restype = sz
+        getattr(L, name).argtypes = [C.POINTER(_FriVerifyDesc)]
     for name, argtypes in sigs.items():
         getattr(L, name).argtypes = argtypes
     L.glp_fri_end.restype = None
@@ -361,7 +378,9 @@ class Context:
         h = C.c_void_p()
         _chk(load_library().glp_batch_from_values_salted(self._h, _p(a), ncols, n.bit_length() - 1, rate_bits, cap_height, int(hasher),
                                                          _p(sd), C.byref(h)))
-        return Batch(self, h, ncols, n.bit_length() - 1, rate_bits, cap_height)
+        b = Batch(self, h, ncols, n.bit_length() - 1, rate_bits, cap_height)
+        b.hasher = int(hasher)
+        return b
 
     def set_salt_seed(self, seed=None):
         """glp_ctx_set_salt_seed: a fixed seed for the salts of zero-knowledge proofs (tests, reproducibility), None = a fresh OS seed
@@ -424,6 +443,7 @@ class Batch:
         self._owner = owner        # a borrowed handle (Session.oracle): the owner frees it, and is kept alive meanwhile
         self._parent = parent      # a member view (Batch.member): freed like any batch, its device memory is the parent's
         self._views = weakref.WeakSet()    # views handed out by member(): they end with this batch
+        self.hasher = 0                    # GLP_HASH_* of the tree; the constructors that take a hasher set it
 
     @classmethod
     def _make_many(cls, ctx, fn, arr, rate_bits, cap_height, hasher, seed):
@@ -437,7 +457,9 @@ class Batch:
         h = C.c_void_p()
         _chk(getattr(load_library(), fn)(ctx._h, _p(a), 0, K, ncols, n.bit_length() - 1, rate_bits, cap_height, int(hasher),
                                          None if sd is None else _p(sd), C.byref(h)))
-        return cls(ctx, h, ncols, n.bit_length() - 1, rate_bits, cap_height)
+        b = cls(ctx, h, ncols, n.bit_length() - 1, rate_bits, cap_height)
+        b.hasher = int(hasher)
+        return b
 
     @property
     def num_proofs(self):
@@ -450,6 +472,7 @@ class Batch:
         h = C.c_void_p()
         _chk(load_library().glp_batch_member(self._h, int(k), C.byref(h)))
         v = Batch(self.ctx, h, self.ncols, self.log_n, self.rate_bits, self.cap_height, parent=self)
+        v.hasher = self.hasher
         self._views.add(v)
         return v
 
@@ -469,7 +492,9 @@ class Batch:
             raise GlpError(-1, "n must be a power of two")
         h = C.c_void_p()
         _chk(getattr(load_library(), fn)(ctx._h, _p(a), ncols, n.bit_length() - 1, rate_bits, cap_height, int(hasher), C.byref(h)))
-        return cls(ctx, h, ncols, n.bit_length() - 1, rate_bits, cap_height)
+        b = cls(ctx, h, ncols, n.bit_length() - 1, rate_bits, cap_height)
+        b.hasher = int(hasher)
+        return b
 
     @classmethod
     def _make_dev(cls, ctx, fn, dev_ptr, ncols, log_n, rate_bits, cap_height):
@@ -1133,3 +1158,136 @@ def fri_prove_many(ctx, oracles, points, zs, reduction_arity_bits, proof_of_work
                                            pend.shape[1], _p(openings), _p(proofs)))
     del keep
     return openings[:, :nopen], proofs
+
+
+# ------------------------------------------------------------------ verifying FriProofs of caller-held instances (glp_fri_verify*)
+def _fri_verify_desc_to_c(shapes, points, log_n, rate_bits, cap_height, hasher, reduction_arity_bits, proof_of_work_bits, num_query_rounds,
+                          num_proofs=1):
+    """shapes: per oracle a (num_cols, salted, shared) triple or a live Batch (its shape; shared = it has one member and num_proofs is
+    larger); points as for FriOpenings.  A geometry argument left None is taken from the first Batch.  -> (glp_fri_verify_desc, keep)"""
+    if len(reduction_arity_bits) > 16:
+        raise GlpError(-1, "more than 16 FRI reductions")
+    first = next((s for s in shapes if isinstance(s, Batch)), None)
+    geo = []
+    for name, v in (("log_n", log_n), ("rate_bits", rate_bits), ("cap_height", cap_height)):
+        if v is None and first is None:
+            raise GlpError(-1, "%s is needed when no oracle is given as a Batch" % name)
+        geo.append(int(getattr(first, name) if v is None else v))
+    sh = (_FriOracleShape * max(1, len(shapes)))()
+    for i, s in enumerate(shapes):
+        if isinstance(s, Batch):
+            sh[i].num_cols, sh[i].salted, sh[i].shared = s.ncols, int(s.leaf_len != s.ncols), int(s.num_proofs == 1 and num_proofs > 1)
+        else:
+            sh[i].num_cols, sh[i].salted, sh[i].shared = int(s[0]), int(bool(s[1])), int(bool(s[2]))
+    fd, keep = _fri_desc_to_c([], points, reduction_arity_bits, proof_of_work_bits, num_query_rounds)
+    d = _FriVerifyDesc()
+    d.num_oracles, d.oracles = len(shapes), C.cast(sh, C.POINTER(_FriOracleShape))
+    d.log_n, d.rate_bits, d.cap_height = geo
+    d.hasher = int(getattr(first, "hasher", 0) if hasher is None else hasher)
+    d.num_points, d.points = fd.num_points, fd.points
+    d.num_reductions, d.proof_of_work_bits, d.num_query_rounds = fd.num_reductions, fd.proof_of_work_bits, fd.num_query_rounds
+    for i in range(16):
+        d.reduction_arity_bits[i] = fd.reduction_arity_bits[i]
+    return d, keep + [sh, fd]
+
+
+def fri_verify_sizes(shapes, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds, log_n=None, rate_bits=None, cap_height=None,
+                     hasher=None):
+    """(glp_fri_verify_proof_words, glp_fri_verify_num_openings) of the description; (0, 0) for one the verifier refuses"""
+    d, keep = _fri_verify_desc_to_c(shapes, points, log_n, rate_bits, cap_height, hasher, reduction_arity_bits, proof_of_work_bits, num_query_rounds)
+    L = load_library()
+    out = int(L.glp_fri_verify_proof_words(C.byref(d))), int(L.glp_fri_verify_num_openings(C.byref(d)))
+    del keep
+    return out
+
+
+def _fri_verify_call(ctx, shapes, points, zs, reduction_arity_bits, proof_of_work_bits, num_query_rounds, openings, proofs, caps, geometry, tail):
+    """shared marshalling of the two many-proof forms; tail(K, d) -> (C function, arguments between proofs and status_out, keep-alive)"""
+    L = load_library()
+    z = _a(zs)
+    if z.ndim != 3 or z.shape[1:] != (len(points), 2):
+        raise GlpError(-1, "zs is [num_proofs][%d][2]" % len(points))
+    K = z.shape[0]
+    d, keep = _fri_verify_desc_to_c(shapes, points, *geometry, reduction_arity_bits, proof_of_work_bits, num_query_rounds, num_proofs=K)
+    words, nopen = int(L.glp_fri_verify_proof_words(C.byref(d))), int(L.glp_fri_verify_num_openings(C.byref(d)))
+    capn = 1 << int(d.cap_height)
+    if caps is None:
+        if not all(isinstance(s, Batch) for s in shapes):
+            raise GlpError(-1, "caps is needed unless every oracle is given as a Batch")
+        caps = [s.caps() for s in shapes]
+    cs = [_a(cp) for cp in caps]
+    if len(cs) != len(shapes):
+        raise GlpError(-1, "%d caps for %d oracles" % (len(cs), len(shapes)))
+    for i, cp in enumerate(cs):
+        want = capn * 4 * (1 if d.oracles[i].shared else K)
+        if words and cp.size != want:
+            raise GlpError(-1, "caps[%d] has %d words, expected %d" % (i, cp.size, want))
+    op, pr = _a(openings), _a(proofs)
+    if words and (pr.size != K * words or op.size != K * nopen * 2):      # a bad description (words == 0) is the library's to name
+        raise GlpError(-1, "proofs is [num_proofs][%d] and openings [num_proofs][%d][2] for this instance" % (words, nopen))
+    cap_ptrs = (C.c_void_p * max(1, len(cs)))(*[cp.ctypes.data for cp in cs])
+    fn, mid, keep2 = tail(K, d)
+    status = np.zeros(max(K, 1), np.int32)
+    buf = C.create_string_buffer(max(K, 1) * 160)
+    _chk(fn(ctx._h, C.byref(d), K, _p(z) if z.size else None, cap_ptrs, _p(op) if op.size else None, _p(pr) if pr.size else None, *mid,
+            status.ctypes.data_as(C.c_void_p), buf))
+    del keep, keep2
+    return status[:K], [buf.raw[160 * k:160 * (k + 1)].split(b"\0", 1)[0].decode() for k in range(K)]
+
+
+def fri_verify_many(ctx, shapes, points, zs, reduction_arity_bits, proof_of_work_bits, num_query_rounds, openings, proofs, sponge_states,
+                    pending_inputs=None, caps=None, log_n=None, rate_bits=None, cap_height=None, hasher=None):
+    """glp_fri_verify_many: num_proofs FriProofs of one instance checked in one launch, each transcript resumed from its own duplex
+    sponge as in fri_prove_many.  shapes: (num_cols, salted, shared) triples (then caps and the geometry are needed) or live Batch
+    objects (shape and caps() taken from them); zs [num_proofs][len(points)][2]; openings [num_proofs][count][2]; proofs
+    [num_proofs][words].  Returns (status [num_proofs] int32: 0 accepted, -5 rejected; reasons [num_proofs] str ending in "[check N]")."""
+    def tail(K, d):
+        st = _a(sponge_states)
+        pend = np.zeros((K, 0), np.uint64) if pending_inputs is None else _a(pending_inputs)
+        pend = pend.reshape(K, pend.size // max(K, 1))
+        if st.shape != (K, 12):
+            raise GlpError(-1, "sponge_states is [num_proofs][12]")
+        return load_library().glp_fri_verify_many, (_p(st), _p(pend) if pend.size else None, pend.shape[1]), (st, pend)
+    return _fri_verify_call(ctx, shapes, points, zs, reduction_arity_bits, proof_of_work_bits, num_query_rounds, openings, proofs, caps,
+                            (log_n, rate_bits, cap_height, hasher), tail)
+
+
+def fri_verify_queries_many(ctx, shapes, points, zs, reduction_arity_bits, proof_of_work_bits, num_query_rounds, openings, proofs, alphas, betas,
+                            indices, caps=None, log_n=None, rate_bits=None, cap_height=None, hasher=None):
+    """glp_fri_verify_queries_many: the same checks under the caller's own Fiat-Shamir: alphas [num_proofs][2], betas
+    [num_proofs][num_reductions][2], indices [num_proofs][num_query_rounds]; the caller has checked the proof of work."""
+    def tail(K, d):
+        al, be, ix = _a(alphas), _a(betas), _a(indices)
+        if al.size != 2 * K or be.size != 2 * K * len(reduction_arity_bits) or ix.size != K * int(num_query_rounds):
+            raise GlpError(-1, "alphas is [num_proofs][2], betas [num_proofs][num_reductions][2], indices [num_proofs][num_query_rounds]")
+        return load_library().glp_fri_verify_queries_many, (_p(al), _p(be) if be.size else None, _p(ix) if ix.size else None), (al, be, ix)
+    return _fri_verify_call(ctx, shapes, points, zs, reduction_arity_bits, proof_of_work_bits, num_query_rounds, openings, proofs, caps,
+                            (log_n, rate_bits, cap_height, hasher), tail)
+
+
+def fri_verify(ctx, shapes, points, reduction_arity_bits, proof_of_work_bits, num_query_rounds, openings, proof, sponge_state, pending_inputs=(),
+               caps=None, log_n=None, rate_bits=None, cap_height=None, hasher=None):
+    """glp_fri_verify: one FriProof at the points' own (a, b).  True if accepted, False if rejected (reason: glp_last_error, ending in
+    "[check N]"); GlpError for a call the library refuses."""
+    L = load_library()
+    d, keep = _fri_verify_desc_to_c(shapes, points, log_n, rate_bits, cap_height, hasher, reduction_arity_bits, proof_of_work_bits, num_query_rounds)
+    words, nopen = int(L.glp_fri_verify_proof_words(C.byref(d))), int(L.glp_fri_verify_num_openings(C.byref(d)))
+    if caps is None:
+        if not all(isinstance(s, Batch) for s in shapes):
+            raise GlpError(-1, "caps is needed unless every oracle is given as a Batch")
+        caps = [s.cap() for s in shapes]
+    cs = [_a(cp) for cp in caps]
+    if len(cs) != len(shapes) or (words and any(cp.size != 4 << int(d.cap_height) for cp in cs)):
+        raise GlpError(-1, "caps is one [2^cap_height][4] array per oracle")
+    op, pr, st, pend = _a(openings), _a(proof), _a(sponge_state), _a(list(pending_inputs))
+    if st.size != 12 or (words and (pr.size != words or op.size != 2 * nopen)):
+        raise GlpError(-1, "proof has %d words and %d openings for this instance; the sponge state is 12 words" % (words, nopen))
+    cap_ptrs = (C.c_void_p * max(1, len(cs)))(*[cp.ctypes.data for cp in cs])
+    rc = L.glp_fri_verify(ctx._h, C.byref(d), cap_ptrs, _p(op) if op.size else None, _p(pr) if pr.size else None, _p(st),
+                          _p(pend) if pend.size else None, pend.size)
+    del keep
+    if rc == 0:
+        return True
+    if rc == -5:
+        return False
+    _chk(rc)

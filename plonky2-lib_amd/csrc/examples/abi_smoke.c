@@ -78,6 +78,24 @@ int main(int argc, char **argv) {
             return 1;
         }
         printf("staged proof equal; batch verifier: ok, ok, rejected (%s)\n", reasons + 2 * GLP_REASON_LEN);
+        {   /* the verifier of the commitment seam: an all-zero FriProof of a one-column instance must be rejected, with a check number */
+            const glp_fri_oracle_shape shape = {1, 0, 0};
+            const glp_fri_range range = {0, 0, 1};
+            glp_fri_point point = {{5, 0}, 1, NULL};
+            glp_fri_verify_desc vd;
+            uint64_t cap[4] = {0, 0, 0, 0}, opening[2] = {0, 0}, state[12] = {0}, zero_proof[64] = {0};
+            const uint64_t *caps[1];
+            point.ranges = &range;
+            memset(&vd, 0, sizeof(vd));
+            vd.num_oracles = 1; vd.oracles = &shape; vd.log_n = 2; vd.rate_bits = 1; vd.num_points = 1; vd.points = &point; vd.num_query_rounds = 1;
+            caps[0] = cap;
+            if (glp_fri_verify_proof_words(&vd) != 22 || glp_fri_verify_num_openings(&vd) != 1) { fprintf(stderr, "glp_fri_verify_proof_words\n"); return 1; }
+            if (glp_fri_verify(ctx, &vd, caps, opening, zero_proof, state, NULL, 0) != GLP_ERR_PROVE || !strstr(glp_last_error(), "[check 4]")) {
+                fprintf(stderr, "glp_fri_verify on an all-zero proof: %s\n", glp_last_error());
+                return 1;
+            }
+            printf("glp_fri_verify: rejected (%s)\n", glp_last_error());
+        }
         free(three);
         free(proof);
         glp_circuit_free(circuit);

@@ -9,6 +9,7 @@
 // The many-proof form (glp_fri_begin_many: K proofs of one instance in lock step) shares the handle, the checks and the step entry
 // points; its steps are the functions of fri_many.inc.
 #include <map>
+#include "fri_shape.h"
 
 namespace {
 ProveGeo fri_geo(const glp_batch *b, const u32 *arity_bits, u32 nq) {
@@ -244,10 +245,7 @@ struct glp_fri {
 namespace {
 // num_proofs == 0: glp_fri_begin / glp_fri_prove (one proof at the description's points); else the many form at points_many[num_proofs][num_points][2]
 int fri_check(glp_ctx *c, const glp_fri_desc *d, u32 num_proofs = 0, const u64 *points_many = nullptr) {
-    GLP_REQUIRE(d->num_oracles >= 1 && d->num_oracles <= GLP_FRI_MAX_ORACLES, "num_oracles = %u outside 1..%d", d->num_oracles, GLP_FRI_MAX_ORACLES);
-    GLP_REQUIRE(d->oracles, "oracles is null");
-    GLP_REQUIRE(d->num_points >= 1 && d->num_points <= GLP_FRI_MAX_POINTS, "num_points = %u outside 1..%d", d->num_points, GLP_FRI_MAX_POINTS);
-    GLP_REQUIRE(d->points, "points is null");
+    GLP_TRY(fri_shape_counts(d->num_oracles, d->oracles, d->num_points, d->points));
     const glp_batch *b0 = d->oracles[0];
     for (u32 i = 0; i < d->num_oracles; i++) {
         const glp_batch *b = d->oracles[i];
@@ -267,38 +265,13 @@ int fri_check(glp_ctx *c, const glp_fri_desc *d, u32 num_proofs = 0, const u64 *
         for (u32 i = 0; i < d->num_oracles; i++) per_proof |= d->oracles[i]->K == num_proofs;
         GLP_REQUIRE(per_proof, "oracles: every one is shared (K = 1), none has K = num_proofs = %u", num_proofs);
     }
-    const u32 lg = (u32)b0->lg, lgN = lg + (u32)b0->rate_bits;
+    const u32 lg = (u32)b0->lg;
     const u64 gn = pow(GEN, (u64)1 << lg);
-    size_t nopen = 0;
-    for (u32 p = 0; p < d->num_points; p++) {
-        const glp_fri_point &pt = d->points[p];
-        GLP_REQUIRE(pt.num_ranges <= GLP_FRI_MAX_RANGES, "points[%u].num_ranges = %u above %d", p, pt.num_ranges, GLP_FRI_MAX_RANGES);
-        GLP_REQUIRE(pt.ranges || pt.num_ranges == 0, "points[%u].ranges is null", p);
-        GLP_REQUIRE(num_proofs || (pt.point[0] < P && pt.point[1] < P), "points[%u].point is not canonical", p);
-        size_t len = 0;
-        for (u32 r = 0; r < pt.num_ranges; r++) {
-            const glp_fri_range &rg = pt.ranges[r];
-            GLP_REQUIRE(rg.oracle < d->num_oracles, "points[%u].ranges[%u].oracle = %u, there are %u oracles", p, r, rg.oracle, d->num_oracles);
-            const u32 ncols = d->oracles[rg.oracle]->ncols;
-            GLP_REQUIRE(rg.col_begin <= ncols && rg.num_cols <= ncols - rg.col_begin,
-                        "points[%u].ranges[%u]: columns [%u, %u + %u) run past ncols = %u of oracle %u (salts are not polynomials)", p, r, rg.col_begin,
-                        rg.col_begin, rg.num_cols, ncols, rg.oracle);
-            len += rg.num_cols;
-        }
-        GLP_REQUIRE(len > 0, "points[%u] names no polynomial", p);
-        GLP_REQUIRE((nopen += len) <= 0x7FFFFFFFu, "points name too many polynomials");
-    }
-    GLP_REQUIRE(d->num_reductions <= 16, "num_reductions = %u above 16", d->num_reductions);
-    u32 sum_ab = 0;
-    for (u32 i = 0; i < d->num_reductions; i++) {
-        GLP_REQUIRE(d->reduction_arity_bits[i] >= 1 && d->reduction_arity_bits[i] <= 4, "reduction_arity_bits[%u] = %u outside 1..4", i, d->reduction_arity_bits[i]);
-        sum_ab += d->reduction_arity_bits[i];
-    }
-    GLP_REQUIRE(sum_ab <= lg, "reduction_arity_bits sum to %u, above log_n = %u", sum_ab, lg);
-    GLP_REQUIRE(lgN - sum_ab >= (u32)b0->cap_height, "reduction_arity_bits: the last layer has fewer leaves than the cap (cap_height = %d)", b0->cap_height);
-    GLP_REQUIRE(d->proof_of_work_bits <= POW_MAX_BITS, "proof_of_work_bits=%u: this build searches at most 2^40 candidates and accepts up to %u bits",
-                d->proof_of_work_bits, POW_MAX_BITS);
-    GLP_REQUIRE(d->num_query_rounds >= 1, "num_query_rounds = 0");
+    u32 ncols[GLP_FRI_MAX_ORACLES];
+    for (u32 i = 0; i < d->num_oracles; i++) ncols[i] = d->oracles[i]->ncols;
+    // the rules a verifier without batches checks too (fri_shape.h)
+    GLP_TRY(fri_shape_rules(ncols, d->num_oracles, lg, (u32)b0->rate_bits, (u32)b0->cap_height, d->num_points, d->points, !num_proofs, d->num_reductions,
+                            d->reduction_arity_bits, d->proof_of_work_bits, d->num_query_rounds));
     // x - z must be invertible on coset plane 0 = g H: z = a + 0 X with (a / g)^n = 1 is a point of it
     for (u32 p = 0; p < d->num_points && !num_proofs; p++)
         if (d->points[p].point[1] == 0 && pow(d->points[p].point[0], (u64)1 << lg) == gn)

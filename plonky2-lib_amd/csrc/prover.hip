@@ -24,6 +24,7 @@
 #include "ntt.h"
 #include "poseidon.h"
 #include "prover_types.h"
+#include "fri_shape.h"      // POW_MAX_BITS and the FRI shape rules
 
 namespace {
 void make_layout(const glp_circuit_desc &c, Layout &L, bool zk) {
@@ -322,9 +323,6 @@ struct glp_session {
     }
 };
 
-// One bound for glp_circuit_create and glp_pow_search: with the search capped at 2^40 candidates, 32 bits leaves a failure
-// probability of exp(-2^8).
-constexpr u32 POW_MAX_BITS = 32;
 // K10: smallest witness w >= 0 such that the sponge (state + pending inputs + w) squeezes a value with `bits` leading
 // zeros.  The search covers candidates in increasing order, so the result does not depend on launch geometry.
 static int pow_search(glp_ctx *c, const u64 st[12], const u64 *pending, u32 npending, u32 bits, u64 *witness, int hasher = GLP_HASH_POSEIDON) {
