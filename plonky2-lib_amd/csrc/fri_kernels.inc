@@ -155,72 +155,16 @@ __global__ __launch_bounds__(256) void k_final_values_small(FVArgs a) {
         a.out[q] = f.a; a.out[n + q] = f.b;
     }
 }
-// K8 for any FRI instance (fri_openings.inc): up to GLP_FRI_MAX_POINTS opening points, each naming its own list of columns:
+// K8 for any FRI instance (fri_openings.inc), K proofs of it in lock step (blockIdx.y = proof; glp_fri_begin makes K = 1): up to
+// GLP_FRI_MAX_POINTS opening points, each naming its own list of columns:
 //   F <- alpha^(len_b) F + (sum_j alpha^j p_{b,j}(x) - red_b) / (x - z_b)     for b = 0 .. npoints - 1, F = 0 before the first
 // One pass over the union of the named columns: prog[e] is one column (its plane 0) and, per point, where that column's alpha
-// power sits in the table (FC_ABSENT: the point does not name it), so a column several points name is loaded once.  The
-// program and the powers are read uniformly (scalar loads, uniform branches), as coset_table is; one carry-free accumulator
-// pair per point, all flushed every ACC_MAX_TERMS columns.  Columns are loaded four at a time to keep four loads in flight:
-// the four pairs cost 96 of the kernel's 130 VGPRs (3 waves per SIMD; bounding it to 128 for a fourth wave spills).
-constexpr u32 FC_ABSENT = 0xFFFFFFFFu;
-struct FCCol { const u64 *plane; u32 ap[GLP_FRI_MAX_POINTS]; };
-struct FCArgs {
-    const FCCol *prog; u32 nprog, npoints;
-    const u64 *apow;            // ext alpha powers, indexed by FCCol::ap
-    u64 *out;                   // [2][n]
-    ext2 red[GLP_FRI_MAX_POINTS], z[GLP_FRI_MAX_POINTS], shift[GLP_FRI_MAX_POINTS];   // shift[b] = alpha^(len_b)
-    u64 w_n, g;
-    u32 lg;
-};
-__global__ __launch_bounds__(256) void k_fri_combine(FCArgs a) {
-    constexpr int NP = GLP_FRI_MAX_POINTS;
-    const size_t n = (size_t)1 << a.lg;
-    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= n) return;
-    ext2 sum[NP];
-    AccLimb xa[NP], xb[NP];
-#pragma unroll
-    for (int b = 0; b < NP; b++) { sum[b] = e_from(0); acc2_zero(xa[b]); acc2_zero(xb[b]); }
-    u32 terms = 0;
-    for (u32 e0 = 0; e0 < a.nprog; e0 += 4) {
-        u64 v[4];
-#pragma unroll
-        for (u32 i = 0; i < 4; i++) v[i] = e0 + i < a.nprog ? a.prog[e0 + i].plane[q] : 0;
-#pragma unroll
-        for (u32 i = 0; i < 4; i++) {
-            if (e0 + i >= a.nprog) break;
-            const u32 v0 = (u32)v[i] & 0x3FFFFFu, v1 = (u32)(v[i] >> 22) & 0x3FFFFFu, v2 = (u32)(v[i] >> 44);
-#pragma unroll
-            for (int b = 0; b < NP; b++) {
-                const u32 j = a.prog[e0 + i].ap[b];
-                if (j != FC_ABSENT) { acc2_fma(xa[b], v0, v1, v2, a.apow[2 * (size_t)j]); acc2_fma(xb[b], v0, v1, v2, a.apow[2 * (size_t)j + 1]); }
-            }
-        }
-        if ((terms += 4) == ACC_MAX_TERMS) {
-#pragma unroll
-            for (int b = 0; b < NP; b++) {
-                sum[b] = e_add(sum[b], e_make(acc2_reduce(xa[b]), acc2_reduce(xb[b])));
-                acc2_zero(xa[b]); acc2_zero(xb[b]);
-            }
-            terms = 0;
-        }
-    }
-    const ext2 x = e_from(mul(a.g, dpow(a.w_n, q)));
-    ext2 f = e_from(0);
-#pragma unroll
-    for (int b = 0; b < NP; b++) {
-        if ((u32)b >= a.npoints) break;
-        const ext2 s = e_add(sum[b], e_make(acc2_reduce(xa[b]), acc2_reduce(xb[b])));
-        f = e_add(e_mul(f, a.shift[b]), e_mul(e_sub(s, a.red[b]), e_inv(e_sub(x, a.z[b]))));
-    }
-    a.out[q] = f.a; a.out[n + q] = f.b;
-}
-
-// ---- the many-proof form of K8 (glp_fri_begin_many): K proofs of one instance in lock step, blockIdx.y = proof.
-// The column program is shared by all proofs; a column's plane advances by `stride` words per proof (0: an oracle all proofs
-// share, else (ncols + salt) N of its oracle).  What k_fri_combine takes as kernel arguments comes per proof from device tables
+// power sits in the table (FC_ABSENT: the point does not name it), so a column several points name is loaded once.  The column
+// program is shared by all proofs; a column's plane advances by `stride` words per proof (0: an oracle all proofs share, else
+// (ncols + salt) N of its oracle).  Alpha, red_b, z_b and shift_b = alpha^(len_b) are each proof's own and come from device tables
 // that k_fri_table fills: apow [K][nopen] ext, pp [K][FCM_PP_WORDS] = red[NP], z[NP], shift[NP] (ext each).  Every table address
 // is made of kernel arguments and blockIdx.y only, so the reads stay scalar.
+constexpr u32 FC_ABSENT = 0xFFFFFFFFu;
 struct FCColM { const u64 *plane; size_t stride; u32 ap[GLP_FRI_MAX_POINTS]; };
 constexpr u32 FCM_PP_WORDS = 6 * GLP_FRI_MAX_POINTS;
 struct FCMArgs {
@@ -236,7 +180,9 @@ struct FCMArgs {
 __device__ __forceinline__ ext2 fcm_pp(const u64 *pp, int part, int b) {
     return e_make(pp[2 * (part * GLP_FRI_MAX_POINTS + b)], pp[2 * (part * GLP_FRI_MAX_POINTS + b) + 1]);
 }
-// 2^8 points per proof and more: k_fri_combine with the proof in blockIdx.y
+// 2^8 points per proof and more: one lane per point.  The program and the powers are read uniformly (scalar loads, uniform branches),
+// as coset_table is; one carry-free accumulator pair per opening point, all flushed every ACC_MAX_TERMS columns.  Columns are loaded
+// four at a time to keep four loads in flight.
 __global__ __launch_bounds__(256) void k_fri_combine_many(FCMArgs a) {
     constexpr int NP = GLP_FRI_MAX_POINTS;
     const size_t n = (size_t)1 << a.lg, pk = blockIdx.y;
@@ -353,7 +299,7 @@ __global__ __launch_bounds__(256) void k_fri_open_finish(const u64 *partial, u64
     for (u32 k = 0; k < nob; k++) { sa = add(sa, partial[2 * (i * nob + k)]); sb = add(sb, partial[2 * (i * nob + k) + 1]); }
     open[2 * i] = sa; open[2 * i + 1] = sb;
 }
-// the per-proof tables of k_fri_combine_many* (the host loop of glp_fri::combine_into, on the device): workgroup (b, k) walks the
+// the per-proof tables of k_fri_combine_many*: workgroup (b, k) walks the
 // len_b polynomials of point b for proof k, 256 lanes a chunk each from alpha_k^(chunk start): apow[k][first_b + j] = alpha_k^j,
 // red_b = sum_j alpha_k^j open[k][first_b + j], shift_b = alpha_k^(len_b), z_b copied next to them.
 struct FTArgs {

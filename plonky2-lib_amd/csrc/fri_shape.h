@@ -15,8 +15,9 @@ inline int fri_shape_counts(u32 num_oracles, const void *oracles, u32 num_points
     GLP_REQUIRE(points, "points is null");
     return GLP_OK;
 }
-// ncols[o]: polynomials of oracle o (salts are not polynomials); lg = log_n.  points_canonical: also require canonical .point words
-// (the one-proof prover form; the many-proof forms and the verifier take their points from an array of their own).
+// ncols[o]: polynomials of oracle o (salts are not polynomials); lg = log_n.  points_canonical: also require canonical .point words,
+// for a caller that reads its points from the description.  No caller sets it today: the prover (fri_check) and the verifier take
+// their points from an array [K][num_points][2] and check that.
 inline int fri_shape_rules(const u32 *ncols, u32 num_oracles, u32 lg, u32 rate_bits, u32 cap_height, u32 num_points, const glp_fri_point *points,
                            bool points_canonical, u32 num_reductions, const u32 *arity_bits, u32 proof_of_work_bits, u32 num_query_rounds) {
     const u32 lgN = lg + rate_bits;

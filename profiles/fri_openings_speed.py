@@ -30,7 +30,7 @@ rng = np.random.default_rng(8)
 chal = [int(x) for x in rng.integers(1, 1 << 62, 64, dtype=np.int64)]
 g = pow(1753635133440165772, 1 << (32 - lg), P)
 SESSION = ("openings", "fri_combine", "fri_commit", "fri_queries")
-GENERIC = ("fri.openings", "fri.combine", "fri.commit", "fri.queries")
+GENERIC = ("fri.openings", "fri.combine", "fri.commit", "fri.fold", "fri.queries")
 ctx.set_profiling(True)
 for rep in range(reps):
     s = glp.Session(gc, dev_wires_ptr=dptr)

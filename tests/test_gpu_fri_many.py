@@ -138,6 +138,40 @@ def test_members_equal_singles_and_restatement(ctx, oracle, log_n, arity_bits, c
     m.free()
 
 
+@pytest.mark.parametrize("log_n", [5, 8])
+def test_one_proof_through_the_many_call_equals_fri_prove(ctx, oracle, log_n):
+    """glp_fri_prove_many with num_proofs = 1 over ordinary batches (K == 1, none a many-proof batch) against glp_fri_prove on the same
+    batches, both against the restatement: two oracles of 6 and 9 columns, point 0 names all of oracle 0 and columns [2, 9) of
+    oracle 1, point 1 columns [1, 3) of oracle 0 and [5, 8) of oracle 1, which point 0 names too.  2^5 points: the small combination
+    kernel; 2^8: the large one."""
+    rng = np.random.default_rng(7700 + log_n)
+    ncols = [6, 9]
+    co = [oracle.rand_field(rng, (nc, 1 << log_n)) for nc in ncols]
+    ranges = [[(0, 0, 6), (1, 2, 7)], [(0, 1, 2), (1, 5, 3)]]
+    zs = oracle.rand_field(rng, (1, 2, 2))
+    points = [(tuple(int(v) for v in zs[0][b]), ranges[b]) for b in range(2)]
+    inst = fr.Instance(log_n, 3, 1, 0, ncols, [False, False], points, [2, 1], 6, 2)
+    gpu = [ctx.batch_from_coeffs(c, 3, 1) for c in co]
+    ref = [fr.commit(oracle, c, 3, 1) for c in co]
+    ch = oracle.Challenger(0)
+    for b, o in zip(gpu, ref):
+        assert b.num_proofs == 1 and (b.cap() == o.cap).all()
+        ch.observe_hashes(o.cap)
+    ch.observe(oracle.rand_field(rng, 3))
+    want_op, want = fr.prove_openings(oracle, inst, ref, fr.challenger_clone(oracle, ch))
+    assert fr.verify_fri_proof(oracle, inst, [o.cap for o in ref], np.array(want_op, np.uint64), want, fr.challenger_clone(oracle, ch)) == 0
+    st, pend = _states([ch])
+    ops, proofs = glp.fri_prove_many(ctx, gpu, [((0, 0), r) for r in ranges], zs, [2, 1], 6, 2, st, pend)
+    op1, proof1 = glp.fri_prove(ctx, gpu, points, [2, 1], 6, 2, st[0], pend[0])
+    assert np.asarray(ops).shape[0] == 1 and np.asarray(proofs).shape[0] == 1
+    _same(ops[0], op1, "openings against glp_fri_prove")
+    _same(proofs[0], proof1, "FriProof against glp_fri_prove")
+    _same(op1, want_op, "openings against the restatement")
+    _same(proof1, want, "FriProof against the restatement")
+    for b in gpu:
+        b.free()
+
+
 # ------------------------------------------------------------------ B. stepped equals one-call
 @pytest.mark.parametrize("hasher", [0, 1])
 def test_stepped_equals_one_call(ctx, oracle, hasher):

@@ -188,13 +188,17 @@ def test_four_points(ctx, oracle):
     _against_restatement(ctx, oracle, inst, coeffs, rng)
 
 
-def test_more_columns_than_one_accumulator_flush(ctx, oracle):
-    """one oracle of ACC_MAX_TERMS + 8 columns at 2^5 points: every lane of k_fri_combine crosses the accumulator flush"""
+@pytest.mark.parametrize("log_n", [5, 8])
+def test_more_columns_than_one_accumulator_flush(ctx, oracle, log_n):
+    """one oracle of ACC_MAX_TERMS + 8 columns through the one-proof API (glp_fri_prove and the stepped handle); the second point
+    names 12 columns around column ACC_MAX_TERMS.  2^5 points reach k_fri_combine_many_small: 8 lanes share a point and take 129
+    program entries each, so this case pins the wide program there and no lane flushes.  2^8 points reach k_fri_combine_many: every
+    lane walks all ACC_MAX_TERMS + 8 entries and crosses the accumulator flush."""
     rng = np.random.default_rng(5)
     ncols = ACC_MAX_TERMS + 8
-    coeffs = [oracle.rand_field(rng, (ncols, 32))]
+    coeffs = [oracle.rand_field(rng, (ncols, 1 << log_n))]
     z = [tuple(int(v) for v in oracle.rand_field(rng, 2)) for _ in range(2)]
-    inst = fr.Instance(5, 3, 1, 0, [ncols], [False], [(z[0], [(0, 0, ncols)]), (z[1], [(0, ACC_MAX_TERMS - 4, 12)])], [2, 1], 6, 2)
+    inst = fr.Instance(log_n, 3, 1, 0, [ncols], [False], [(z[0], [(0, 0, ncols)]), (z[1], [(0, ACC_MAX_TERMS - 4, 12)])], [2, 1], 6, 2)
     _against_restatement(ctx, oracle, inst, coeffs, rng)
 
 
