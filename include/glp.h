@@ -187,6 +187,48 @@ GLP_API int glp_batch_member(const glp_batch *b, uint32_t k, glp_batch **view_ou
 /* every member's merkle_tree.cap in one copy: [num_proofs][2^cap_height][4] */
 GLP_API int glp_batch_caps(const glp_batch *b, uint64_t *caps_out);
 
+/* ---- the caller's quotient at the commitment seam ------------------------------------------------------------------------------
+ * An integrator that keeps its own quotient (see the next block) computes it from the committed oracles' values on the coset
+ * g <W_M>, g = 7, M = 2^(log_n + sub_bits), W_M = primitive_root_of_unity(log_n + sub_bits), sub_bits = plonky2's
+ * quotient_degree_bits <= rate_bits, and commits what comes out.  With the batches in HBM these three calls are both ends:
+ *   glp_batch_lde_values         `PolynomialBatch::get_lde_values(i, step)` / `get_lde_values_packed`, for whole row windows
+ *   glp_coset_ifft               `PolynomialValues::coset_ifft(shift)`
+ *   glp_batch_from_coset_values  the tail of `prove_with_partition_witness`: `coset_ifft(g)`, `quotient_poly.chunks(degree)`,
+ *                                `PolynomialBatch::from_coeffs`
+ *
+ * glp_batch_lde_values: the value for (i, c), i in [row_begin, row_begin + num_rows) inside [0, M), c < num_cols, is
+ * p_{col_begin + c}(g * W_M^i) = word col_begin + c of glp_batch_leaf(b, bitrev(i * step)), step = 2^(rate_bits - sub_bits):
+ * row i is the slice `get_lde_values(i, step)` returns.  Salts are never returned: the column range is held to the ncols
+ * polynomials, as in glp_batch_coeffs.  The row window lets a CPU quotient stream row blocks instead of holding M x ncols words.
+ *   layout         GLP_LDE_ROW_MAJOR: out[i - row_begin][c];  GLP_LDE_COL_MAJOR: out[c][i - row_begin]
+ *   out_on_device  0: out is host memory and the call returns after the copy.  Else out is an HBM pointer on the batch's context
+ *                  (a caller whose quotient is its own kernel) and the call is asynchronous on the ctx stream.
+ * Unlike the one-tree accessors it also takes a many-proof batch: out gets a leading [num_proofs], the same window for every
+ * member, in one launch.  A glp_batch_member view is the case of one member.
+ * Errors: GLP_ERR_ARG naming the field for a null pointer, num_cols or num_rows of 0, a column range past ncols, sub_bits >
+ * rate_bits, a row window past M, an unknown layout. */
+#define GLP_LDE_ROW_MAJOR 0u   /* out[i - row_begin][c]: row i is the slice get_lde_values(i, step) returns */
+#define GLP_LDE_COL_MAJOR 1u   /* out[c][i - row_begin] */
+GLP_API int glp_batch_lde_values(const glp_batch *b, uint32_t col_begin, uint32_t num_cols, uint32_t sub_bits,
+                                 uint64_t row_begin, uint64_t num_rows, uint32_t layout,
+                                 uint64_t *out, int out_on_device);
+/* `PolynomialValues::coset_ifft(shift)` in place on host memory, cols [ncols][2^log_n]: natural-order values on shift * <w> in,
+ * natural-order coefficients out.  The shape of glp_fft / glp_ifft, and the inverse of glp_lde with rate_bits = 0.  shift must be a
+ * non-zero canonical field element (GLP_ERR_ARG otherwise). */
+GLP_API int glp_coset_ifft(glp_ctx *ctx, uint64_t *cols, uint32_t ncols, uint32_t log_n, uint64_t shift);
+/* values [num_proofs][num_polys][M], natural order on g <W_M> (the transposed `quotient_values` of `compute_quotient_polys`); host
+ * memory, or (values_on_device != 0) an HBM pointer on the ctx's GPU.  Per polynomial `coset_ifft(g)` gives M coefficients, split
+ * into 2^sub_bits chunks of n (`trim_to_len(quotient_degree)` is a no-op: M is the quotient degree).  The result is a batch of
+ * num_polys << sub_bits polynomials, column p * 2^sub_bits + j = chunk j of polynomial p (the order of
+ * `quotient_poly.chunks(degree)`), committed as `PolynomialBatch::from_coeffs(.., rate_bits, blinding = (seed != NULL),
+ * cap_height)` under `hasher`: word for word glp_batch_many_from_coeffs on those chunks with the same seed (tag
+ * GLP_SALT_TAG_BATCH, member k salted with seed3 + k), and glp_batch_from_coeffs_h at num_proofs == 1 without a seed.
+ * num_proofs and the size bounds are those of glp_batch_many_from_coeffs; sub_bits in 0..rate_bits (0: one chunk, a plain coset
+ * iFFT).  Every accessor, glp_batch_member, glp_fri_begin* and glp_batch_lde_values take the result like any other batch. */
+GLP_API int glp_batch_from_coset_values(glp_ctx *ctx, const uint64_t *values, int values_on_device, uint32_t num_proofs,
+                                        uint32_t num_polys, uint32_t log_n, uint32_t sub_bits, uint32_t rate_bits,
+                                        uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out);
+
 /* ---- openings and FRI of caller-held batches (fri/oracle.rs `PolynomialBatch::prove_openings`) ----------------------------------
  * For an integrator that keeps its own quotient (circuits with lookup tables, Poseidon2Gate, custom gates, starky AIRs: anything
  * glp_circuit_create answers with GLP_ERR_UNSUPPORTED): commit with glp_batch_from_values / _from_coeffs, evaluate the committed

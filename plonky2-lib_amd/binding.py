@@ -67,6 +67,9 @@ class _FriVerifyDesc(C.Structure):
                 ("num_query_rounds", C.c_uint32)]
 
 
+LDE_ROW_MAJOR, LDE_COL_MAJOR = 0, 1      # GLP_LDE_* of glp_batch_lde_values
+
+
 def library_path():
     return _SO
 
@@ -178,6 +181,9 @@ def load_library():
         "glp_batch_many_from_coeffs": [vp, vp, C.c_int, u32, u32, u32, u32, u32, u32, vp, C.POINTER(vp)],
         "glp_batch_member": [vp, u32, C.POINTER(vp)],
         "glp_batch_caps": [vp, vp],
+        "glp_batch_lde_values": [vp, u32, u32, u32, u64, u64, u32, vp, C.c_int],
+        "glp_coset_ifft": [vp, vp, u32, u32, u64],
+        "glp_batch_from_coset_values": [vp, vp, C.c_int, u32, u32, u32, u32, u32, u32, u32, vp, C.POINTER(vp)],
         "glp_fri_begin_many": [vp, C.POINTER(_FriDesc), u32, vp, C.POINTER(vp)],
         "glp_fri_queries_many": [vp, vp, vp],
         "glp_pow_search_many": [vp, u32, u32, vp, vp, u32, u32, vp],
@@ -328,6 +334,12 @@ class Context:
         _chk(load_library().glp_lde(self._h, _p(a), a.shape[0], int(a.shape[1]).bit_length() - 1, rate_bits, shift, _p(out)))
         return out
 
+    def coset_ifft(self, cols, shift=7):
+        """PolynomialValues::coset_ifft(shift) (glp_coset_ifft): natural-order values on shift * <w> -> natural-order coefficients"""
+        a = np.atleast_2d(_a(cols)).copy()
+        _chk(load_library().glp_coset_ifft(self._h, _p(a), a.shape[0], int(a.shape[1]).bit_length() - 1, int(shift)))
+        return a
+
     def dev_alloc(self, nbytes):
         """Device buffer from the context's pool (for the *_device entry points); returns the pointer as an int."""
         p = C.c_void_p()
@@ -403,6 +415,28 @@ class Context:
 
     def batch_many_from_coeffs(self, coeffs, rate_bits=3, cap_height=4, hasher=0, seed=None):
         return Batch._make_many(self, "glp_batch_many_from_coeffs", coeffs, rate_bits, cap_height, hasher, seed)
+
+    def batch_from_coset_values(self, values, sub_bits, rate_bits=3, cap_height=4, hasher=0, seed=None, dev_ptr=None, shape=None):
+        """glp_batch_from_coset_values: values [num_polys][M] (or [num_proofs][num_polys][M] for K proofs), natural order on the
+        coset 7 <W_M>, M = n << sub_bits -> the Batch of the num_polys << sub_bits chunk polynomials.  dev_ptr (with shape): the
+        values are already in HBM at that pointer."""
+        if dev_ptr is None:
+            a = _a(values)
+            shape = a.shape
+        if len(shape) not in (2, 3) or shape[-1] & (shape[-1] - 1) or shape[-1] < (1 << sub_bits):
+            raise GlpError(-1, "expected a [num_polys][M] or [num_proofs][num_polys][M] array, M = n << sub_bits a power of two")
+        K, num_polys, M = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+        log_n = M.bit_length() - 1 - sub_bits
+        sd = None if seed is None else _a(seed)
+        if sd is not None and sd.size != 4:
+            raise GlpError(-1, "the salt seed is 4 words")
+        h = C.c_void_p()
+        _chk(load_library().glp_batch_from_coset_values(self._h, _p(a) if dev_ptr is None else C.c_void_p(dev_ptr), 0 if dev_ptr is None else 1,
+                                                        K, num_polys, log_n, int(sub_bits), rate_bits, cap_height, int(hasher),
+                                                        None if sd is None else _p(sd), C.byref(h)))
+        b = Batch(self, h, num_polys << sub_bits, log_n, rate_bits, cap_height)
+        b.hasher = int(hasher)
+        return b
 
     def pow_search_many(self, hasher, sponge_states, pending_inputs, bits):
         """glp_pow_search_many: sponge_states [K][12], pending_inputs [K][num_pending] (num_pending < 8) -> the K smallest witnesses"""
@@ -531,6 +565,23 @@ class Batch:
         ncols = self.ncols - col_begin if ncols is None else ncols
         out = np.empty((ncols, 1 << self.log_n), np.uint64)
         _chk(load_library().glp_batch_coeffs(self._h, col_begin, ncols, _p(out)))
+        return out
+
+    def lde_values(self, col_begin, num_cols, sub_bits, row_begin=0, num_rows=None, layout=LDE_ROW_MAJOR, dev_ptr=None):
+        """glp_batch_lde_values: rows [row_begin, row_begin + num_rows) of the coset 7 <W_M>, M = n << sub_bits, for columns
+        [col_begin, col_begin + num_cols): row i is `get_lde_values(i, 2^(rate_bits - sub_bits))`.  Returns [num_rows][num_cols]
+        (LDE_ROW_MAJOR) or [num_cols][num_rows] (LDE_COL_MAJOR), with a leading [num_proofs] for a many-proof batch.  dev_ptr: the
+        values go to that HBM pointer instead (asynchronous on the ctx stream) and None is returned."""
+        if num_rows is None:
+            num_rows = (1 << (self.log_n + sub_bits)) - row_begin
+        L = load_library()
+        if dev_ptr is not None:
+            _chk(L.glp_batch_lde_values(self._h, col_begin, num_cols, sub_bits, row_begin, num_rows, layout, C.c_void_p(dev_ptr), 1))
+            return None
+        K = self.num_proofs if self._h else 1
+        inner = (max(num_rows, 0), num_cols) if layout == LDE_ROW_MAJOR else (num_cols, max(num_rows, 0))
+        out = np.empty(((K,) + inner) if K > 1 else inner, np.uint64)
+        _chk(L.glp_batch_lde_values(self._h, col_begin, num_cols, sub_bits, row_begin, num_rows, layout, _p(out if out.size else np.empty(1, np.uint64)), 0))   # an empty window is the library's error to name
         return out
 
     @property

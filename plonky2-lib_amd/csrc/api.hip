@@ -298,6 +298,26 @@ int glp_lde(glp_ctx *c, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, 
     return GLP_OK;
 }
 
+// PolynomialValues::coset_ifft(shift): the transform of glp_batch_from_coset_values at one plane (sub_bits = 0), on its own
+int glp_coset_ifft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n, uint64_t shift) {
+    GLP_REQUIRE(c && (cols || !ncols), "null argument");
+    GLP_REQUIRE(shift != 0 && shift < glf::P, "shift must be a nonzero canonical field element");
+    GLP_TRY(bind(c));
+    if (!ncols) return GLP_OK;
+    if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
+    const size_t tot = (size_t)ncols << log_n;
+    Scratch s(c);
+    u64 *a, *b;
+    GLP_TRY(s.get(&a, tot));
+    GLP_TRY(s.get(&b, tot));
+    GLP_HIP(hipMemcpyAsync(a, cols, tot * 8, hipMemcpyHostToDevice, c->stream));
+    GLP_TRY(coset_planes_to_chunk_coeffs(c, a, b, b, ncols, (int)log_n, 0, shift));
+    GLP_TRY(bitrev_copy(c, b, a, ncols, (int)log_n));
+    GLP_HIP(hipMemcpyAsync(cols, a, tot * 8, hipMemcpyDeviceToHost, c->stream));
+    GLP_HIP(hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
+
 }  // extern "C"
 
 __global__ void k_fill_random(u64 *out, size_t count, u64 seed) {
@@ -640,6 +660,79 @@ int glp_batch_from_coeffs_device(glp_ctx *c, const uint64_t *dev_coeffs, uint32_
     GLP_TRY(bind(c));
     return batch_build(c, dev_coeffs, BATCH_COEFFS_NATURAL, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out);
 }
+
+// ---- the caller's quotient at the commitment seam
+int glp_batch_lde_values(const glp_batch *b, uint32_t col_begin, uint32_t num_cols, uint32_t sub_bits, uint64_t row_begin, uint64_t num_rows,
+                         uint32_t layout, uint64_t *out, int out_on_device) {
+    GLP_REQUIRE(b, "glp_batch_lde_values: b is null");
+    GLP_REQUIRE(out, "glp_batch_lde_values: out is null");
+    GLP_REQUIRE(num_cols > 0, "glp_batch_lde_values: num_cols is 0");
+    GLP_REQUIRE(num_rows > 0, "glp_batch_lde_values: num_rows is 0");
+    GLP_REQUIRE((u64)col_begin + num_cols <= b->ncols, "glp_batch_lde_values: col_begin + num_cols = %u + %u runs past ncols = %u (salts are not served)",
+                col_begin, num_cols, b->ncols);
+    GLP_REQUIRE(sub_bits <= (u32)b->rate_bits, "glp_batch_lde_values: sub_bits = %u is more than rate_bits = %d", sub_bits, b->rate_bits);
+    const u64 M = (u64)1 << (b->lg + (int)sub_bits);
+    GLP_REQUIRE(row_begin < M && num_rows <= M - row_begin, "glp_batch_lde_values: row_begin + num_rows = %llu + %llu runs past M = 2^(log_n + sub_bits) = %llu",
+                (unsigned long long)row_begin, (unsigned long long)num_rows, (unsigned long long)M);
+    GLP_REQUIRE(layout == GLP_LDE_ROW_MAJOR || layout == GLP_LDE_COL_MAJOR, "glp_batch_lde_values: layout = %u is not one of GLP_LDE_*", layout);
+    glp_ctx *c = b->ctx;
+    GLP_TRY(bind(c));
+    const size_t N = (size_t)1 << (b->lg + b->rate_bits), words = (size_t)b->K * num_cols * num_rows;
+    const u64 *src = b->lde + (size_t)col_begin * N;
+    const bool row_major = layout == GLP_LDE_ROW_MAJOR;
+    if (out_on_device)       // asynchronous on the ctx stream
+        return lde_sub_coset_rows(c, src, (size_t)(b->ncols + b->salt) * N, b->K, num_cols, b->lg, b->rate_bits, (int)sub_bits, row_begin, num_rows,
+                                  row_major, out);
+    Scratch s(c);
+    u64 *t;
+    GLP_TRY(s.get(&t, words));
+    GLP_TRY(lde_sub_coset_rows(c, src, (size_t)(b->ncols + b->salt) * N, b->K, num_cols, b->lg, b->rate_bits, (int)sub_bits, row_begin, num_rows,
+                               row_major, t));
+    GLP_HIP(hipMemcpyAsync(out, t, words * 8, hipMemcpyDeviceToHost, c->stream));
+    GLP_HIP(hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
+
+int glp_batch_from_coset_values(glp_ctx *c, const uint64_t *values, int values_on_device, uint32_t num_proofs, uint32_t num_polys, uint32_t log_n,
+                                uint32_t sub_bits, uint32_t rate_bits, uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out) {
+    GLP_REQUIRE(c, "glp_batch_from_coset_values: ctx is null");
+    GLP_REQUIRE(values, "glp_batch_from_coset_values: values is null");
+    GLP_REQUIRE(out, "glp_batch_from_coset_values: out is null");
+    *out = nullptr;
+    GLP_REQUIRE(num_proofs >= 1 && num_proofs <= 4096, "num_proofs = %u outside 1..4096", num_proofs);
+    if (log_n > (u32)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
+    GLP_REQUIRE(rate_bits <= 4, "rate_bits=%u outside 0..4", rate_bits);
+    GLP_REQUIRE(sub_bits <= rate_bits, "sub_bits = %u is more than rate_bits = %u", sub_bits, rate_bits);
+    GLP_REQUIRE(cap_height <= log_n + rate_bits, "cap_height=%u should be at most log2(leaves)=%u", cap_height, log_n + rate_bits);
+    GLP_REQUIRE(num_polys > 0, "num_polys must be positive");
+    const size_t ncols = (size_t)num_polys << sub_bits;
+    GLP_REQUIRE((size_t)num_proofs * ncols * ((size_t)8 << (log_n + rate_bits)) <= ((size_t)64 << 30),
+                "batch too large (num_proofs * (num_polys << sub_bits) * 2^(log_n + rate_bits) words)");
+    GLP_REQUIRE((size_t)num_proofs * ncols <= 0x7FFFFFFFu, "batch too wide");
+    GLP_TRY(bind(c));
+    u64 sd[4];
+    if (seed) for (int i = 0; i < 4; i++) sd[i] = glf::canon(seed[i]);
+    const size_t channels = (size_t)num_proofs * num_polys, tot = (channels << sub_bits) << log_n;
+    Scratch s(c);
+    u64 *x, *y;
+    GLP_TRY(s.get(&x, tot));
+    const u64 *planes = values;
+    if (!values_on_device) {
+        GLP_TRY(s.get(&y, tot));
+        GLP_HIP(hipMemcpyAsync(y, values, tot * 8, hipMemcpyHostToDevice, c->stream));
+        planes = y;
+        if (sub_bits) { GLP_TRY(coset_values_to_planes(c, y, x, channels, (int)log_n, (int)sub_bits)); planes = x; std::swap(x, y); }
+    } else if (sub_bits) {
+        GLP_TRY(s.get(&y, tot));
+        GLP_TRY(coset_values_to_planes(c, values, y, channels, (int)log_n, (int)sub_bits));
+        planes = y;
+    }
+    // planes -> x (per-plane inverse transform), combined in place: x holds the chunks' coefficients, bit-reversed
+    GLP_TRY(coset_planes_to_chunk_coeffs(c, planes, x, x, (u32)channels, (int)log_n, (int)sub_bits, glf::GEN));
+    return batch_build(c, x, BATCH_COEFFS_BITREV, (u32)ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, nullptr, num_proofs, (int)hasher,
+                       seed ? sd : nullptr, GLP_SALT_TAG_BATCH);
+}
+
 void glp_batch_free(glp_batch *b) { batch_destroy(b); }
 
 int glp_batch_info(const glp_batch *b, uint32_t *ncols, uint32_t *log_n, uint32_t *rate_bits, uint32_t *cap_height) {

@@ -23,4 +23,9 @@ int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg
                 const u64 *salt_seed = nullptr /* non-null: blinded, 4 salt columns (merkle_fill_salts) */, u32 salt_tag = 0);
 constexpr u32 SALT_SIZE = 4;
 void batch_destroy(glp_batch *b);
+// Values on the planes of `channels` cosets shift * <w_M>, M = n << sub_bits, to their coefficients in chunks of n (prover.hip).
+//   pv   [channels][S][n], S = 2^sub_bits: plane r slot q holds the value at shift * w_M^(q S + r)
+//   out  [channels * S][n], bit-reversed order: chunk j of a channel is its X^(j n) block (`coeffs.chunks(n)`)
+//   pV   scratch of the same size; out may be pV
+int coset_planes_to_chunk_coeffs(glp_ctx *c, const u64 *pv, u64 *pV, u64 *out, u32 channels, int lg, int sub_bits, u64 shift);
 }  // namespace glp

@@ -84,5 +84,12 @@ int lde_coeffs(glp_ctx *c, const u64 *dev_coeffs, u64 *dev_lde, u32 ncols, int l
 int bitrev_copy(glp_ctx *c, const u64 *dev_in, u64 *dev_out, u32 ncols, int lg);
 // coset-major [ncols][R][n] -> natural [ncols][N]  (accessor only)
 int lde_to_natural(glp_ctx *c, const u64 *dev_lde, u64 *dev_out, u32 ncols, int lg, int rate_bits);
+// The sub-coset shift * <W_M>, M = n << sub_bits, sub_bits <= rate_bits, read out of K coset-major members [ncols][R][n] that lie
+// member_stride words apart: rows [row_begin, row_begin + num_rows) of columns [0, num_cols) of dev_lde, row i = q S + r being slot q
+// of plane r * 2^(rate_bits - sub_bits).  row_major: out [K][num_rows][num_cols] (an LDS-tiled transpose), else [K][num_cols][num_rows].
+int lde_sub_coset_rows(glp_ctx *c, const u64 *dev_lde, size_t member_stride, u32 K, u32 num_cols, int lg, int rate_bits, int sub_bits,
+                       u64 row_begin, u64 num_rows, bool row_major, u64 *dev_out);
+// natural order on such a coset [ncols][M] -> its S = 2^sub_bits planes [ncols][S][n]: index q S + r to plane r, slot q (sub_bits 1..4)
+int coset_values_to_planes(glp_ctx *c, const u64 *dev_in, u64 *dev_out, size_t ncols, int lg, int sub_bits);
 
 }  // namespace glp

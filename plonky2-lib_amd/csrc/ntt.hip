@@ -338,6 +338,72 @@ __global__ void k_lde_to_natural(const u64 *__restrict__ in, u64 *__restrict__ o
     out[col * N + (q << rate_bits) + r] = in[col * N + pos];
 }
 
+// Sub-coset reads (glp_batch_lde_values).  The coset g <W_M>, M = n S, S = 2^sub_bits, is every step-th point of the stored one,
+// step = 2^(rate_bits - sub_bits): its row i = q S + r is slot q of plane r * step.
+// Column-major out [K][num_cols][num_rows]: a block's 256 consecutive rows are runs of 256 / S slots in S planes of one column.
+__global__ __launch_bounds__(256) void k_lde_rows_colmajor(const u64 *__restrict__ lde, u64 *__restrict__ out, size_t member_stride, int lg,
+                                                           int rate_bits, int sub_bits, u64 row_begin, u64 num_rows, u32 col0, u32 num_cols) {
+    const u64 j = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (j >= num_rows) return;
+    const size_t col = (size_t)col0 + blockIdx.y, k = blockIdx.z;
+    const u64 i = row_begin + j;
+    const size_t plane = (size_t)(i & (((u64)1 << sub_bits) - 1)) << (rate_bits - sub_bits), q = (size_t)(i >> sub_bits);
+    out[(k * num_cols + col) * num_rows + j] = lde[k * member_stride + ((((col << rate_bits) + plane) << lg) + q)];
+}
+// Row-major out [K][num_rows][num_cols]: a transpose, columns by rows, through an LDS tile of 4096 words: TR = 2^LGTR rows by
+// TC = 4096 / TR columns.  LGTR = 7 (32 columns x 128 rows) wherever the coset has 128 rows or more; a shorter coset (the many small
+// proofs of a lock-step batch: M = 64 at the zkdsa shape) takes the tile of its own height, down to 16 rows, and spends the words on
+// columns instead of on rows that do not exist.  Tiles are aligned to absolute rows (TR is a multiple of every S), so a tile is
+// TR / S consecutive slots of S planes per column: the global reads run along q.  The tile keeps that order, [column][plane][slot]
+// with the column pitch TR + 1, an odd word count, at every tile height.  The stores into it: a 16-lane group holds 16 consecutive
+// slots of one column (TR >= 16), unit stride, 16 distinct 8-byte banks.  The loads out of it: a 32-lane group holds 32 consecutive
+// columns of one row (TC >= 32; at TR = 16 or 32 a whole wave is 64 columns of one row), TR + 1 words apart, and an odd stride
+// visits every 8-byte bank of the 256-byte row once.  The global writes run along c.  Ragged edges (columns past num_cols, rows outside the window, the window's first tile
+// starting before row_begin) are masked on both sides.
+constexpr int LR_LG_WORDS = 12, LR_LGTR_MAX = 7, LR_LGTR_MIN = 4;
+template <int LGTR>
+__global__ __launch_bounds__(256) void k_lde_rows_rowmajor(const u64 *__restrict__ lde, u64 *__restrict__ out, size_t member_stride, int lg,
+                                                           int rate_bits, int sub_bits, u64 row_begin, u64 num_rows, u32 num_cols,
+                                                           u32 col_tiles, u64 row_tile0) {
+    constexpr int TR = 1 << LGTR, TC = 1 << (LR_LG_WORDS - LGTR), PITCH = TR + 1;
+    __shared__ u64 tile[TC * PITCH];
+    const u32 tid = threadIdx.x, c0 = (blockIdx.x % col_tiles) * TC;
+    const u64 i0 = (row_tile0 + blockIdx.x / col_tiles) << LGTR, row_end = row_begin + num_rows;
+    const size_t k = blockIdx.y;
+    const int lgq = LGTR - sub_bits;                     // log2 slots per plane in a tile
+    const u64 q0 = i0 >> sub_bits;
+    const u64 *src = lde + k * member_stride;
+    for (int it = 0; it < TC * TR / 256; it++) {
+        const u32 e = it * 256 + tid, c = e >> LGTR, inner = e & (TR - 1);
+        const u32 rp = inner >> lgq;
+        const u64 q = q0 + (inner & ((1u << lgq) - 1)), i = (q << sub_bits) + rp;
+        if (c0 + c < num_cols && i >= row_begin && i < row_end)
+            tile[c * PITCH + inner] = src[((((size_t)(c0 + c) << rate_bits) + ((size_t)rp << (rate_bits - sub_bits))) << lg) + q];
+    }
+    __syncthreads();
+    u64 *dst = out + k * num_rows * num_cols;
+    for (int it = 0; it < TC * TR / 256; it++) {
+        const u32 e = it * 256 + tid, c = e & (TC - 1), rl = e / TC;
+        const u64 i = i0 + rl;
+        const u32 inner = ((rl & ((1u << sub_bits) - 1)) << lgq) + (rl >> sub_bits);
+        if (c0 + c < num_cols && i >= row_begin && i < row_end) dst[(size_t)(i - row_begin) * num_cols + c0 + c] = tile[c * PITCH + inner];
+    }
+}
+// The way in (glp_batch_from_coset_values): natural order on g <W_M> to the S planes the per-plane inverse transform takes.  A thread
+// reads the S consecutive values of one slot (a wave reads one run of 64 S words) and writes one word to each plane (64-word runs).
+template <int SB>
+__global__ __launch_bounds__(256) void k_coset_to_planes(const u64 *__restrict__ in, u64 *__restrict__ out, int lg) {
+    const size_t n = (size_t)1 << lg, q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const size_t col = blockIdx.y;
+    const u64 *s = in + ((col * n + q) << SB);
+    u64 v[1 << SB];
+#pragma unroll
+    for (int r = 0; r < (1 << SB); r++) v[r] = s[r];
+#pragma unroll
+    for (int r = 0; r < (1 << SB); r++) out[(((col << SB) + r) << lg) + q] = v[r];
+}
+
 // ------------------------------------------------------------------------------------------
 // Register transforms: the one butterfly family of this file.  Every 64th root of unity of the Goldilocks field is a power of
 // two (w_64 = 2^39, 2^96 = -1), so a transform of up to 64 points on a thread's registers multiplies by shifts only, no
@@ -1082,6 +1148,55 @@ int lde_to_natural(glp_ctx *c, const u64 *dev_lde, u64 *dev_out, u32 ncols, int 
     dim3 g((unsigned)((N + 255) / 256), ncols);
     hipLaunchKernelGGL(k_lde_to_natural, g, dim3(256), 0, c->stream, dev_lde, dev_out, lg, rate_bits);
     GLP_HIP(hipGetLastError());
+    return GLP_OK;
+}
+
+int lde_sub_coset_rows(glp_ctx *c, const u64 *dev_lde, size_t member_stride, u32 K, u32 num_cols, int lg, int rate_bits, int sub_bits,
+                       u64 row_begin, u64 num_rows, bool row_major, u64 *dev_out) {
+    if (num_cols == 0 || num_rows == 0 || K == 0) return GLP_OK;
+    if (sub_bits < 0 || sub_bits > rate_bits || rate_bits > 4 || row_begin + num_rows > ((u64)1 << (lg + sub_bits)) || K > 65535u)
+        return set_error(GLP_ERR_ARG, "lde_sub_coset_rows: window or shape out of range");
+    if (!row_major) {
+        for (u32 c0 = 0; c0 < num_cols; c0 += 65535) {        // the column rides in grid.y
+            const dim3 g((unsigned)((num_rows + 255) / 256), std::min(65535u, num_cols - c0), K);
+            hipLaunchKernelGGL(k_lde_rows_colmajor, g, dim3(256), 0, c->stream, dev_lde, dev_out, member_stride, lg, rate_bits, sub_bits,
+                               row_begin, num_rows, c0, num_cols);
+            GLP_HIP(hipGetLastError());
+        }
+        return GLP_OK;
+    }
+    // column tiles vary fastest in grid.x, so the blocks that share an output row's cache lines run together
+    const int lgtr = std::min(LR_LGTR_MAX, std::max(LR_LGTR_MIN, lg + sub_bits));      // the tile is as tall as the coset, 16..128 rows
+    const u32 tc = 1u << (LR_LG_WORDS - lgtr), col_tiles = (u32)(((u64)num_cols + tc - 1) / tc);
+    if (col_tiles > (1u << 23)) return set_error(GLP_ERR_ARG, "lde_sub_coset_rows: num_cols = %u is more than one launch takes row-major", num_cols);
+    const u64 t0 = row_begin >> lgtr, t1 = ((row_begin + num_rows - 1) >> lgtr) + 1;
+    const u64 per = ((u64)1 << 23) / col_tiles;                        // >= 1: grid.x * 256 threads stays below 2^32
+    for (u64 t = t0; t < t1; t += per) {
+        const dim3 g((unsigned)(std::min(per, t1 - t) * col_tiles), K);
+#define GLP_LR_LAUNCH(L) case L: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lde_rows_rowmajor<L>), g, dim3(256), 0, c->stream, dev_lde, dev_out, \
+                                                     member_stride, lg, rate_bits, sub_bits, row_begin, num_rows, num_cols, col_tiles, t); break;
+        switch (lgtr) { GLP_LR_LAUNCH(4) GLP_LR_LAUNCH(5) GLP_LR_LAUNCH(6) default: GLP_LR_LAUNCH(7) }
+#undef GLP_LR_LAUNCH
+        GLP_HIP(hipGetLastError());
+    }
+    return GLP_OK;
+}
+
+int coset_values_to_planes(glp_ctx *c, const u64 *dev_in, u64 *dev_out, size_t ncols, int lg, int sub_bits) {
+    if (sub_bits < 1 || sub_bits > 4) return set_error(GLP_ERR_ARG, "coset_values_to_planes: sub_bits=%d outside 1..4 (0: the values are the one plane)", sub_bits);
+    const size_t n = (size_t)1 << lg;
+    for (size_t c0 = 0; c0 < ncols; c0 += 65535) {            // the column rides in grid.y
+        const dim3 g((unsigned)((n + 255) / 256), (unsigned)std::min<size_t>(65535, ncols - c0));
+        const u64 *in = dev_in + ((c0 * n) << sub_bits);
+        u64 *out = dev_out + ((c0 * n) << sub_bits);
+        switch (sub_bits) {
+        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coset_to_planes<1>), g, dim3(256), 0, c->stream, in, out, lg); break;
+        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coset_to_planes<2>), g, dim3(256), 0, c->stream, in, out, lg); break;
+        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coset_to_planes<3>), g, dim3(256), 0, c->stream, in, out, lg); break;
+        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coset_to_planes<4>), g, dim3(256), 0, c->stream, in, out, lg); break;
+        }
+        GLP_HIP(hipGetLastError());
+    }
     return GLP_OK;
 }
 

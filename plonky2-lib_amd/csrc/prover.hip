@@ -121,6 +121,28 @@ int batch_cap_host(glp_ctx *c, const glp_batch *b, std::vector<u64> &cap) {
     return d2h(c, cap.data(), b->digests + 4 * merkle_cap_offset(N, b->cap_height), cap.size() * 8);
 }
 }  // namespace
+
+// The half of the quotient's way back to coefficients that needs no circuit (batch.h): the library's own quotient
+// (stage_quotient_coeffs) and a caller's (glp_batch_from_coset_values, glp_coset_ifft) both end here.  One n-point inverse
+// transform per plane, then k_quotient_combine: undo the plane twist, inverse DFT across the planes, undo the coset shift.
+int glp::coset_planes_to_chunk_coeffs(glp_ctx *c, const u64 *pv, u64 *pV, u64 *out, u32 channels, int lg, int sub_bits, u64 shift) {
+    const u32 Rq = 1u << sub_bits;
+    const size_t n = (size_t)1 << lg;
+    GLP_TRY(intt_values_to_coeffs(c, pv, pV, channels * Rq, lg));
+    QCArgs q;
+    q.lg = (u32)lg; q.Rq = Rq;
+    q.wM_inv = inv(root_of_unity(lg + sub_bits)); q.wR_inv = inv(root_of_unity(sub_bits)); q.g_inv = inv(shift);
+    q.rq_inv = inv((u64)Rq);
+    const u64 gni = inv(pow(shift, (u64)n));
+    u64 x = 1;
+    for (u32 cidx = 0; cidx < Rq; cidx++) { q.gn_inv_pow[cidx] = x; x = mul(x, gni); }
+    for (u32 c0 = 0; c0 < channels; c0 += 65535) {            // the channel rides in grid.y; the prover's [K][nch] channels fit one launch
+        q.V = pV + (size_t)c0 * Rq * n; q.out = out + (size_t)c0 * Rq * n;
+        hipLaunchKernelGGL(k_quotient_combine, dim3(nblk(n), std::min(65535u, channels - c0)), dim3(256), 0, c->stream, q);
+        GLP_HIP(hipGetLastError());
+    }
+    return GLP_OK;
+}
 #include "prover_stages.inc"
 
 // One proof in flight, cut at the points where the Fiat-Shamir transcript needs something from the device or the device

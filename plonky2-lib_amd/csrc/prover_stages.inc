@@ -156,17 +156,7 @@ int stage_quotient_eval(glp_ctx *c, const ProveGeo &g, const QProof &qp, const Q
 }
 // values on the planes (qv) -> the quotient chunks' coefficients (qc, bit-reversed order); qV: scratch.  All [K][nch][Rq][n].
 int stage_quotient_coeffs(glp_ctx *c, const ProveGeo &g, u64 *qv, u64 *qV, u64 *qc) {
-    GLP_TRY(intt_values_to_coeffs(c, qv, qV, g.K * g.nch * g.Rq, g.lg));
-    QCArgs q;
-    q.V = qV; q.out = qc; q.lg = (u32)g.lg; q.Rq = g.Rq;
-    q.wM_inv = inv(root_of_unity(g.lg + g.qdb)); q.wR_inv = inv(root_of_unity(g.qdb)); q.g_inv = inv(GEN);
-    q.rq_inv = inv((u64)g.Rq);
-    const u64 gni = inv(pow(GEN, (u64)g.n));
-    u64 x = 1;
-    for (u32 cidx = 0; cidx < g.Rq; cidx++) { q.gn_inv_pow[cidx] = x; x = mul(x, gni); }
-    hipLaunchKernelGGL(k_quotient_combine, dim3(nblk(g.n), g.K * g.nch), dim3(256), 0, c->stream, q);     // [K][nch] channels, contiguous
-    GLP_HIP(hipGetLastError());
-    return GLP_OK;
+    return coset_planes_to_chunk_coeffs(c, qv, qV, qc, g.K * g.nch, g.lg, g.qdb, GEN);
 }
 
 // K7.  Partial sums of one proof: the four oracles at zeta, then the Z columns at g zeta; poff[b] = where block b starts, poff[5] = words per proof
