@@ -8,6 +8,7 @@ import pytest
 
 import plonky2_lib_amd as glp
 import plonky2_lib_amd.synth as synth
+import proof_sections
 
 pytestmark = pytest.mark.gpu
 
@@ -20,39 +21,8 @@ def ctx():
 
 
 def _sections(desc):
-    """word ranges of a proof by section, from the documented layout (include/glp.h)"""
-    nch, capn = desc.num_challenges, 1 << desc.cap_height
-    cols = [desc.num_constants + desc.num_routed_wires, desc.num_wires, nch * (1 + desc.num_partial_products), nch * desc.quotient_degree_factor]
-    nopen = sum(cols) + nch
-    depth0 = desc.degree_bits + desc.rate_bits - desc.cap_height
-    o = {}
-    o["wires_cap"] = (0, 4 * capn)
-    o["zs_cap"] = (4 * capn, 8 * capn)
-    o["quotient_cap"] = (8 * capn, 12 * capn)
-    o["openings"] = (12 * capn, 12 * capn + 2 * nopen)
-    p = 12 * capn + 2 * nopen
-    nred = len(desc.reduction_arity_bits)
-    o["fri_caps"] = (p, p + 4 * capn * nred)
-    p += 4 * capn * nred
-    q0 = p
-    at = q0
-    for k in range(4):
-        o["q0_leaf%d" % k] = (at, at + cols[k]); at += cols[k]
-        o["q0_path%d" % k] = (at, at + 4 * depth0); at += 4 * depth0
-    lg = desc.degree_bits + desc.rate_bits
-    for r, ab in enumerate(desc.reduction_arity_bits):
-        lg -= ab
-        o["q0_step%d_evals" % r] = (at, at + (2 << ab)); at += 2 << ab
-        o["q0_step%d_path" % r] = (at, at + 4 * (lg - desc.cap_height)); at += 4 * (lg - desc.cap_height)
-    stride = at - q0
-    last = q0 + (desc.num_query_rounds - 1) * stride
-    o["qlast_leaf1"] = (last + cols[0] + 4 * depth0, last + cols[0] + 4 * depth0 + cols[1])
-    p = q0 + desc.num_query_rounds * stride
-    fl = 1 << (desc.degree_bits - sum(desc.reduction_arity_bits))
-    o["final_poly"] = (p, p + 2 * fl)
-    o["pow"] = (p + 2 * fl, p + 2 * fl + 1)
-    o["public_inputs"] = (p + 2 * fl + 1, p + 2 * fl + 1 + len(desc.public_inputs))
-    return {k: v for k, v in o.items() if v[1] > v[0]}
+    """word ranges of a proof by section: tests/proof_sections.py, the map written from the documented layout (include/glp.h)"""
+    return proof_sections.legacy_ranges(desc)
 
 
 def _tampered_batch(proof, desc, rng):
