@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void k_final_values_small(FVArgs a) {
     u32 base = 0;
     for (int k = 0; k < 4; k++) {
         const u64 *l = a.lde[k] + q;
-        for (u32 c = t; c < a.ncols[k]; c += lpp) {          // fewer than ACC_MAX_TERMS terms per lane: no flush
+        for (u32 c = t; c < a.ncols[k]; c += lpp) {          // at most ACC_MAX_TERMS terms per lane (final_values_small_fits): no flush
             const u32 j = base + c;
             const u64 v = l[(size_t)c * N];
             const u32 v0 = (u32)v & 0x3FFFFFu, v1 = (u32)(v >> 22) & 0x3FFFFFu, v2 = (u32)(v >> 44);

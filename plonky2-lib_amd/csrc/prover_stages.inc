@@ -247,6 +247,16 @@ int fri_values_to_coeffs(glp_ctx *c, const ProveGeo &g, const u64 *fv, u64 *fcoe
     GLP_HIP(hipGetLastError());
     return GLP_OK;
 }
+// k_final_values_small never flushes its carry-free accumulators, so it serves 4..128 points only while no lane can pass
+// ACC_MAX_TERMS terms: lane t of a point takes the columns t, t + lpp, .. of each oracle, lane 0 the most, sum_b ceil(ncols[b] / lpp).
+// The bound is the worst case of acc.h, not what natural data needs.  Wider circuits go to k_final_values, which flushes.
+inline bool final_values_small_fits(const ProveGeo &g, const glp_batch *const ob[4]) {
+    if (g.lg < 2 || g.lg > 7) return false;
+    const u32 lpp = 256u >> g.lg;
+    size_t lane_terms = 0;
+    for (int b = 0; b < 4; b++) lane_terms += (ob[b]->ncols + lpp - 1) / lpp;
+    return lane_terms <= ACC_MAX_TERMS;
+}
 // K8: alpha-combination of all openings batches, quotient by (X - zeta) / (X - g zeta) -> fcoef [K][2][n], the FRI polynomial's
 // coefficients; fv: scratch of the same size.  dev_ap [K][2 oracle_cols]; pt != nullptr: one proof with the values of
 // fri_alpha_powers; else they come from dev_pp[K][10].
@@ -259,8 +269,8 @@ int stage_fri_values(glp_ctx *c, const ProveGeo &g, const glp_batch *const ob[4]
     a.red0 = pt ? pt[0] : zero; a.red1 = pt ? pt[1] : zero; a.zeta = pt ? pt[2] : zero; a.zeta_next = pt ? pt[3] : zero; a.shift_acc = pt ? pt[4] : zero;
     a.w_n = root_of_unity(g.lg); a.g = GEN; a.lg = (u32)g.lg; a.rb = (u32)g.rb; a.nch = g.nch;
     a.pp = pt ? nullptr : dev_pp; a.apow_stride = 2 * oracle_cols(ob); a.out_stride = 2 * g.n;
-    if (g.lg >= 2 && g.lg <= 7) hipLaunchKernelGGL(k_final_values_small, dim3(1, g.K), dim3(256), 0, c->stream, a);      // 4..128 points: 256 / n lanes per point
-    else hipLaunchKernelGGL(k_final_values, dim3(nblk(g.n), g.K), dim3(256), 0, c->stream, a);
+    if (final_values_small_fits(g, ob)) hipLaunchKernelGGL(k_final_values_small, dim3(1, g.K), dim3(256), 0, c->stream, a);      // 4..128 points: 256 / n lanes per point
+    else hipLaunchKernelGGL(k_final_values, dim3(nblk(g.n), g.K), dim3(256), 0, c->stream, a);            // any n (and lg < 2), one lane per point
     GLP_HIP(hipGetLastError());
     return fri_values_to_coeffs(c, g, fv, fcoef);
 }

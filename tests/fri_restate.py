@@ -49,6 +49,18 @@ def eval_ext(coeffs, z):
     return acc
 
 
+def periodic_opening(C, log_n, z):
+    """f(z) for f = sum_p C[p mod len(C)] X^p with deg f < n = 2^log_n and m = len(C) dividing n, in closed form:
+    (sum_i C_i z^i) (z^n - 1) / (z^m - 1).  The reference for openings too long to walk term by term (pinned against eval_ext in
+    test_fri_openings.py)."""
+    head, zi = (0, 0), (1, 0)
+    for c in C:
+        head = e_add(head, e_scale(zi, int(c)))
+        zi = e_mul(zi, z)
+    num = e_sub(e_pow(z, 1 << log_n), (1, 0))
+    return e_mul(head, e_mul(num, e_inv(e_sub(zi, (1, 0)))))
+
+
 # ------------------------------------------------------------------ instance, oracles
 class Instance:
     """points: [((a, b), [(oracle, col_begin, num_cols), ...]), ...]; ncols / salted: per oracle"""

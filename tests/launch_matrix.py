@@ -5,6 +5,7 @@ The prover chooses its kernels at run time from the circuit's shape.  `launch_pl
 names each one; `CASES` lists circuits, each with the paths it exists for.  A rule change in the C++ that this module
 does not follow makes test_launch_plan.py fail (a path no case reaches any more, or a case that lost its path)."""
 import collections
+import os
 
 import numpy as np
 
@@ -14,6 +15,7 @@ LIMB_SLOTS, LIMB_GROUPS = 5, 4            # quotient_kernels.inc: constexpr int 
 LIGHT_MAX, EXTRA_MAX = 8, 4               # quotient_kernels.inc: LightArgs::gi[8], LimbArgs::extra_gi[4]
 PP_SMALL_LDS = 64 * 1024                  # prover_stages.inc stage_partial_products(): small_lds <= 64 KiB
 MERKLE_COOP_MAX, MERKLE_QUAD_MAX = 4096, 32768   # common.h: glp_ctx::merkle_coop_max / merkle_quad_max (GLP_MERKLE_COOP_MAX / _QUAD_MAX)
+ACC_MAX_TERMS = 1024                      # acc.h: terms a carry-free AccLimb holds before it must be reduced
 
 # context thresholds that force one FRI leaf-hash form (the values test_gpu_commit.py::test_leaf_hash_forms uses)
 MERKLE_FORMS = {"lane": (0, 0), "quad": (0, 1 << 40), "coop": (1 << 40, 1 << 40)}
@@ -57,6 +59,22 @@ def quotient_plan(desc):
                 keep.append(gi)
         single = keep
     return dict(limb=limb, groups=-(-len(limb) // LIMB_SLOTS), light=light, arith=arith, single=single, extra=extra, demoted=demoted)
+
+
+def opened_columns(desc):
+    """polynomials of the four oracles the FRI batch polynomial sums: constants ++ sigmas, wires, Zs ++ partial products, quotient chunks"""
+    nch = desc.num_challenges
+    return [desc.num_constants + desc.num_routed_wires, desc.num_wires, nch * (1 + desc.num_partial_products),
+            nch * desc.quotient_degree_factor]
+
+
+def final_values_terms(desc):
+    """terms the busiest lane of the final-values kernel adds up.  4..128 rows (k_final_values_small): 256 / n lanes share a point,
+    lane t takes the columns t, t + lpp, .. of each oracle, so lane 0 carries sum_k ceil(ncols[k] / lpp).  Otherwise
+    (k_final_values) one lane walks every column."""
+    lg = desc.degree_bits
+    lpp = 256 >> lg if 2 <= lg <= 7 else 1
+    return sum(-(-c // lpp) for c in opened_columns(desc))
 
 
 def launch_plan(desc, K=1, coop_max=MERKLE_COOP_MAX, quad_max=MERKLE_QUAD_MAX):
@@ -108,11 +126,18 @@ def launch_plan(desc, K=1, coop_max=MERKLE_COOP_MAX, quad_max=MERKLE_QUAD_MAX):
         out.add("pp_small_lg%d" % lg)
     else:
         out.add("pp_large_lds_fallback" if lg <= 7 else "pp_large")
-    # final values (FRI combination): stage_fri_values(); 256 / n lanes per point
-    if 2 <= lg <= 7:
+    # final values (FRI combination): stage_fri_values(); 256 / n lanes per point while no lane passes ACC_MAX_TERMS terms
+    # (final_values_small_fits(): k_final_values_small never flushes), else k_final_values, which flushes every ACC_MAX_TERMS columns
+    if 2 <= lg <= 7 and final_values_terms(desc) <= ACC_MAX_TERMS:
         out.add("fv_small_lg%d_nch%d" % (lg, nch) if lg in (2, 3, 7) else "fv_small_nch%d" % nch)
+    elif 2 <= lg <= 7:
+        # the fallback runs k_final_values on more than ACC_MAX_TERMS columns by construction, so this name implies its flush
+        # too; fv_large_flush is kept for 2^8 rows and more, where the two can be told apart
+        out.add("fv_small_wide_fallback")
     else:
         out.add("fv_large_nch%d" % nch)
+        if sum(opened_columns(desc)) > ACC_MAX_TERMS:
+            out.add("fv_large_flush")
     # FRI leaf hash of each reduction: stage_fri_commit() (nleaves * K)
     lgcur = lg
     for ab in desc.reduction_arity_bits:
@@ -142,6 +167,7 @@ ALL_PATHS = sorted(
     + ["pp_small_lg%d" % lg for lg in range(2, 8)] + ["pp_large_lds_fallback", "pp_large"]
     + ["fv_small_lg%d_nch%d" % (lg, n) for lg in (2, 3, 7) for n in (1, 2, 3, 4)]
     + ["fv_small_nch%d" % n for n in (1, 2, 3, 4)] + ["fv_large_nch%d" % n for n in (1, 2, 3, 4)]
+    + ["fv_small_wide_fallback", "fv_large_flush"]
     + ["fri_leaf_coop", "fri_leaf_quad", "fri_leaf_lane", "fri_leaf_keccak", "batch_k2", "batch_k9"])
 
 # ------------------------------------------------------------------------------------------------ circuit builders
@@ -307,4 +333,79 @@ BATCH_PATHS = {"arith_lg10_batch9": {"fri_leaf_quad", "batch_k9"}, "ecdsa_nch2_l
 # cases the forced leaf-hash forms are run on (test_gpu_launch_paths.py::test_forced_merkle_forms)
 FORM_CASES = ["ecdsa_nch2_lg7", "smt_nch2_lg8", "keccak_nch2_lg6", "limbs13"]
 
-BY_ID = {c.id: c for c in CASES}
+# Circuits wide enough to reach the term bounds of the carry-free accumulators in the final-values kernels (a list of its own:
+# test_gpu_wide_shapes.py proves these, test_gpu_launch_paths.py keeps to CASES).  mixed(lg, [], nw=W) opens [83, W, 20, 16] columns.
+# 128 rows, two lanes per point, lane 0 carries 60 + ceil(W / 2) terms; 256 rows, one lane walks all 119 + W columns.
+WIDE_WIDTHS = [
+    (7, 1928, {"fv_small_lg7_nch2"}),                # lane 0 has exactly ACC_MAX_TERMS terms: the last width the small kernel may take
+    (7, 1929, {"fv_small_wide_fallback"}),           # 1025 terms: the first width past the bound
+    (7, 10000, {"fv_small_wide_fallback"}),          # about 5060 terms per lane: past where natural data wraps an accumulator
+    (8, 905, {"fv_large_nch2"}),                     # 1024 columns: k_final_values flushes on its last term
+    (8, 906, {"fv_large_flush"}),                    # 1025 columns: one term after the flush
+    (8, 2100, {"fv_large_flush"}),                   # two flushes and a remainder
+    (8, 6000, {"fv_large_flush"}),                   # 6119 terms: a missing flush is certain to wrap
+]
+WIDE_TERMS = {(7, 1928): 1024, (7, 1929): 1025, (7, 10000): 5060, (8, 905): 1024, (8, 906): 1025, (8, 2100): 2219, (8, 6000): 6119}
+
+
+def wide_id(lg, nw):
+    return "wide_lg%d_w%d" % (lg, nw)
+
+
+WIDE_CASES = [_case(wide_id(lg, nw), (lambda lg=lg, nw=nw: mixed(lg, [], nw=nw)), paths) for lg, nw, paths in WIDE_WIDTHS] + [
+    # 2000 routed wires: 249 partial products per challenge, 500 columns in the third oracle, 1 MiB of running products
+    _case("wide_routed_lg7", lambda: synth.arith_circuit(7, synth.Config(2100, 2000), seed=3), {"fv_small_wide_fallback", "pp_large_lds_fallback"}),
+    # arity 32 (glp_circuit_create's largest): one reduction 2^10 -> 2^5, leaves of 64 words
+    _case("arity32_lg10", lambda: mixed(10, [], arity_bits=5, final_poly_bits=0, num_query_rounds=3), {"fv_large_nch2", "fri_leaf_coop"}),
+]
+
+BY_ID = {c.id: c for c in CASES + WIDE_CASES}
+
+
+# ------------------------------------------------------------------------------------------------ shared by the GPU parity tests
+_REFS = {}                                   # case id -> (desc, oracle circuit, oracle proof): made once per session, left unchanged
+
+
+def oracle_ref(oracle, cid):
+    """the case's description, its oracle circuit and the oracle's proof (which the oracle verifier accepts)"""
+    if cid not in _REFS:
+        desc = BY_ID[cid].build()
+        oc = oracle.OracleCircuit(desc)
+        rc, ref = oc.prove()
+        assert rc == 0 and oc.verify(ref) == 0
+        _REFS[cid] = desc, oc, ref
+    return _REFS[cid]
+
+
+def head_sections(desc):
+    """name -> slice of the proof words (layout: include/glp.h)"""
+    cap = 4 << desc.cap_height
+    nch = desc.num_challenges
+    nopen = (desc.num_constants + desc.num_routed_wires + desc.num_wires + 2 * nch + nch * desc.num_partial_products +
+             nch * desc.quotient_degree_factor)
+    o, out = 0, {}
+    for name, ln in (("wires_cap", cap), ("zs_pp_cap", cap), ("quotient_cap", cap), ("openings", 2 * nopen),
+                     ("fri_caps", cap * len(desc.reduction_arity_bits))):
+        out[name] = slice(o, o + ln)
+        o += ln
+    out["rest"] = slice(o, None)
+    return out
+
+
+def assert_sections_equal(got, ref, desc, what):
+    for name, sl in head_sections(desc).items():
+        assert (got[sl] == ref[sl]).all(), "%s: first mismatch in section %s at word %d" % (
+            what, name, sl.start + int(np.argmax(got[sl] != ref[sl])))
+
+
+def prove_batch(gc, desc, K, host_transcript=False):
+    """glp_prove_batch of K copies of the case's witness, under the device transcript or the host one"""
+    wires = np.stack([desc.wires] * K)
+    pis = np.stack([desc.public_inputs] * K) if len(desc.public_inputs) else None
+    if not host_transcript:
+        return gc.prove_batch(wires, pis)
+    os.environ["GLP_BATCH_HOST_TRANSCRIPT"] = "1"
+    try:
+        return gc.prove_batch(wires, pis)
+    finally:
+        del os.environ["GLP_BATCH_HOST_TRANSCRIPT"]

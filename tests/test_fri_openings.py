@@ -117,3 +117,17 @@ def test_restated_prover_against_the_restated_verifier(oracle):
         c2 = fr.challenger_clone(oracle, replay)
         c2.observe([cand])
         assert (c2.get() >> (64 - inst.pow_bits) == 0) == (cand == wit)
+
+
+def test_periodic_opening_closed_form():
+    """fri_restate.periodic_opening, the reference test_gpu_wide_shapes.py opens 2^24 coefficients against, equals Horner over all
+    coefficients at sizes Python walks in no time: both coefficient sets of that test and a random one, periods 4 and 2"""
+    P = fr.P
+    z = (0x0123456789ABCDEF, 0xFEDCBA9876543210 % P)
+    rng = np.random.default_rng(14)
+    sets = [[P - 2, P - 1, 1, 0x9E3779B97F4A7C15 % P], [P - 2, P - 1, P - 3, P - 4], [int(v) % P for v in rng.integers(0, 1 << 63, 4)], [5, P - 7]]
+    for C in sets:
+        for log_n in (2, 3, 10):
+            coeffs = np.tile(np.array(C, np.uint64), (1 << log_n) // len(C))
+            assert fr.periodic_opening(C, log_n, z) == fr.eval_ext(coeffs, z)
+            assert fr.periodic_opening(C, log_n, (3, 0)) == fr.eval_ext(coeffs, (3, 0))

@@ -15,7 +15,6 @@ pytestmark = pytest.mark.gpu
 
 SPECIAL = np.array([0, 1, 2, 3, glp.P - 1, glp.P - 2, glp.P - 3, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, 0xFFFFFFFF00000000,
                     0xFFFFFFFE00000001, 0xFFFFFFFEFFFFFFFF, 1 << 63, (1 << 63) - 1, 0xFFFFFFFF], dtype=np.uint64)
-_REFS = {}                                   # case id -> (desc, oracle circuit, oracle proof): shared by the tests of the module
 
 
 @pytest.fixture(scope="module")
@@ -25,35 +24,7 @@ def ctx():
     c.close()
 
 
-def _ref(oracle, cid):
-    if cid not in _REFS:
-        desc = lm.BY_ID[cid].build()
-        oc = oracle.OracleCircuit(desc)
-        rc, ref = oc.prove()
-        assert rc == 0 and oc.verify(ref) == 0
-        _REFS[cid] = desc, oc, ref
-    return _REFS[cid]
-
-
-def _sections(desc):
-    """name -> slice of the proof words (layout: include/glp.h)"""
-    cap = 4 << desc.cap_height
-    nch = desc.num_challenges
-    nopen = (desc.num_constants + desc.num_routed_wires + desc.num_wires + 2 * nch + nch * desc.num_partial_products +
-             nch * desc.quotient_degree_factor)
-    o, out = 0, {}
-    for name, ln in (("wires_cap", cap), ("zs_pp_cap", cap), ("quotient_cap", cap), ("openings", 2 * nopen),
-                     ("fri_caps", cap * len(desc.reduction_arity_bits))):
-        out[name] = slice(o, o + ln)
-        o += ln
-    out["rest"] = slice(o, None)
-    return out
-
-
-def _assert_equal(got, ref, desc, what):
-    for name, sl in _sections(desc).items():
-        assert (got[sl] == ref[sl]).all(), "%s: first mismatch in section %s at word %d" % (
-            what, name, sl.start + int(np.argmax(got[sl] != ref[sl])))
+_ref, _sections, _assert_equal, _prove_batch = lm.oracle_ref, lm.head_sections, lm.assert_sections_equal, lm.prove_batch
 
 
 def _boundary_wires(desc):
@@ -63,18 +34,6 @@ def _boundary_wires(desc):
     keep = rng.random(desc.wires.shape) < 0.3
     w[keep] = desc.wires[keep]
     return w
-
-
-def _prove_batch(gc, desc, K, host_transcript=False):
-    wires = np.stack([desc.wires] * K)
-    pis = np.stack([desc.public_inputs] * K) if len(desc.public_inputs) else None
-    if not host_transcript:
-        return gc.prove_batch(wires, pis)
-    os.environ["GLP_BATCH_HOST_TRANSCRIPT"] = "1"
-    try:
-        return gc.prove_batch(wires, pis)
-    finally:
-        del os.environ["GLP_BATCH_HOST_TRANSCRIPT"]
 
 
 @pytest.mark.parametrize("case", lm.CASES, ids=[c.id for c in lm.CASES])

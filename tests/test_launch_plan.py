@@ -1,13 +1,16 @@
 """CPU checks of the launch-path matrix (launch_matrix.py): every case reaches the paths it exists for, the cases together
-reach every path the prover has, and every case's witness satisfies its circuit (the oracle proves and accepts it)."""
+reach every path the prover has, and every case's witness satisfies its circuit (the oracle proves and accepts it).  The wide
+circuits of launch_matrix.WIDE_CASES are cases like any other here; their term counts are pinned to the accumulator bound."""
 import pytest
 
 import launch_matrix as lm
 
+CASES = lm.CASES + lm.WIDE_CASES
+
 
 @pytest.fixture(scope="module")
 def descs():
-    return {c.id: c.build() for c in lm.CASES}
+    return {c.id: c.build() for c in CASES}
 
 
 def _plans(c, desc):
@@ -21,11 +24,11 @@ def _plans(c, desc):
 
 
 def test_case_ids_are_unique():
-    assert len(lm.BY_ID) == len(lm.CASES)
+    assert len(lm.BY_ID) == len(CASES)
     assert set(lm.FORM_CASES) <= set(lm.BY_ID) and set(lm.BATCH_PATHS) <= set(lm.BY_ID)
 
 
-@pytest.mark.parametrize("case", lm.CASES, ids=[c.id for c in lm.CASES])
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_case_reaches_its_paths(descs, case):
     desc = descs[case.id]
     plan = lm.launch_plan(desc)
@@ -37,7 +40,7 @@ def test_case_reaches_its_paths(descs, case):
 
 def test_cases_cover_every_path(descs):
     reached = set()
-    for c in lm.CASES:
+    for c in CASES:
         for p in _plans(c, descs[c.id]):
             reached |= p
     assert sorted(reached) == lm.ALL_PATHS, dict(orphaned=sorted(set(lm.ALL_PATHS) - reached), unlisted=sorted(reached - set(lm.ALL_PATHS)))
@@ -64,7 +67,24 @@ def test_plan_follows_the_limb_group_rules(descs):
     assert len(q["light"]) == 8 and len(q["single"]) == 2 and q["arith"] is not None
 
 
-@pytest.mark.parametrize("case", lm.CASES, ids=[c.id for c in lm.CASES])
+def test_wide_cases_sit_on_the_accumulator_bound(descs):
+    """the widths were chosen from these counts: a change in synth's column counts must not move a case off its boundary in silence"""
+    for lg, nw, paths in lm.WIDE_WIDTHS:
+        desc = descs[lm.wide_id(lg, nw)]
+        assert lm.opened_columns(desc) == [83, nw, 20, 16] and desc.degree_bits == lg
+        assert lm.final_values_terms(desc) == lm.WIDE_TERMS[lg, nw]
+    t = lm.WIDE_TERMS
+    assert t[7, 1928] == t[8, 905] == lm.ACC_MAX_TERMS and t[7, 1929] == t[8, 906] == lm.ACC_MAX_TERMS + 1
+    assert 2 * lm.ACC_MAX_TERMS < t[8, 2100] < 3 * lm.ACC_MAX_TERMS and min(t[7, 10000], t[8, 6000]) > 4400
+    # which kernel each takes: the small one up to the bound and not past it; the flush path only past 1024 columns
+    plans = {(lg, nw): lm.launch_plan(descs[lm.wide_id(lg, nw)]) for lg, nw, _ in lm.WIDE_WIDTHS}
+    assert "fv_small_wide_fallback" not in plans[7, 1928] and "fv_small_lg7_nch2" not in plans[7, 1929]
+    assert "fv_large_flush" not in plans[8, 905] and "fv_large_flush" in plans[8, 906]
+    # the batch of small proofs the benchmark runs stays on the small kernel
+    assert "fv_small_lg3_nch2" in lm.launch_plan(descs["zkdsa_nch2"], K=2)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_oracle_proves_and_accepts_the_witness(oracle, descs, case):
     desc = descs[case.id]
     oc = oracle.OracleCircuit(desc)
