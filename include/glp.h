@@ -229,6 +229,60 @@ GLP_API int glp_batch_from_coset_values(glp_ctx *ctx, const uint64_t *values, in
                                         uint32_t num_polys, uint32_t log_n, uint32_t sub_bits, uint32_t rate_bits,
                                         uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out);
 
+/* ---- the permutation argument at the commitment seam ----------------------------------------------------------------------------
+ * Two steps of `prove_with_partition_witness` that are the same for every plonky2 circuit, whatever its gates, for the integrator of
+ * the blocks around this one (no glp_circuit exists for its circuit): Z and the partial products
+ * (`wires_permutation_partial_products_and_zs`, committed as plonk_zs_partial_products) and the permutation terms of the vanishing
+ * polynomial on the quotient's coset.  With them the caller's own quotient code evaluates its gate constraints only.
+ * glp_perm_desc is the part of CommonCircuitData these steps read.  Challenges are host arrays [num_proofs][num_challenges],
+ * canonical; `*_on_device` != 0 marks an HBM pointer on the context's GPU; num_proofs is 1..4096 and every array gets a leading
+ * [num_proofs] (one proof is num_proofs = 1).  Every refusal is GLP_ERR_ARG, names the field and happens before any launch. */
+typedef struct {
+    uint32_t log_n;
+    uint32_t num_wires;          /* columns of the wires oracle; the routed ones come first */
+    uint32_t num_routed_wires;   /* 1..num_wires */
+    uint32_t num_challenges;     /* 1..4 */
+    uint32_t chunk_size;         /* plonky2's quotient_degree_factor: routed wires per partial-product chunk, >= 1;
+                                    num_partial_products = ceil(num_routed_wires / chunk_size) - 1, last chunk may be short */
+    const uint64_t *k_is;        /* [num_routed_wires] coset shifts, canonical */
+} glp_perm_desc;
+/* num_challenges * (1 + num_partial_products): the polynomials of plonk_zs_partial_products; 0 for a refused description */
+GLP_API uint32_t glp_perm_num_polys(const glp_perm_desc *desc);
+/* Z and the partial products of num_proofs witnesses on H, committed: a batch of num_proofs members of glp_perm_num_polys columns
+ * each, in the layout of `all_wires_permutation_partial_products` (the Z of every challenge first, then each challenge's partial
+ * products).  Word for word glp_batch_many_from_values(those values, .., seed): seed NULL = no blinding, else member k is salted with
+ * (seed0, seed1, seed2, seed3 + k) and tag GLP_SALT_TAG_BATCH; at num_proofs == 1 without a seed it is glp_batch_from_values_h.  For a
+ * circuit the library can prove, the result's cap is what glp_session_partial_products returns.  A zero denominator (probability about
+ * n * num_routed_wires * 2^-64) is not detected, as in the session.
+ *   wires    [num_proofs][num_wires][n] values on H      sigmas   [num_routed_wires][n] values on H, shared by all proofs
+ * Size bounds, log_n, rate_bits, cap_height and hasher: those of glp_batch_many_from_values. */
+GLP_API int glp_perm_zs_commit(glp_ctx *ctx, const glp_perm_desc *desc, uint32_t num_proofs,
+                               const uint64_t *wires, int wires_on_device, const uint64_t *sigmas, int sigmas_on_device,
+                               const uint64_t *betas, const uint64_t *gammas,
+                               uint32_t rate_bits, uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out);
+/* With M = 2^(log_n + sub_bits), S = 2^sub_bits, x_i = g W_M^i (the coset of glp_batch_lde_values) and T = num_challenges *
+ * (num_partial_products + 2) permutation terms, for proof k and challenge c:
+ *     out[k][c][i] = ( sum_{t < T} alpha_{k,c}^t term_t(x_i)  +  alpha_{k,c}^T gate_sums[k][c][i] ) / Z_H(x_i)
+ * The terms in plonky2's order (`eval_vanishing_poly_base_batch`): L_0(x) (Z_j(x) - 1) for j < num_challenges; then per challenge j
+ * and chunk  prev prod(w + beta_j k x + gamma_j) - next prod(w + beta_j sigma + gamma_j),  Z "next" being row (i + S) mod M.
+ *   sigmas_oracle   columns [sigma_col_begin, sigma_col_begin + num_routed_wires) are the sigmas (plonky2 keeps them after the
+ *                   constants); one member, shared by all proofs, or num_proofs members
+ *   wires_oracle    at least num_wires polynomials;  zs_oracle: glp_perm_num_polys polynomials (glp_perm_zs_commit's result);
+ *                   num_proofs members each (a glp_batch_member view is a batch of one).  Salted or not, each.
+ *   gate_sums       NULL, or [num_proofs][num_challenges][M]: the caller's sum_t alpha^t (filtered gate constraint t), natural order on
+ *                   the same coset.  With NULL the second summand is absent; the map is linear, so a caller may add its share afterwards.
+ *   out             [num_proofs][num_challenges][M]: what glp_batch_from_coset_values takes with num_polys = num_challenges.  Host
+ *                   memory: the call returns after the copy; an HBM pointer: nothing is copied back.
+ * Refused beyond the common rules: sub_bits > rate_bits; chunk_size > 2^sub_bits (the chunk check would exceed the quotient's
+ * degree); oracles that disagree in log_n (with desc and each other), rate_bits or ctx; wires_oracle with fewer than num_wires
+ * polynomials; zs_oracle whose polynomial count is not glp_perm_num_polys; a sigma range past its oracle's polynomials (salts are not
+ * polynomials); a member count that is neither num_proofs nor, for the sigmas only, 1. */
+GLP_API int glp_perm_quotient_values(glp_ctx *ctx, const glp_perm_desc *desc, uint32_t num_proofs,
+                                     const glp_batch *sigmas_oracle, uint32_t sigma_col_begin,
+                                     const glp_batch *wires_oracle, const glp_batch *zs_oracle, uint32_t sub_bits,
+                                     const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                                     const uint64_t *gate_sums, int gate_sums_on_device, uint64_t *out, int out_on_device);
+
 /* ---- openings and FRI of caller-held batches (fri/oracle.rs `PolynomialBatch::prove_openings`) ----------------------------------
  * For an integrator that keeps its own quotient (circuits with lookup tables, Poseidon2Gate, custom gates, starky AIRs: anything
  * glp_circuit_create answers with GLP_ERR_UNSUPPORTED): commit with glp_batch_from_values / _from_coeffs, evaluate the committed

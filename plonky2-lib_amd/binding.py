@@ -67,6 +67,11 @@ class _FriVerifyDesc(C.Structure):
                 ("num_query_rounds", C.c_uint32)]
 
 
+class _PermDesc(C.Structure):
+    _fields_ = [("log_n", C.c_uint32), ("num_wires", C.c_uint32), ("num_routed_wires", C.c_uint32), ("num_challenges", C.c_uint32),
+                ("chunk_size", C.c_uint32), ("k_is", C.c_void_p)]
+
+
 LDE_ROW_MAJOR, LDE_COL_MAJOR = 0, 1      # GLP_LDE_* of glp_batch_lde_values
 
 
@@ -135,6 +140,8 @@ def load_library():
     }
     L.glp_batch_leaf_len.restype = u32
     L.glp_batch_leaf_len.argtypes = [vp]
+    L.glp_perm_num_polys.restype = u32
+    L.glp_perm_num_polys.argtypes = [C.POINTER(_PermDesc)]
     for name in ("glp_batch_num_proofs", "glp_fri_num_proofs"):
         getattr(L, name).restype = u32
         getattr(L, name).argtypes = [vp]
@@ -184,6 +191,8 @@ def load_library():
         "glp_batch_lde_values": [vp, u32, u32, u32, u64, u64, u32, vp, C.c_int],
         "glp_coset_ifft": [vp, vp, u32, u32, u64],
         "glp_batch_from_coset_values": [vp, vp, C.c_int, u32, u32, u32, u32, u32, u32, u32, vp, C.POINTER(vp)],
+        "glp_perm_zs_commit": [vp, C.POINTER(_PermDesc), u32, vp, C.c_int, vp, C.c_int, vp, vp, u32, u32, u32, vp, C.POINTER(vp)],
+        "glp_perm_quotient_values": [vp, C.POINTER(_PermDesc), u32, vp, u32, vp, vp, u32, vp, vp, vp, vp, C.c_int, vp, C.c_int],
         "glp_fri_begin_many": [vp, C.POINTER(_FriDesc), u32, vp, C.POINTER(vp)],
         "glp_fri_queries_many": [vp, vp, vp],
         "glp_pow_search_many": [vp, u32, u32, vp, vp, u32, u32, vp],
@@ -438,6 +447,59 @@ class Context:
         b.hasher = int(hasher)
         return b
 
+    def perm_zs_commit(self, desc, wires, sigmas, betas, gammas, rate_bits=3, cap_height=4, hasher=0, seed=None, wires_dev_ptr=None,
+                       sigmas_dev_ptr=None):
+        """glp_perm_zs_commit: Z and the partial products of the permutation argument, committed.  desc: the attributes perm_desc()
+        reads.  betas, gammas [num_challenges] with wires [num_wires][n] for one proof, or [num_proofs][num_challenges] with wires
+        [num_proofs][num_wires][n]; sigmas [num_routed_wires][n].  *_dev_ptr: that array is already in HBM at the pointer (the host
+        argument is ignored).  Returns the Batch of num_proofs members, perm_num_polys(desc) columns each."""
+        d, keep = perm_desc(desc)
+        b, g = _a(betas), _a(gammas)
+        K = b.shape[0] if b.ndim == 2 else 1
+        w = None if wires_dev_ptr is not None else _a(wires)
+        sg = None if sigmas_dev_ptr is not None else _a(sigmas)
+        n = 1 << d.log_n
+        if w is not None and w.size != K * d.num_wires * n:
+            raise GlpError(-1, "wires has %d elements, expected num_proofs * num_wires * n = %d" % (w.size, K * d.num_wires * n))
+        if sg is not None and sg.size != d.num_routed_wires * n:
+            raise GlpError(-1, "sigmas has %d elements, expected num_routed_wires * n = %d" % (sg.size, d.num_routed_wires * n))
+        if b.size != K * d.num_challenges or g.size != b.size:
+            raise GlpError(-1, "betas and gammas are [num_challenges] or [num_proofs][num_challenges]")
+        sd = None if seed is None else _a(seed)
+        if sd is not None and sd.size != 4:
+            raise GlpError(-1, "the salt seed is 4 words")
+        L = load_library()
+        h = C.c_void_p()
+        _chk(L.glp_perm_zs_commit(self._h, C.byref(d), K, C.c_void_p(wires_dev_ptr) if w is None else _p(w), 0 if w is not None else 1,
+                                  C.c_void_p(sigmas_dev_ptr) if sg is None else _p(sg), 0 if sg is not None else 1, _p(b), _p(g), rate_bits,
+                                  cap_height, int(hasher), None if sd is None else _p(sd), C.byref(h)))
+        out = Batch(self, h, int(L.glp_perm_num_polys(C.byref(d))), d.log_n, rate_bits, cap_height)
+        out.hasher = int(hasher)
+        return out
+
+    def perm_quotient_values(self, desc, sigmas_oracle, sigma_col_begin, wires_oracle, zs_oracle, sub_bits, betas, gammas, alphas,
+                             gate_sums=None, gate_sums_dev_ptr=None, out_dev_ptr=None):
+        """glp_perm_quotient_values: the permutation terms of the vanishing polynomial (plus alpha^T gate_sums) over Z_H on the coset
+        7 <W_M>, M = n << sub_bits, natural order: [num_challenges][M] for challenges [num_challenges], [num_proofs][num_challenges][M]
+        for [num_proofs][num_challenges] -- what batch_from_coset_values takes.  gate_sums: None, or an array of the result's shape
+        (gate_sums_dev_ptr: already in HBM).  out_dev_ptr: the values go to that HBM pointer and None is returned."""
+        d, keep = perm_desc(desc)
+        b, g, al = _a(betas), _a(gammas), _a(alphas)
+        K = b.shape[0] if b.ndim == 2 else 1
+        if b.size != K * d.num_challenges or g.size != b.size or al.size != b.size:
+            raise GlpError(-1, "betas, gammas and alphas are [num_challenges] or [num_proofs][num_challenges]")
+        M = 1 << (d.log_n + int(sub_bits))
+        shape = (K, d.num_challenges, M) if b.ndim == 2 else (d.num_challenges, M)
+        gs = None if gate_sums is None or gate_sums_dev_ptr is not None else _a(gate_sums)
+        if gs is not None and gs.size != K * d.num_challenges * M:
+            raise GlpError(-1, "gate_sums has %d elements, expected num_proofs * num_challenges * M = %d" % (gs.size, K * d.num_challenges * M))
+        gs_arg = C.c_void_p(gate_sums_dev_ptr) if gate_sums_dev_ptr is not None else (None if gs is None else _p(gs))
+        out = None if out_dev_ptr is not None else np.empty(shape, np.uint64)
+        _chk(load_library().glp_perm_quotient_values(self._h, C.byref(d), K, sigmas_oracle._h, int(sigma_col_begin), wires_oracle._h, zs_oracle._h,
+                                                     int(sub_bits), _p(b), _p(g), _p(al), gs_arg, 0 if gate_sums_dev_ptr is None else 1,
+                                                     C.c_void_p(out_dev_ptr) if out is None else _p(out), 0 if out is not None else 1))
+        return out
+
     def pow_search_many(self, hasher, sponge_states, pending_inputs, bits):
         """glp_pow_search_many: sponge_states [K][12], pending_inputs [K][num_pending] (num_pending < 8) -> the K smallest witnesses"""
         st = _a(sponge_states).reshape(-1, 12)
@@ -605,6 +667,23 @@ class Batch:
         out = np.empty((n, 4), np.uint64)
         _chk(load_library().glp_batch_digests(self._h, _p(out)))
         return out
+
+
+def perm_desc(desc):
+    """attribute bag (a synth circuit, or anything with degree_bits, num_wires, num_routed_wires, num_challenges, quotient_degree_factor
+    and k_is) -> (glp_perm_desc, the k_is array that must stay alive while it is used)"""
+    k = _a(desc.k_is)
+    if k.size != int(desc.num_routed_wires):
+        raise GlpError(-1, "k_is has %d entries, num_routed_wires is %d" % (k.size, desc.num_routed_wires))
+    d = _PermDesc(int(desc.degree_bits), int(desc.num_wires), int(desc.num_routed_wires), int(desc.num_challenges),
+                  int(desc.quotient_degree_factor), k.ctypes.data)
+    return d, k
+
+
+def perm_num_polys(desc):
+    """glp_perm_num_polys: num_challenges * (1 + num_partial_products), 0 for a description the library refuses"""
+    d, _keep = perm_desc(desc)
+    return int(load_library().glp_perm_num_polys(C.byref(d)))
 
 
 def _desc_to_c(desc):

@@ -165,11 +165,7 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
     cc->d = d;
     cc->gates.assign(d.gates, d.gates + d.num_gates);
     cc->k_is.assign(d.k_is, d.k_is + d.num_routed_wires);
-    if (cc->k_is.size() >= 2 && cc->k_is[0] == 1 && cc->k_is[1] > 1 && cc->k_is[1] < (1ull << 32)) {
-        cc->k_ratio = (u32)cc->k_is[1];
-        for (size_t j = 1; j < cc->k_is.size(); j++)
-            if (cc->k_is[j] != mul(cc->k_is[j - 1], (u64)cc->k_ratio)) { cc->k_ratio = 0; break; }
-    }
+    cc->k_ratio = coset_shift_ratio(cc->k_is.data(), cc->k_is.size());
     cc->d.gates = cc->gates.data(); cc->d.k_is = cc->k_is.data(); cc->d.constants = nullptr; cc->d.sigmas = nullptr;
     cc->zk = (flags & GLP_CIRCUIT_ZERO_KNOWLEDGE) != 0;
     make_layout(cc->d, cc->L, cc->zk);

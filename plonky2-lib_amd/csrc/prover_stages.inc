@@ -43,17 +43,30 @@ ProveGeo prove_geo(const glp_circuit *cc, u32 K) {
 inline size_t per_proof(int oracle, size_t words) { return oracle ? words : 0; }
 inline size_t oracle_cols(const glp_batch *const ob[4]) { return (size_t)ob[0]->ncols + ob[1]->ncols + ob[2]->ncols + ob[3]->ncols; }
 
-// K5: partial products and Z.  chal == nullptr: one proof, challenges from betas / gammas; else chal[K][2 MAXCH] on the device.
-int stage_partial_products(glp_ctx *c, const ProveGeo &g, const u64 *wires, const u64 *betas, const u64 *gammas, const u64 *chal,
-                           u64 *zp, u64 *dens, u64 *tot) {
-    const glp_circuit *cc = g.cc;
-    const u32 nch = g.nch, npp = g.npp, K = g.K, lg = (u32)g.lg, nblocks = nblk(g.n);
+// K5 without a circuit: what the kernels read of the permutation argument.  The library's own drivers fill it from the circuit
+// (stage_partial_products below), the seam from the caller's description (perm_seam.inc).
+struct PermGeo { int lg; u32 nw, nr, nch, npp, qdf, K; };
+// g if k_is[j] = g^j for every j with g < 2^32 (plonky2's get_unique_coset_shifts: powers of the generator 7), else 0: then the
+// quotient kernels chain beta k_j x by g instead of multiplying by k_j
+inline u32 coset_shift_ratio(const u64 *k_is, size_t nr) {
+    if (nr < 2 || k_is[0] != 1 || k_is[1] <= 1 || k_is[1] >= (1ull << 32)) return 0;
+    const u32 g = (u32)k_is[1];
+    for (size_t j = 1; j < nr; j++)
+        if (k_is[j] != mul(k_is[j - 1], (u64)g)) return 0;
+    return g;
+}
+// wires [K][nw][n], sigmas [nr][n] and k_is [nr] on the device.  chal == nullptr: one proof, challenges from betas / gammas; else
+// chal[K][2 MAXCH] on the device.  zp, dens: [K][nch (npp + 1)][n]; tot: [K][nch][blocks of 256 rows].
+int launch_partial_products(glp_ctx *c, const PermGeo &g, const u64 *wires, const u64 *sigmas, const u64 *k_is, const u64 *betas,
+                            const u64 *gammas, const u64 *chal, u64 *zp, u64 *dens, u64 *tot) {
+    const size_t n = (size_t)1 << g.lg;
+    const u32 nch = g.nch, npp = g.npp, K = g.K, lg = (u32)g.lg, nblocks = nblk(n);
     PPArgs a;
-    a.wires = wires; a.sigmas = cc->dev_sigmas; a.k_is = cc->dev_k_is; a.zp = zp; a.dens = dens;
+    a.wires = wires; a.sigmas = sigmas; a.k_is = k_is; a.zp = zp; a.dens = dens;
     for (u32 i = 0; i < MAXCH; i++) { a.betas[i] = !chal && i < nch ? betas[i] : 0; a.gammas[i] = !chal && i < nch ? gammas[i] : 0; }
     a.w_n = root_of_unity(g.lg); a.lg = lg; a.nr = g.nr; a.nch = nch; a.npp = npp; a.qdf = g.qdf;
-    a.chal = chal; a.wires_stride = (size_t)g.nw * g.n; a.zp_stride = (size_t)g.nzp * g.n;
-    const size_t small_lds = (size_t)2 * nch * (npp + 2) * g.n * sizeof(u64);       // k_pp_rows_small: chunk products, row products and running products of one proof in LDS
+    a.chal = chal; a.wires_stride = (size_t)g.nw * n; a.zp_stride = (size_t)nch * (1 + npp) * n;
+    const size_t small_lds = (size_t)2 * nch * (npp + 2) * n * sizeof(u64);       // k_pp_rows_small: chunk products, row products and running products of one proof in LDS
     if (g.lg <= 7 && small_lds <= 64 * 1024) {     // at most 128 rows: (row, chunk, challenge) per lane, one workgroup per proof; the running product too
         hipLaunchKernelGGL(k_pp_rows_small, dim3(1, K), dim3(256), small_lds, c->stream, a);
         GLP_HIP(hipGetLastError());
@@ -71,6 +84,12 @@ int stage_partial_products(glp_ctx *c, const ProveGeo &g, const u64 *wires, cons
     hipLaunchKernelGGL(k_pp_apply, dim3(nblocks, nch, K), dim3(256), 0, c->stream, zp, tot, lg, nblocks, nch, npp, a.zp_stride);
     GLP_HIP(hipGetLastError());
     return GLP_OK;
+}
+// K5 of a circuit: partial products and Z from its sigmas and coset shifts
+int stage_partial_products(glp_ctx *c, const ProveGeo &g, const u64 *wires, const u64 *betas, const u64 *gammas, const u64 *chal,
+                           u64 *zp, u64 *dens, u64 *tot) {
+    const PermGeo pg = {g.lg, g.nw, g.nr, g.nch, g.npp, g.qdf, g.K};
+    return launch_partial_products(c, pg, wires, g.cc->dev_sigmas, g.cc->dev_k_is, betas, gammas, chal, zp, dens, tot);
 }
 
 // alpha powers twice: whole (permutation terms) and as 22-bit limbs of m and m 2^32 (gate constraints, AccHL):
