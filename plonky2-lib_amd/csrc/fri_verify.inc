@@ -1,121 +1,15 @@
 // fri_verify.inc -- glp_fri_verify*: plonky2 `fri/verifier.rs::verify_fri_proof` for any FriInstanceInfo the prover side (glp_fri_*,
-// fri_openings.inc) accepts, for K proofs of one instance in one launch.  Included by verifier.hip after glp_verify_batch, whose
-// structure it mirrors: per proof the canonical-form scan and (one-call form) the transcript run on the context's host threads
-// beside the upload of the proofs; every query round of every proof is one launch of k_fri_verify_queries, the generic sibling of
-// k_verify_queries (same launch shape, same helpers: verify_dev.h).  The verifier holds no glp_batch, only caps: it has its own
-// description (glp_fri_verify_desc) and shares the shape rules with the prover through fri_shape.h.
+// fri_openings.inc) accepts, for K proofs of one instance in one launch.  Included by verifier.hip after glp_verify_batch, with which
+// it shares the query-round kernel (k_fri_verify_queries, verify_dev.h: glp_verify_batch runs it on the plonk instance) and what
+// surrounds its launch (verifier.hip: Scratch, Uploader, launch_queries, read_status, write_verdicts): per proof the canonical-form
+// scan and (one-call form) the transcript run on the context's host threads beside the upload of the proofs; every query round of
+// every proof is one launch.  The verifier holds no glp_batch, only caps: it has its own description (glp_fri_verify_desc) and shares
+// the shape rules with the prover through fri_shape.h.
 // The Python restatement the tests hold it to is tests/fri_restate.py::verify_fri_proof; the check numbers are that function's.
 #include <stdarg.h>
 #include "fri_shape.h"
 
 namespace {
-// per-proof table, one stride per proof (the `vchal` style): alpha, z_b, red_b = sum_j alpha^j opening_{b,j}, betas (ext each), x_index[nq]
-constexpr u32 FT_ALPHA = 0, FT_Z = 2, FT_RED = FT_Z + 2 * GLP_FRI_MAX_POINTS, FT_BETAS = FT_RED + 2 * GLP_FRI_MAX_POINTS, FT_XIDX = FT_BETAS + 32;
-// status word of one (proof, query): 0 = accepted, else check | detail << 8 (detail: oracle for 4, point for 3, reduction for 5 and 6)
-constexpr u32 FV_POINT = 3, FV_INITIAL = 4, FV_FOLD = 5, FV_LAYER = 6, FV_FINAL = 7;
-
-struct FVArgs {
-    const u64 *proofs;      // [K][total]
-    const u64 *table;       // [K][tstride]
-    const u32 *prog;        // the range program, shared by all proofs: per range (leaf offset in the query record, col_begin, num_cols), points in order
-    const u64 *caps[GLP_FRI_MAX_ORACLES];       // oracle o of proof k: caps[o] + k * cap_stride[o]
-    u32 *status;            // [K][nq]
-    size_t total, queries, query_stride, final_poly;
-    u32 tstride, nq, K, lgN, cap_height, depth0, nred, final_len, nor, npts;
-    u32 leaf_len[GLP_FRI_MAX_ORACLES], cap_stride[GLP_FRI_MAX_ORACLES];     // polynomials + salts; 0 for a shared cap, else 4 << cap_height
-    u32 nranges[GLP_FRI_MAX_POINTS];
-    u32 ab[16], step_depth[16];
-    u64 wN, gA[16];         // root_of_unity(lgN), root_of_unity(ab[r])
-};
-
-template <int HASHER>
-__global__ __launch_bounds__(256) void k_fri_verify_queries(FVArgs a) {
-    const int tid = threadIdx.x, l = tid & 15, lane = tid & 63, gb = lane & ~15;
-    const size_t grp0 = (size_t)blockIdx.x * 16 + (tid >> 4), ngrp = (size_t)a.K * a.nq;
-    const bool live = grp0 < ngrp;
-    const size_t grp = live ? grp0 : 0;                   // idle groups redo group 0 (the shuffles need every lane) and write nothing
-    const u32 k = (u32)(grp / a.nq), q = (u32)(grp % a.nq);
-    const u64 *proof = a.proofs + (size_t)k * a.total, *tb = a.table + (size_t)k * a.tstride;
-    const u64 *rec = proof + a.queries + (size_t)q * a.query_stride;
-    const u64 *w = rec;
-    size_t x_index = (size_t)tb[FT_XIDX + q];
-    const ext2 alpha = rd2(tb + FT_ALPHA);
-    const u32 capn4 = 4u << a.cap_height;
-    u32 code = 0;
-#define FV_FAIL(C, DETAIL) do { if (code == 0) code = (C) | ((u32)(DETAIL) << 8); } while (0)
-    // ---- initial trees: the path covers the whole leaf, salts included; the evaluations stay where they are in the proof image
-    for (u32 o = 0; o < a.nor; o++) {
-        const u32 leaf_len = a.leaf_len[o];
-        const u64 *cap = a.caps[o] + (size_t)k * a.cap_stride[o];
-        if (merkle_bad<HASHER>(w, leaf_len, x_index, w + leaf_len, a.depth0, cap, l, gb)) FV_FAIL(FV_INITIAL, o);
-        w += leaf_len + 4 * (size_t)a.depth0;
-    }
-    // ---- fri_combine_initial: sum <- sum alpha^(len_b) + (sum_j alpha^j eval_{b,j} - red_b) / (x - z_b), j across the point's ranges in order
-    ext2 a16 = alpha;
-#pragma unroll
-    for (int i = 0; i < 4; i++) a16 = e_sqr(a16);
-    const ext2 al = e_pow(alpha, (u64)l);
-    u64 subgroup_x = mul(GEN, dvpow(a.wN, (u64)(__brevll((unsigned long long)x_index) >> (64 - a.lgN))));
-    ext2 old_eval = e_from(0);
-    {
-        const u32 *pe = a.prog;
-        for (u32 b = 0; b < a.npts; b++) {
-            ext2 mine = e_from(0), off = e_from(1);       // this lane's share of sum_j alpha^j eval_j; alpha^(polynomials of the point so far)
-            for (u32 i = 0; i < a.nranges[b]; i++, pe += 3) {
-                const u32 ncols = pe[2];
-                const u64 *ev = rec + pe[0] + pe[1];
-                ext2 part = e_from(0);                    // lane l: sum_i ev[l + 16 i] (alpha^16)^i, Horner from the top
-                if ((u32)l < ncols)
-                    for (int j = (int)(((ncols - 1 - (u32)l) >> 4) << 4) + l; j >= 0; j -= 16) part = e_add(e_mul(part, a16), e_from(ev[j]));
-                mine = e_add(mine, e_mul(off, part));
-                off = e_mul(off, e_pow(alpha, (u64)ncols));
-            }
-            const ext2 r = group_sum(e_mul(mine, al));
-            const ext2 d = e_sub(e_from(subgroup_x), rd2(tb + FT_Z + 2 * b));
-            if (d.a == 0 && d.b == 0) FV_FAIL(FV_POINT, b);       // reject, never divide by zero
-            old_eval = e_add(e_mul(old_eval, off), e_mul(e_sub(r, rd2(tb + FT_RED + 2 * b)), e_inv(d)));
-        }
-    }
-    // ---- reductions: consistency with the previous layer, interpolation of the coset at beta, Merkle path of the layer
-    for (u32 r = 0; r < a.nred; r++) {
-        const u32 ab = a.ab[r], arity = 1u << ab;
-        const u64 *ev = w, *path = w + 2 * (size_t)arity;
-        const size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
-        if (!e_eq(rd2(ev + 2 * within), old_eval)) FV_FAIL(FV_FOLD, r);
-        {   // compute_evaluation: sum_i vals_i prod_{j != i} (beta - p_j) / (p_i - p_j), p_j = coset_start gA^j; lane l takes i = l
-            const u64 gA = a.gA[r];
-            const u32 rw = (u32)(__brev((unsigned)within) >> (32 - ab));
-            const u64 coset_start = mul(subgroup_x, dvpow(gA, (u64)(arity - rw)));
-            const ext2 beta = rd2(tb + FT_BETAS + 2 * r);
-            ext2 acc = e_from(0);
-            for (u32 i = (u32)l; i < arity; i += 16) {
-                const u64 pi = mul(coset_start, dvpow(gA, (u64)i));
-                ext2 num = e_from(1);
-                u64 den = 1, pj = coset_start;
-                for (u32 j = 0; j < arity; j++) {
-                    if (j != i) { num = e_mul(num, e_sub(beta, e_from(pj))); den = mul(den, sub(pi, pj)); }
-                    pj = mul(pj, gA);
-                }
-                const u32 bi = (u32)(__brev((unsigned)i) >> (32 - ab));                   // reverse_index_bits(evals)
-                acc = e_add(acc, e_scale(e_mul(rd2(ev + 2 * bi), num), glf::inv(den)));
-            }
-            old_eval = group_sum(acc);
-        }
-        const u64 *cap = proof + (size_t)r * capn4;
-        if (merkle_bad<HASHER>(ev, 2 * arity, coset_index, path, a.step_depth[r], cap, l, gb)) FV_FAIL(FV_LAYER, r);
-        for (u32 i = 0; i < ab; i++) subgroup_x = sqr(subgroup_x);
-        x_index = coset_index;
-        w += 2 * (size_t)arity + 4 * (size_t)a.step_depth[r];
-    }
-    {   // final_poly.eval(subgroup_x)
-        ext2 acc = e_from(0);
-        for (u32 i = a.final_len; i-- > 0;) acc = e_add(e_scale(acc, subgroup_x), rd2(proof + a.final_poly + 2 * (size_t)i));
-        if (!e_eq(acc, old_eval)) FV_FAIL(FV_FINAL, 0);
-    }
-#undef FV_FAIL
-    if (live && l == 0) a.status[grp] = code;
-}
-
 // red_b = sum_j alpha^j opening_{b,j} of every (point, proof) from the uploaded openings into the table: the shape of k_fri_table
 // (fri_kernels.inc: one workgroup per (point, proof)), without its alpha-power output.  Thread t sums the openings t, t + 256, ..
 struct FRArgs {
@@ -312,20 +206,19 @@ int fri_verify_core(glp_ctx *c, const glp_fri_verify_desc *d, u32 K, const u64 *
     for (u32 o = 0; o < p.nor; o++) memcpy(&hv[cap_at[o]], caps[o], (size_t)(p.shared[o] ? 1 : K) * capn4 * 8);
     memcpy(&hv[prog_at], p.prog.data(), p.prog.size() * 4);
 
-    struct Scratch { glp_ctx *c; std::vector<void *> p; ~Scratch() { (void)hipStreamSynchronize(c->stream); for (void *q : p) c->release(q); } } sc{c, {}};
-    auto get = [&](void **ptr, size_t bytes) -> int { int r = c->alloc(ptr, bytes); if (r == GLP_OK) sc.p.push_back(*ptr); return r; };
+    Scratch sc(c);
     u64 *dev_proofs = nullptr, *dev_hv = nullptr, *dev_open = nullptr;
     u32 *dev_status = nullptr;
-    GLP_TRY(get((void **)&dev_proofs, (size_t)K * p.total * 8));
-    GLP_TRY(get((void **)&dev_hv, hv.size() * 8));
-    GLP_TRY(get((void **)&dev_status, (size_t)K * nq * 4));
-    if (stepped) GLP_TRY(get((void **)&dev_open, (size_t)K * p.nopen * 16));
+    GLP_TRY(sc.get(&dev_proofs, (size_t)K * p.total * 8));
+    GLP_TRY(sc.get(&dev_hv, hv.size() * 8));
+    GLP_TRY(sc.get(&dev_status, (size_t)K * nq * 4));
+    if (stepped) GLP_TRY(sc.get(&dev_open, (size_t)K * p.nopen * 16));
     // the proofs (and, stepped, the openings) go up on a thread of their own while the host half runs
-    hipError_t up_err = hipSuccess;
-    std::thread uploader([&] {
-        up_err = hipSetDevice(c->device);
-        if (up_err == hipSuccess) up_err = hipMemcpyAsync(dev_proofs, proofs, (size_t)K * p.total * 8, hipMemcpyHostToDevice, c->stream);
-        if (up_err == hipSuccess && stepped) up_err = hipMemcpyAsync(dev_open, openings, (size_t)K * p.nopen * 16, hipMemcpyHostToDevice, c->stream);
+    const size_t proof_bytes = (size_t)K * p.total * 8, open_bytes = (size_t)K * p.nopen * 16;
+    Uploader up(c, [=] {
+        hipError_t e = hipMemcpyAsync(dev_proofs, proofs, proof_bytes, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && stepped) e = hipMemcpyAsync(dev_open, openings, open_bytes, hipMemcpyHostToDevice, c->stream);
+        return e;
     });
     // ---- host half, one proof per task: canonical form of everything the proof brings, then the challenges
     std::vector<std::string> why(K);
@@ -387,8 +280,7 @@ int fri_verify_core(glp_ctx *c, const glp_fri_verify_desc *d, u32 K, const u64 *
         tb[FT_ALPHA] = alpha.a; tb[FT_ALPHA + 1] = alpha.b;
         for (u32 b = 0; b < 2 * npts; b++) tb[FT_Z + b] = z[b];
     });
-    uploader.join();
-    if (up_err != hipSuccess) return set_error(GLP_ERR_HIP, "upload of the proofs: %s", hipGetErrorString(up_err));
+    GLP_TRY(up.done());
     for (u32 k = 0; k < K; k++) {
         GLP_REQUIRE(arg_err[k] != 1, "alphas[%u] is not canonical", k);
         GLP_REQUIRE(arg_err[k] != 2, "betas[%u] holds a word that is not canonical", k);
@@ -414,26 +306,10 @@ int fri_verify_core(glp_ctx *c, const glp_fri_verify_desc *d, u32 K, const u64 *
     for (u32 b = 0; b < npts; b++) a.nranges[b] = p.nranges[b];
     for (u32 r = 0; r < nred; r++) { a.ab[r] = p.ab[r]; a.step_depth[r] = p.step_depth[r]; a.gA[r] = root_of_unity((int)p.ab[r]); }
     a.wN = root_of_unity((int)p.lgN);
-    {
-        StageScope st(c, "fri_verify_queries", 8.0 * K * p.total);
-        const unsigned nblocks = (unsigned)(((size_t)K * nq + 15) / 16);
-        if (p.hasher == GLP_HASH_KECCAK25) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fri_verify_queries<GLP_HASH_KECCAK25>), dim3(nblocks), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fri_verify_queries<GLP_HASH_POSEIDON>), dim3(nblocks), dim3(256), 0, c->stream, a);
-        GLP_HIP(hipGetLastError());
-    }
-    std::vector<u32> hs((size_t)K * nq);
-    GLP_HIP(hipMemcpyAsync(hs.data(), dev_status, hs.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));
-    for (u32 k = 0; k < K; k++) {
-        for (u32 q = 0; q < nq && why[k].empty(); q++)
-            if (hs[(size_t)k * nq + q]) why[k] = fv_query_reason(q, hs[(size_t)k * nq + q]);
-        status_out[k] = why[k].empty() ? GLP_OK : GLP_ERR_PROVE;
-        if (reasons_out) {
-            char *o = reasons_out + (size_t)k * GLP_REASON_LEN;
-            memset(o, 0, GLP_REASON_LEN);
-            strncpy(o, why[k].c_str(), GLP_REASON_LEN - 1);
-        }
-    }
+    GLP_TRY(launch_queries(c, p.hasher, "fri_verify_queries", a));
+    std::vector<u32> hs;
+    GLP_TRY(read_status(c, a, hs));
+    write_verdicts(K, nq, hs, why, fv_query_reason, status_out, reasons_out);
     return GLP_OK;
 }
 }  // namespace

@@ -17,6 +17,10 @@ constexpr int MAXCH = 4;      // num_challenges supported
 constexpr int MAXR = 16;      // 2^rate_bits supported
 constexpr u32 APL_WORDS = 4;  // table words per alpha power in the quotient kernels' limb form (quotient_kernels.inc AccHL): m0 | m1 << 32, m2, m0' | m1' << 32, m2'
 
+// per-proof table of the query-round kernel (verify_dev.h), one stride per proof: alpha, z_b, red_b = sum_j alpha^j opening_{b,j}, betas (ext each),
+// x_index[nq].  Here because k_trv_pack (transcript_dev.h, compiled into the prover's object too) writes it.
+constexpr u32 FT_ALPHA = 0, FT_Z = 2, FT_RED = FT_Z + 2 * GLP_FRI_MAX_POINTS, FT_BETAS = FT_RED + 2 * GLP_FRI_MAX_POINTS, FT_XIDX = FT_BETAS + 32;
+
 struct DevGate { u32 type, selector_index, group_start, group_end, row, num_constraints, p0, p1; };
 // CosetInterpolationGate's interpolation domain and barycentric weights, built once in glp_circuit_create and stored behind the
 // device gate table (so no kernel argument changes): for subgroup_bits b = 1 .. COSET_MAX_BITS the 2^b pairs

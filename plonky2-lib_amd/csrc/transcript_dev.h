@@ -4,7 +4,8 @@
 //               previous device stage left there;
 //   verifier.hip (glp_verify_batch):    the uploaded proofs ARE that image -- the same kernels (caps "copied" onto themselves) plus
 //               k_trv_final / k_trv_queries, which read the final polynomial and the proof-of-work witness from the image instead of
-//               from the prover's buffers, and k_trv_pack, which lays the challenges out for k_verify_queries.
+//               from the prover's buffers, and k_trv_pack, which lays the challenges out as the per-proof table of
+//               k_fri_verify_queries (verify_dev.h).
 // [REF: reached from `data.prove(pw)` / `data.verify(proof)`, src/zkdsa/circuits/mod.rs:326-347]
 #pragma once
 #include "poseidon.h"
@@ -289,18 +290,16 @@ __global__ __launch_bounds__(256) void k_trv_queries(TrGeo g, u32 pow_bits, size
     ds_store(s, dch, l, live);
 }
 #undef TR_PROLOGUE
-// what k_verify_queries reads per proof: fri_alpha, zeta, zeta_next, red0, red1, alpha^nch, betas[r] (ext each) from word 12, x_index[q] from word 44
-__global__ __launch_bounds__(256) void k_trv_pack(u32 K, u32 vstride, const u64 *fap, u32 total_cols, const u64 *fpp, const u64 *betas, u32 nred,
-                                                  const u64 *idx, u32 nq, u64 *vc) {
+// the per-proof table k_fri_verify_queries reads (FT_*: prover_types.h) for the plonk instance: points zeta and g zeta, red0 and red1
+__global__ __launch_bounds__(256) void k_trv_pack(u32 K, u32 tstride, const u64 *fap, u32 total_cols, const u64 *fpp, const u64 *betas, u32 nred,
+                                                  const u64 *idx, u32 nq, u64 *table) {
     const u32 k = blockIdx.x * 256 + threadIdx.x;
     if (k >= K) return;
-    u64 *o = vc + (size_t)k * vstride;
+    u64 *o = table + (size_t)k * tstride;
     const u64 *v = fpp + (size_t)k * 10, *ap = fap + (size_t)k * 2 * total_cols;
-    o[0] = ap[2]; o[1] = ap[3];                           // alpha^1 (every circuit has more than one opened column)
-    o[2] = v[4]; o[3] = v[5]; o[4] = v[6]; o[5] = v[7];   // zeta, zeta_next
-    o[6] = v[0]; o[7] = v[1]; o[8] = v[2]; o[9] = v[3];   // red0, red1
-    o[10] = v[8]; o[11] = v[9];                           // alpha^nch
-    for (u32 r = 0; r < nred; r++) { o[12 + 2 * r] = betas[((size_t)r * K + k) * 2]; o[13 + 2 * r] = betas[((size_t)r * K + k) * 2 + 1]; }
-    for (u32 q = 0; q < nq; q++) o[44 + q] = idx[(size_t)k * nq + q];
+    o[FT_ALPHA] = ap[2]; o[FT_ALPHA + 1] = ap[3];         // alpha^1 (every circuit has more than one opened column)
+    for (u32 i = 0; i < 4; i++) { o[FT_Z + i] = v[4 + i]; o[FT_RED + i] = v[i]; }       // zeta, zeta_next; red0, red1
+    for (u32 r = 0; r < nred; r++) { o[FT_BETAS + 2 * r] = betas[((size_t)r * K + k) * 2]; o[FT_BETAS + 2 * r + 1] = betas[((size_t)r * K + k) * 2 + 1]; }
+    for (u32 q = 0; q < nq; q++) o[FT_XIDX + q] = idx[(size_t)k * nq + q];
 }
 }  // namespace

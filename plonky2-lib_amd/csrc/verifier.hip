@@ -5,16 +5,22 @@
 // `gates/*::eval_unfiltered` (extension-field form), `fri/verifier.rs::{verify_fri_proof, fri_combine_initial,
 // compute_evaluation}` and `hash/merkle_proofs.rs::verify_merkle_proof_to_cap`.
 //
-// Verification is a few thousand Poseidon permutations and one constraint evaluation at a single point: it runs on the
-// host, like the transcript, and touches no device memory (the circuit handle supplies the gate table, the coset
+// Verification is a few thousand Poseidon permutations and one constraint evaluation at a single point: glp_verify runs on
+// the host, like the transcript, and touches no device memory (the circuit handle supplies the gate table, the coset
 // shifts, the digest and the constants/sigmas cap).  It shares no code with the CPU checker the tests use: the two
 // verifiers and the two provers are cross-checked against each other in tests/test_gpu_prove.py.
+//
+// The FRI query rounds are stated twice, once per side: verify_fri_host below (glp_verify, the independent host restatement)
+// and k_fri_verify_queries (verify_dev.h), the one device kernel behind glp_verify_batch (the plonk instance of a circuit) and
+// glp_fri_verify* (fri_verify.inc: any instance).  Both report a failure as the same status word (FV_*), query_failure() words it.
 #include <chrono>
 #include <string>
 #include <thread>
+#include "host_pool.h"
 #include "merkle.h"
 #include "prover_types.h"
 #include "transcript_dev.h"
+#include "verify_dev.h"
 
 namespace {
 
@@ -537,26 +543,26 @@ int verify_front(const glp_circuit *cc, const u64 *proof, VChal &vc) {
     return GLP_OK;
 }
 
-// messages of the query rounds, shared by the host and the device path (code: see k_verify_queries)
-int query_failure(u32 q, u32 code, u32 nred) {
-    if (code >= 1 && code <= 4) return set_error(GLP_ERR_PROVE, "Invalid Merkle proof (query %u, initial tree %d)", q, (int)code - 1);
-    if (code == 5) return set_error(GLP_ERR_PROVE, "query point equals an opening point");
-    if (code >= 6 && code < 6 + 2 * nred) {
-        const u32 r = (code - 6) / 2;
-        if ((code - 6) % 2 == 0) return set_error(GLP_ERR_PROVE, "FRI consistency check failed (query %u, reduction %u)", q, r);
-        return set_error(GLP_ERR_PROVE, "Invalid Merkle proof (query %u, reduction %u)", q, r);
+// messages of the query rounds, shared by the host and the device path (word: the status word of k_fri_verify_queries, verify_dev.h)
+int query_failure(u32 q, u32 word) {
+    const u32 check = word & 0xFF, detail = word >> 8;
+    switch (check) {
+    case FV_POINT: return set_error(GLP_ERR_PROVE, "query point equals an opening point");
+    case FV_INITIAL: return set_error(GLP_ERR_PROVE, "Invalid Merkle proof (query %u, initial tree %d)", q, (int)detail);
+    case FV_FOLD: return set_error(GLP_ERR_PROVE, "FRI consistency check failed (query %u, reduction %u)", q, detail);
+    case FV_LAYER: return set_error(GLP_ERR_PROVE, "Invalid Merkle proof (query %u, reduction %u)", q, detail);
+    default: return set_error(GLP_ERR_PROVE, "Final polynomial evaluation is invalid (query %u)", q);
     }
-    return set_error(GLP_ERR_PROVE, "Final polynomial evaluation is invalid (query %u)", q);
 }
 
 int verify_fri_host(const glp_circuit *cc, const u64 *proof, const VChal &vc) {
     const glp_circuit_desc &d = cc->d;
     const Layout &L = cc->L;
     const int lg = (int)d.degree_bits, rb = (int)d.rate_bits, lgN = lg + rb;
-    const u32 nch = d.num_challenges, capn = 1u << d.cap_height, nred = d.num_reductions;
+    const u32 nch = d.num_challenges, capn = 1u << d.cap_height;
     const E zeta = vc.zeta, zeta_next = vc.zeta_next, fri_alpha = vc.fri_alpha, red0 = vc.red0, red1 = vc.red1, shift1 = vc.shift1;
     const std::vector<E> &fri_betas = vc.fri_betas;
-#define FAIL(CODE) return query_failure(q, (CODE), nred)
+#define FAIL(CHECK, DETAIL) return query_failure(q, (CHECK) | ((u32)(DETAIL) << 8))
     const u64 *caps4[4] = {cc->cs_cap.data(), proof + L.caps, proof + L.caps + capn * 4, proof + L.caps + 2 * capn * 4};
     size_t cols_total = 0;
     for (int k = 0; k < 4; k++) cols_total += L.oracle_cols[k];
@@ -570,7 +576,7 @@ int verify_fri_host(const glp_circuit *cc, const u64 *proof, const VChal &vc) {
             evals[k] = w;
             // the Merkle path covers the whole leaf, salts included; fri_combine_initial reads its first oracle_cols values (unsalted_eval)
             if (!merkle_ok((int)d.hasher, w, L.leaf_len[k], x_index, caps4[k], w + L.leaf_len[k], L.depth0))
-                FAIL(1 + (u32)k);
+                FAIL(FV_INITIAL, k);
             w += L.leaf_len[k] + 4 * (size_t)L.depth0;
         }
         u64 subgroup_x = mul(GEN, pow(wN, (u64)brev(x_index, lgN)));
@@ -583,7 +589,7 @@ int verify_fri_host(const glp_circuit *cc, const u64 *proof, const VChal &vc) {
             ap = ONE;
             for (u32 j = 0; j < nch; j++) { r1 = r1 + ap * evals[2][j]; ap = ap * fri_alpha; }
             const E sx((u64)subgroup_x);
-            if (sx == zeta || sx == zeta_next) FAIL(5);
+            if (sx == zeta || sx == zeta_next) FAIL(FV_POINT, 0);
             E sum = ZERO;
             sum = sum * shift0 + (r0 - red0) * inv(sx - zeta);
             sum = sum * shift1 + (r1 - red1) * inv(sx - zeta_next);
@@ -593,7 +599,7 @@ int verify_fri_host(const glp_circuit *cc, const u64 *proof, const VChal &vc) {
             const u32 ab = d.reduction_arity_bits[r], arity = 1u << ab;
             const u64 *ev = w, *path = w + 2 * arity;
             const size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
-            if (!(rd(ev + 2 * within) == old_eval)) FAIL(6 + 2 * r);
+            if (!(rd(ev + 2 * within) == old_eval)) FAIL(FV_FOLD, r);
             {   // compute_evaluation: interpolate the coset and evaluate at beta
                 const u64 gA = root_of_unity((int)ab);
                 const u64 coset_start = mul(subgroup_x, pow(gA, (u64)(arity - brev(within, (int)ab))));
@@ -614,14 +620,14 @@ int verify_fri_host(const glp_circuit *cc, const u64 *proof, const VChal &vc) {
                 old_eval = acc;
             }
             if (!merkle_ok((int)d.hasher, ev, 2 * (size_t)arity, coset_index, proof + L.fri_caps + (size_t)r * capn * 4, path, L.step_depth[r]))
-                FAIL(7 + 2 * r);
+                FAIL(FV_LAYER, r);
             for (u32 i = 0; i < ab; i++) subgroup_x = sqr(subgroup_x);
             x_index = coset_index;
             w += 2 * (size_t)arity + 4 * (size_t)L.step_depth[r];
         }
         E acc = ZERO;       // final_poly.eval(subgroup_x)
         for (u32 i = L.final_len; i-- > 0;) acc = acc * (u64)subgroup_x + rd(proof + L.final_poly + 2 * (size_t)i);
-        if (!(acc == old_eval)) FAIL(6 + 2 * nred);
+        if (!(acc == old_eval)) FAIL(FV_FINAL, 0);
     }
 #undef FAIL
     return GLP_OK;
@@ -639,107 +645,64 @@ int verify_impl(const glp_circuit *cc, const u64 *proof) {
 // work and the one constraint evaluation at zeta stay on host threads (verify_front: a few dozen permutations); the query
 // rounds -- K x num_query_rounds independent checks, each a few dozen to a few hundred permutations (Merkle paths of the four
 // initial oracles and of every FRI layer), `fri_combine_initial`, the arity-2^k interpolations and the final polynomial -- are
-// one launch: a 16-lane group per (proof, query), hashes in the 12-lane cooperative form (poseidon.h permute_coop: ~5x lower
-// latency per hash than one state per lane, which is what matters for a chain of dependent hashes), the alpha-combination and
-// the Lagrange terms spread over the lanes of the group.
-#include "verify_dev.h"
+// one launch of k_fri_verify_queries (verify_dev.h) on the plonk instance of the circuit: a 16-lane group per (proof, query),
+// hashes in the 12-lane cooperative form (poseidon.h permute_coop: ~5x lower latency per hash than one state per lane, which is
+// what matters for a chain of dependent hashes), the alpha-combination and the Lagrange terms spread over the lanes of the group.
+//
+// What surrounds that launch is the same for glp_verify_batch and glp_fri_verify* (fri_verify.inc) and stands here once.
 namespace {
-constexpr u32 VC_ALPHA = 0, VC_ZETA = 2, VC_ZETA_NEXT = 4, VC_RED0 = 6, VC_RED1 = 8, VC_SHIFT1 = 10, VC_BETAS = 12, VC_XIDX = 44;
-struct VQArgs {
-    const u64 *proofs;      // [K][total]
-    const u64 *vchal;       // [K][vstride]: fri_alpha, zeta, zeta_next, red0, red1, alpha^nch, betas[16] (ext each), x_index[nq]
-    const u64 *cs_cap;      // [2^cap_height][4]
-    u32 *status;            // [K][nq]: 0 = accepted, else the code query_failure() turns into the verifier's message
-    size_t total, caps, fri_caps, queries, query_stride, final_poly;
-    u32 vstride, nq, K, nch, lgN, cap_height, depth0, nred, final_len;
-    u32 oracle_cols[4], ab[16], step_depth[16];
-    u32 leaf_len[4];        // oracle_cols, + 4 salts for oracles 1..3 of a zk circuit (Layout::leaf_len)
-    u64 wN, gA[16];         // root_of_unity(lgN), root_of_unity(ab[r])
+// device buffers of one call: released, once the stream has drained, however the call returns
+struct Scratch {
+    glp_ctx *c;
+    std::vector<void *> p;
+    explicit Scratch(glp_ctx *ctx) : c(ctx) {}
+    Scratch(const Scratch &) = delete;
+    ~Scratch() { (void)hipStreamSynchronize(c->stream); for (void *q : p) c->release(q); }
+    template <class T> int get(T **ptr, size_t bytes) { int r = c->alloc((void **)ptr, bytes); if (r == GLP_OK) p.push_back(*ptr); return r; }
 };
-
-template <int HASHER>
-__global__ __launch_bounds__(256) void k_verify_queries(VQArgs a) {
-    const int tid = threadIdx.x, l = tid & 15, lane = tid & 63, gb = lane & ~15;
-    const size_t grp0 = (size_t)blockIdx.x * 16 + (tid >> 4), ngrp = (size_t)a.K * a.nq;
-    const bool live = grp0 < ngrp;
-    const size_t grp = live ? grp0 : 0;                   // idle groups redo group 0 (the shuffles need every lane) and write nothing
-    const u32 k = (u32)(grp / a.nq), q = (u32)(grp % a.nq);
-    const u64 *proof = a.proofs + (size_t)k * a.total, *vc = a.vchal + (size_t)k * a.vstride;
-    const u64 *w = proof + a.queries + (size_t)q * a.query_stride;
-    size_t x_index = (size_t)vc[VC_XIDX + q];
-    const ext2 alpha = rd2(vc + VC_ALPHA), zeta = rd2(vc + VC_ZETA), zeta_next = rd2(vc + VC_ZETA_NEXT);
-    const u32 capn4 = 4u << a.cap_height;
-    u32 code = 0;
-#define VQ_FAIL(C) do { if (code == 0) code = (C); } while (0)
-    // ---- initial trees; sum_j alpha^j evals_j over the four oracles in order (batch 0) and the Z columns (batch 1)
-    ext2 a16 = alpha;
-#pragma unroll
-    for (int i = 0; i < 4; i++) a16 = e_sqr(a16);
-    const ext2 al = e_pow(alpha, (u64)l);
-    ext2 r0 = e_from(0), r1 = e_from(0), off = e_from(1);
-    for (int t = 0; t < 4; t++) {
-        const u32 ncols = a.oracle_cols[t], leaf_len = a.leaf_len[t];     // the path covers the salted leaf, the combination its polynomials
-        const u64 *cap = t == 0 ? a.cs_cap : proof + a.caps + (size_t)(t - 1) * capn4;
-        if (merkle_bad<HASHER>(w, leaf_len, x_index, w + leaf_len, a.depth0, cap, l, gb)) VQ_FAIL(1 + (u32)t);
-        ext2 part = e_from(0);                            // lane l: sum_i evals[l + 16 i] (alpha^16)^i, Horner from the top
-        if ((u32)l < ncols)
-            for (int j = (int)(((ncols - 1 - (u32)l) >> 4) << 4) + l; j >= 0; j -= 16) part = e_add(e_mul(part, a16), e_from(w[j]));
-        r0 = e_add(r0, e_mul(off, group_sum(e_mul(part, al))));
-        off = e_mul(off, e_pow(alpha, (u64)ncols));
-        if (t == 2) { ext2 ap = e_from(1); for (u32 j = 0; j < a.nch; j++) { r1 = e_add(r1, e_scale(ap, w[j])); ap = e_mul(ap, alpha); } }
-        w += leaf_len + 4 * (size_t)a.depth0;
-    }
-    u64 subgroup_x = mul(GEN, dvpow(a.wN, (u64)(__brevll((unsigned long long)x_index) >> (64 - a.lgN))));
-    ext2 old_eval;
-    {
-        const ext2 d0 = e_sub(e_from(subgroup_x), zeta), d1 = e_sub(e_from(subgroup_x), zeta_next);
-        if ((d0.a == 0 && d0.b == 0) || (d1.a == 0 && d1.b == 0)) VQ_FAIL(5);
-        ext2 sum = e_mul(e_sub(r0, rd2(vc + VC_RED0)), e_inv(d0));
-        sum = e_add(e_mul(sum, rd2(vc + VC_SHIFT1)), e_mul(e_sub(r1, rd2(vc + VC_RED1)), e_inv(d1)));
-        old_eval = sum;
-    }
-    // ---- reductions: consistency with the previous layer, interpolation of the coset at beta, Merkle path of the layer
-    for (u32 r = 0; r < a.nred; r++) {
-        const u32 ab = a.ab[r], arity = 1u << ab;
-        const u64 *ev = w, *path = w + 2 * (size_t)arity;
-        const size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
-        if (!e_eq(rd2(ev + 2 * within), old_eval)) VQ_FAIL(6 + 2 * r);
-        {   // compute_evaluation: sum_i vals_i prod_{j != i} (beta - p_j) / (p_i - p_j), p_j = coset_start gA^j; lane l takes i = l, l + 16
-            const u64 gA = a.gA[r];
-            const u32 rw = (u32)(__brev((unsigned)within) >> (32 - ab));
-            const u64 coset_start = mul(subgroup_x, dvpow(gA, (u64)(arity - rw)));
-            const ext2 beta = rd2(vc + VC_BETAS + 2 * r);
-            ext2 acc = e_from(0);
-            for (u32 i = (u32)l; i < arity; i += 16) {
-                const u64 pi = mul(coset_start, dvpow(gA, (u64)i));
-                ext2 num = e_from(1);
-                u64 den = 1, pj = coset_start;
-                for (u32 j = 0; j < arity; j++) {
-                    if (j != i) { num = e_mul(num, e_sub(beta, e_from(pj))); den = mul(den, sub(pi, pj)); }
-                    pj = mul(pj, gA);
-                }
-                const u32 bi = (u32)(__brev((unsigned)i) >> (32 - ab));                   // reverse_index_bits(evals)
-                acc = e_add(acc, e_scale(e_mul(rd2(ev + 2 * bi), num), glf::inv(den)));
-            }
-            old_eval = group_sum(acc);
+// The proofs go up (pageable host memory: the copy blocks its caller) on a thread of their own while the host half runs.  done() joins
+// it; so does the destructor, when the call returns early or a host task throws.  Declared after the Scratch whose buffers it fills.
+struct Uploader {
+    hipError_t err = hipSuccess;
+    std::thread t;
+    template <class F> Uploader(glp_ctx *c, F copies) : t([this, c, copies] { err = hipSetDevice(c->device); if (err == hipSuccess) err = copies(); }) {}
+    Uploader(const Uploader &) = delete;
+    ~Uploader() { if (t.joinable()) t.join(); }
+    int done() { t.join(); return err == hipSuccess ? GLP_OK : set_error(GLP_ERR_HIP, "upload of the proofs: %s", hipGetErrorString(err)); }
+};
+// every query round of every proof in one launch, timed as `stage`
+int launch_queries(glp_ctx *c, int hasher, const char *stage, const FVArgs &a) {
+    StageScope st(c, stage, 8.0 * a.K * a.total);
+    const unsigned nblocks = (unsigned)(((size_t)a.K * a.nq + 15) / 16);
+    if (hasher == GLP_HASH_KECCAK25) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fri_verify_queries<GLP_HASH_KECCAK25>), dim3(nblocks), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fri_verify_queries<GLP_HASH_POSEIDON>), dim3(nblocks), dim3(256), 0, c->stream, a);
+    GLP_HIP(hipGetLastError());
+    return GLP_OK;
+}
+// its status words, back on the host (a copy into pageable memory blocks its caller until the stream gets there)
+int read_status(glp_ctx *c, const FVArgs &a, std::vector<u32> &hs) {
+    hs.resize((size_t)a.K * a.nq);
+    GLP_HIP(hipMemcpyAsync(hs.data(), a.status, hs.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    GLP_HIP(hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
+// why[k] is empty for the proofs the host half accepted: for those the first failing check of the first failing query becomes the
+// reason (reason(q, status word)); then the verdict and the reason of every proof go out
+template <class Reason>
+void write_verdicts(u32 K, u32 nq, const std::vector<u32> &hs, std::vector<std::string> &why, Reason reason, int32_t *status_out, char *reasons_out) {
+    for (u32 k = 0; k < K; k++) {
+        for (u32 q = 0; q < nq && why[k].empty(); q++)
+            if (hs[(size_t)k * nq + q]) why[k] = reason(q, hs[(size_t)k * nq + q]);
+        status_out[k] = why[k].empty() ? GLP_OK : GLP_ERR_PROVE;
+        if (reasons_out) {
+            char *o = reasons_out + (size_t)k * GLP_REASON_LEN;
+            memset(o, 0, GLP_REASON_LEN);
+            strncpy(o, why[k].c_str(), GLP_REASON_LEN - 1);
         }
-        const u64 *cap = proof + a.fri_caps + (size_t)r * capn4;
-        if (merkle_bad<HASHER>(ev, 2 * arity, coset_index, path, a.step_depth[r], cap, l, gb)) VQ_FAIL(7 + 2 * r);
-        for (u32 i = 0; i < ab; i++) subgroup_x = sqr(subgroup_x);
-        x_index = coset_index;
-        w += 2 * (size_t)arity + 4 * (size_t)a.step_depth[r];
     }
-    {   // final_poly.eval(subgroup_x)
-        ext2 acc = e_from(0);
-        for (u32 i = a.final_len; i-- > 0;) acc = e_add(e_scale(acc, subgroup_x), rd2(proof + a.final_poly + 2 * (size_t)i));
-        if (!e_eq(acc, old_eval)) VQ_FAIL(6 + 2 * a.nred);
-    }
-#undef VQ_FAIL
-    if (live && l == 0) a.status[grp] = code;
 }
 }  // namespace
 
-#include "host_pool.h"
 extern "C" int glp_verify_batch(glp_ctx *c, const glp_circuit *cc, uint32_t K, const uint64_t *proofs, int32_t *status_out, char *reasons_out) {
     GLP_REQUIRE(c && cc && proofs && status_out, "null argument");
     GLP_REQUIRE(cc->ctx == c, "circuit belongs to another context");
@@ -747,33 +710,40 @@ extern "C" int glp_verify_batch(glp_ctx *c, const glp_circuit *cc, uint32_t K, c
     GLP_TRY(bind(c));
     const glp_circuit_desc &d = cc->d;
     const Layout &L = cc->L;
-    const u32 nq = d.num_query_rounds, nred = d.num_reductions;
-    const u32 vstride = (VC_XIDX + nq + 3) & ~3u;
-    std::vector<VChal> vcs(K);
-    std::vector<int> rc(K, GLP_OK);
-    std::vector<std::string> why(K);
-    std::vector<u64> hv((size_t)K * vstride, 0);
-    // the proofs go up (pageable host memory: the copy blocks its caller) on a thread of their own while the host half runs
-    struct Scratch { glp_ctx *c; std::vector<void *> p; ~Scratch() { (void)hipStreamSynchronize(c->stream); for (void *q : p) c->release(q); } } sc{c, {}};
-    auto get = [&](void **p, size_t bytes) -> int { int r = c->alloc(p, bytes); if (r == GLP_OK) sc.p.push_back(*p); return r; };
-    u64 *dev_proofs = nullptr, *dev_vc = nullptr;
+    const u32 nq = d.num_query_rounds, nred = d.num_reductions, nch = d.num_challenges, capn = 1u << d.cap_height;
+    GLP_REQUIRE(L.total <= 0xFFFFFFFFu, "glp_verify_batch: proofs of %zu words (the query kernel takes a cap stride below 2^32 words)", L.total);
+    // one host block: the K per-proof tables (FT_*), then the range program of the plonk instance (tests/fri_restate.py::plonk_instance):
+    // every column of the four oracles at zeta (point 0), the Z columns also at g zeta (point 1)
+    const u32 tstride = (FT_XIDX + nq + 3) & ~3u;
+    const size_t prog_at = (size_t)K * tstride;
+    u32 prog[15], leaf_off = 0;
+    for (u32 o = 0; o < 4; o++) {
+        prog[3 * o] = leaf_off; prog[3 * o + 1] = 0; prog[3 * o + 2] = L.oracle_cols[o];
+        if (o == 2) { prog[12] = leaf_off; prog[13] = 0; prog[14] = nch; }
+        leaf_off += L.leaf_len[o] + 4 * L.depth0;
+    }
+    std::vector<std::string> why(K);        // empty: accepted so far
+    std::vector<u64> hv(prog_at + (sizeof(prog) + 7) / 8, 0);
+    memcpy(&hv[prog_at], prog, sizeof(prog));
+    const size_t proof_bytes = (size_t)K * L.total * 8;
+    Scratch sc(c);
+    u64 *dev_proofs = nullptr, *dev_hv = nullptr;
     u32 *dev_status = nullptr;
-    GLP_TRY(get((void **)&dev_proofs, (size_t)K * L.total * 8));
-    GLP_TRY(get((void **)&dev_vc, hv.size() * 8));
-    GLP_TRY(get((void **)&dev_status, (size_t)K * nq * 4));
+    GLP_TRY(sc.get(&dev_proofs, proof_bytes));
+    GLP_TRY(sc.get(&dev_hv, hv.size() * 8));
+    GLP_TRY(sc.get(&dev_status, (size_t)K * nq * 4));
     const bool trace = getenv("GLP_BATCH_TRACE") != nullptr;
     const auto t_start = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); };
-    hipError_t up_err = hipSuccess;
-    std::thread uploader([&] {
-        up_err = hipSetDevice(c->device);
-        if (up_err == hipSuccess) up_err = hipMemcpyAsync(dev_proofs, proofs, (size_t)K * L.total * 8, hipMemcpyHostToDevice, c->stream);
+    const u64 *host_prog = &hv[prog_at];
+    Uploader up(c, [=] {        // the proofs, and behind them the range program: nothing waits for it on the calling thread
+        hipError_t e = hipMemcpyAsync(dev_proofs, proofs, proof_bytes, hipMemcpyHostToDevice, c->stream);
+        return e != hipSuccess ? e : hipMemcpyAsync(dev_hv + prog_at, host_prog, sizeof(prog), hipMemcpyHostToDevice, c->stream);
     });
     // PoseidonGoldilocksConfig: the K transcripts run on the device, as the batch prover's do (transcript_dev.h; the uploaded proofs are
     // the image its kernels read).  The host keeps the canonical-form scan (beside the upload) and the vanishing-polynomial identity
     // (beside the query rounds).  KeccakGoldilocksConfig, or GLP_VERIFY_HOST_TRANSCRIPT=1: everything of verify_front on host threads.
     const bool dev_tr = d.hasher == GLP_HASH_POSEIDON && getenv("GLP_VERIFY_HOST_TRANSCRIPT") == nullptr;
-    const u32 nch = d.num_challenges, capn = 1u << d.cap_height;
     u64 *dev_chal = nullptr, *dev_qpp = nullptr, *dev_apow = nullptr, *dev_zetas = nullptr;
     u32 *dev_err = nullptr;
     std::vector<u64> h_back;
@@ -785,44 +755,40 @@ extern "C" int glp_verify_batch(glp_ctx *c, const glp_circuit *cc, uint32_t K, c
     if (!dev_tr) {
         // host half, one proof per task on the context's pool: canonical form, transcript, proof of work, vanishing polynomial at zeta
         ctx_host_pool(c).run(K, [&](size_t k) {
-            rc[k] = verify_front(cc, proofs + k * L.total, vcs[k]);
-            if (rc[k] != GLP_OK) { why[k] = g_last_error; return; }
-            const VChal &v = vcs[k];
-            u64 *o = &hv[k * vstride];
+            VChal v;
+            if (verify_front(cc, proofs + k * L.total, v) != GLP_OK) { why[k] = g_last_error; return; }
+            u64 *o = &hv[k * tstride];
             auto put = [&](u32 at, const E &e) { o[at] = e.v.a; o[at + 1] = e.v.b; };
-            put(VC_ALPHA, v.fri_alpha); put(VC_ZETA, v.zeta); put(VC_ZETA_NEXT, v.zeta_next); put(VC_RED0, v.red0); put(VC_RED1, v.red1); put(VC_SHIFT1, v.shift1);
-            for (u32 r = 0; r < nred; r++) put(VC_BETAS + 2 * r, v.fri_betas[r]);
-            for (u32 q = 0; q < nq; q++) o[VC_XIDX + q] = v.x_index[q];
+            put(FT_ALPHA, v.fri_alpha); put(FT_Z, v.zeta); put(FT_Z + 2, v.zeta_next); put(FT_RED, v.red0); put(FT_RED + 2, v.red1);
+            for (u32 r = 0; r < nred; r++) put(FT_BETAS + 2 * r, v.fri_betas[r]);
+            for (u32 q = 0; q < nq; q++) o[FT_XIDX + q] = v.x_index[q];
         });
         // device half: every query round of every proof in one launch.  Proofs the host half already rejected still ride along
         // (their slots hold zero challenges and every index is in range); their device status is ignored.
         t_front = since();
-        uploader.join();
+        GLP_TRY(up.done());
         t_up = since();
-        if (up_err != hipSuccess) return set_error(GLP_ERR_HIP, "upload of the proofs: %s", hipGetErrorString(up_err));
-        GLP_HIP(hipMemcpyAsync(dev_vc, hv.data(), hv.size() * 8, hipMemcpyHostToDevice, c->stream));
+        GLP_HIP(hipMemcpyAsync(dev_hv, hv.data(), prog_at * 8, hipMemcpyHostToDevice, c->stream));
     } else {
         ctx_host_pool(c).run(K, [&](size_t k) {
-            rc[k] = verify_canonical(cc, proofs + k * L.total);
-            if (rc[k] != GLP_OK) why[k] = g_last_error;
+            if (verify_canonical(cc, proofs + k * L.total) != GLP_OK) why[k] = g_last_error;
         });
         t_front = since();
-        uploader.join();
+        GLP_TRY(up.done());
         t_up = since();
-        if (up_err != hipSuccess) return set_error(GLP_ERR_HIP, "upload of the proofs: %s", hipGetErrorString(up_err));
         const u32 total_cols = L.oracle_cols[0] + L.oracle_cols[1] + L.oracle_cols[2] + L.oracle_cols[3];
         u64 *dch, *dev_apl, *dev_fap, *dev_fpp, *dev_betas, *dev_idx;
-        GLP_TRY(get((void **)&dch, (size_t)K * DCH_WORDS * 8));
+        GLP_TRY(sc.get(&dch, (size_t)K * DCH_WORDS * 8));
         // betas | gammas, public-input hash, alpha powers, zetas, error bits: one block, one copy back
         const size_t w_chal = (size_t)K * 2 * MAXCH, w_qpp = (size_t)K * 3 * MAXCH, w_apow = (size_t)K * nch * 2, w_zetas = (size_t)K * 4, w_err = (K + 1) / 2;
         u64 *dev_back;
-        GLP_TRY(get((void **)&dev_back, (w_chal + w_qpp + w_apow + w_zetas + w_err) * 8));
+        GLP_TRY(sc.get(&dev_back, (w_chal + w_qpp + w_apow + w_zetas + w_err) * 8));
         dev_chal = dev_back; dev_qpp = dev_chal + w_chal; dev_apow = dev_qpp + w_qpp; dev_zetas = dev_apow + w_apow; dev_err = (u32 *)(dev_zetas + w_zetas);
-        GLP_TRY(get((void **)&dev_apl, (size_t)K * nch * 2 * APL_WORDS * 8));
-        GLP_TRY(get((void **)&dev_fap, (size_t)K * 2 * total_cols * 8));
-        GLP_TRY(get((void **)&dev_fpp, (size_t)K * 10 * 8));
-        GLP_TRY(get((void **)&dev_betas, (size_t)std::max<u32>(nred, 1) * K * 2 * 8));
-        GLP_TRY(get((void **)&dev_idx, (size_t)K * nq * 8));
+        GLP_TRY(sc.get(&dev_apl, (size_t)K * nch * 2 * APL_WORDS * 8));
+        GLP_TRY(sc.get(&dev_fap, (size_t)K * 2 * total_cols * 8));
+        GLP_TRY(sc.get(&dev_fpp, (size_t)K * 10 * 8));
+        GLP_TRY(sc.get(&dev_betas, (size_t)std::max<u32>(nred, 1) * K * 2 * 8));
+        GLP_TRY(sc.get(&dev_idx, (size_t)K * nq * 8));
         GLP_HIP(hipMemsetAsync(dev_back, 0, (w_chal + w_qpp + w_apow + w_zetas + w_err) * 8, c->stream));
         TrGeo g;
         g.dch = dch; g.image = dev_proofs; g.total = L.total; g.K = K; g.capn = capn; g.nch = nch;
@@ -843,7 +809,7 @@ extern "C" int glp_verify_batch(glp_ctx *c, const glp_circuit *cc, uint32_t K, c
             hipLaunchKernelGGL(k_tr_beta, tg, tb, 0, c->stream, g, dev_proofs + L.fri_caps + r * cap4, L.total, L.fri_caps + r * cap4, dev_betas + (size_t)r * K * 2);
         hipLaunchKernelGGL(k_trv_final, tg, tb, 0, c->stream, g, L.final_poly, 2u * L.final_len);
         hipLaunchKernelGGL(k_trv_queries, tg, tb, 0, c->stream, g, d.proof_of_work_bits, L.pow, nq, (u64)1 << (d.degree_bits + d.rate_bits), dev_idx, dev_err);
-        hipLaunchKernelGGL(k_trv_pack, dim3((K + 255) / 256), dim3(256), 0, c->stream, K, vstride, dev_fap, total_cols, dev_fpp, dev_betas, nred, dev_idx, nq, dev_vc);
+        hipLaunchKernelGGL(k_trv_pack, dim3((K + 255) / 256), dim3(256), 0, c->stream, K, tstride, dev_fap, total_cols, dev_fpp, dev_betas, nred, dev_idx, nq, dev_hv);
         GLP_HIP(hipGetLastError());
         // what the host's half of the check needs comes back while the query rounds run
         h_back.resize(w_chal + w_qpp + w_apow + w_zetas + w_err);
@@ -852,60 +818,45 @@ extern "C" int glp_verify_batch(glp_ctx *c, const glp_circuit *cc, uint32_t K, c
         GLP_HIP(hipEventRecord(ev_chal, c->stream));
         h_chal = h_back.data(); h_qpp = h_chal + w_chal; h_apow = h_qpp + w_qpp; h_zetas = h_apow + w_apow; h_err = (const u32 *)(h_zetas + w_zetas);
     }
-    VQArgs a;
+    // the FRI part of a proof, fri_caps | queries | final_poly | pow, is the FriProof layout the kernel reads (layer caps at offset 0); the
+    // circuit's constants / sigmas cap is shared, the three caps of a proof sit at its front
+    FVArgs a;
     memset(&a, 0, sizeof(a));
-    a.proofs = dev_proofs; a.vchal = dev_vc; a.status = dev_status;
-    const size_t N = (size_t)1 << (d.degree_bits + d.rate_bits);
-    a.cs_cap = cc->cs->digests + 4 * merkle_cap_offset(N, (int)d.cap_height);
-    a.total = L.total; a.caps = L.caps; a.fri_caps = L.fri_caps; a.queries = L.queries; a.query_stride = L.query_stride; a.final_poly = L.final_poly;
-    a.vstride = vstride; a.nq = nq; a.K = K; a.nch = d.num_challenges; a.lgN = d.degree_bits + d.rate_bits; a.cap_height = d.cap_height;
-    a.depth0 = L.depth0; a.nred = nred; a.final_len = L.final_len;
-    for (int t = 0; t < 4; t++) { a.oracle_cols[t] = L.oracle_cols[t]; a.leaf_len[t] = L.leaf_len[t]; }
+    a.proofs = dev_proofs + L.fri_caps; a.table = dev_hv; a.prog = (const u32 *)(dev_hv + prog_at); a.status = dev_status;
+    a.total = L.total; a.queries = L.queries - L.fri_caps; a.query_stride = L.query_stride; a.final_poly = L.final_poly - L.fri_caps;
+    a.tstride = tstride; a.nq = nq; a.K = K; a.lgN = d.degree_bits + d.rate_bits; a.cap_height = d.cap_height; a.depth0 = L.depth0; a.nred = nred;
+    a.final_len = L.final_len; a.nor = 4; a.npts = 2; a.nranges[0] = 4; a.nranges[1] = 1;
+    a.caps[0] = cc->cs->digests + 4 * merkle_cap_offset((size_t)1 << a.lgN, (int)d.cap_height);
+    for (u32 o = 1; o < 4; o++) { a.caps[o] = dev_proofs + L.caps + (size_t)(o - 1) * capn * 4; a.cap_stride[o] = (u32)L.total; }
+    for (u32 o = 0; o < 4; o++) a.leaf_len[o] = L.leaf_len[o];
     for (u32 r = 0; r < nred; r++) { a.ab[r] = d.reduction_arity_bits[r]; a.step_depth[r] = L.step_depth[r]; a.gA[r] = root_of_unity((int)d.reduction_arity_bits[r]); }
     a.wN = root_of_unity((int)a.lgN);
-    {
-        StageScope st(c, "verify_queries", 8.0 * K * L.total);
-        const unsigned nblocks = (unsigned)(((size_t)K * nq + 15) / 16);
-        if (d.hasher == GLP_HASH_KECCAK25) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify_queries<GLP_HASH_KECCAK25>), dim3(nblocks), dim3(256), 0, c->stream, a);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify_queries<GLP_HASH_POSEIDON>), dim3(nblocks), dim3(256), 0, c->stream, a);
-        GLP_HIP(hipGetLastError());
-    }
-    std::vector<u32> hs((size_t)K * nq);
+    GLP_TRY(launch_queries(c, (int)d.hasher, "verify_queries", a));
     double t_chal = 0, t_van = 0;
     if (dev_tr) {
         GLP_HIP(hipEventSynchronize(ev_chal));
         t_chal = since();
         // same order of checks as verify_front: canonical form (above), proof of work, then the identity at zeta
         ctx_host_pool(c).run(K, [&](size_t k) {
-            if (rc[k] != GLP_OK) return;
-            if (h_err[k] & 8u) { rc[k] = set_error(GLP_ERR_PROVE, "Invalid proof of work witness."); why[k] = g_last_error; return; }
+            if (!why[k].empty()) return;
+            if (h_err[k] & 8u) { set_error(GLP_ERR_PROVE, "Invalid proof of work witness."); why[k] = g_last_error; return; }
             u64 alphas[MAXCH] = {0, 0, 0, 0};
             for (u32 i = 0; i < nch; i++) alphas[i] = h_apow[(k * nch + i) * 2 + 1];
             const E zeta(e_make(h_zetas[4 * k], h_zetas[4 * k + 1]));
-            rc[k] = verify_vanishing(cc, proofs + k * L.total, &h_chal[k * 2 * MAXCH], &h_chal[k * 2 * MAXCH + MAXCH], alphas, zeta, &h_qpp[k * 3 * MAXCH + 2 * MAXCH]);
-            if (rc[k] != GLP_OK) why[k] = g_last_error;
+            if (verify_vanishing(cc, proofs + k * L.total, &h_chal[k * 2 * MAXCH], &h_chal[k * 2 * MAXCH + MAXCH], alphas, zeta, &h_qpp[k * 3 * MAXCH + 2 * MAXCH]) != GLP_OK)
+                why[k] = g_last_error;
         });
         t_van = since();
     }
-    // (a copy into pageable memory blocks its caller until the stream gets there: enqueued only now, the identity at zeta ran beside the query rounds)
-    GLP_HIP(hipMemcpyAsync(hs.data(), dev_status, hs.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));
+    // (enqueued only now: the identity at zeta ran beside the query rounds)
+    std::vector<u32> hs;
+    GLP_TRY(read_status(c, a, hs));
     if (trace) {
         if (dev_tr) fprintf(stderr, "[glp_verify_batch K=%u dev] canonical scan %.3f ms | upload done at %.3f | challenges back at %.3f | identity at zeta done at %.3f | query rounds done at %.3f ms\n",
                             K, t_front, t_up, t_chal, t_van, since());
         else fprintf(stderr, "[glp_verify_batch K=%u] host half %.3f ms | upload done at %.3f | query rounds done at %.3f ms\n", K, t_front, t_up, since());
     }
-    for (u32 k = 0; k < K; k++) {
-        if (rc[k] == GLP_OK)
-            for (u32 q = 0; q < nq && rc[k] == GLP_OK; q++)
-                if (hs[(size_t)k * nq + q]) { rc[k] = query_failure(q, hs[(size_t)k * nq + q], nred); why[k] = g_last_error; }
-        status_out[k] = rc[k];
-        if (reasons_out) {
-            char *o = reasons_out + (size_t)k * GLP_REASON_LEN;
-            memset(o, 0, GLP_REASON_LEN);
-            if (rc[k] != GLP_OK) strncpy(o, why[k].c_str(), GLP_REASON_LEN - 1);
-        }
-    }
+    write_verdicts(K, nq, hs, why, [](u32 q, u32 word) { query_failure(q, word); return g_last_error; }, status_out, reasons_out);
     return GLP_OK;
 }
 

@@ -1,15 +1,17 @@
-"""glp_fri_verify_many against the query-round stage of glp_verify_batch, on the same proofs (profiles/r09_fri_verify.txt).
+"""The query-round kernel through its two entry points, glp_verify_batch and glp_fri_verify_many, on the same proofs.  Both launch
+k_fri_verify_queries (csrc/verify_dev.h); profiles/r09_fri_verify.txt is the record from when glp_verify_batch still had a kernel of
+its own (k_verify_queries), measured by this script as it was then.
 
   python profiles/fri_verify_timing.py [--out profiles/r09_fri_verify.txt] [--batches 32 256] [--reps 9]
   python profiles/fri_verify_timing.py --rehearse      # no GPU: the slicing alone, on the CPU prover's proof, held to the restatement
 
 K proofs of the zkdsa circuit (`bench.py --workload zkdsa-batch`: 2^3 rows, standard_recursion_config) come from glp_prove_batch.
-  baseline:  glp_verify_batch on them; the device time of its `verify_queries` stage (k_verify_queries)
-  measured:  the same proofs sliced into their plonk FRI instance -- four oracles (constants_sigmas shared, the other three per
+  whole:     glp_verify_batch on them (the plonk instance filled from the circuit's layout); the device time of its `verify_queries` stage
+  seam:      the same proofs sliced into their plonk FRI instance -- four oracles (constants_sigmas shared, the other three per
              proof), zeta and g zeta, the openings in point order, the FriProof words, the transcript state right after the
              openings (tests/fri_restate.py: plonk_instance, plonk_openings_to_points) -- through glp_fri_verify_many; the device
-             time of its `fri_verify_queries` stage (k_fri_verify_queries) and the wall time of the whole call
-Every witness of the batch is the same one, so the K proofs are equal words; the kernels walk the same hash chains either way.
+             time of its `fri_verify_queries` stage and the wall time of the whole call
+Every witness of the batch is the same one, so the K proofs are equal words; the kernel walks the same hash chains either way.
 Stage times: hipEvent pairs with profiling on, median of --reps calls after two warm-up calls, the two verifiers alternating; wall
 times: profiling off, host clock around the call (which ends synchronised: it copies the verdicts back)."""
 import argparse
@@ -78,7 +80,7 @@ def main():
     lines = ["glp_fri_verify_many against glp_verify_batch on the same K zkdsa proofs (2^3 rows, %d query rounds, arities %s, %d-word proofs); stage = device "
              "time between hipEvent pairs with profiling on, wall = host clock with profiling off; median (min..max) of %d calls after 2 warm-up calls, "
              "the two verifiers alternating" % (desc.num_query_rounds, list(desc.reduction_arity_bits), gc.proof_words, a.reps),
-             "%6s | %-34s | %-34s | %6s | %-30s | %-30s" % ("K", "verify_queries stage ms (baseline)", "fri_verify_queries stage ms", "ratio",
+             "%6s | %-34s | %-34s | %6s | %-30s | %-30s" % ("K", "verify_queries stage ms", "fri_verify_queries stage ms", "ratio",
                                                           "glp_verify_batch wall ms", "glp_fri_verify_many wall ms")]
     for K in a.batches:
         proofs = gc.prove_batch(np.stack([desc.wires] * K), np.stack([desc.public_inputs] * K))

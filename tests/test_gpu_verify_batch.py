@@ -120,6 +120,59 @@ def test_a_batch_of_different_proofs(ctx, oracle):
     gc.free()
 
 
+def _three_witnesses(which):
+    """three descriptions of ONE circuit with three different witnesses (the first is the circuit's own)"""
+    if which == "smt10":
+        # two reductions.  The builder draws no input to redraw, but a BaseSumGate<2> row (wire 0 = sum of the 63 bits in wires 1..63) holds a
+        # value that only its bit 0 ties to other rows: members 1 and 2 flip bit 1, bit 2 of the first such row
+        descs = [synth.smt_shape_circuit(10, seed=9) for _ in range(3)]
+        w = np.asarray(descs[0].wires)
+        rows = [r for r in np.nonzero((w[1:64] <= 1).all(axis=0) & (w[0] > 1))[0]
+                if sum(int(w[1 + j, r]) << j for j in range(63)) == int(w[0, r])]
+        assert rows, "no BaseSumGate<2> row found"
+        for k in (1, 2):
+            wk = np.array(descs[k].wires, np.uint64)
+            wk[1 + k, rows[0]] ^= np.uint64(1)
+            wk[0, rows[0]] ^= np.uint64(1 << k)
+            descs[k].wires = wk
+        return descs
+    rng = np.random.default_rng(77)
+    keys = [dict(private_key=synth.gl.rand(rng, 4), message=synth.gl.rand(rng, 4)) for _ in range(3)]
+    if which == "zk":           # salted leaves, two rounds: the "zk" case of tests/test_gpu_verify_sweep.py
+        return [synth.zkdsa_circuit(config=synth.Config.standard_recursion_zk_config(num_query_rounds=2), blinding_seed=7, **kw) for kw in keys]
+    descs = [synth.zkdsa_circuit(3, **kw) for kw in keys]       # "keccak": KeccakHash<25> caps and paths
+    for d in descs:
+        d.hasher, d.circuit_digest = 1, None
+    return descs
+
+
+@pytest.mark.parametrize("which", ["smt10", "zk", "keccak"])
+def test_each_member_is_checked_against_its_own_caps(ctx, which):
+    """K = 3 proofs of different witnesses, so every member carries caps of its own (the sweeps tile one proof; the 256 different proofs above
+    are zkdsa under Poseidon: no reductions, unsalted leaves): all accepted, by glp_verify too.  Then members 0 and 1 trade their query
+    sections: the transcript of neither moves, so the query rounds are what rejects both, for glp_verify's reason, and member 2 stays accepted."""
+    descs = _three_witnesses(which)
+    gc = glp.Circuit(ctx, descs[0])
+    proofs = gc.prove_batch(np.stack([d.wires for d in descs]), np.stack([d.public_inputs for d in descs]))
+    capw = 4 << descs[0].cap_height
+    assert len({proofs[k, :capw].tobytes() for k in range(3)}) == 3, "the members share a wires cap"
+    assert list(gc.verify_batch(proofs)) == [True] * 3
+    assert all(gc.verify(p) for p in proofs)
+    secs = proof_sections.sections(descs[0])
+    assert proof_sections.tiles(secs, gc.proof_words)
+    lo, hi = min(s.lo for s in secs if s.q is not None), max(s.hi for s in secs if s.q is not None)
+    swapped = proofs.copy()
+    swapped[0, lo:hi], swapped[1, lo:hi] = proofs[1, lo:hi], proofs[0, lo:hi]
+    ok, reasons = gc.verify_batch(swapped, reasons=True)
+    assert list(ok) == [False, False, True] and reasons[2] == ""
+    L = glp.load_library()
+    for k in (0, 1):
+        assert not gc.verify(swapped[k])
+        assert reasons[k] == L.glp_last_error().decode() and reasons[k].startswith("Invalid Merkle proof (query 0, initial tree"), (k, reasons[k])
+    assert gc.verify(swapped[2])
+    gc.free()
+
+
 def test_headline_shape_proof(ctx, oracle):
     """one proof of the 2^16-row, 136-wire shape (depth-15 paths, arity-16 folds): device verdict = host verdict = oracle verdict"""
     desc = synth.arith_circuit(16, synth.Config.standard_ecc_config(), seed=16)

@@ -1,5 +1,5 @@
 """glp_verify_batch swept word by word: member j of the batch is an accepted proof with word j replaced by itself + 1 mod p, for
-EVERY word j of the proof, on the circuits at which k_verify_queries branches.  The true verifier rejects each of them, for the
+EVERY word j of the proof, on the circuits at which k_fri_verify_queries branches.  The true verifier rejects each of them, for the
 reason plonky2's order of checks dictates, and accepts the untouched copies that sit between them.
 
 Where the words live and which reason each query-phase word must give comes from tests/proof_sections.py (pinned against the

@@ -122,7 +122,7 @@ def test_wide_routed_circuit(ctx, oracle):
 
 
 def test_arity_32(ctx, oracle):
-    """arity_bits = 5, the largest glp_circuit_create takes and the only arity where a 16-lane group of k_verify_queries takes two
+    """arity_bits = 5, the largest glp_circuit_create takes and the only arity where a 16-lane group of k_fri_verify_queries takes two
     interpolation points per lane: parity, the three verifiers, and one damaged word of the layer's 64-word leaf rejected for the same
     reason by glp_verify and glp_verify_batch"""
     desc, oc, _ = lm.oracle_ref(oracle, "arity32_lg10")
