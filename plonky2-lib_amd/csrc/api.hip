@@ -210,32 +210,31 @@ int glp_ctx_stage_get(glp_ctx *c, int index, const char **name, float *ms, doubl
     return GLP_OK;
 }
 
+}  // extern "C"
+
 // ------------------------------------------------------------------------------------------ primitives
-struct Scratch {  // RAII for pool blocks inside one API call
-    glp_ctx *c;
-    std::vector<void *> ptrs;
-    explicit Scratch(glp_ctx *ctx) : c(ctx) {}
-    ~Scratch() { (void)hipStreamSynchronize(c->stream); for (void *p : ptrs) c->release(p); }
-    int get(u64 **p, size_t elems) {
-        void *v = nullptr;
-        int rc = c->alloc(&v, elems * sizeof(u64));
-        if (rc == GLP_OK) { ptrs.push_back(v); *p = (u64 *)v; }
-        return rc;
-    }
-};
+// What the primitive entry points share: `in` goes up into a block of the call's scratch, `run(scratch, dev_in, &dev_result)`
+// transforms it (in further blocks of that scratch, if it needs them) and names where the result is, and that comes back into `out`.
+template <class F>
+static int on_device_copy(glp_ctx *c, const u64 *in, size_t in_words, u64 *out, size_t out_words, F run) {
+    Scratch s(c);
+    u64 *a, *res = nullptr;
+    GLP_TRY(s.words(&a, in_words));
+    GLP_HIP(hipMemcpyAsync(a, in, in_words * 8, hipMemcpyHostToDevice, c->stream));
+    GLP_TRY(run(s, a, &res));
+    return d2h(c, out, res, out_words * 8);
+}
+
+extern "C" {
 
 int glp_poseidon_permute(glp_ctx *c, uint64_t *states, size_t count) {
     GLP_REQUIRE(c && (states || !count), "null argument");
     GLP_TRY(bind(c));
     if (!count) return GLP_OK;
-    Scratch s(c);
-    u64 *d;
-    GLP_TRY(s.get(&d, count * 12));
-    GLP_HIP(hipMemcpyAsync(d, states, count * 96, hipMemcpyHostToDevice, c->stream));
-    GLP_TRY(poseidon_permute_states(c, d, count));
-    GLP_HIP(hipMemcpyAsync(states, d, count * 96, hipMemcpyDeviceToHost, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));
-    return GLP_OK;
+    return on_device_copy(c, states, count * 12, states, count * 12, [&](Scratch &, u64 *a, u64 **res) {
+        *res = a;
+        return poseidon_permute_states(c, a, count);
+    });
 }
 
 int glp_fft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n) {
@@ -244,16 +243,13 @@ int glp_fft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n) {
     if (!ncols) return GLP_OK;
     if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
     const size_t tot = (size_t)ncols << log_n;
-    Scratch s(c);
-    u64 *a, *b;
-    GLP_TRY(s.get(&a, tot));
-    GLP_TRY(s.get(&b, tot));
-    GLP_HIP(hipMemcpyAsync(a, cols, tot * 8, hipMemcpyHostToDevice, c->stream));
-    GLP_TRY(bitrev_copy(c, a, b, ncols, (int)log_n));
-    GLP_TRY(ntt_coeffs_to_values(c, b, a, ncols, (int)log_n));
-    GLP_HIP(hipMemcpyAsync(cols, a, tot * 8, hipMemcpyDeviceToHost, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));
-    return GLP_OK;
+    return on_device_copy(c, cols, tot, cols, tot, [&](Scratch &s, u64 *a, u64 **res) {
+        u64 *b;
+        GLP_TRY(s.words(&b, tot));
+        GLP_TRY(bitrev_copy(c, a, b, ncols, (int)log_n));
+        *res = a;
+        return ntt_coeffs_to_values(c, b, a, ncols, (int)log_n);
+    });
 }
 
 int glp_ifft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n) {
@@ -262,16 +258,13 @@ int glp_ifft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n) {
     if (!ncols) return GLP_OK;
     if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
     const size_t tot = (size_t)ncols << log_n;
-    Scratch s(c);
-    u64 *a, *b;
-    GLP_TRY(s.get(&a, tot));
-    GLP_TRY(s.get(&b, tot));
-    GLP_HIP(hipMemcpyAsync(a, cols, tot * 8, hipMemcpyHostToDevice, c->stream));
-    GLP_TRY(intt_values_to_coeffs(c, a, b, ncols, (int)log_n));
-    GLP_TRY(bitrev_copy(c, b, a, ncols, (int)log_n));
-    GLP_HIP(hipMemcpyAsync(cols, a, tot * 8, hipMemcpyDeviceToHost, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));
-    return GLP_OK;
+    return on_device_copy(c, cols, tot, cols, tot, [&](Scratch &s, u64 *a, u64 **res) {
+        u64 *b;
+        GLP_TRY(s.words(&b, tot));
+        GLP_TRY(intt_values_to_coeffs(c, a, b, ncols, (int)log_n));
+        *res = a;
+        return bitrev_copy(c, b, a, ncols, (int)log_n);
+    });
 }
 
 int glp_lde(glp_ctx *c, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, uint32_t rate_bits, uint64_t shift,
@@ -283,19 +276,15 @@ int glp_lde(glp_ctx *c, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, 
     if (!ncols) return GLP_OK;
     if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
     const size_t tot = (size_t)ncols << log_n, TOT = tot << rate_bits;
-    Scratch s(c);
-    u64 *a, *b, *l, *o;
-    GLP_TRY(s.get(&a, tot));
-    GLP_TRY(s.get(&b, tot));
-    GLP_TRY(s.get(&l, TOT));
-    GLP_TRY(s.get(&o, TOT));
-    GLP_HIP(hipMemcpyAsync(a, coeffs, tot * 8, hipMemcpyHostToDevice, c->stream));
-    GLP_TRY(bitrev_copy(c, a, b, ncols, (int)log_n));
-    GLP_TRY(lde_coeffs(c, b, l, ncols, (int)log_n, (int)rate_bits, shift));
-    GLP_TRY(lde_to_natural(c, l, o, ncols, (int)log_n, (int)rate_bits));
-    GLP_HIP(hipMemcpyAsync(out, o, TOT * 8, hipMemcpyDeviceToHost, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));
-    return GLP_OK;
+    return on_device_copy(c, coeffs, tot, out, TOT, [&](Scratch &s, u64 *a, u64 **res) {
+        u64 *b, *l;
+        GLP_TRY(s.words(&b, tot));
+        GLP_TRY(s.words(&l, TOT));
+        GLP_TRY(s.words(res, TOT));
+        GLP_TRY(bitrev_copy(c, a, b, ncols, (int)log_n));
+        GLP_TRY(lde_coeffs(c, b, l, ncols, (int)log_n, (int)rate_bits, shift));
+        return lde_to_natural(c, l, *res, ncols, (int)log_n, (int)rate_bits);
+    });
 }
 
 // PolynomialValues::coset_ifft(shift): the transform of glp_batch_from_coset_values at one plane (sub_bits = 0), on its own
@@ -306,16 +295,13 @@ int glp_coset_ifft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n, u
     if (!ncols) return GLP_OK;
     if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
     const size_t tot = (size_t)ncols << log_n;
-    Scratch s(c);
-    u64 *a, *b;
-    GLP_TRY(s.get(&a, tot));
-    GLP_TRY(s.get(&b, tot));
-    GLP_HIP(hipMemcpyAsync(a, cols, tot * 8, hipMemcpyHostToDevice, c->stream));
-    GLP_TRY(coset_planes_to_chunk_coeffs(c, a, b, b, ncols, (int)log_n, 0, shift));
-    GLP_TRY(bitrev_copy(c, b, a, ncols, (int)log_n));
-    GLP_HIP(hipMemcpyAsync(cols, a, tot * 8, hipMemcpyDeviceToHost, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));
-    return GLP_OK;
+    return on_device_copy(c, cols, tot, cols, tot, [&](Scratch &s, u64 *a, u64 **res) {
+        u64 *b;
+        GLP_TRY(s.words(&b, tot));
+        GLP_TRY(coset_planes_to_chunk_coeffs(c, a, b, b, ncols, (int)log_n, 0, shift));
+        *res = a;
+        return bitrev_copy(c, b, a, ncols, (int)log_n);
+    });
 }
 
 }  // extern "C"
@@ -355,8 +341,8 @@ extern "C" int glp_keccak256(glp_ctx *c, const uint8_t *msgs, size_t count, size
     if (!count) return GLP_OK;
     Scratch s(c);
     u64 *dm, *dd;
-    GLP_TRY(s.get(&dm, (count * len + 7) / 8 + 1));
-    GLP_TRY(s.get(&dd, count * 4));
+    GLP_TRY(s.words(&dm, (count * len + 7) / 8 + 1));
+    GLP_TRY(s.words(&dd, count * 4));
     if (len) GLP_HIP(hipMemcpyAsync(dm, msgs, count * len, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_keccak256, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t *)dm, count, len, (uint8_t *)dd);
     GLP_HIP(hipGetLastError());
@@ -415,140 +401,117 @@ void batch_destroy(glp_batch *b) {
     delete b;
 }
 
-// dev_in: values (natural) if from_values, else coefficients in natural order.
-// host_src != nullptr (BATCH_VALUES only): the values are still in host memory; they are copied into dev_in in column
+int batch_shape_check(const char *fn, u32 K, size_t ncols, u32 log_n, u32 rate_bits, u32 cap_height, u32 hasher, size_t max_bytes) {
+    const std::string at = fn ? std::string(fn) + ": " : std::string();
+    const char *p = at.c_str();
+    GLP_REQUIRE(K >= 1 && K <= 65535, "%sbatch of %u trees outside 1..65535", p, K);
+    if (log_n > (u32)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "%slog_n=%u > %d", p, log_n, NTT_MAX_LG);
+    GLP_REQUIRE(rate_bits <= 4, "%srate_bits=%u outside 0..4", p, rate_bits);
+    GLP_REQUIRE(cap_height <= log_n + rate_bits, "%scap_height=%u should be at most log2(leaves)=%u", p, cap_height, log_n + rate_bits);
+    GLP_REQUIRE(ncols > 0, "%sncols must be positive", p);
+    GLP_REQUIRE(ncols <= 0x7FFFFFFFu / K, "%sbatch too wide (num_proofs * ncols = %u * %zu columns)", p, K, ncols);
+    GLP_REQUIRE(!max_bytes || (size_t)K * ncols <= max_bytes >> (3 + log_n + rate_bits),
+                "%sbatch too large (num_proofs * ncols * 2^(log_n + rate_bits) words)", p);
+    if (hasher != GLP_HASH_POSEIDON && hasher != GLP_HASH_KECCAK25) return set_error(GLP_ERR_UNSUPPORTED, "%shasher %u is not one of GLP_HASH_*", p, hasher);
+    return GLP_OK;
+}
+
+// dev_in [K * ncols][n]: values in natural order (BATCH_VALUES), or coefficients in natural or bit-reversed order.
+// host_src != nullptr (BATCH_VALUES, K = 1): the values are still in host memory; they are copied into dev_in in column
 // chunks on the copy stream while the transforms of the chunks already on the device run on the compute stream.
 int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg, int rate_bits, int cap_height,
                 glp_batch **out, const u64 *host_src, u32 K, int hasher, const u64 *salt_seed, u32 salt_tag) {
     GLP_REQUIRE(out, "out is null");
     *out = nullptr;
-    if (hasher != GLP_HASH_POSEIDON && hasher != GLP_HASH_KECCAK25) return set_error(GLP_ERR_UNSUPPORTED, "hasher %d is not one of GLP_HASH_*", hasher);
-    GLP_REQUIRE(ncols > 0, "ncols must be positive");
-    GLP_REQUIRE(K >= 1 && (K == 1 || host_src == nullptr), "bad batch arguments");
-    if (K > 1) {
-        // K oracles of one shape: the transforms see K * ncols independent columns, the trees get a proof index
-        GLP_REQUIRE(rate_bits >= 0 && rate_bits <= 4 && cap_height >= 0 && cap_height <= lg + rate_bits && lg <= NTT_MAX_LG, "bad batch shape");
-        const size_t n = (size_t)1 << lg, N = n << rate_bits;
-        std::unique_ptr<glp_batch, void (*)(glp_batch *)> b(new glp_batch(), batch_destroy);
-        b->ctx = c; b->ncols = ncols; b->lg = lg; b->rate_bits = rate_bits; b->cap_height = cap_height; b->K = K; b->hasher = hasher;
-        b->salt = salt_seed ? SALT_SIZE : 0;
-        b->ndigests = merkle_num_digests(N, cap_height);
-        const size_t tot = (size_t)K * ncols, leaf_len = ncols + b->salt;
-        GLP_REQUIRE(tot <= 0x7FFFFFFFu, "batch too wide");
-        GLP_TRY(c->alloc((void **)&b->coeffs, tot * n * 8));
-        GLP_TRY(c->alloc((void **)&b->lde, (size_t)K * leaf_len * N * 8));
-        GLP_TRY(c->alloc((void **)&b->digests, (size_t)K * b->ndigests * 32));
-        if (input_kind == BATCH_VALUES) GLP_TRY(intt_values_to_coeffs(c, dev_in, b->coeffs, (u32)tot, lg));
-        else if (input_kind == BATCH_COEFFS_NATURAL) {
-            for (size_t c0 = 0; c0 < tot; c0 += 65535)        // bitrev_copy keeps the column in grid.y
-                GLP_TRY(bitrev_copy(c, dev_in + c0 * n, b->coeffs + c0 * n, (u32)std::min<size_t>(65535, tot - c0), lg));
-        } else GLP_HIP(hipMemcpyAsync(b->coeffs, dev_in, tot * n * 8, hipMemcpyDeviceToDevice, c->stream));
-        if (!b->salt) {
-            GLP_TRY(lde_coeffs(c, b->coeffs, b->lde, (u32)tot, lg, rate_bits, glf::GEN));
-        } else {
-            // the salt columns of proof k sit between its polynomial columns and those of proof k + 1: one wide LDE into scratch, then
-            // one strided copy into place (K LDE calls of one proof each underfill the device: profiles/r05_zero_knowledge.txt)
-            void *t = nullptr;
-            GLP_TRY(c->alloc(&t, tot * N * 8));
-            int rc = lde_coeffs(c, b->coeffs, (u64 *)t, (u32)tot, lg, rate_bits, glf::GEN);
-            if (rc == GLP_OK) {
-                const hipError_t e = hipMemcpy2DAsync(b->lde, leaf_len * N * 8, t, (size_t)ncols * N * 8, (size_t)ncols * N * 8, K,
-                                                      hipMemcpyDeviceToDevice, c->stream);
-                if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "strided LDE copy: %s", hipGetErrorString(e));
-            }
-            (void)hipStreamSynchronize(c->stream);
-            c->release(t);
-            GLP_TRY(rc);
-            GLP_TRY(merkle_fill_salts(c, b->lde, ncols, lg, rate_bits, salt_seed, salt_tag, K, leaf_len * N));
-        }
-        GLP_TRY(merkle_from_lde(c, b->lde, (u32)leaf_len, lg, rate_bits, cap_height, b->digests, K, leaf_len * N, b->ndigests * 4, hasher));
-        *out = b.release();
-        return GLP_OK;
-    }
-    if (lg > NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%d > %d (three-pass NTT not built yet)", lg, NTT_MAX_LG);
-    GLP_REQUIRE(rate_bits >= 0 && rate_bits <= 4, "rate_bits=%d outside 0..4", rate_bits);
-    GLP_REQUIRE(cap_height >= 0 && cap_height <= lg + rate_bits, "cap_height=%d should be at most log2(leaves)=%d", cap_height,
-                lg + rate_bits);
-    const size_t n = (size_t)1 << lg, N = n << rate_bits;
+    GLP_TRY(batch_shape_check(nullptr, K, ncols, (u32)lg, (u32)rate_bits, (u32)cap_height, (u32)hasher));
+    GLP_REQUIRE(host_src == nullptr || (K == 1 && input_kind == BATCH_VALUES), "bad batch arguments");
+    // K oracles of one shape: the transforms see K * ncols independent columns, the salts and the trees get a proof index
+    const size_t n = (size_t)1 << lg, N = n << rate_bits, tot = (size_t)K * ncols;
     std::unique_ptr<glp_batch, void (*)(glp_batch *)> b(new glp_batch(), batch_destroy);
-    b->ctx = c; b->ncols = ncols; b->lg = lg; b->rate_bits = rate_bits; b->cap_height = cap_height; b->hasher = hasher;
+    b->ctx = c; b->ncols = ncols; b->lg = lg; b->rate_bits = rate_bits; b->cap_height = cap_height; b->K = K; b->hasher = hasher;
     b->salt = salt_seed ? SALT_SIZE : 0;
     b->ndigests = merkle_num_digests(N, cap_height);
-    GLP_TRY(c->alloc((void **)&b->coeffs, (size_t)ncols * n * 8));
-    GLP_TRY(c->alloc((void **)&b->lde, (size_t)(ncols + b->salt) * N * 8));
-    GLP_TRY(c->alloc((void **)&b->digests, b->ndigests * 32));
-    if (input_kind == BATCH_VALUES && host_src != nullptr) {
-        // chunking pays when a chunk's copy is long against a few launches: below 64 MB the witness goes up in one piece
-        const u32 nchunks = ((size_t)ncols * n * 8 < ((size_t)64 << 20)) ? 1u : std::min<u32>(8, ncols), per = (ncols + nchunks - 1) / nchunks;
-        int rc = GLP_OK;
+    const size_t leaf_len = ncols + b->salt;
+    GLP_TRY(c->alloc((void **)&b->coeffs, tot * n * 8));
+    GLP_TRY(c->alloc((void **)&b->lde, (size_t)K * leaf_len * N * 8));
+    GLP_TRY(c->alloc((void **)&b->digests, (size_t)K * b->ndigests * 32));
+    {
+        // The salt columns of proof k sit between its polynomial columns and those of proof k + 1.  One member: they follow its columns and
+        // the LDE goes straight into place.  Several: one wide LDE into scratch, then one strided copy into place (K LDE calls of one
+        // proof each underfill the device: profiles/r05_zero_knowledge.txt).
+        Scratch sc(c);
+        const bool strided = b->salt && K > 1;
+        u64 *lde = b->lde;
+        if (strided) GLP_TRY(sc.words(&lde, tot * N));
+        // The column ranges the coefficients and the LDE are made in: every column at once, or the chunks of a host upload.  Chunking pays
+        // when a chunk's copy is long against a few launches: below 64 MB the witness goes up in one piece.
+        const size_t nchunks = !host_src || tot * n * 8 < ((size_t)64 << 20) ? 1 : std::min<size_t>(8, tot), per = (tot + nchunks - 1) / nchunks;
         std::vector<hipEvent_t> evs;
-        for (u32 c0 = 0; c0 < ncols && rc == GLP_OK; c0 += per) {
-            const u32 cn = std::min(per, ncols - c0);
-            hipEvent_t ev = nullptr;
-            hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e == hipSuccess) evs.push_back(ev);
-            if (e == hipSuccess) e = hipMemcpyAsync(const_cast<u64 *>(dev_in) + (size_t)c0 * n, host_src + (size_t)c0 * n, (size_t)cn * n * 8,
-                                                    hipMemcpyHostToDevice, c->copy_stream);
-            if (e == hipSuccess) e = hipEventRecord(ev, c->copy_stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
-            if (e != hipSuccess) { rc = set_error(GLP_ERR_HIP, "witness upload: %s", hipGetErrorString(e)); break; }
-            {
+        int rc = GLP_OK;
+        for (size_t c0 = 0; c0 < tot && rc == GLP_OK; c0 += per) {
+            const u32 cn = (u32)std::min(per, tot - c0);
+            const u64 *in = dev_in + c0 * n;
+            u64 *co = b->coeffs + c0 * n;
+            if (host_src) {
+                hipEvent_t ev = nullptr;
+                hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+                if (e == hipSuccess) evs.push_back(ev);
+                if (e == hipSuccess) e = hipMemcpyAsync(const_cast<u64 *>(in), host_src + c0 * n, (size_t)cn * n * 8, hipMemcpyHostToDevice, c->copy_stream);
+                if (e == hipSuccess) e = hipEventRecord(ev, c->copy_stream);
+                if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
+                if (e != hipSuccess) { rc = set_error(GLP_ERR_HIP, "witness upload: %s", hipGetErrorString(e)); break; }
+            }
+            if (input_kind == BATCH_VALUES) {
                 StageScope st(c, "intt", 16.0 * n * cn);
-                rc = intt_values_to_coeffs(c, dev_in + (size_t)c0 * n, b->coeffs + (size_t)c0 * n, cn, lg);
+                rc = intt_values_to_coeffs(c, in, co, cn, lg);
+            } else if (input_kind == BATCH_COEFFS_NATURAL) {
+                StageScope st(c, "bitrev_coeffs", 16.0 * n * cn);
+                for (u32 p0 = 0; p0 < cn && rc == GLP_OK; p0 += 65535)        // bitrev_copy keeps the column in grid.y
+                    rc = bitrev_copy(c, in + (size_t)p0 * n, co + (size_t)p0 * n, std::min<u32>(65535, cn - p0), lg);
+            } else {
+                StageScope st(c, "copy_coeffs", 16.0 * n * cn);
+                const hipError_t e = hipMemcpyAsync(co, in, (size_t)cn * n * 8, hipMemcpyDeviceToDevice, c->stream);
+                if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "coefficient copy: %s", hipGetErrorString(e));
             }
             if (rc == GLP_OK) {
                 StageScope st(c, "lde", (8.0 * n + 8.0 * N) * cn);
-                rc = lde_coeffs(c, b->coeffs + (size_t)c0 * n, b->lde + (size_t)c0 * N, cn, lg, rate_bits, glf::GEN);
+                rc = lde_coeffs(c, co, lde + c0 * N, cn, lg, rate_bits, glf::GEN);
+                if (rc == GLP_OK && strided) {
+                    const hipError_t e = hipMemcpy2DAsync(b->lde, leaf_len * N * 8, lde, (size_t)ncols * N * 8, (size_t)ncols * N * 8, K,
+                                                          hipMemcpyDeviceToDevice, c->stream);
+                    if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "strided LDE copy: %s", hipGetErrorString(e));
+                }
             }
         }
-        if (rc != GLP_OK || !evs.empty()) (void)hipStreamSynchronize(c->copy_stream);
-        for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
+        if (host_src) {         // on every exit: the copy stream drained, its events gone
+            (void)hipStreamSynchronize(c->copy_stream);
+            for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
+        }
         GLP_TRY(rc);
-        if (b->salt) GLP_TRY(merkle_fill_salts(c, b->lde, ncols, lg, rate_bits, salt_seed, salt_tag));
-        GLP_TRY(merkle_from_lde(c, b->lde, ncols + b->salt, lg, rate_bits, cap_height, b->digests, 1, 0, 0, hasher));
-        *out = b.release();
-        return GLP_OK;
     }
-    if (input_kind == BATCH_VALUES) {
-        StageScope st(c, "intt", 16.0 * n * ncols);
-        GLP_TRY(intt_values_to_coeffs(c, dev_in, b->coeffs, ncols, lg));
-    } else if (input_kind == BATCH_COEFFS_NATURAL) {
-        StageScope st(c, "bitrev_coeffs", 16.0 * n * ncols);
-        GLP_TRY(bitrev_copy(c, dev_in, b->coeffs, ncols, lg));
-    } else {
-        StageScope st(c, "copy_coeffs", 16.0 * n * ncols);
-        GLP_HIP(hipMemcpyAsync(b->coeffs, dev_in, (size_t)ncols * n * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    {
-        StageScope st(c, "lde", (8.0 * n + 8.0 * N) * ncols);
-        GLP_TRY(lde_coeffs(c, b->coeffs, b->lde, ncols, lg, rate_bits, glf::GEN));
-    }
-    if (b->salt) GLP_TRY(merkle_fill_salts(c, b->lde, ncols, lg, rate_bits, salt_seed, salt_tag));
-    GLP_TRY(merkle_from_lde(c, b->lde, ncols + b->salt, lg, rate_bits, cap_height, b->digests, 1, 0, 0, hasher));
+    if (b->salt) GLP_TRY(merkle_fill_salts(c, b->lde, ncols, lg, rate_bits, salt_seed, salt_tag, K, leaf_len * N));
+    GLP_TRY(merkle_from_lde(c, b->lde, (u32)leaf_len, lg, rate_bits, cap_height, b->digests, K, leaf_len * N, b->ndigests * 4, hasher));
     *out = b.release();
     return GLP_OK;
 }
 
+// the single-batch entry points that take host memory
 static int batch_from_host(glp_ctx *c, const u64 *host, bool from_values, u32 ncols, u32 log_n, u32 rate_bits, u32 cap_height,
                            glp_batch **out, int hasher = GLP_HASH_POSEIDON, const u64 *salt_seed = nullptr, u32 salt_tag = 0) {
     GLP_REQUIRE(c && host && out, "null argument");
+    *out = nullptr;
+    GLP_TRY(batch_shape_check(nullptr, 1, ncols, log_n, rate_bits, cap_height, (u32)hasher));
     GLP_TRY(bind(c));
-    if (log_n > (u32)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
+    Scratch s(c);
     const size_t tot = (size_t)ncols << log_n;
-    void *d = nullptr;
-    GLP_TRY(c->alloc(&d, tot * 8));
-    int rc = GLP_OK;
-    if (from_values) {       // upload pipelined with the transforms
-        rc = batch_build(c, (const u64 *)d, BATCH_VALUES, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, host, 1, hasher,
-                         salt_seed, salt_tag);
-    } else {
-        hipError_t e = hipMemcpyAsync(d, host, tot * 8, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-        if (rc == GLP_OK) rc = batch_build(c, (const u64 *)d, BATCH_COEFFS_NATURAL, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, nullptr, 1, hasher);
+    if (from_values) {       // not copied here: the upload is batch_build's own, pipelined with the transforms
+        u64 *d;
+        GLP_TRY(s.words(&d, tot));
+        return batch_build(c, d, BATCH_VALUES, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, host, 1, hasher, salt_seed, salt_tag);
     }
-    (void)hipStreamSynchronize(c->stream);
-    c->release(d);
-    return rc;
+    const u64 *d;
+    GLP_TRY(s.input(host, 0, tot, &d));
+    return batch_build(c, d, BATCH_COEFFS_NATURAL, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, nullptr, 1, hasher);
 }
 
 // glp_batch_many_from_*: K batches of one shape from [K][ncols][n], host or device memory
@@ -557,30 +520,15 @@ static int batch_many(glp_ctx *c, const u64 *in, int on_device, bool from_values
     GLP_REQUIRE(c && in && out, "null argument");
     *out = nullptr;
     GLP_REQUIRE(K >= 1 && K <= 4096, "num_proofs = %u outside 1..4096", K);
-    if (log_n > (u32)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
-    GLP_REQUIRE(rate_bits <= 4, "rate_bits=%u outside 0..4", rate_bits);
-    GLP_REQUIRE(cap_height <= log_n + rate_bits, "cap_height=%u should be at most log2(leaves)=%u", cap_height, log_n + rate_bits);
-    GLP_REQUIRE(ncols > 0, "ncols must be positive");
-    GLP_REQUIRE((size_t)K * ncols * ((size_t)8 << (log_n + rate_bits)) <= ((size_t)64 << 30),
-                "batch too large (num_proofs * ncols * 2^(log_n + rate_bits) words)");
+    GLP_TRY(batch_shape_check(nullptr, K, ncols, log_n, rate_bits, cap_height, hasher, BATCH_MAX_BYTES));
     GLP_TRY(bind(c));
-    u64 s[4];
-    if (seed) for (int i = 0; i < 4; i++) s[i] = glf::canon(seed[i]);
-    const int kind = from_values ? BATCH_VALUES : BATCH_COEFFS_NATURAL;
-    const u64 *salt = seed ? s : nullptr;
-    if (on_device)
-        return batch_build(c, in, kind, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, nullptr, K, (int)hasher, salt, GLP_SALT_TAG_BATCH);
-    const size_t tot = ((size_t)K * ncols) << log_n;
-    void *d = nullptr;
-    GLP_TRY(c->alloc(&d, tot * 8));
-    int rc = GLP_OK;
-    const hipError_t e = hipMemcpyAsync(d, in, tot * 8, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-    if (rc == GLP_OK)
-        rc = batch_build(c, (const u64 *)d, kind, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, nullptr, K, (int)hasher, salt, GLP_SALT_TAG_BATCH);
-    (void)hipStreamSynchronize(c->stream);
-    c->release(d);
-    return rc;
+    u64 sd[4];
+    if (seed) for (int i = 0; i < 4; i++) sd[i] = glf::canon(seed[i]);
+    Scratch s(c);
+    const u64 *d;
+    GLP_TRY(s.input(in, on_device, ((size_t)K * ncols) << log_n, &d));
+    return batch_build(c, d, from_values ? BATCH_VALUES : BATCH_COEFFS_NATURAL, ncols, (int)log_n, (int)rate_bits, (int)cap_height, out, nullptr, K,
+                       (int)hasher, seed ? sd : nullptr, GLP_SALT_TAG_BATCH);
 }
 
 }  // namespace glp
@@ -685,7 +633,7 @@ int glp_batch_lde_values(const glp_batch *b, uint32_t col_begin, uint32_t num_co
                                   row_major, out);
     Scratch s(c);
     u64 *t;
-    GLP_TRY(s.get(&t, words));
+    GLP_TRY(s.words(&t, words));
     GLP_TRY(lde_sub_coset_rows(c, src, (size_t)(b->ncols + b->salt) * N, b->K, num_cols, b->lg, b->rate_bits, (int)sub_bits, row_begin, num_rows,
                                row_major, t));
     GLP_HIP(hipMemcpyAsync(out, t, words * 8, hipMemcpyDeviceToHost, c->stream));
@@ -700,32 +648,26 @@ int glp_batch_from_coset_values(glp_ctx *c, const uint64_t *values, int values_o
     GLP_REQUIRE(out, "glp_batch_from_coset_values: out is null");
     *out = nullptr;
     GLP_REQUIRE(num_proofs >= 1 && num_proofs <= 4096, "num_proofs = %u outside 1..4096", num_proofs);
-    if (log_n > (u32)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
-    GLP_REQUIRE(rate_bits <= 4, "rate_bits=%u outside 0..4", rate_bits);
-    GLP_REQUIRE(sub_bits <= rate_bits, "sub_bits = %u is more than rate_bits = %u", sub_bits, rate_bits);
-    GLP_REQUIRE(cap_height <= log_n + rate_bits, "cap_height=%u should be at most log2(leaves)=%u", cap_height, log_n + rate_bits);
     GLP_REQUIRE(num_polys > 0, "num_polys must be positive");
-    const size_t ncols = (size_t)num_polys << sub_bits;
-    GLP_REQUIRE((size_t)num_proofs * ncols * ((size_t)8 << (log_n + rate_bits)) <= ((size_t)64 << 30),
-                "batch too large (num_proofs * (num_polys << sub_bits) * 2^(log_n + rate_bits) words)");
-    GLP_REQUIRE((size_t)num_proofs * ncols <= 0x7FFFFFFFu, "batch too wide");
+    const size_t ncols = (size_t)num_polys << (sub_bits & 31);      // the mask keeps the shift defined until sub_bits is refused below
+    GLP_TRY(batch_shape_check("glp_batch_from_coset_values", num_proofs, ncols, log_n, rate_bits, cap_height, hasher, BATCH_MAX_BYTES));
+    GLP_REQUIRE(sub_bits <= rate_bits, "sub_bits = %u is more than rate_bits = %u", sub_bits, rate_bits);
     GLP_TRY(bind(c));
     u64 sd[4];
     if (seed) for (int i = 0; i < 4; i++) sd[i] = glf::canon(seed[i]);
     const size_t channels = (size_t)num_proofs * num_polys, tot = (channels << sub_bits) << log_n;
     Scratch s(c);
-    u64 *x, *y;
-    GLP_TRY(s.get(&x, tot));
-    const u64 *planes = values;
-    if (!values_on_device) {
-        GLP_TRY(s.get(&y, tot));
-        GLP_HIP(hipMemcpyAsync(y, values, tot * 8, hipMemcpyHostToDevice, c->stream));
-        planes = y;
-        if (sub_bits) { GLP_TRY(coset_values_to_planes(c, y, x, channels, (int)log_n, (int)sub_bits)); planes = x; std::swap(x, y); }
-    } else if (sub_bits) {
-        GLP_TRY(s.get(&y, tot));
-        GLP_TRY(coset_values_to_planes(c, values, y, channels, (int)log_n, (int)sub_bits));
-        planes = y;
+    const u64 *planes;
+    u64 *x;
+    GLP_TRY(s.input(values, values_on_device, tot, &planes));
+    GLP_TRY(s.words(&x, tot));
+    if (sub_bits) {
+        GLP_TRY(coset_values_to_planes(c, planes, x, channels, (int)log_n, (int)sub_bits));
+        // the planes are in x; the coefficients go to a second block: the scratch's own copy of a host input, never the caller's device values
+        u64 *y = values_on_device ? nullptr : const_cast<u64 *>(planes);
+        if (!y) GLP_TRY(s.words(&y, tot));
+        planes = x;
+        x = y;
     }
     // planes -> x (per-plane inverse transform), combined in place: x holds the chunks' coefficients, bit-reversed
     GLP_TRY(coset_planes_to_chunk_coeffs(c, planes, x, x, (u32)channels, (int)log_n, (int)sub_bits, glf::GEN));
@@ -768,7 +710,7 @@ int glp_batch_coeffs(const glp_batch *b, uint32_t col_begin, uint32_t ncols, uin
     const size_t n = (size_t)1 << b->lg;
     Scratch s(c);
     u64 *t;
-    GLP_TRY(s.get(&t, (size_t)ncols * n));
+    GLP_TRY(s.words(&t, (size_t)ncols * n));
     GLP_TRY(bitrev_copy(c, b->coeffs + (size_t)col_begin * n, t, ncols, b->lg));
     GLP_HIP(hipMemcpyAsync(out, t, (size_t)ncols * n * 8, hipMemcpyDeviceToHost, c->stream));
     GLP_HIP(hipStreamSynchronize(c->stream));
@@ -784,9 +726,9 @@ int glp_batch_leaf(const glp_batch *b, uint64_t leaf_index, uint64_t *out) {
     GLP_TRY(bind(c));
     Scratch s(c);
     u64 *idx, *t;
-    GLP_TRY(s.get(&idx, 1));
+    GLP_TRY(s.words(&idx, 1));
     const u32 leaf_len = b->ncols + b->salt;
-    GLP_TRY(s.get(&t, leaf_len));
+    GLP_TRY(s.words(&t, leaf_len));
     GLP_HIP(hipMemcpyAsync(idx, &leaf_index, 8, hipMemcpyHostToDevice, c->stream));
     GLP_TRY(merkle_gather_lde_rows(c, b->lde, leaf_len, b->lg, b->rate_bits, idx, 1, t));
     GLP_HIP(hipMemcpyAsync(out, t, (size_t)leaf_len * 8, hipMemcpyDeviceToHost, c->stream));
@@ -806,8 +748,8 @@ int glp_batch_merkle_proof(const glp_batch *b, uint64_t leaf_index, uint64_t *si
     GLP_TRY(bind(c));
     Scratch s(c);
     u64 *idx, *t;
-    GLP_TRY(s.get(&idx, 1));
-    GLP_TRY(s.get(&t, (size_t)depth * 4));
+    GLP_TRY(s.words(&idx, 1));
+    GLP_TRY(s.words(&t, (size_t)depth * 4));
     GLP_HIP(hipMemcpyAsync(idx, &leaf_index, 8, hipMemcpyHostToDevice, c->stream));
     GLP_TRY(merkle_gather_paths(c, b->digests, N, b->cap_height, idx, 1, t));
     GLP_HIP(hipMemcpyAsync(siblings_out, t, (size_t)depth * 32, hipMemcpyDeviceToHost, c->stream));

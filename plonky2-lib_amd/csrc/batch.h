@@ -18,6 +18,13 @@ struct glp_batch {
 
 namespace glp {
 enum BatchInput { BATCH_VALUES = 0, BATCH_COEFFS_NATURAL = 1, BATCH_COEFFS_BITREV = 2 };
+// The shape rules of a batch of K oracles, stated once: K in 1..65535 (the tree index rides in grid.y), log_n <= NTT_MAX_LG and a known
+// hasher (GLP_ERR_UNSUPPORTED), rate_bits <= 4, cap_height <= log_n + rate_bits, ncols > 0, K * ncols columns in 31 bits and, where
+// max_bytes is given, an LDE of at most that many bytes (GLP_ERR_ARG).  `fn`, if not null, names the entry point in the message.
+// batch_build calls it first; an entry point that allocates or uploads before batch_build calls it up front, with BATCH_MAX_BYTES.
+constexpr size_t BATCH_MAX_BYTES = (size_t)64 << 30;
+int batch_shape_check(const char *fn, u32 K, size_t ncols, u32 log_n, u32 rate_bits, u32 cap_height, u32 hasher, size_t max_bytes = 0);
+// One pipeline for every K >= 1: coeffs [K * ncols][n], LDE [K][ncols + salt][N], one tree per member; K = 1 is the one-member case.
 int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg, int rate_bits, int cap_height,
                 glp_batch **out, const u64 *host_src = nullptr, u32 K = 1, int hasher = GLP_HASH_POSEIDON,
                 const u64 *salt_seed = nullptr /* non-null: blinded, 4 salt columns (merkle_fill_salts) */, u32 salt_tag = 0);

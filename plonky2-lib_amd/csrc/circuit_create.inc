@@ -187,22 +187,12 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
     GLP_TRY(h2d(c, cc->dev_consts, d.constants, (size_t)nc * n * 8));
     GLP_TRY(build_quotient_plan(c, cc.get()));
     {
-        void *v = nullptr;
-        GLP_TRY(c->alloc(&v, (size_t)(nc + nr) * n * 8));
-        u64 *csv = (u64 *)v;
-        int rc = GLP_OK;
-        {
-            hipError_t e = hipMemcpyAsync(csv, cc->dev_consts, (size_t)nc * n * 8, hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "D2D copy: %s", hipGetErrorString(e));
-        }
-        if (rc == GLP_OK) {
-            hipError_t e = hipMemcpyAsync(csv + (size_t)nc * n, cc->dev_sigmas, (size_t)nr * n * 8, hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) rc = set_error(GLP_ERR_HIP, "D2D copy: %s", hipGetErrorString(e));
-        }
-        if (rc == GLP_OK) rc = batch_build(c, csv, BATCH_VALUES, nc + nr, (int)d.degree_bits, (int)d.rate_bits, (int)d.cap_height, &cc->cs, nullptr, 1, (int)d.hasher);
-        (void)hipStreamSynchronize(c->stream);
-        c->release(v);
-        GLP_TRY(rc);
+        Scratch sc(c);
+        u64 *csv;
+        GLP_TRY(sc.words(&csv, (size_t)(nc + nr) * n));
+        GLP_HIP(hipMemcpyAsync(csv, cc->dev_consts, (size_t)nc * n * 8, hipMemcpyDeviceToDevice, c->stream));
+        GLP_HIP(hipMemcpyAsync(csv + (size_t)nc * n, cc->dev_sigmas, (size_t)nr * n * 8, hipMemcpyDeviceToDevice, c->stream));
+        GLP_TRY(batch_build(c, csv, BATCH_VALUES, nc + nr, (int)d.degree_bits, (int)d.rate_bits, (int)d.cap_height, &cc->cs, nullptr, 1, (int)d.hasher));
     }
     GLP_TRY(batch_cap_host(c, cc->cs, cc->cs_cap));
     bool zero = true;

@@ -100,4 +100,47 @@ inline int bind(glp_ctx *c) {
     hipError_t e = hipSetDevice(c->device);
     return e == hipSuccess ? GLP_OK : set_error(GLP_ERR_HIP, "hipSetDevice(%d): %s", c->device, hipGetErrorString(e));
 }
+// Synchronising copies: the host side is usually a stack or std::vector temporary that must not outlive the copy.
+inline int d2h(glp_ctx *c, void *dst, const void *src, size_t bytes) {
+    GLP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    GLP_HIP(hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
+inline int h2d(glp_ctx *c, void *dst, const void *src, size_t bytes) {
+    GLP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    GLP_HIP(hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
+// The pool blocks of one call: released, once the stream has drained, however the call returns.  Sizes are counts of elements,
+// never bytes: words() counts 64-bit words, array() elements of T.
+struct Scratch {
+    glp_ctx *c;
+    std::vector<void *> ptrs;
+    explicit Scratch(glp_ctx *ctx) : c(ctx) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() {
+        if (ptrs.empty()) return;           // nothing to release: a call on the caller's own device buffers stays asynchronous
+        (void)hipStreamSynchronize(c->stream);
+        for (void *p : ptrs) c->release(p);
+    }
+    template <class T> int array(T **p, size_t count) {
+        void *v = nullptr;
+        GLP_TRY(c->alloc(&v, count * sizeof(T)));
+        ptrs.push_back(v);
+        *p = (T *)v;
+        return GLP_OK;
+    }
+    int words(u64 **p, size_t count) { return array(p, count); }
+    // host or device input -> a device pointer: the caller's own, or a block of this scratch filled from the host.  The copy is
+    // asynchronous on the ctx stream: `in` is a caller's buffer that outlives the call (h2d above for stack and vector sources).
+    int input(const u64 *in, int on_device, size_t count, const u64 **dev) {
+        if (on_device) { *dev = in; return GLP_OK; }
+        u64 *d;
+        GLP_TRY(words(&d, count));
+        GLP_HIP(hipMemcpyAsync(d, in, count * 8, hipMemcpyHostToDevice, c->stream));
+        *dev = d;
+        return GLP_OK;
+    }
+};
 }  // namespace glp

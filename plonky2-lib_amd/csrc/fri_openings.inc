@@ -42,7 +42,7 @@ struct glp_fri {
     u32 arity_bits[16] = {0};
     u32 nred = 0, pow_bits = 0;
     ProveGeo g;                        // g.K proofs, no circuit; arity_bits points into this object
-    Tmp tmp;
+    Scratch tmp;
     size_t nopen = 0;                  // openings of one proof, points in order
     FriState fri;
     bool layer_open = false;
@@ -104,15 +104,15 @@ struct glp_fri {
         const u32 K = g.K, nob = open_blocks(n);
         StageScope st(c, "fri.openings", 8.0 * n * nopen * K);
         u64 *partial;
-        GLP_TRY(tmp.get(&partial, (size_t)K * nopen * nob * 2));
-        GLP_TRY(tmp.get(&dev_zs, zs.size()));
+        GLP_TRY(tmp.words(&partial, (size_t)K * nopen * nob * 2));
+        GLP_TRY(tmp.words(&dev_zs, zs.size()));
         GLP_TRY(h2d(c, dev_zs, zs.data(), zs.size() * 8));
         std::vector<u64 *> zt(npts, nullptr);
         for (size_t b = 0; b < npts; b++) {
             const FriPointPlan &p = pts[b];
             if (p.table != b) zt[b] = zt[p.table];
             else {
-                GLP_TRY(tmp.get(&zt[b], (size_t)K * 2 * n));
+                GLP_TRY(tmp.words(&zt[b], (size_t)K * 2 * n));
                 ZTArgs za;
                 za.zt = zt[b]; za.lg = (u32)g.lg;
                 if (K == 1) {       // one point: its squarings are made here once and ride in the kernel arguments, not lg per lane on the device
@@ -140,7 +140,7 @@ struct glp_fri {
                 }
             }
         }
-        GLP_TRY(tmp.get(&dev_open, (size_t)K * nopen * 2));
+        GLP_TRY(tmp.words(&dev_open, (size_t)K * nopen * 2));
         hipLaunchKernelGGL(k_fri_open_finish, dim3(nblk((size_t)K * nopen)), dim3(256), 0, c->stream, partial, dev_open, (size_t)K * nopen, nob);
         GLP_HIP(hipGetLastError());
         GLP_TRY(d2h(c, openings_out, dev_open, (size_t)K * nopen * 16));
@@ -190,13 +190,13 @@ struct glp_fri {
         std::vector<u64> up(prog_words + (size_t)K * 2);
         memcpy(up.data(), prog.data(), prog_words * 8);
         memcpy(up.data() + prog_words, alphas, (size_t)K * 16);
-        GLP_TRY(tmp.get(&dev_prog, up.size()));
+        GLP_TRY(tmp.words(&dev_prog, up.size()));
         GLP_TRY(h2d(c, dev_prog, up.data(), up.size() * 8));
         const u64 *dev_alpha = dev_prog + prog_words;
-        GLP_TRY(tmp.get(&dev_ap, (size_t)K * 2 * nopen));
-        GLP_TRY(tmp.get(&dev_pp, (size_t)K * FCM_PP_WORDS));
-        GLP_TRY(tmp.get(&fv, (size_t)K * 2 * g.n));
-        GLP_TRY(tmp.get(&fcoef, (size_t)K * 2 * g.n));
+        GLP_TRY(tmp.words(&dev_ap, (size_t)K * 2 * nopen));
+        GLP_TRY(tmp.words(&dev_pp, (size_t)K * FCM_PP_WORDS));
+        GLP_TRY(tmp.words(&fv, (size_t)K * 2 * g.n));
+        GLP_TRY(tmp.words(&fcoef, (size_t)K * 2 * g.n));
         ta.alpha = dev_alpha; ta.open = dev_open; ta.z = dev_zs; ta.apow = dev_ap; ta.pp = dev_pp; ta.nopen = nopen;
         hipLaunchKernelGGL(k_fri_table, dim3((unsigned)pts.size(), K), dim3(256), 0, c->stream, ta);
         GLP_HIP(hipGetLastError());
@@ -236,7 +236,7 @@ struct glp_fri {
         StageScope st(c, "fri.fold", 0.0);
         u64 *dev_betas = nullptr;                               // one beta rides in the kernel arguments: no upload per layer
         if (K > 1) {
-            GLP_TRY(tmp.get(&dev_betas, (size_t)K * 2));
+            GLP_TRY(tmp.words(&dev_betas, (size_t)K * 2));
             GLP_TRY(h2d(c, dev_betas, betas, (size_t)K * 16));
         }
         GLP_TRY(stage_fri_fold(c, g, tmp, fri, K > 1 ? e_from(0) : e_make(betas[0], betas[1]), dev_betas));      // k_fri_fold reads dev_betas when set
@@ -274,8 +274,8 @@ struct glp_fri {
         StageScope st(c, "fri.queries", 0.0);
         u64 *dev_idx, *dev_q;
         const size_t qsec = (size_t)nq * query_stride;
-        GLP_TRY(tmp.get(&dev_idx, (size_t)K * nq));
-        GLP_TRY(tmp.get(&dev_q, (size_t)K * qsec));
+        GLP_TRY(tmp.words(&dev_idx, (size_t)K * nq));
+        GLP_TRY(tmp.words(&dev_q, (size_t)K * qsec));
         GLP_TRY(h2d(c, dev_idx, indices, (size_t)K * nq * 8));
         size_t off = 0;
         for (const glp_batch *b : ob) GLP_TRY(queries_oracle(c, g, b, shared(b), dev_idx, dev_q, query_stride, qsec, off));
@@ -345,7 +345,7 @@ int pow_search_many(glp_ctx *c, int hasher, const u64 *states, const u64 *pendin
     for (u32 k = 0; k < K; k++)
         for (u32 i = 0; i < npending; i++) pst[(size_t)k * 12 + i] = pending[(size_t)k * npending + i];
     const std::vector<u32> ppos(K, npending);
-    Tmp tmp(c);
+    Scratch tmp(c);
     GLP_TRY(pow_search_batch(c, tmp, hasher, pst, ppos, bits, best));
     for (u32 k = 0; k < K; k++) {
         if (best[k] == ~0ull) return set_error(GLP_ERR_PROVE, "Proof of work failed. This is highly unlikely! (proof %u)", k);

@@ -1,7 +1,7 @@
 // fri_verify.inc -- glp_fri_verify*: plonky2 `fri/verifier.rs::verify_fri_proof` for any FriInstanceInfo the prover side (glp_fri_*,
 // fri_openings.inc) accepts, for K proofs of one instance in one launch.  Included by verifier.hip after glp_verify_batch, with which
 // it shares the query-round kernel (k_fri_verify_queries, verify_dev.h: glp_verify_batch runs it on the plonk instance) and what
-// surrounds its launch (verifier.hip: Scratch, Uploader, launch_queries, read_status, write_verdicts): per proof the canonical-form
+// surrounds its launch (common.h: Scratch; verifier.hip: Uploader, launch_queries, read_status, write_verdicts): per proof the canonical-form
 // scan and (one-call form) the transcript run on the context's host threads beside the upload of the proofs; every query round of
 // every proof is one launch.  The verifier holds no glp_batch, only caps: it has its own description (glp_fri_verify_desc) and shares
 // the shape rules with the prover through fri_shape.h.
@@ -209,10 +209,10 @@ int fri_verify_core(glp_ctx *c, const glp_fri_verify_desc *d, u32 K, const u64 *
     Scratch sc(c);
     u64 *dev_proofs = nullptr, *dev_hv = nullptr, *dev_open = nullptr;
     u32 *dev_status = nullptr;
-    GLP_TRY(sc.get(&dev_proofs, (size_t)K * p.total * 8));
-    GLP_TRY(sc.get(&dev_hv, hv.size() * 8));
-    GLP_TRY(sc.get(&dev_status, (size_t)K * nq * 4));
-    if (stepped) GLP_TRY(sc.get(&dev_open, (size_t)K * p.nopen * 16));
+    GLP_TRY(sc.words(&dev_proofs, (size_t)K * p.total));
+    GLP_TRY(sc.words(&dev_hv, hv.size()));
+    GLP_TRY(sc.array(&dev_status, (size_t)K * nq));
+    if (stepped) GLP_TRY(sc.words(&dev_open, (size_t)K * p.nopen * 2));
     // the proofs (and, stepped, the openings) go up on a thread of their own while the host half runs
     const size_t proof_bytes = (size_t)K * p.total * 8, open_bytes = (size_t)K * p.nopen * 16;
     Uploader up(c, [=] {

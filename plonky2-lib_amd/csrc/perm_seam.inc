@@ -142,15 +142,6 @@ int perm_challenges_check(const char *fn, const char *name, const u64 *v, u32 K,
                 (unsigned long long)v[bad == cnt ? 0 : bad]);
     return GLP_OK;
 }
-// host or device input -> a device pointer (a pool block filled from the host, or the caller's own)
-int perm_input(glp_ctx *c, Tmp &tmp, const u64 *in, int on_device, size_t words, const u64 **dev) {
-    if (on_device) { *dev = in; return GLP_OK; }
-    u64 *d;
-    GLP_TRY(tmp.get(&d, words));
-    GLP_HIP(hipMemcpyAsync(d, in, words * 8, hipMemcpyHostToDevice, c->stream));
-    *dev = d;
-    return GLP_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -173,21 +164,20 @@ int glp_perm_zs_commit(glp_ctx *c, const glp_perm_desc *desc, uint32_t num_proof
     GLP_REQUIRE(sigmas, "%s: sigmas is null", fn);
     const u32 K = num_proofs;
     GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
-    GLP_REQUIRE(rate_bits <= 4, "%s: rate_bits = %u outside 0..4", fn, rate_bits);
-    GLP_REQUIRE(cap_height <= s.lg + rate_bits, "%s: cap_height = %u should be at most log2(leaves) = %u", fn, cap_height, s.lg + rate_bits);
+    // an argument error here, as every refusal of this entry point (batch_shape_check's is GLP_ERR_UNSUPPORTED)
     GLP_REQUIRE(hasher == GLP_HASH_POSEIDON || hasher == GLP_HASH_KECCAK25, "%s: hasher = %u is not one of GLP_HASH_*", fn, hasher);
+    GLP_TRY(batch_shape_check(fn, K, s.nzp, s.lg, rate_bits, cap_height, hasher, BATCH_MAX_BYTES));
     GLP_TRY(perm_challenges_check(fn, "betas", betas, K, s.nch));
     GLP_TRY(perm_challenges_check(fn, "gammas", gammas, K, s.nch));
     const size_t n = (size_t)1 << s.lg;
-    GLP_REQUIRE((size_t)K * std::max<size_t>((size_t)s.nzp << rate_bits, s.nw) * n * 8 <= ((size_t)64 << 30),
-                "%s: batch too large (num_proofs * columns * 2^(log_n + rate_bits) words)", fn);
+    GLP_REQUIRE((size_t)K * s.nw <= BATCH_MAX_BYTES / (8 * n), "%s: wires too large (num_proofs * num_wires * 2^log_n words)", fn);
     GLP_TRY(bind(c));
     u64 sd[4];
     if (seed) for (int i = 0; i < 4; i++) sd[i] = canon(seed[i]);
-    Tmp tmp(c);
+    Scratch tmp(c);
     const u64 *dev_wires, *dev_sigmas;
-    GLP_TRY(perm_input(c, tmp, wires, wires_on_device, (size_t)K * s.nw * n, &dev_wires));
-    GLP_TRY(perm_input(c, tmp, sigmas, sigmas_on_device, (size_t)s.nr * n, &dev_sigmas));
+    GLP_TRY(tmp.input(wires, wires_on_device, (size_t)K * s.nw * n, &dev_wires));
+    GLP_TRY(tmp.input(sigmas, sigmas_on_device, (size_t)s.nr * n, &dev_sigmas));
     // one table: k_is [nr], then chal [K][2 MAXCH] (betas, gammas), the layout k_pp_rows reads
     std::vector<u64> tab((size_t)s.nr + (size_t)K * 2 * MAXCH, 0);
     memcpy(tab.data(), desc->k_is, (size_t)s.nr * 8);
@@ -197,11 +187,11 @@ int glp_perm_zs_commit(glp_ctx *c, const glp_perm_desc *desc, uint32_t num_proof
             tab[s.nr + (size_t)k * 2 * MAXCH + MAXCH + i] = gammas[(size_t)k * s.nch + i];
         }
     u64 *dev_tab, *zp, *dens, *tot;
-    GLP_TRY(tmp.get(&dev_tab, tab.size()));
+    GLP_TRY(tmp.words(&dev_tab, tab.size()));
     GLP_TRY(h2d(c, dev_tab, tab.data(), tab.size() * 8));
-    GLP_TRY(tmp.get(&zp, (size_t)K * s.nzp * n));
-    GLP_TRY(tmp.get(&dens, (size_t)K * s.nzp * n));
-    GLP_TRY(tmp.get(&tot, (size_t)K * s.nch * nblk(n)));
+    GLP_TRY(tmp.words(&zp, (size_t)K * s.nzp * n));
+    GLP_TRY(tmp.words(&dens, (size_t)K * s.nzp * n));
+    GLP_TRY(tmp.words(&tot, (size_t)K * s.nch * nblk(n)));
     {
         StageScope st(c, "perm.partial_products", 8.0 * n * K * (2.0 * s.nr + s.nzp));
         const PermGeo pg = {(int)s.lg, s.nw, s.nr, s.nch, s.npp, s.qdf, K};
@@ -248,7 +238,7 @@ int glp_perm_quotient_values(glp_ctx *c, const glp_perm_desc *desc, uint32_t num
     GLP_TRY(bind(c));
     const u32 nch = s.nch, S = 1u << sub_bits, nt = nch * (s.npp + 2) + 1;
     const size_t n = (size_t)1 << s.lg, N = n << rb, M = n << sub_bits, words = (size_t)K * nch * M;
-    Tmp tmp(c);
+    Scratch tmp(c);
     // one table: k_is [nr], then per proof betas[MAXCH], gammas[MAXCH], alpha powers [nch][nt]
     const u32 tab_stride = 2 * MAXCH + nch * nt;
     std::vector<u64> tab((size_t)s.nr + (size_t)K * tab_stride, 0);
@@ -263,13 +253,13 @@ int glp_perm_quotient_values(glp_ctx *c, const glp_perm_desc *desc, uint32_t num
         }
     }
     u64 *dev_tab, *l0t;
-    GLP_TRY(tmp.get(&dev_tab, tab.size()));
+    GLP_TRY(tmp.words(&dev_tab, tab.size()));
     GLP_TRY(h2d(c, dev_tab, tab.data(), tab.size() * 8));
-    GLP_TRY(tmp.get(&l0t, (size_t)S * n));
+    GLP_TRY(tmp.words(&l0t, (size_t)S * n));
     const u64 *dev_gs = nullptr;
-    if (gate_sums) GLP_TRY(perm_input(c, tmp, gate_sums, gate_sums_on_device, words, &dev_gs));
+    if (gate_sums) GLP_TRY(tmp.input(gate_sums, gate_sums_on_device, words, &dev_gs));
     u64 *dev_out = out;
-    if (!out_on_device) GLP_TRY(tmp.get(&dev_out, words));
+    if (!out_on_device) GLP_TRY(tmp.words(&dev_out, words));
 
     PQArgs a;
     memset(&a, 0, sizeof(a));

@@ -73,27 +73,15 @@ __device__ __forceinline__ u64 dpow(u64 b, u64 e) {
 
 // ------------------------------------------------------------------------------------------ host side
 namespace {
-struct Tmp {   // pool-backed scratch for one prove() call
-    glp_ctx *c;
-    std::vector<void *> ptrs;
-    explicit Tmp(glp_ctx *ctx) : c(ctx) {}
-    ~Tmp() { (void)hipStreamSynchronize(c->stream); for (void *p : ptrs) c->release(p); }
-    int get(u64 **p, size_t elems) {
-        void *v = nullptr;
-        int rc = c->alloc(&v, elems * sizeof(u64));
-        if (rc == GLP_OK) { ptrs.push_back(v); *p = (u64 *)v; }
-        return rc;
-    }
-};
 struct BatchHolder {
     glp_batch *b = nullptr;
     ~BatchHolder() { batch_destroy(b); }
 };
 inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
 // the batch proof-of-work search for PoseidonGoldilocksConfig (k_pow_prepare + k_pow_batch2); st / pos / best / next as for k_pow_batch
-int pow_batch_launch(glp_ctx *c, Tmp &tmp, const u64 *dev_pst, const u32 *dev_ppos, u32 bits, u64 *dev_best, u64 *dev_next, u32 K) {
+int pow_batch_launch(glp_ctx *c, Scratch &tmp, const u64 *dev_pst, const u32 *dev_ppos, u32 bits, u64 *dev_best, u64 *dev_next, u32 K) {
     u64 *dev_k;
-    GLP_TRY(tmp.get(&dev_k, (size_t)K * 12 + 1));              // + the ticket counter
+    GLP_TRY(tmp.words(&dev_k, (size_t)K * 12 + 1));              // + the ticket counter
     hipLaunchKernelGGL(k_pow_prepare, dim3((K + 63) / 64), dim3(64), 0, c->stream, dev_pst, dev_ppos, dev_k, K);
     GLP_HIP(hipGetLastError());
     constexpr u32 CHUNKS = 8;                                  // chunks of 256 candidates per non-persistent workgroup
@@ -103,16 +91,6 @@ int pow_batch_launch(glp_ctx *c, Tmp &tmp, const u64 *dev_pst, const u32 *dev_pp
     hipLaunchKernelGGL(k_pow_batch2, dim3(body + tail), dim3(256), 0, c->stream, dev_k, dev_ppos, bits,
                        (unsigned long long *)dev_best, (unsigned long long *)dev_next, K, CHUNKS, body);
     GLP_HIP(hipGetLastError());
-    return GLP_OK;
-}
-int d2h(glp_ctx *c, void *dst, const void *src, size_t bytes) {
-    GLP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));
-    return GLP_OK;
-}
-int h2d(glp_ctx *c, void *dst, const void *src, size_t bytes) {
-    GLP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    GLP_HIP(hipStreamSynchronize(c->stream));   // the source is usually a stack/vector temporary
     return GLP_OK;
 }
 int batch_cap_host(glp_ctx *c, const glp_batch *b, std::vector<u64> &cap) {
@@ -154,7 +132,7 @@ struct glp_session {
     const glp_circuit_desc &d;
     const Layout &L;
     const ProveGeo g;                  // K = 1
-    Tmp tmp;
+    Scratch tmp;
     u64 *owned_wires = nullptr;        // device copy made by begin() when the caller passed host memory
     const u64 *dev_wires = nullptr;
     u64 pih[4] = {0, 0, 0, 0};
@@ -201,9 +179,9 @@ struct glp_session {
         GLP_REQUIRE(stage == S_WIRES, "partial_products: call after begin");
         for (u32 i = 0; i < g.nch; i++) { betas[i] = betas_in[i]; gammas[i] = gammas_in[i]; }
         u64 *zp, *dens, *tot;
-        GLP_TRY(tmp.get(&zp, (size_t)g.nzp * g.n));
-        GLP_TRY(tmp.get(&dens, (size_t)g.nzp * g.n));
-        GLP_TRY(tmp.get(&tot, (size_t)g.nch * nblk(g.n)));
+        GLP_TRY(tmp.words(&zp, (size_t)g.nzp * g.n));
+        GLP_TRY(tmp.words(&dens, (size_t)g.nzp * g.n));
+        GLP_TRY(tmp.words(&tot, (size_t)g.nch * nblk(g.n)));
         {
             StageScope st(c, "partial_products", 8.0 * g.n * (2.0 * g.nr + g.nzp));
             GLP_TRY(stage_partial_products(c, g, dev_wires, betas, gammas, nullptr, zp, dens, tot));
@@ -220,11 +198,11 @@ struct glp_session {
         std::vector<u64> apow((1 + APL_WORDS) * apn);
         alpha_power_table(alphas, nch, g.nterms, apow.data(), apow.data() + apn);
         u64 *dev_apow, *qv, *qV, *qc;
-        GLP_TRY(tmp.get(&dev_apow, apow.size()));
+        GLP_TRY(tmp.words(&dev_apow, apow.size()));
         GLP_TRY(h2d(c, dev_apow, apow.data(), apow.size() * 8));
-        GLP_TRY(tmp.get(&qv, qlen));
-        GLP_TRY(tmp.get(&qV, qlen));
-        GLP_TRY(tmp.get(&qc, qlen));
+        GLP_TRY(tmp.words(&qv, qlen));
+        GLP_TRY(tmp.words(&qV, qlen));
+        GLP_TRY(tmp.words(&qc, qlen));
         QProof qp;
         QBatch qbt;
         quotient_proof_args(g, wb.b, zb.b, qv, dev_apow, nullptr, qp, qbt);      // pp == nullptr: one proof, described by qp
@@ -233,7 +211,7 @@ struct glp_session {
         {
             StageScope st(c, "quotient_eval", 8.0 * g.n * g.Rq * (g.nc + g.nr + g.nw + g.nzp + 2.0 * nch));
             u64 *l0t;
-            GLP_TRY(tmp.get(&l0t, (size_t)g.Rq * g.n));
+            GLP_TRY(tmp.words(&l0t, (size_t)g.Rq * g.n));
             GLP_TRY(stage_quotient_eval(c, g, qp, qbt, l0t));
         }
         {
@@ -260,8 +238,8 @@ struct glp_session {
         u64 *zt, *partial;
         size_t poff[6];
         open_offsets(g, ob, poff);
-        GLP_TRY(tmp.get(&zt, 2 * g.n));
-        GLP_TRY(tmp.get(&partial, poff[5]));
+        GLP_TRY(tmp.words(&zt, 2 * g.n));
+        GLP_TRY(tmp.words(&partial, poff[5]));
         const ext2 points[2] = {zeta, zeta_next};
         GLP_TRY(stage_open(c, g, ob, points, nullptr, zt, partial, poff));
         std::vector<u64> hp(poff[5]);
@@ -274,15 +252,15 @@ struct glp_session {
     int fri_combine(ext2 alpha) {
         GLP_REQUIRE(stage == S_OPEN, "fri_combine: call after open");
         u64 *fcoef, *dev_ap, *fv;
-        GLP_TRY(tmp.get(&fcoef, 2 * g.n));
+        GLP_TRY(tmp.words(&fcoef, 2 * g.n));
         {
             StageScope st(c, "fri_combine", 8.0 * g.n * (L.oracle_cols[0] + L.oracle_cols[1] + L.oracle_cols[2] + L.oracle_cols[3]));
             std::vector<u64> ap(2 * oracle_cols(ob));
             ext2 pt[5];
             fri_alpha_powers(g, ob, open, zs_next, alpha, zeta, zeta_next, ap.data(), pt);
-            GLP_TRY(tmp.get(&dev_ap, ap.size()));
+            GLP_TRY(tmp.words(&dev_ap, ap.size()));
             GLP_TRY(h2d(c, dev_ap, ap.data(), ap.size() * 8));
-            GLP_TRY(tmp.get(&fv, 2 * g.n));
+            GLP_TRY(tmp.words(&fv, 2 * g.n));
             GLP_TRY(stage_fri_values(c, g, ob, dev_ap, pt, nullptr, fv, fcoef));
         }
         fri.start(fcoef, g.lg);
@@ -335,8 +313,8 @@ struct glp_session {
         // every gather writes straight into a device image of the proof's query section; one copy brings it back
         u64 *dev_idx, *dev_q;
         const size_t qsec = (size_t)nq * L.query_stride;
-        GLP_TRY(tmp.get(&dev_idx, nq));
-        GLP_TRY(tmp.get(&dev_q, qsec));
+        GLP_TRY(tmp.words(&dev_idx, nq));
+        GLP_TRY(tmp.words(&dev_q, qsec));
         GLP_TRY(h2d(c, dev_idx, xi.data(), nq * 8));
         GLP_TRY(stage_queries(c, g, ob, fri.layers, dev_idx, dev_q, L.query_stride, qsec));
         GLP_TRY(d2h(c, proof() + L.queries, dev_q, qsec * 8));
@@ -354,9 +332,9 @@ static int pow_search(glp_ctx *c, const u64 st[12], const u64 *pending, u32 npen
     memcpy(a.st, st, 96);
     for (u32 i = 0; i < npending; i++) a.st[i] = pending[i];
     a.pos = npending; a.bits = bits;
-    Tmp tmp(c);
+    Scratch tmp(c);
     u64 *best;
-    GLP_TRY(tmp.get(&best, 1));
+    GLP_TRY(tmp.words(&best, 1));
     a.best = (unsigned long long *)best;
     const u64 none = ~0ull;
     u64 found = none;
@@ -547,12 +525,10 @@ int glp_prove(glp_ctx *c, const glp_circuit *cc, const uint64_t *wires, const ui
     GLP_REQUIRE(public_inputs || cc->d.num_public_inputs == 0, "public_inputs is null");
     GLP_TRY(bind(c));
     const size_t tot = (size_t)cc->d.num_wires << cc->d.degree_bits;
-    void *dv = nullptr;
-    GLP_TRY(c->alloc(&dv, tot * 8));
-    const int rc = prove_impl(c, cc, (const u64 *)dv, public_inputs, proof_out, wires);
-    (void)hipStreamSynchronize(c->stream);
-    c->release(dv);
-    return rc;
+    Scratch sc(c);
+    u64 *dv;                  // filled by the wires commitment's own chunked upload (batch_build, host_src)
+    GLP_TRY(sc.words(&dv, tot));
+    return prove_impl(c, cc, dv, public_inputs, proof_out, wires);
 }
 
 // ---- staged witnesses (include/glp.h "witnesses that start in host memory, pipelined")

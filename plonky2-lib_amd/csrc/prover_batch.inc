@@ -24,14 +24,14 @@ int caps_to_host(glp_ctx *c, const u64 *dev_digests, size_t dig_stride_words, si
 
 // K10 for K sponges at once: pst [K][12] (the pending inputs already in place), ppos [K] where the witness goes -> best [K], the smallest
 // witness of each (~0: none below 2^40).  One launch (Poseidon: k_pow_prepare + k_pow_batch2), one copy back.
-int pow_search_batch(glp_ctx *c, Tmp &tmp, int hasher, const std::vector<u64> &pst, const std::vector<u32> &ppos, u32 bits, std::vector<u64> &best) {
+int pow_search_batch(glp_ctx *c, Scratch &tmp, int hasher, const std::vector<u64> &pst, const std::vector<u32> &ppos, u32 bits, std::vector<u64> &best) {
     const u32 K = (u32)ppos.size();
     u64 *dev_pst, *dev_best, *dev_ppos, *dev_next;
-    GLP_TRY(tmp.get(&dev_pst, pst.size()));
-    GLP_TRY(tmp.get(&dev_best, K));
-    GLP_TRY(tmp.get(&dev_next, K));
+    GLP_TRY(tmp.words(&dev_pst, pst.size()));
+    GLP_TRY(tmp.words(&dev_best, K));
+    GLP_TRY(tmp.words(&dev_next, K));
     GLP_HIP(hipMemsetAsync(dev_next, 0, (size_t)K * 8, c->stream));
-    GLP_TRY(tmp.get(&dev_ppos, (K + 1) / 2));
+    GLP_TRY(tmp.words(&dev_ppos, (K + 1) / 2));
     GLP_TRY(h2d(c, dev_pst, pst.data(), pst.size() * 8));
     GLP_TRY(h2d(c, dev_ppos, ppos.data(), (size_t)K * 4));
     best.assign(K, ~0ull);
@@ -57,7 +57,7 @@ int prove_batch_impl(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *dev_wi
     const u32 nred = d.num_reductions, nq = d.num_query_rounds;
     HostPool &pool = ctx_host_pool(c);       // persistent: thread start-up costs more than a small batch
     BatchTrace mark(c, K, "");
-    Tmp tmp(c);
+    Scratch tmp(c);
     auto P = [&](u32 k) { return proofs_out + (size_t)k * L.total; };      // every word of the layout is written below
     std::vector<Challenger> ch(K, Challenger(hasher));
     std::vector<u64> pih((size_t)K * 4, 0), caps;
@@ -89,11 +89,11 @@ int prove_batch_impl(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *dev_wi
     mark("transcript 1 (host)");
     // ---- partial products + Z, commitment
     u64 *dev_chal, *zp, *dens, *tot;
-    GLP_TRY(tmp.get(&dev_chal, chal.size()));
+    GLP_TRY(tmp.words(&dev_chal, chal.size()));
     GLP_TRY(h2d(c, dev_chal, chal.data(), chal.size() * 8));
-    GLP_TRY(tmp.get(&zp, (size_t)K * nzp * n));
-    GLP_TRY(tmp.get(&dens, (size_t)K * nzp * n));
-    GLP_TRY(tmp.get(&tot, (size_t)K * nch * nblk(n)));
+    GLP_TRY(tmp.words(&zp, (size_t)K * nzp * n));
+    GLP_TRY(tmp.words(&dens, (size_t)K * nzp * n));
+    GLP_TRY(tmp.words(&tot, (size_t)K * nch * nblk(n)));
     GLP_TRY(stage_partial_products(c, g, dev_wires, nullptr, nullptr, dev_chal, zp, dens, tot));
     GLP_TRY(batch_build(c, zp, BATCH_VALUES, nzp, lg, rb, (int)d.cap_height, &zb.b, nullptr, K, hasher, salt, GLP_SALT_TAG_ZS));
     GLP_TRY(caps_to_host(c, zb.b->digests, ndig * 4, cap_off, capn, K, caps));
@@ -113,15 +113,15 @@ int prove_batch_impl(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *dev_wi
     });
     mark("transcript 2 + alpha powers (host)");
     u64 *dev_apow, *dev_qpp, *qv, *qV, *qc, *l0t;
-    GLP_TRY(tmp.get(&dev_apow, apow.size()));
+    GLP_TRY(tmp.words(&dev_apow, apow.size()));
     GLP_TRY(h2d(c, dev_apow, apow.data(), apow.size() * 8));
-    GLP_TRY(tmp.get(&dev_qpp, qpp.size()));
+    GLP_TRY(tmp.words(&dev_qpp, qpp.size()));
     GLP_TRY(h2d(c, dev_qpp, qpp.data(), qpp.size() * 8));
     const size_t qstride = (size_t)nch * g.Rq * n;
-    GLP_TRY(tmp.get(&qv, (size_t)K * qstride));
-    GLP_TRY(tmp.get(&qV, (size_t)K * qstride));
-    GLP_TRY(tmp.get(&qc, (size_t)K * qstride));
-    GLP_TRY(tmp.get(&l0t, (size_t)g.Rq * n));
+    GLP_TRY(tmp.words(&qv, (size_t)K * qstride));
+    GLP_TRY(tmp.words(&qV, (size_t)K * qstride));
+    GLP_TRY(tmp.words(&qc, (size_t)K * qstride));
+    GLP_TRY(tmp.words(&l0t, (size_t)g.Rq * n));
     {
         QProof qp;
         QBatch qbt;
@@ -151,12 +151,12 @@ int prove_batch_impl(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *dev_wi
     mark("transcript 3 (host)");
     const glp_batch *ob[4] = {cc->cs, wb.b, zb.b, qb.b};
     u64 *dev_zetas, *zt, *partial;
-    GLP_TRY(tmp.get(&dev_zetas, zetas.size()));
+    GLP_TRY(tmp.words(&dev_zetas, zetas.size()));
     GLP_TRY(h2d(c, dev_zetas, zetas.data(), zetas.size() * 8));
-    GLP_TRY(tmp.get(&zt, (size_t)K * 2 * n));
+    GLP_TRY(tmp.words(&zt, (size_t)K * 2 * n));
     size_t poff[6];                                     // per proof, in partial-sum words
     open_offsets(g, ob, poff);
-    GLP_TRY(tmp.get(&partial, (size_t)K * poff[5]));
+    GLP_TRY(tmp.words(&partial, (size_t)K * poff[5]));
     GLP_TRY(stage_open(c, g, ob, nullptr, dev_zetas, zt, partial, poff));
     std::vector<u64> hp((size_t)K * poff[5]);
     GLP_TRY(d2h(c, hp.data(), partial, hp.size() * 8));
@@ -178,17 +178,17 @@ int prove_batch_impl(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *dev_wi
     mark("transcript 4 + fri alpha powers (host)");
     // ---- FRI: batch polynomial, commit phase
     u64 *dev_fap, *dev_fpp, *fv, *fcoef;
-    GLP_TRY(tmp.get(&dev_fap, fap.size()));
+    GLP_TRY(tmp.words(&dev_fap, fap.size()));
     GLP_TRY(h2d(c, dev_fap, fap.data(), fap.size() * 8));
-    GLP_TRY(tmp.get(&dev_fpp, fpp.size()));
+    GLP_TRY(tmp.words(&dev_fpp, fpp.size()));
     GLP_TRY(h2d(c, dev_fpp, fpp.data(), fpp.size() * 8));
-    GLP_TRY(tmp.get(&fv, (size_t)K * 2 * n));
-    GLP_TRY(tmp.get(&fcoef, (size_t)K * 2 * n));
+    GLP_TRY(tmp.words(&fv, (size_t)K * 2 * n));
+    GLP_TRY(tmp.words(&fcoef, (size_t)K * 2 * n));
     GLP_TRY(stage_fri_values(c, g, ob, dev_fap, nullptr, dev_fpp, fv, fcoef));
     FriState fri;
     fri.start(fcoef, lg);
     u64 *dev_betas;
-    GLP_TRY(tmp.get(&dev_betas, (size_t)K * 2));
+    GLP_TRY(tmp.words(&dev_betas, (size_t)K * 2));
     std::vector<u64> betas_h((size_t)K * 2);
     for (u32 r = 0; r < nred; r++) {
         GLP_TRY(stage_fri_commit(c, g, tmp, fri));
@@ -249,8 +249,8 @@ int prove_batch_impl(glp_ctx *c, const glp_circuit *cc, u32 K, const u64 *dev_wi
     // ---- query phase: every gather writes into a device image of the K query sections
     u64 *dev_idx, *dev_q;
     const size_t stride = L.query_stride, qsec = (size_t)nq * stride;
-    GLP_TRY(tmp.get(&dev_idx, xi.size()));
-    GLP_TRY(tmp.get(&dev_q, (size_t)K * qsec));
+    GLP_TRY(tmp.words(&dev_idx, xi.size()));
+    GLP_TRY(tmp.words(&dev_q, (size_t)K * qsec));
     GLP_TRY(h2d(c, dev_idx, xi.data(), xi.size() * 8));
     GLP_TRY(stage_queries(c, g, ob, fri.layers, dev_idx, dev_q, stride, qsec));
     // one strided copy puts every proof's query section in its place

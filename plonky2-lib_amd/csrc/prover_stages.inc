@@ -304,15 +304,15 @@ struct FriState {
     void start(u64 *fcoef, int lg) { cur = fcoef; lgcur = lg; shift = GEN; }
 };
 // first half: LDE of the current polynomial on its coset, Merkle tree over the leaves (buffers from tmp); the new layer is f.layers.back()
-int stage_fri_commit(glp_ctx *c, const ProveGeo &g, Tmp &tmp, FriState &f) {
+int stage_fri_commit(glp_ctx *c, const ProveGeo &g, Scratch &tmp, FriState &f) {
     const u32 K = g.K, rb = (u32)g.rb;
     FriLayer ly;
     ly.ab = g.arity_bits[f.layers.size()]; ly.lgL = (u32)(f.lgcur + g.rb);
     const u32 ab = ly.ab, lgL = ly.lgL;
     const size_t Lsz = (size_t)1 << lgL, nleaves = Lsz >> ab;
     ly.ndig = merkle_num_digests(nleaves, g.cap_height);
-    GLP_TRY(tmp.get(&ly.vals, (size_t)K * 2 * Lsz));
-    GLP_TRY(tmp.get(&ly.dig, (size_t)K * ly.ndig * 4));
+    GLP_TRY(tmp.words(&ly.vals, (size_t)K * 2 * Lsz));
+    GLP_TRY(tmp.words(&ly.dig, (size_t)K * ly.ndig * 4));
     GLP_TRY(lde_coeffs(c, f.cur, ly.vals, 2 * K, f.lgcur, g.rb, f.shift));
     if (g.hasher == GLP_HASH_KECCAK25)
         hipLaunchKernelGGL(k_fri_leaf_hash_keccak, dim3(nblk(nleaves), K), dim3(256), 0, c->stream, ly.vals, ly.dig, lgL, rb, ab, 2 * Lsz, ly.ndig * 4);
@@ -333,11 +333,11 @@ inline const u64 *fri_layer_cap(const ProveGeo &g, const FriLayer &ly) {
     return ly.dig + 4 * merkle_cap_offset(((size_t)1 << ly.lgL) >> ly.ab, g.cap_height);
 }
 // second half: fold the coefficients (arity 2^ab of the last layer), shift <- shift^arity.  dev_betas == nullptr: one proof, beta by value
-int stage_fri_fold(glp_ctx *c, const ProveGeo &g, Tmp &tmp, FriState &f, ext2 beta, const u64 *dev_betas) {
+int stage_fri_fold(glp_ctx *c, const ProveGeo &g, Scratch &tmp, FriState &f, ext2 beta, const u64 *dev_betas) {
     const u32 ab = f.layers.back().ab;
     const size_t nnew = ((size_t)1 << f.lgcur) >> ab;
     u64 *nxt;
-    GLP_TRY(tmp.get(&nxt, (size_t)g.K * 2 * nnew));
+    GLP_TRY(tmp.words(&nxt, (size_t)g.K * 2 * nnew));
     hipLaunchKernelGGL(k_fri_fold, dim3(nblk(nnew), g.K), dim3(256), 0, c->stream, f.cur, nxt, beta, (u32)f.lgcur, ab, dev_betas);
     GLP_HIP(hipGetLastError());
     f.cur = nxt; f.lgcur -= (int)ab;

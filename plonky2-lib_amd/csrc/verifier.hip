@@ -651,15 +651,6 @@ int verify_impl(const glp_circuit *cc, const u64 *proof) {
 //
 // What surrounds that launch is the same for glp_verify_batch and glp_fri_verify* (fri_verify.inc) and stands here once.
 namespace {
-// device buffers of one call: released, once the stream has drained, however the call returns
-struct Scratch {
-    glp_ctx *c;
-    std::vector<void *> p;
-    explicit Scratch(glp_ctx *ctx) : c(ctx) {}
-    Scratch(const Scratch &) = delete;
-    ~Scratch() { (void)hipStreamSynchronize(c->stream); for (void *q : p) c->release(q); }
-    template <class T> int get(T **ptr, size_t bytes) { int r = c->alloc((void **)ptr, bytes); if (r == GLP_OK) p.push_back(*ptr); return r; }
-};
 // The proofs go up (pageable host memory: the copy blocks its caller) on a thread of their own while the host half runs.  done() joins
 // it; so does the destructor, when the call returns early or a host task throws.  Declared after the Scratch whose buffers it fills.
 struct Uploader {
@@ -729,9 +720,9 @@ extern "C" int glp_verify_batch(glp_ctx *c, const glp_circuit *cc, uint32_t K, c
     Scratch sc(c);
     u64 *dev_proofs = nullptr, *dev_hv = nullptr;
     u32 *dev_status = nullptr;
-    GLP_TRY(sc.get(&dev_proofs, proof_bytes));
-    GLP_TRY(sc.get(&dev_hv, hv.size() * 8));
-    GLP_TRY(sc.get(&dev_status, (size_t)K * nq * 4));
+    GLP_TRY(sc.words(&dev_proofs, (size_t)K * L.total));
+    GLP_TRY(sc.words(&dev_hv, hv.size()));
+    GLP_TRY(sc.array(&dev_status, (size_t)K * nq));
     const bool trace = getenv("GLP_BATCH_TRACE") != nullptr;
     const auto t_start = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); };
@@ -778,17 +769,17 @@ extern "C" int glp_verify_batch(glp_ctx *c, const glp_circuit *cc, uint32_t K, c
         t_up = since();
         const u32 total_cols = L.oracle_cols[0] + L.oracle_cols[1] + L.oracle_cols[2] + L.oracle_cols[3];
         u64 *dch, *dev_apl, *dev_fap, *dev_fpp, *dev_betas, *dev_idx;
-        GLP_TRY(sc.get(&dch, (size_t)K * DCH_WORDS * 8));
+        GLP_TRY(sc.words(&dch, (size_t)K * DCH_WORDS));
         // betas | gammas, public-input hash, alpha powers, zetas, error bits: one block, one copy back
         const size_t w_chal = (size_t)K * 2 * MAXCH, w_qpp = (size_t)K * 3 * MAXCH, w_apow = (size_t)K * nch * 2, w_zetas = (size_t)K * 4, w_err = (K + 1) / 2;
         u64 *dev_back;
-        GLP_TRY(sc.get(&dev_back, (w_chal + w_qpp + w_apow + w_zetas + w_err) * 8));
+        GLP_TRY(sc.words(&dev_back, w_chal + w_qpp + w_apow + w_zetas + w_err));
         dev_chal = dev_back; dev_qpp = dev_chal + w_chal; dev_apow = dev_qpp + w_qpp; dev_zetas = dev_apow + w_apow; dev_err = (u32 *)(dev_zetas + w_zetas);
-        GLP_TRY(sc.get(&dev_apl, (size_t)K * nch * 2 * APL_WORDS * 8));
-        GLP_TRY(sc.get(&dev_fap, (size_t)K * 2 * total_cols * 8));
-        GLP_TRY(sc.get(&dev_fpp, (size_t)K * 10 * 8));
-        GLP_TRY(sc.get(&dev_betas, (size_t)std::max<u32>(nred, 1) * K * 2 * 8));
-        GLP_TRY(sc.get(&dev_idx, (size_t)K * nq * 8));
+        GLP_TRY(sc.words(&dev_apl, (size_t)K * nch * 2 * APL_WORDS));
+        GLP_TRY(sc.words(&dev_fap, (size_t)K * 2 * total_cols));
+        GLP_TRY(sc.words(&dev_fpp, (size_t)K * 10));
+        GLP_TRY(sc.words(&dev_betas, (size_t)std::max<u32>(nred, 1) * K * 2));
+        GLP_TRY(sc.words(&dev_idx, (size_t)K * nq));
         GLP_HIP(hipMemsetAsync(dev_back, 0, (w_chal + w_qpp + w_apow + w_zetas + w_err) * 8, c->stream));
         TrGeo g;
         g.dch = dch; g.image = dev_proofs; g.total = L.total; g.K = K; g.capn = capn; g.nch = nch;
