@@ -283,6 +283,88 @@ GLP_API int glp_perm_quotient_values(glp_ctx *ctx, const glp_perm_desc *desc, ui
                                      const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
                                      const uint64_t *gate_sums, int gate_sums_on_device, uint64_t *out, int out_on_device);
 
+/* ---- caller-defined gate constraints at the commitment seam: gate programs --------------------------------------------------------
+ * The one step of `prove_with_partition_witness` the blocks above leave to the caller is the gate share of the vanishing polynomial,
+ * glp_perm_quotient_values' gate_sums.  A gate program states it as a straight-line register machine over F_p (no branches, no loops)
+ * that the library runs on every point x_i = g W_M^i of the quotient's coset, so the trace never leaves HBM.  The interpreter knows
+ * nothing about selectors or gate types: a plonky2 selector filter is ordinary SUB / MUL instructions ending in END, an AIR is one
+ * gate closed by END IMM(1).
+ *
+ * One instruction is one 64-bit word (bit 63 is zero):
+ *     bits  3..0   opcode GLP_GP_OP_*          bits  8..4   dst register (ADD, SUB, MUL, MOV; else 0)
+ *     bits 35..9   operand a                   bits 62..36  operand b (ADD, SUB, MUL; else 0)
+ * An operand is 27 bits: kind GLP_GP_* in its bits 2..0, a payload in its bits 26..3:
+ *     GLP_GP_REG       register r < num_regs (it must have been written by an earlier instruction)
+ *     GLP_GP_COL       polynomial c (payload bits 21..0) of oracle o (payload bits 23..22) at x_i
+ *     GLP_GP_COL_NEXT  the same polynomial at w_n x_i: natural row (i + S) mod M, S = 2^sub_bits (AIR transition constraints)
+ *     GLP_GP_IMM       word j of the constant pool (canonical, shared by all proofs)
+ *     GLP_GP_PARAM     word j of params[proof][num_params] (per-proof values such as the public-input hash)
+ *     GLP_GP_X         x_i itself (payload 0)
+ * Operations, every result canonical:
+ *     ADD / SUB / MUL dst, a, b     field operations          MOV dst, a
+ *     EMIT a    constraint t of the current gate: acc_c += a * alpha_c^t for every challenge c, then t += 1
+ *     END a     closes the gate with filter value a: total_c += reduce(acc_c) * a, acc_c = 0, t = 0
+ * and the result for proof k, challenge c, point i is total_c = sum_gates filter_g sum_t alpha_{k,c}^t v_{g,t}(x_i). */
+#define GLP_GP_MAX_REGS 24u
+#define GLP_GP_MAX_INSTRUCTIONS 65536u
+#define GLP_GP_MAX_CONSTRAINTS 4096u   /* EMITs between two ENDs */
+#define GLP_GP_MAX_ORACLES 4u
+#define GLP_GP_OP_ADD 1u
+#define GLP_GP_OP_SUB 2u
+#define GLP_GP_OP_MUL 3u
+#define GLP_GP_OP_MOV 4u
+#define GLP_GP_OP_EMIT 5u
+#define GLP_GP_OP_END 6u
+#define GLP_GP_REG 0u
+#define GLP_GP_COL 1u
+#define GLP_GP_COL_NEXT 2u
+#define GLP_GP_IMM 3u
+#define GLP_GP_PARAM 4u
+#define GLP_GP_X 5u
+#define GLP_GP_DST_SHIFT 4
+#define GLP_GP_A_SHIFT 9
+#define GLP_GP_B_SHIFT 36
+#define GLP_GP_OPERAND_BITS 27
+#define GLP_GP_COL_ORACLE_SHIFT 22     /* inside the payload of GLP_GP_COL / GLP_GP_COL_NEXT */
+#define GLP_GP_OPERAND(kind, payload) ((uint64_t)(kind) | ((uint64_t)(payload) << 3))
+#define GLP_GP_COL_PAYLOAD(oracle, col) (((uint64_t)(oracle) << GLP_GP_COL_ORACLE_SHIFT) | (uint64_t)(col))
+#define GLP_GP_INSTR(op, dst, a, b) \
+    ((uint64_t)(op) | ((uint64_t)(dst) << GLP_GP_DST_SHIFT) | ((uint64_t)(a) << GLP_GP_A_SHIFT) | ((uint64_t)(b) << GLP_GP_B_SHIFT))
+
+typedef struct glp_gate_program glp_gate_program;
+typedef struct {
+    const uint64_t *code;  uint32_t num_instructions;   /* 1..GLP_GP_MAX_INSTRUCTIONS, the last one END */
+    const uint64_t *pool;  uint32_t num_pool;           /* canonical words; NULL with num_pool == 0 */
+    uint32_t num_regs, num_params, num_oracles;         /* 1..GLP_GP_MAX_REGS; any; 1..GLP_GP_MAX_ORACLES */
+    const uint32_t *oracle_cols;      /* [num_oracles]: polynomials the program may read of each */
+} glp_gate_program_desc;
+/* Host only, no context: GLP_OK and the largest number of EMITs in any one gate (the length of the alpha-power table), or
+ * GLP_ERR_ARG with a message "instruction <index>, field <op | dst | a | b>: ..." for an unknown opcode or operand kind, a set bit
+ * the opcode does not use, a register index >= num_regs, a register read before it is written, a pool, param or oracle index out of
+ * range, a column index >= oracle_cols[o], more than GLP_GP_MAX_CONSTRAINTS EMITs in one gate, a last instruction that is not END;
+ * and naming the description's field for a non-canonical pool word, num_regs of 0 or above GLP_GP_MAX_REGS, num_oracles outside
+ * 1..GLP_GP_MAX_ORACLES, an empty program or one of more than GLP_GP_MAX_INSTRUCTIONS instructions. */
+GLP_API int  glp_gate_program_check(const glp_gate_program_desc *d, uint32_t *max_constraints_out);
+/* Checks the program as above and keeps a copy of it in HBM; the description's arrays may be freed afterwards. */
+GLP_API int  glp_gate_program_create(glp_ctx *ctx, const glp_gate_program_desc *d, glp_gate_program **out);
+GLP_API void glp_gate_program_free(glp_gate_program *p);
+/* Runs the program on the coset g <W_M>, M = 2^(log_n + sub_bits), of num_proofs proofs (1..4096) in one launch.
+ *   oracles   [num_oracles] committed batches of one log_n, rate_bits and ctx, oracle o with at least oracle_cols[o] polynomials and
+ *             num_proofs members, or 1 member shared by all proofs.  Salted or not, each; salts are never read.
+ *   alphas    [num_proofs][num_challenges], canonical, num_challenges in 1..4
+ *   params    [num_proofs][num_params], canonical; NULL only with num_params == 0
+ *   out       [num_proofs][num_challenges][M], natural order on g <W_M>: the layout and coset of glp_perm_quotient_values' gate_sums,
+ *             so an HBM out (out_on_device != 0) is passed straight on with gate_sums_on_device = 1.  With host memory the call
+ *             returns after the copy.
+ * Refused beyond the common rules: sub_bits > rate_bits; oracles that disagree in log_n, rate_bits or ctx; an oracle with fewer
+ * polynomials than oracle_cols[o]; a member count that is neither num_proofs nor 1; num_challenges outside 1..4; a non-canonical alpha
+ * or param; params == NULL with num_params > 0.  Every refusal is GLP_ERR_ARG, names the field and happens before any launch. */
+GLP_API int  glp_gate_program_sums(glp_ctx *ctx, const glp_gate_program *p, uint32_t num_proofs,
+                                   const glp_batch *const *oracles, uint32_t sub_bits, uint32_t num_challenges,
+                                   const uint64_t *alphas /* [num_proofs][num_challenges] */,
+                                   const uint64_t *params /* [num_proofs][num_params] or NULL */,
+                                   uint64_t *out, int out_on_device);
+
 /* ---- openings and FRI of caller-held batches (fri/oracle.rs `PolynomialBatch::prove_openings`) ----------------------------------
  * For an integrator that keeps its own quotient (circuits with lookup tables, Poseidon2Gate, custom gates, starky AIRs: anything
  * glp_circuit_create answers with GLP_ERR_UNSUPPORTED): commit with glp_batch_from_values / _from_coeffs, evaluate the committed

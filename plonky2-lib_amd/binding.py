@@ -72,6 +72,11 @@ class _PermDesc(C.Structure):
                 ("chunk_size", C.c_uint32), ("k_is", C.c_void_p)]
 
 
+class _GateProgramDesc(C.Structure):
+    _fields_ = [("code", C.c_void_p), ("num_instructions", C.c_uint32), ("pool", C.c_void_p), ("num_pool", C.c_uint32), ("num_regs", C.c_uint32),
+                ("num_params", C.c_uint32), ("num_oracles", C.c_uint32), ("oracle_cols", C.c_void_p)]
+
+
 LDE_ROW_MAJOR, LDE_COL_MAJOR = 0, 1      # GLP_LDE_* of glp_batch_lde_values
 
 
@@ -193,6 +198,10 @@ def load_library():
         "glp_batch_from_coset_values": [vp, vp, C.c_int, u32, u32, u32, u32, u32, u32, u32, vp, C.POINTER(vp)],
         "glp_perm_zs_commit": [vp, C.POINTER(_PermDesc), u32, vp, C.c_int, vp, C.c_int, vp, vp, u32, u32, u32, vp, C.POINTER(vp)],
         "glp_perm_quotient_values": [vp, C.POINTER(_PermDesc), u32, vp, u32, vp, vp, u32, vp, vp, vp, vp, C.c_int, vp, C.c_int],
+        "glp_gate_program_check": [C.POINTER(_GateProgramDesc), C.POINTER(u32)],
+        "glp_gate_program_create": [vp, C.POINTER(_GateProgramDesc), C.POINTER(vp)],
+        "glp_gate_program_free": [vp],
+        "glp_gate_program_sums": [vp, vp, u32, C.POINTER(vp), u32, u32, vp, vp, vp, C.c_int],
         "glp_fri_begin_many": [vp, C.POINTER(_FriDesc), u32, vp, C.POINTER(vp)],
         "glp_fri_queries_many": [vp, vp, vp],
         "glp_pow_search_many": [vp, u32, u32, vp, vp, u32, u32, vp],
@@ -244,6 +253,7 @@ def load_library():
     L.glp_session_end.restype = None
     L.glp_circuit_file_close.restype = None
     L.glp_witness_free.restype = None
+    L.glp_gate_program_free.restype = None
     _lib = L
     return L
 
@@ -500,6 +510,14 @@ class Context:
                                                      C.c_void_p(out_dev_ptr) if out is None else _p(out), 0 if out is not None else 1))
         return out
 
+    def gate_program(self, prog):
+        """glp_gate_program_create: prog is what gate_program.Assembler.assemble() returns (or anything gate_program_desc() takes).
+        Returns the GateProgram, resident in HBM until free()."""
+        d, keep = gate_program_desc(prog)
+        h = C.c_void_p()
+        _chk(load_library().glp_gate_program_create(self._h, C.byref(d), C.byref(h)))
+        return GateProgram(self, h, int(d.num_params), int(d.num_oracles))
+
     def pow_search_many(self, hasher, sponge_states, pending_inputs, bits):
         """glp_pow_search_many: sponge_states [K][12], pending_inputs [K][num_pending] (num_pending < 8) -> the K smallest witnesses"""
         st = _a(sponge_states).reshape(-1, 12)
@@ -667,6 +685,65 @@ class Batch:
         out = np.empty((n, 4), np.uint64)
         _chk(load_library().glp_batch_digests(self._h, _p(out)))
         return out
+
+
+def gate_program_desc(prog, **fields):
+    """attribute bag (code, pool, num_regs, num_params, oracle_cols: a gate_program.Program) -> (glp_gate_program_desc, the arrays that
+    must stay alive while it is used).  fields: struct fields set afterwards, for descriptions the library is meant to refuse."""
+    code, pool, cols = _a(prog.code), _a(prog.pool), np.ascontiguousarray(prog.oracle_cols, np.uint32)
+    d = _GateProgramDesc(code.ctypes.data if code.size else None, code.size, pool.ctypes.data if pool.size else None, pool.size, int(prog.num_regs),
+                         int(prog.num_params), cols.size, cols.ctypes.data if cols.size else None)
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return d, (code, pool, cols)
+
+
+def gate_program_check(prog, **fields):
+    """glp_gate_program_check (host only, no context): the largest number of EMITs in one gate, or GlpError naming the instruction
+    and the field"""
+    d, _keep = gate_program_desc(prog, **fields)
+    out = C.c_uint32()
+    _chk(load_library().glp_gate_program_check(C.byref(d), C.byref(out)))
+    return int(out.value)
+
+
+class GateProgram:
+    """A gate program resident on the GPU (glp_gate_program_create)."""
+
+    def __init__(self, ctx, handle, num_params, num_oracles):
+        self.ctx, self._h, self.num_params, self.num_oracles = ctx, handle, num_params, num_oracles
+
+    def sums(self, oracles, sub_bits, alphas, params=None, out_dev_ptr=None):
+        """glp_gate_program_sums: the program on every point of the coset 7 <W_M>, M = n << sub_bits, natural order.  oracles: the
+        Batches the program's COL operands name, in order.  alphas [num_challenges] (then params [num_params]) for one proof: returns
+        [num_challenges][M]; alphas [num_proofs][num_challenges] (params [num_proofs][num_params]): [num_proofs][num_challenges][M] --
+        what perm_quotient_values takes as gate_sums.  out_dev_ptr: the values go to that HBM pointer and None is returned."""
+        al = _a(alphas)
+        K, nch = (al.shape[0], al.shape[1]) if al.ndim == 2 else (1, al.size)
+        pr = None if params is None else _a(params)
+        if pr is not None and pr.size != K * self.num_params:
+            raise GlpError(-1, "params has %d elements, expected num_proofs * num_params = %d" % (pr.size, K * self.num_params))
+        oracles = list(oracles)
+        if len(oracles) != self.num_oracles:
+            raise GlpError(-1, "%d oracles, the program reads %d" % (len(oracles), self.num_oracles))
+        hs = (C.c_void_p * len(oracles))(*[o._h for o in oracles])
+        M = 1 << (oracles[0].log_n + int(sub_bits))
+        out = None if out_dev_ptr is not None else np.empty((K, nch, M) if al.ndim == 2 else (nch, M), np.uint64)
+        _chk(load_library().glp_gate_program_sums(self.ctx._h, self._h, K, hs, int(sub_bits), nch, _p(al), None if pr is None or not pr.size else _p(pr),
+                                                  C.c_void_p(out_dev_ptr) if out is None else _p(out), 0 if out is not None else 1))
+        return out
+
+    def free(self):
+        if self._h:
+            if getattr(self.ctx, "_h", None):             # never touch a handle whose context is already gone
+                load_library().glp_gate_program_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def perm_desc(desc):
