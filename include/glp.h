@@ -365,6 +365,64 @@ GLP_API int  glp_gate_program_sums(glp_ctx *ctx, const glp_gate_program *p, uint
                                    const uint64_t *params /* [num_proofs][num_params] or NULL */,
                                    uint64_t *out, int out_on_device);
 
+/* ---- the vanishing identity at zeta for caller-held circuits ------------------------------------------------------------------------
+ * The verifier's side of the seam.  glp_fri_verify_many shows that the claimed openings are openings of the committed polynomials;
+ * plonky2's `verify_with_challenges` first checks that they satisfy the circuit:
+ *     vanishing(zeta) == Z_H(zeta) * reduce_with_powers(quotient chunks, zeta^n).
+ * A gate program is straight-line code over F_p whose inputs are polynomials, so it evaluates at any point of F_p^2 (elements are two
+ * canonical words a, b = a + b X, X^2 = 7): the program object made for the prover serves the verifier unchanged.  The reading is
+ *     GLP_GP_COL       the opening of polynomial c of oracle o at the point         GLP_GP_COL_NEXT  its opening at w_n * point
+ *     GLP_GP_X         the point itself            GLP_GP_IMM, GLP_GP_PARAM   base elements, embedded
+ *     ADD / SUB / MUL  the F_p^2 operations (an extension-gate body traced over pairs of wires becomes plonky2's extension algebra
+ *                      over F_p^2);  EMIT and END keep their meaning: alphas are base-field challenges, the accumulators F_p^2 elements.
+ * Openings arrive through glp_ext_openings, which may point straight into the openings array of glp_fri_verify_many (the order of
+ * glp_fri_open: for the plonk instance every polynomial of oracles 0..3 at zeta, then the first num_challenges polynomials of the zs
+ * oracle at g zeta).  num_proofs is 1..4096 and every array gets a leading [num_proofs].  Host inputs (inputs_on_device == 0) are
+ * scanned, and a word >= p is refused naming proof and word index; device inputs (HBM pointers on the context's GPU) are reduced mod p
+ * once as they are loaded.  Canonical-form checking of proof bytes stays with glp_proof_from_bytes and glp_fri_verify*.  Every refusal
+ * is GLP_ERR_ARG, names the field and happens before any launch. */
+typedef struct {
+    const uint64_t *at;        /* element (proof k, polynomial c) = at + k * proof_stride + 2 c, two words (F_p^2) */
+    const uint64_t *at_next;   /* the same at w_n * point; NULL where nothing reads it */
+    size_t proof_stride;       /* words between proofs, >= 2 * polynomials read (and at most 2^32) */
+} glp_ext_openings;
+/* The program at points[k] over the openings of num_proofs proofs, one launch: out[k][c] = sum_gates filter_g sum_t alpha_{k,c}^t v_{g,t},
+ * the program's gate_sums at zeta.
+ *   points    [num_proofs][2]                 openings  [num_oracles], oracle o with oracle_cols[o] polynomials; at_next is needed
+ *                                                       only for an oracle one of whose COL_NEXT the program reads
+ *   alphas    [num_proofs][num_challenges] and params [num_proofs][num_params] (NULL only with num_params == 0): host, canonical
+ *   out       [num_proofs][num_challenges][2]; an HBM out (out_on_device != 0) is glp_perm_check_zeta's gate_sums as it stands
+ * Refused: null pointers; num_proofs outside 1..4096 or num_challenges outside 1..4; proof_stride < 2 * oracle_cols[o]; at_next ==
+ * NULL for an oracle whose COL_NEXT the program reads; a non-canonical alpha or param; params == NULL with num_params > 0; a
+ * non-canonical host point or opening. */
+GLP_API int  glp_gate_program_eval_ext(glp_ctx *ctx, const glp_gate_program *p, uint32_t num_proofs, uint32_t num_challenges,
+                                       const uint64_t *points /* [K][2] */, const glp_ext_openings *openings /* [num_oracles] */,
+                                       int inputs_on_device, const uint64_t *alphas /* [K][nch], host */,
+                                       const uint64_t *params /* [K][num_params], host, or NULL */,
+                                       uint64_t *out /* [K][nch][2] */, int out_on_device);
+/* With n = 2^log_n and T = num_challenges * (num_partial_products + 2), checks for proof k and every challenge c
+ *     sum_{t < T} alpha_{k,c}^t term_t(zeta_k) + alpha_{k,c}^T gate_sums[k][c] == (zeta_k^n - 1) sum_j quotient[c * chunks + j] zeta_k^(n j)
+ * with the terms of the formula above glp_perm_quotient_values evaluated at zeta, L_0(zeta) = (zeta^n - 1) / (n (zeta - 1)) and Z "next"
+ * zs.at_next: the algebra of glp_verify's identity check with the gate terms taken from the caller.
+ *   sigmas, wires   num_routed_wires polynomials each are read (the routed wires come first)
+ *   zs              glp_perm_num_polys polynomials at zeta; at_next: the first num_challenges at g zeta
+ *   quotient        num_challenges * num_quotient_chunks polynomials, num_quotient_chunks in 1..256
+ *   betas, gammas, alphas   host [num_proofs][num_challenges], canonical
+ *   gate_sums       NULL (the gate term is absent), or [num_proofs][num_challenges][2]; with gate_sums_on_device != 0 the HBM out of
+ *                   glp_gate_program_eval_ext passed straight on: nothing returns to the host between the two calls
+ *   status_out      [num_proofs]: GLP_OK = the identity holds, GLP_ERR_PROVE = rejected (the convention of glp_fri_verify_many)
+ *   reasons_out     NULL or [num_proofs][GLP_REASON_LEN], empty if accepted, else in glp_verify's words: "zeta = 1" or
+ *                   "Mismatch between evaluation and opening of quotient polynomial (challenge <c>)", c the first such challenge
+ * The call returns GLP_OK when it ran.  Refused: null pointers (at_next of zs included), num_proofs or num_quotient_chunks out of range,
+ * a description glp_perm_num_polys refuses, a proof_stride below twice the polynomials read, non-canonical challenges or host inputs. */
+GLP_API int  glp_perm_check_zeta(glp_ctx *ctx, const glp_perm_desc *desc, uint32_t num_proofs, uint32_t num_quotient_chunks,
+                                 const uint64_t *zetas /* [K][2] */,
+                                 const glp_ext_openings *sigmas, const glp_ext_openings *wires, const glp_ext_openings *zs,
+                                 const glp_ext_openings *quotient, int inputs_on_device,
+                                 const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas /* host [K][nch] */,
+                                 const uint64_t *gate_sums /* NULL or [K][nch][2] */, int gate_sums_on_device,
+                                 int32_t *status_out /* [K] */, char *reasons_out /* NULL or [K][GLP_REASON_LEN] */);
+
 /* ---- openings and FRI of caller-held batches (fri/oracle.rs `PolynomialBatch::prove_openings`) ----------------------------------
  * For an integrator that keeps its own quotient (circuits with lookup tables, Poseidon2Gate, custom gates, starky AIRs: anything
  * glp_circuit_create answers with GLP_ERR_UNSUPPORTED): commit with glp_batch_from_values / _from_coeffs, evaluate the committed

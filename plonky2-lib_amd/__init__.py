@@ -5,4 +5,5 @@ and bench.py.  There is no CPU fallback anywhere in this package."""
 from .binding import (GlpError, Context, Batch, Circuit, Session, StagedWitness, build_library, library_path, load_library,  # noqa: F401
                       exported_symbols, splitmix_field, P, CircuitFile, write_circuit_file, FriOpenings, fri_prove, fri_proof_words,
                       FriOpeningsMany, fri_prove_many, fri_verify, fri_verify_many, fri_verify_queries_many, fri_verify_sizes,
-                      LDE_ROW_MAJOR, LDE_COL_MAJOR, perm_desc, perm_num_polys, GateProgram, gate_program_check, gate_program_desc)
+                      LDE_ROW_MAJOR, LDE_COL_MAJOR, perm_desc, perm_num_polys, GateProgram, gate_program_check, gate_program_desc,
+                      ExtOpenings, plonk_ext_openings)

@@ -77,7 +77,11 @@ class _GateProgramDesc(C.Structure):
                 ("num_params", C.c_uint32), ("num_oracles", C.c_uint32), ("oracle_cols", C.c_void_p)]
 
 
-LDE_ROW_MAJOR, LDE_COL_MAJOR = 0, 1      # GLP_LDE_* of glp_batch_lde_values
+class _ExtOpenings(C.Structure):
+    _fields_ = [("at", C.c_void_p), ("at_next", C.c_void_p), ("proof_stride", C.c_size_t)]
+
+
+LDE_ROW_MAJOR, LDE_COL_MAJOR = 0, 1     # GLP_LDE_* of glp_batch_lde_values
 
 
 def library_path():
@@ -202,6 +206,9 @@ def load_library():
         "glp_gate_program_create": [vp, C.POINTER(_GateProgramDesc), C.POINTER(vp)],
         "glp_gate_program_free": [vp],
         "glp_gate_program_sums": [vp, vp, u32, C.POINTER(vp), u32, u32, vp, vp, vp, C.c_int],
+        "glp_gate_program_eval_ext": [vp, vp, u32, u32, vp, C.POINTER(_ExtOpenings), C.c_int, vp, vp, vp, C.c_int],
+        "glp_perm_check_zeta": [vp, C.POINTER(_PermDesc), u32, u32, vp, C.POINTER(_ExtOpenings), C.POINTER(_ExtOpenings), C.POINTER(_ExtOpenings),
+                                C.POINTER(_ExtOpenings), C.c_int, vp, vp, vp, vp, C.c_int, vp, vp],
         "glp_fri_begin_many": [vp, C.POINTER(_FriDesc), u32, vp, C.POINTER(vp)],
         "glp_fri_queries_many": [vp, vp, vp],
         "glp_pow_search_many": [vp, u32, u32, vp, vp, u32, u32, vp],
@@ -510,6 +517,43 @@ class Context:
                                                      C.c_void_p(out_dev_ptr) if out is None else _p(out), 0 if out is not None else 1))
         return out
 
+    def perm_check_zeta(self, desc, num_quotient_chunks, zetas, sigmas, wires, zs, zs_next, quotient, betas, gammas, alphas, gate_sums=None,
+                        gate_sums_dev_ptr=None, reasons=False):
+        """glp_perm_check_zeta: the vanishing identity at zeta of num_proofs proofs, the gate terms taken from the caller.  desc: the
+        attributes perm_desc() reads.  sigmas, wires, zs, zs_next, quotient: ExtOpenings (plonk_ext_openings() slices them out of a
+        fri_verify_many openings array); zs_next shares zs's stride.  zetas [num_proofs][2]; betas, gammas, alphas [num_challenges]
+        for one proof or [num_proofs][num_challenges].  gate_sums: None, or [num_proofs][num_challenges][2] (gate_sums_dev_ptr: in HBM,
+        the out_dev_ptr of GateProgram.eval_ext).  With ExtOpenings over HBM zetas is an HBM pointer too.  Returns status [num_proofs]
+        int32 (0 accepted, -5 rejected), with reasons=True (status, [num_proofs] str)."""
+        d, keep = perm_desc(desc)
+        b, g, al = _a(betas), _a(gammas), _a(alphas)
+        K = b.shape[0] if b.ndim == 2 else 1
+        if b.size != K * d.num_challenges or g.size != b.size or al.size != b.size:
+            raise GlpError(-1, "betas, gammas and alphas are [num_challenges] or [num_proofs][num_challenges]")
+        if zs_next is not None and (zs_next.proof_stride != zs.proof_stride or zs_next.on_device != zs.on_device):
+            raise GlpError(-1, "zs_next has another proof_stride or memory than zs")
+        parts = [sigmas, wires, zs, quotient]
+        on_dev = _ext_on_device(parts)
+        z = zetas if on_dev else _a(zetas)
+        if not on_dev and z.size != 2 * K:
+            raise GlpError(-1, "zetas has %d words, expected 2 * num_proofs = %d" % (z.size, 2 * K))
+        cs = [o._c() for o in parts]
+        if zs_next is not None:
+            cs[2].at_next = zs_next._c().at
+        gs = None if gate_sums is None or gate_sums_dev_ptr is not None else _a(gate_sums)
+        if gs is not None and gs.size != 2 * K * d.num_challenges:
+            raise GlpError(-1, "gate_sums has %d words, expected 2 * num_proofs * num_challenges = %d" % (gs.size, 2 * K * d.num_challenges))
+        gs_arg = C.c_void_p(gate_sums_dev_ptr) if gate_sums_dev_ptr is not None else (None if gs is None else _p(gs))
+        status = np.zeros(K, np.int32)
+        buf = C.create_string_buffer(K * 160) if reasons else None
+        _chk(load_library().glp_perm_check_zeta(self._h, C.byref(d), K, int(num_quotient_chunks), C.c_void_p(z) if on_dev else _p(z), C.byref(cs[0]),
+                                                C.byref(cs[1]), C.byref(cs[2]), C.byref(cs[3]), 1 if on_dev else 0, _p(b), _p(g), _p(al), gs_arg,
+                                                0 if gate_sums_dev_ptr is None else 1, status.ctypes.data_as(C.c_void_p), buf))
+        del keep
+        if not reasons:
+            return status
+        return status, [buf.raw[160 * k:160 * (k + 1)].split(b"\0", 1)[0].decode() for k in range(K)]
+
     def gate_program(self, prog):
         """glp_gate_program_create: prog is what gate_program.Assembler.assemble() returns (or anything gate_program_desc() takes).
         Returns the GateProgram, resident in HBM until free()."""
@@ -733,6 +777,31 @@ class GateProgram:
                                                   C.c_void_p(out_dev_ptr) if out is None else _p(out), 0 if out is not None else 1))
         return out
 
+    def eval_ext(self, points, openings, alphas, params=None, out_dev_ptr=None):
+        """glp_gate_program_eval_ext: the program over F_p^2 at points[k], on the openings of num_proofs proofs: the gate_sums at zeta
+        that perm_check_zeta takes.  openings: one ExtOpenings per oracle the program names, in order (all over host memory, or all
+        over HBM: then points is an HBM pointer too).  points [num_proofs][2]; alphas [num_challenges] (then params [num_params]) for
+        one proof: returns [num_challenges][2]; alphas [num_proofs][num_challenges]: [num_proofs][num_challenges][2].  out_dev_ptr:
+        the values go to that HBM pointer and None is returned."""
+        al = _a(alphas)
+        K, nch = (al.shape[0], al.shape[1]) if al.ndim == 2 else (1, al.size)
+        pr = None if params is None else _a(params)
+        if pr is not None and pr.size != K * self.num_params:
+            raise GlpError(-1, "params has %d elements, expected num_proofs * num_params = %d" % (pr.size, K * self.num_params))
+        openings = list(openings)
+        if len(openings) != self.num_oracles:
+            raise GlpError(-1, "%d openings, the program reads %d oracles" % (len(openings), self.num_oracles))
+        on_dev = _ext_on_device(openings)
+        pts = points if on_dev else _a(points)
+        if not on_dev and pts.size != 2 * K:
+            raise GlpError(-1, "points has %d words, expected 2 * num_proofs = %d" % (pts.size, 2 * K))
+        cs = (_ExtOpenings * len(openings))(*[o._c() for o in openings])
+        out = None if out_dev_ptr is not None else np.empty((K, nch, 2) if al.ndim == 2 else (nch, 2), np.uint64)
+        _chk(load_library().glp_gate_program_eval_ext(self.ctx._h, self._h, K, nch, C.c_void_p(pts) if on_dev else _p(pts), cs, 1 if on_dev else 0,
+                                                      _p(al), None if pr is None or not pr.size else _p(pr),
+                                                      C.c_void_p(out_dev_ptr) if out is None else _p(out), 0 if out is not None else 1))
+        return out
+
     def free(self):
         if self._h:
             if getattr(self.ctx, "_h", None):             # never touch a handle whose context is already gone
@@ -744,6 +813,56 @@ class GateProgram:
             self.free()
         except Exception:
             pass
+
+
+class ExtOpenings:
+    """glp_ext_openings: the F_p^2 openings of one oracle for num_proofs proofs.  array: the uint64 host array that holds them (the
+    whole openings array of fri_verify_many will do; it is kept alive); at: the word offset in it of (proof 0, polynomial 0); at_next:
+    the same for the openings at w_n * point, or None; proof_stride: words between proofs (default: the size of array[0]).
+    dev_ptr: the words are in HBM from that pointer on, and array is ignored."""
+
+    def __init__(self, array, at=0, at_next=None, proof_stride=None, dev_ptr=None):
+        self.dev_ptr = dev_ptr
+        self.array = None if dev_ptr is not None else _a(array)
+        if proof_stride is None:
+            if self.array is None:
+                raise GlpError(-1, "proof_stride is needed with dev_ptr")
+            proof_stride = self.array.size // self.array.shape[0] if self.array.ndim > 1 else self.array.size
+        self.at, self.at_next, self.proof_stride = int(at), None if at_next is None else int(at_next), int(proof_stride)
+
+    @property
+    def on_device(self):
+        return self.dev_ptr is not None
+
+    def _c(self):
+        base = int(self.dev_ptr) if self.on_device else self.array.ctypes.data
+        return _ExtOpenings(base + 8 * self.at, None if self.at_next is None else base + 8 * self.at_next, self.proof_stride)
+
+
+def _ext_on_device(openings):
+    dev = [o.on_device for o in openings]
+    if any(dev) != all(dev):
+        raise GlpError(-1, "the openings are all over host memory or all over HBM")
+    return all(dev)
+
+
+def plonk_ext_openings(desc, openings=None, dev_ptr=None):
+    """The openings array of fri_verify_many for the plonk instance of `desc` ([num_proofs][count][2] or [count][2], the order of
+    glp_fri_open: constants ++ sigmas, wires, zs ++ partial products, quotient at zeta, then the Z polynomials at g zeta), sliced into
+    ExtOpenings: a dict with "program" ([constants ++ sigmas, wires]: what GateProgram.eval_ext takes for a program that names those
+    two oracles), "sigmas", "wires", "zs", "zs_next" and "quotient" (what Context.perm_check_zeta takes), and "count"."""
+    nc, nr, nw, nch = int(desc.num_constants), int(desc.num_routed_wires), int(desc.num_wires), int(desc.num_challenges)
+    nzp, nq = nch * (1 + int(desc.num_partial_products)), nch * int(desc.quotient_degree_factor)
+    count = nc + nr + nw + nzp + nq + nch
+    if dev_ptr is None:
+        openings = _a(openings)
+        if openings.size % (2 * count):
+            raise GlpError(-1, "openings has %d words, no multiple of 2 * %d" % (openings.size, count))
+
+    def part(at):
+        return ExtOpenings(openings, 2 * at, None, 2 * count, dev_ptr)
+    return {"program": [part(0), part(nc + nr)], "sigmas": part(nc), "wires": part(nc + nr), "zs": part(nc + nr + nw),
+            "zs_next": part(nc + nr + nw + nzp + nq), "quotient": part(nc + nr + nw + nzp), "count": count}
 
 
 def perm_desc(desc):

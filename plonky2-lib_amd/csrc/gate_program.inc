@@ -99,10 +99,11 @@ struct glp_gate_program {
     u32 oracle_cols[GLP_GP_MAX_ORACLES] = {0, 0, 0, 0};
     u32 maxc = 0;                  // the largest number of EMITs in one gate
     u32 cols_named = 0;            // distinct (oracle, polynomial) pairs the program reads: the stage record's bytes
+    u32 next_mask = 0;             // bit o: the program reads a COL_NEXT of oracle o (zeta_check.inc asks for at_next only then)
 };
 
 namespace {
-struct GPInfo { u32 maxc, cols_named; };
+struct GPInfo { u32 maxc, cols_named, next_mask; };
 // the rules of glp_gate_program_check; `fn` names the entry point in the message
 int gate_program_check(const char *fn, const glp_gate_program_desc *d, GPInfo &info) {
     GLP_REQUIRE(d, "%s: desc is null", fn);
@@ -122,7 +123,7 @@ int gate_program_check(const char *fn, const glp_gate_program_desc *d, GPInfo &i
                 (unsigned long long)d->pool[bad == d->num_pool ? 0 : bad]);
     u32 written = 0, emits = 0;
     std::vector<u32> named;
-    info.maxc = 0;
+    info.maxc = 0; info.next_mask = 0;
     for (u32 i = 0; i < d->num_instructions; i++) {
         const u64 ins = d->code[i];
         const u32 op = (u32)ins & 15, dst = ((u32)ins >> GLP_GP_DST_SHIFT) & 31;
@@ -147,6 +148,7 @@ int gate_program_check(const char *fn, const glp_gate_program_desc *d, GPInfo &i
                 GLP_REQUIRE(col < d->oracle_cols[o], "%s: instruction %u, field %s: column index %u is not below oracle_cols[%u] = %u", fn, i, field, col, o,
                             d->oracle_cols[o]);
                 named.push_back(pl);
+                if (kind == GLP_GP_COL_NEXT) info.next_mask |= 1u << o;
                 break;
             }
             case GLP_GP_IMM:
@@ -204,7 +206,7 @@ int glp_gate_program_create(glp_ctx *c, const glp_gate_program_desc *d, glp_gate
     p->ninstr = d->num_instructions; p->code_words = (d->num_instructions + 3) & ~3u; p->npool = d->num_pool;
     p->nregs = d->num_regs; p->nparams = d->num_params; p->noracles = d->num_oracles;
     for (u32 o = 0; o < d->num_oracles; o++) p->oracle_cols[o] = d->oracle_cols[o];
-    p->maxc = info.maxc; p->cols_named = info.cols_named;
+    p->maxc = info.maxc; p->cols_named = info.cols_named; p->next_mask = info.next_mask;
     std::vector<u64> img((size_t)p->code_words + p->npool, 0);
     memcpy(img.data(), d->code, (size_t)p->ninstr * 8);
     if (p->npool) memcpy(img.data() + p->code_words, d->pool, (size_t)p->npool * 8);
