@@ -485,7 +485,8 @@ GLP_API void glp_fri_end(glp_fri *f);
  * `duplexing` refills the output buffer; the library resumes either way from (state, num_pending) alone.  The permutation is that of
  * the batches' hasher.  Order (fri/prover.rs): alpha; per reduction observe the cap, draw beta; observe
  * the final polynomial; the SMALLEST proof-of-work witness; num_query_rounds indices, get() % N.  openings_out
- * [2 * sum of the points' polynomial counts] is filled for the caller's proof (they are computed inside the call anyway). */
+ * [2 * sum of the points' polynomial counts] is filled for the caller's proof (they are computed inside the call anyway).
+ * sponge_state and pending_inputs are field elements: a word >= p is GLP_ERR_ARG naming it, decided before any launch. */
 GLP_API int glp_fri_prove(glp_ctx *ctx, const glp_fri_desc *desc, const uint64_t sponge_state[12], const uint64_t *pending_inputs,
                           uint32_t num_pending, uint64_t *openings_out, uint64_t *proof_out);
 
@@ -513,12 +514,14 @@ GLP_API int glp_fri_begin_many(glp_ctx *ctx, const glp_fri_desc *desc, uint32_t 
 GLP_API uint32_t glp_fri_num_proofs(const glp_fri *f);                  /* 1 for a glp_fri_begin handle */
 GLP_API int glp_fri_queries_many(glp_fri *f, const uint64_t *pow_witnesses, const uint64_t *indices);
 /* glp_pow_search_h for num_proofs sponges with num_pending (< 8) buffered inputs each: sponge_states [num_proofs][12], pending_inputs
- * [num_proofs][num_pending], witnesses_out [num_proofs], the smallest witness of each */
+ * [num_proofs][num_pending], witnesses_out [num_proofs], the smallest witness of each.  A state or pending word >= p is GLP_ERR_ARG
+ * naming sponge_states[k][i] or pending_inputs[k][i], decided before any launch. */
 GLP_API int glp_pow_search_many(glp_ctx *ctx, uint32_t hasher, uint32_t num_proofs, const uint64_t *sponge_states, const uint64_t *pending_inputs,
                                 uint32_t num_pending, uint32_t bits, uint64_t *witnesses_out);
 /* One-call form: glp_fri_prove's transcript order for each proof, the num_proofs transcripts on the context's host threads
  * (GLP_HOST_THREADS, as glp_prove_batch).  sponge_states [num_proofs][12], pending_inputs [num_proofs][num_pending], openings_out
- * [num_proofs][openings][2], proofs_out [num_proofs][FriProof words]. */
+ * [num_proofs][openings][2], proofs_out [num_proofs][FriProof words].  A state or pending word >= p is GLP_ERR_ARG, as for
+ * glp_pow_search_many. */
 GLP_API int glp_fri_prove_many(glp_ctx *ctx, const glp_fri_desc *desc, uint32_t num_proofs, const uint64_t *points, const uint64_t *sponge_states,
                                const uint64_t *pending_inputs, uint32_t num_pending, uint64_t *openings_out, uint64_t *proofs_out);
 
@@ -808,10 +811,12 @@ GLP_API int glp_session_fri_fold(glp_session *s, const uint64_t beta[2]);
 GLP_API size_t glp_final_poly_len(const glp_circuit *circuit);          /* ext coefficients */
 GLP_API int glp_session_fri_final_poly(glp_session *s, uint64_t *coeffs_out /* [2 * glp_final_poly_len] */);
 /* smallest w such that a duplex sponge in `sponge_state` with `num_pending` (< 8) buffered inputs, after also
- * observing w, squeezes an element with `bits` leading zero bits (fri_proof_of_work) */
+ * observing w, squeezes an element with `bits` leading zero bits (fri_proof_of_work).  The twelve state words and the pending
+ * inputs are field elements, canonical as every field argument of this API: a word >= p is GLP_ERR_ARG naming sponge_state[i] or
+ * pending_inputs[i], decided on the host before any launch (the permutations take canonical words). */
 GLP_API int glp_pow_search(glp_ctx *ctx, const uint64_t sponge_state[12], const uint64_t *pending_inputs, uint32_t num_pending,
                            uint32_t bits, uint64_t *witness_out);
-/* the same for a transcript whose permutation is that of `hasher` (GLP_HASH_KECCAK25: KeccakPermutation) */
+/* the same, with the same refusals, for a transcript whose permutation is that of `hasher` (GLP_HASH_KECCAK25: KeccakPermutation) */
 GLP_API int glp_pow_search_h(glp_ctx *ctx, uint32_t hasher, const uint64_t sponge_state[12], const uint64_t *pending_inputs,
                              uint32_t num_pending, uint32_t bits, uint64_t *witness_out);
 /* The session's committed oracles, index 0..3: constants_sigmas, wires, zs and partial products, quotient.  Valid once the stage that

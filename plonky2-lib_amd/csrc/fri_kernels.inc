@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256) void k_pow(PowArgs a) {
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = a.st[i];
 #pragma unroll
-    for (int i = 0; i < 8; i++) if ((u32)i == a.pos) s[i] = cand;        // candidates stay far below p
+    for (int i = 0; i < 8; i++) if ((u32)i == a.pos) s[i] = cand;        // cand < 2^40 + 2^20 < p: a canonical word, as permute() takes
     if constexpr (HASHER == GLP_HASH_KECCAK25) kec::permute(s); else pos::permute(s);
     if (a.bits == 0 || (s[7] >> (64 - a.bits)) == 0) atomicMin(a.best, (unsigned long long)cand);
 }
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(256) void k_pow_batch(const u64 *st_b, const u32 *p
         for (int i = 0; i < 12; i++) s[i] = st_b[(size_t)pk * 12 + i];
         const u32 pos = pos_b[pk];
         const u64 cand = base + threadIdx.x;
-        for (u32 i = 0; i < 8; i++) if (i == pos) s[i] = cand;      // candidates stay far below p
+        for (u32 i = 0; i < 8; i++) if (i == pos) s[i] = cand;      // cand < 2^40 + 256 < p: a canonical word, as permute() takes
         if constexpr (HASHER == GLP_HASH_KECCAK25) kec::permute(s); else pos::permute(s);
         if (bits == 0 || (s[7] >> (64 - bits)) == 0) atomicMin(best + pk, (unsigned long long)cand);
     }
@@ -608,7 +608,9 @@ __global__ __launch_bounds__(256, 4) void k_pow_batch2(u64 *k_b, const u32 *pos_
         if (base == ~0ull) continue;
         const u32 pos_ = pos_b[pk];
         const u64 cand = base + t;
-        const u64 sp = pos::sbox7_nc(cand + pos::RC[pos_]);          // candidates stay far below p: the sum cannot wrap
+        // a plain add, no reduction: cand < 2^40 + 256 and pos_ < 8, and RC[0..7] < 2^64 - 2^41 (static_assert at pblk::RC_CE,
+        // poseidon.h), so the sum stays a u64; it may pass p, which sbox7_nc takes
+        const u64 sp = pos::sbox7_nc(cand + pos::RC[pos_]);
         u64 s[12];
 #pragma unroll
         for (int r = 0; r < 12; r++) s[r] = add_cnc(k_b[(size_t)pk * 12 + r], mul_small_nc(sp, pos::mds_entry(r, (int)pos_)));

@@ -358,6 +358,7 @@ int pow_search_many(glp_ctx *c, int hasher, const u64 *states, const u64 *pendin
 int fri_prove(glp_ctx *c, const glp_fri_desc *desc, u32 K, const u64 *points, bool many, const u64 *sponge_states, const u64 *pending_inputs,
               u32 num_pending, u64 *openings_out, u64 *proofs_out) {
     GLP_REQUIRE(num_pending < 8, "%u pending inputs (the rate is 8)", num_pending);
+    GLP_TRY(sponge_args_check(sponge_states, pending_inputs, num_pending, K, many));
     GLP_TRY(fri_check(c, desc, K, points, many));
     GLP_TRY(bind(c));
     glp_fri f(c, *desc, K, points, many);
@@ -516,6 +517,7 @@ int glp_pow_search_many(glp_ctx *c, uint32_t hasher, uint32_t num_proofs, const 
     GLP_REQUIRE(bits <= POW_MAX_BITS, "proof_of_work_bits=%u: this build searches at most 2^40 candidates and accepts up to %u bits", bits,
                 POW_MAX_BITS);
     if (hasher != GLP_HASH_POSEIDON && hasher != GLP_HASH_KECCAK25) return set_error(GLP_ERR_UNSUPPORTED, "hasher %u is not one of GLP_HASH_*", hasher);
+    GLP_TRY(sponge_args_check(sponge_states, pending_inputs, num_pending, num_proofs, true));
     GLP_TRY(bind(c));
     return pow_search_many(c, (int)hasher, sponge_states, pending_inputs, num_pending, bits, num_proofs, witnesses_out);
 }

@@ -92,6 +92,11 @@ namespace pblk {
 constexpr u64 PRIME = 0xFFFFFFFF00000001ULL;
 constexpr u32 CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
 constexpr u64 RC_CE[360] = { GLP_POSEIDON_RC_LIST };
+// k_pow_batch2 (fri_kernels.inc) adds a proof-of-work candidate to the round-0 constant of its slot with a plain 64-bit add.  A
+// candidate is below 2^40 + 256 and goes to one of the rate slots 0..7, so the sum stays a u64 as long as these eight constants
+// leave 2^41 of headroom (the largest, RC[7], is 0xef78...).  RC_CE expands the same list as pos::RC.
+constexpr bool pow_round0_add_fits(int i = 0) { return i == 8 || (RC_CE[i] < 0xFFFFFE0000000000ULL && pow_round0_add_fits(i + 1)); }
+static_assert(pow_round0_add_fits(), "RC[0..7] must stay below 2^64 - 2^41: k_pow_batch2 adds the candidate without reduction");
 constexpr u64 m_at(int r, int c) { return CIRC[(c - r + 12) % 12] + ((r == 0 && c == 0) ? 8u : 0u); }
 template <int K, bool MERGED> struct Tab {
     u32 g0[K][12] = {};      // g0[j-1] = row 0 of G_j           (j = 1..K-1 used)

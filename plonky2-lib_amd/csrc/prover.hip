@@ -323,6 +323,27 @@ struct glp_session {
     }
 };
 
+// The sponge a proof-of-work search or a one-call FRI proof resumes from: K states of 12 words, K x npending buffered inputs.  Every
+// word is a field element and must be canonical: pos::permute and pos::pow_round0_consts add round constants with glf::add
+// (canonical in), and a word >= p names no state that a transcript can be in.  Host check, before any launch.
+static int sponge_args_check(const u64 *states, const u64 *pending, u32 npending, u32 K, bool many) {
+    for (u32 k = 0; k < K; k++) {
+        for (u32 i = 0; i < 12; i++) {
+            const u64 v = states[(size_t)k * 12 + i];
+            if (v < P) continue;
+            if (many) return set_error(GLP_ERR_ARG, "sponge_states[%u][%u] = 0x%016llx is not canonical", k, i, (unsigned long long)v);
+            return set_error(GLP_ERR_ARG, "sponge_state[%u] = 0x%016llx is not canonical", i, (unsigned long long)v);
+        }
+        for (u32 i = 0; i < npending; i++) {
+            const u64 v = pending[(size_t)k * npending + i];
+            if (v < P) continue;
+            if (many) return set_error(GLP_ERR_ARG, "pending_inputs[%u][%u] = 0x%016llx is not canonical", k, i, (unsigned long long)v);
+            return set_error(GLP_ERR_ARG, "pending_inputs[%u] = 0x%016llx is not canonical", i, (unsigned long long)v);
+        }
+    }
+    return GLP_OK;
+}
+
 // K10: smallest witness w >= 0 such that the sponge (state + pending inputs + w) squeezes a value with `bits` leading
 // zeros.  The search covers candidates in increasing order, so the result does not depend on launch geometry.
 static int pow_search(glp_ctx *c, const u64 st[12], const u64 *pending, u32 npending, u32 bits, u64 *witness, int hasher = GLP_HASH_POSEIDON) {
@@ -482,6 +503,8 @@ int glp_pow_search(glp_ctx *c, const uint64_t sponge_state[12], const uint64_t *
     GLP_REQUIRE(c && sponge_state && witness_out && (pending_inputs || num_pending == 0), "null argument");
     GLP_REQUIRE(bits <= POW_MAX_BITS, "proof_of_work_bits=%u: this build searches at most 2^40 candidates and accepts up to %u bits", bits,
                 POW_MAX_BITS);
+    GLP_REQUIRE(num_pending < 8, "proof of work: %u pending inputs (the rate is 8)", num_pending);
+    GLP_TRY(sponge_args_check(sponge_state, pending_inputs, num_pending, 1, false));
     GLP_TRY(bind(c));
     return pow_search(c, sponge_state, pending_inputs, num_pending, bits, witness_out);
 }
@@ -491,6 +514,8 @@ int glp_pow_search_h(glp_ctx *c, uint32_t hasher, const uint64_t sponge_state[12
     GLP_REQUIRE(bits <= POW_MAX_BITS, "proof_of_work_bits=%u: this build searches at most 2^40 candidates and accepts up to %u bits", bits,
                 POW_MAX_BITS);
     if (hasher != GLP_HASH_POSEIDON && hasher != GLP_HASH_KECCAK25) return set_error(GLP_ERR_UNSUPPORTED, "hasher %u is not one of GLP_HASH_*", hasher);
+    GLP_REQUIRE(num_pending < 8, "proof of work: %u pending inputs (the rate is 8)", num_pending);
+    GLP_TRY(sponge_args_check(sponge_state, pending_inputs, num_pending, 1, false));
     GLP_TRY(bind(c));
     return pow_search(c, sponge_state, pending_inputs, num_pending, bits, witness_out, (int)hasher);
 }
