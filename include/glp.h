@@ -423,6 +423,70 @@ GLP_API int  glp_perm_check_zeta(glp_ctx *ctx, const glp_perm_desc *desc, uint32
                                  const uint64_t *gate_sums /* NULL or [K][nch][2] */, int gate_sums_on_device,
                                  int32_t *status_out /* [K] */, char *reasons_out /* NULL or [K][GLP_REASON_LEN] */);
 
+/* ---- caller-defined running arguments at the commitment seam: trace programs and running columns ------------------------------------
+ * A lookup table, a logUp or cross-table argument and a custom permutation are all the same two steps over the witness: new columns
+ * (numerators and denominators under a challenge) computed from committed ones on the rows of H, then helper columns h = num / den
+ * and a running column Z over them.  The library recites nobody's lookup layout: the caller states its argument as a gate program,
+ * and the witness never leaves HBM.  The pipeline is five calls:
+ *     glp_gate_program_rows        numerators and denominators on H from the witness columns and a challenge (a PARAM)
+ *     glp_running_columns          h_t = num_t / den_t and Z, with the totals that say whether the argument closes
+ *     glp_batch_many_from_values   commits them (values_on_device = 1, ncols = num_args * (num_terms + 1))
+ *     glp_gate_program_sums        the constraints over the committed h and Z -- h den - num, and Z(w x) - Z(x) - sum_t h_t(x) with
+ *                                  GLP_GP_COL_NEXT -- on the quotient's coset
+ *     then the quotient, FRI and zeta calls above, as for any caller-held circuit.
+ * num_proofs is 1..4096 and every array gets a leading [num_proofs].  Host inputs (inputs_on_device == 0) are scanned, and a word
+ * >= p is refused by name; device inputs (HBM pointers on the context's GPU) are reduced mod p once as they are loaded.  Every
+ * refusal is GLP_ERR_ARG, names the field and happens before any launch.
+ *
+ * glp_gate_program_rows runs a program on the n = 2^log_n rows of H.  It is the third reading of a program object (the coset:
+ * glp_gate_program_sums; F_p^2 at zeta: glp_gate_program_eval_ext); at row i of proof k
+ *     GLP_GP_COL       column c of input o at row i               GLP_GP_COL_NEXT  the same column at row (i + 1) mod n
+ *     GLP_GP_X         w_n^i                                      GLP_GP_IMM, GLP_GP_PARAM, ADD / SUB / MUL / MOV   as before
+ *     EMIT a           number t, counted from the start of the program: out[k][t][i] = a
+ * The program must be a single gate: exactly one END, its last instruction, whose operand is a GLP_GP_IMM with the pool word 1 (the
+ * AIR shape "closed by END IMM(1)"), and at least one EMIT.  Any other shape is refused naming the instruction and the field.
+ *   inputs          [num_oracles] arrays [members][oracle_cols[o]][n], values on H in natural order: the layout of glp_perm_zs_commit's
+ *                   wires and of glp_batch_many_from_values (a batch holds coefficients and the LDE on g H, not values on H)
+ *   input_members   [num_oracles]: num_proofs, or 1 for an input shared by all proofs (a table, say)
+ *   params          [num_proofs][num_params], host, canonical; NULL only with num_params == 0
+ *   out             [num_proofs][num_out][n], num_out = the max_constraints glp_gate_program_check reports.  With host memory the call
+ *                   returns after the copy; with an HBM pointer nothing is copied back and the call is asynchronous.
+ * Refused: null pointers; num_proofs outside 1..4096; log_n above the largest batch's; input_members[o] neither 1 nor num_proofs;
+ * more than 64 GiB of inputs or of out; params == NULL with num_params > 0; a non-canonical param; a non-canonical host input word,
+ * naming the input and the word index. */
+GLP_API int  glp_gate_program_rows(glp_ctx *ctx, const glp_gate_program *p, uint32_t num_proofs, uint32_t log_n,
+                                   const uint64_t *const *inputs /* [num_oracles] */,
+                                   const uint32_t *input_members /* [num_oracles]: 1 or num_proofs */, int inputs_on_device,
+                                   const uint64_t *params /* [K][num_params] or NULL */,
+                                   uint64_t *out /* [K][num_out][n] */, int out_on_device);
+/* The helper columns and the running column of num_args arguments of num_terms terms each, for num_proofs proofs, with K = num_proofs,
+ * A = num_args, T = num_terms, n = 2^log_n:
+ *     out[k][a][t][i] = nums(k, a, t, i) / dens(k, a, t, i)    for t < T
+ *     out[k][a][T][i] = Z[i]:    Z[0] = 0, Z[i + 1] = Z[i] + sum_t out[k][a][t][i]     (GLP_RUN_SUM, logUp)
+ *                                Z[0] = 1, Z[i + 1] = Z[i] * prod_t out[k][a][t][i]    (GLP_RUN_PRODUCT, grand product)
+ *     totals_out[k][a] = the value Z would take at row n: Z[n - 1] combined with row n - 1's contribution.
+ * A closed argument has total 0 (sum) or 1 (product); cross-table arguments compare totals across calls.
+ *   nums, dens        element (k, a, t, i) at k * in_proof_stride + (a T + t) n + i; nums == NULL means every numerator is 1.  The
+ *                     stride (>= A T n, at most 2^33) lets a rows program that EMITs all denominators and then all numerators be
+ *                     passed straight on: dens = rows_out, nums = rows_out + A T n, in_proof_stride = 2 A T n, no copy.  Neither
+ *                     may overlap out.
+ *   out               [K][A (T + 1)][n], contiguous: what glp_batch_many_from_values(.., values_on_device = 1, ..) takes with
+ *                     ncols = A (T + 1)
+ *   totals_out        host [K][A], required: the call is synchronous
+ * A zero denominator is GLP_ERR_PROVE, its message naming proof, argument, term and row of the first one in (k, a, t, i) order;
+ * out and totals_out are unspecified then.  (Inversion is batched over a row's terms; a zero is kept out of the batch, so it
+ * spoils no other term's value before it is reported.)
+ * Refused: null ctx, dens, out or totals_out; kind not one of GLP_RUN_*; num_proofs outside 1..4096, num_args outside 1..16,
+ * num_terms outside 1..64; log_n above the largest batch's; more than 64 GiB of out; in_proof_stride below A T n or above 2^33; a
+ * non-canonical host word of nums or dens, naming the array, the proof and the word index. */
+#define GLP_RUN_SUM 0u       /* logUp:          Z[0] = 0, Z[i+1] = Z[i] + sum_t h_t[i] */
+#define GLP_RUN_PRODUCT 1u   /* grand product:  Z[0] = 1, Z[i+1] = Z[i] * prod_t h_t[i] */
+GLP_API int  glp_running_columns(glp_ctx *ctx, uint32_t kind, uint32_t num_proofs, uint32_t num_args, uint32_t num_terms,
+                                 uint32_t log_n, const uint64_t *nums /* NULL = all ones */, const uint64_t *dens,
+                                 size_t in_proof_stride, int inputs_on_device,
+                                 uint64_t *out /* [K][num_args][num_terms + 1][n] */, int out_on_device,
+                                 uint64_t *totals_out /* host [K][num_args] */);
+
 /* ---- openings and FRI of caller-held batches (fri/oracle.rs `PolynomialBatch::prove_openings`) ----------------------------------
  * For an integrator that keeps its own quotient (circuits with lookup tables, Poseidon2Gate, custom gates, starky AIRs: anything
  * glp_circuit_create answers with GLP_ERR_UNSUPPORTED): commit with glp_batch_from_values / _from_coeffs, evaluate the committed

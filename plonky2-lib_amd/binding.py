@@ -82,6 +82,7 @@ class _ExtOpenings(C.Structure):
 
 
 LDE_ROW_MAJOR, LDE_COL_MAJOR = 0, 1     # GLP_LDE_* of glp_batch_lde_values
+RUN_SUM, RUN_PRODUCT = 0, 1             # GLP_RUN_* of glp_running_columns
 
 
 def library_path():
@@ -207,6 +208,8 @@ def load_library():
         "glp_gate_program_free": [vp],
         "glp_gate_program_sums": [vp, vp, u32, C.POINTER(vp), u32, u32, vp, vp, vp, C.c_int],
         "glp_gate_program_eval_ext": [vp, vp, u32, u32, vp, C.POINTER(_ExtOpenings), C.c_int, vp, vp, vp, C.c_int],
+        "glp_gate_program_rows": [vp, vp, u32, u32, C.POINTER(vp), C.POINTER(u32), C.c_int, vp, vp, C.c_int],
+        "glp_running_columns": [vp, u32, u32, u32, u32, u32, vp, vp, sz, C.c_int, vp, C.c_int, vp],
         "glp_perm_check_zeta": [vp, C.POINTER(_PermDesc), u32, u32, vp, C.POINTER(_ExtOpenings), C.POINTER(_ExtOpenings), C.POINTER(_ExtOpenings),
                                 C.POINTER(_ExtOpenings), C.c_int, vp, vp, vp, vp, C.c_int, vp, vp],
         "glp_fri_begin_many": [vp, C.POINTER(_FriDesc), u32, vp, C.POINTER(vp)],
@@ -560,7 +563,44 @@ class Context:
         d, keep = gate_program_desc(prog)
         h = C.c_void_p()
         _chk(load_library().glp_gate_program_create(self._h, C.byref(d), C.byref(h)))
-        return GateProgram(self, h, int(d.num_params), int(d.num_oracles))
+        g = GateProgram(self, h, int(d.num_params), int(d.num_oracles))
+        g.num_out = gate_program_check(prog)                     # columns of GateProgram.rows: the EMITs of a single-gate program
+        return g
+
+    def running_columns(self, kind, nums, dens, num_proofs=None, num_args=None, num_terms=None, log_n=None, in_proof_stride=None,
+                        nums_dev_ptr=None, dens_dev_ptr=None, out_dev_ptr=None):
+        """glp_running_columns: the helper columns nums / dens and the running column of kind RUN_SUM (logUp) or RUN_PRODUCT (grand
+        product).  dens (and nums, or None for all ones): [num_terms][n] for one argument of one proof, [num_args][num_terms][n], or
+        [num_proofs][num_args][num_terms][n]; the result has dens's leading dimensions: out [..][num_terms + 1][n] (the helper columns,
+        then Z) and totals [num_proofs][num_args] (0 for a closed sum, 1 for a closed product).  dens_dev_ptr / nums_dev_ptr: the
+        inputs are in HBM at these pointers (both or neither; nums_dev_ptr None: all ones) and num_proofs, num_args, num_terms, log_n
+        and, unless the proofs are packed, in_proof_stride (words between proofs) say how.  out_dev_ptr: the columns go to that HBM
+        pointer and (None, totals) is returned.  A zero denominator is GlpError -5 naming proof, argument, term and row."""
+        if dens_dev_ptr is None:
+            d = _a(dens)
+            if not 2 <= d.ndim <= 4:
+                raise GlpError(-1, "dens is [num_terms][n], [num_args][num_terms][n] or [num_proofs][num_args][num_terms][n]")
+            lead = d.shape[:-2]
+            K, A = ((1, 1), (1, d.shape[0]), d.shape[:2])[d.ndim - 2]
+            T, n = d.shape[-2:]
+            if n & (n - 1) or n == 0:
+                raise GlpError(-1, "n must be a power of two")
+            log_n = n.bit_length() - 1
+            nm = None if nums is None else _a(nums)
+            if nm is not None and nm.shape != d.shape:
+                raise GlpError(-1, "nums has another shape than dens")
+            stride = A * T * n
+            d_arg, n_arg, on_dev = _p(d), None if nm is None else _p(nm), 0
+        else:
+            K, A, T, n = int(num_proofs), int(num_args), int(num_terms), 1 << int(log_n)
+            lead = (K, A)
+            stride = A * T * n if in_proof_stride is None else int(in_proof_stride)
+            d_arg, n_arg, on_dev = C.c_void_p(dens_dev_ptr), None if nums_dev_ptr is None else C.c_void_p(nums_dev_ptr), 1
+        out = None if out_dev_ptr is not None else np.empty(lead + (T + 1, n), np.uint64)
+        totals = np.zeros((K, A), np.uint64)
+        _chk(load_library().glp_running_columns(self._h, int(kind), K, A, T, int(log_n), n_arg, d_arg, stride, on_dev,
+                                                C.c_void_p(out_dev_ptr) if out is None else _p(out), 0 if out is not None else 1, _p(totals)))
+        return out, totals
 
     def pow_search_many(self, hasher, sponge_states, pending_inputs, bits):
         """glp_pow_search_many: sponge_states [K][12], pending_inputs [K][num_pending] (num_pending < 8) -> the K smallest witnesses"""
@@ -756,6 +796,7 @@ class GateProgram:
 
     def __init__(self, ctx, handle, num_params, num_oracles):
         self.ctx, self._h, self.num_params, self.num_oracles = ctx, handle, num_params, num_oracles
+        self.num_out = 0
 
     def sums(self, oracles, sub_bits, alphas, params=None, out_dev_ptr=None):
         """glp_gate_program_sums: the program on every point of the coset 7 <W_M>, M = n << sub_bits, natural order.  oracles: the
@@ -775,6 +816,36 @@ class GateProgram:
         out = None if out_dev_ptr is not None else np.empty((K, nch, M) if al.ndim == 2 else (nch, M), np.uint64)
         _chk(load_library().glp_gate_program_sums(self.ctx._h, self._h, K, hs, int(sub_bits), nch, _p(al), None if pr is None or not pr.size else _p(pr),
                                                   C.c_void_p(out_dev_ptr) if out is None else _p(out), 0 if out is not None else 1))
+        return out
+
+    def rows(self, inputs, params=None, in_dev_ptrs=None, out_dev_ptr=None):
+        """glp_gate_program_rows: the program on the n rows of H; EMIT number t is column t of the result.  The program is a single
+        gate closed by END IMM(1).  inputs: one array per oracle the program names, values on H: [oracle_cols[o]][n] (shared by all
+        proofs) or [num_proofs][oracle_cols[o]][n].  params [num_params] for one proof: returns [num_out][n]; [num_proofs][num_params],
+        or any input with a leading [num_proofs]: [num_proofs][num_out][n].  in_dev_ptrs: the inputs are in HBM at these pointers and
+        `inputs` holds their shapes instead.  out_dev_ptr: the values go to that HBM pointer and None is returned."""
+        on_dev = in_dev_ptrs is not None
+        ins = [tuple(int(v) for v in i) for i in inputs] if on_dev else [_a(i) for i in inputs]
+        shapes = ins if on_dev else [i.shape for i in ins]
+        if len(shapes) != self.num_oracles or (on_dev and len(in_dev_ptrs) != len(shapes)):
+            raise GlpError(-1, "%d inputs, the program reads %d" % (len(shapes), self.num_oracles))
+        if any(len(s) not in (2, 3) or s[-1] & (s[-1] - 1) or s[-1] != shapes[0][-1] or s[-1] == 0 for s in shapes):
+            raise GlpError(-1, "an input is [columns][n] or [num_proofs][columns][n], n one power of two")
+        pr = None if params is None else _a(params)
+        K = pr.shape[0] if pr is not None and pr.ndim == 2 else max([s[0] for s in shapes if len(s) == 3], default=1)
+        many = (pr is not None and pr.ndim == 2) or any(len(s) == 3 for s in shapes)
+        if pr is not None and pr.size != K * self.num_params:
+            raise GlpError(-1, "params has %d elements, expected num_proofs * num_params = %d" % (pr.size, K * self.num_params))
+        n = shapes[0][-1]
+        ptrs = (C.c_void_p * len(shapes))(*(in_dev_ptrs if on_dev else [i.ctypes.data for i in ins]))
+        members = (C.c_uint32 * len(shapes))(*[s[0] if len(s) == 3 else 1 for s in shapes])
+        out = None
+        if out_dev_ptr is None:
+            out = np.empty((K, self.num_out, n) if many else (self.num_out, n), np.uint64)
+        _chk(load_library().glp_gate_program_rows(self.ctx._h, self._h, K, n.bit_length() - 1, ptrs, members, 1 if on_dev else 0,
+                                                  None if pr is None or not pr.size else _p(pr),
+                                                  C.c_void_p(out_dev_ptr) if out is None else _p(out if out.size else np.empty(1, np.uint64)),
+                                                  0 if out is not None else 1))
         return out
 
     def eval_ext(self, points, openings, alphas, params=None, out_dev_ptr=None):

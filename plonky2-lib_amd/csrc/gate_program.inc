@@ -100,6 +100,10 @@ struct glp_gate_program {
     u32 maxc = 0;                  // the largest number of EMITs in one gate
     u32 cols_named = 0;            // distinct (oracle, polynomial) pairs the program reads: the stage record's bytes
     u32 next_mask = 0;             // bit o: the program reads a COL_NEXT of oracle o (zeta_check.inc asks for at_next only then)
+    // the shape trace_program.inc asks for (one gate closed by END IMM(1)): the number of ENDs, the index of the first one, and the
+    // last END's operand kind and, for an IMM, its pool word
+    u32 num_ends = 0, first_end = 0, end_kind = 0;
+    u64 end_word = 0;
 };
 
 namespace {
@@ -207,6 +211,11 @@ int glp_gate_program_create(glp_ctx *c, const glp_gate_program_desc *d, glp_gate
     p->nregs = d->num_regs; p->nparams = d->num_params; p->noracles = d->num_oracles;
     for (u32 o = 0; o < d->num_oracles; o++) p->oracle_cols[o] = d->oracle_cols[o];
     p->maxc = info.maxc; p->cols_named = info.cols_named; p->next_mask = info.next_mask;
+    for (u32 i = 0; i < d->num_instructions; i++)
+        if (((u32)d->code[i] & 15) == GLP_GP_OP_END && ++p->num_ends == 1) p->first_end = i;
+    const u32 end_a = (u32)(d->code[d->num_instructions - 1] >> GLP_GP_A_SHIFT) & ((1u << GLP_GP_OPERAND_BITS) - 1);
+    p->end_kind = end_a & 7;
+    if (p->end_kind == GLP_GP_IMM) p->end_word = d->pool[end_a >> 3];
     std::vector<u64> img((size_t)p->code_words + p->npool, 0);
     memcpy(img.data(), d->code, (size_t)p->ninstr * 8);
     if (p->npool) memcpy(img.data() + p->code_words, d->pool, (size_t)p->npool * 8);
