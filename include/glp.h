@@ -836,6 +836,38 @@ GLP_API int glp_witness_fill(glp_ctx *ctx, const glp_circuit *circuit, uint64_t 
 /* role_out[col] for rows of gate `gate_index`: 1 = written by glp_witness_fill, 2 = read as a generator input, 0 = untouched */
 GLP_API int glp_witness_columns(const glp_circuit *circuit, uint32_t gate_index, uint8_t *role_out /* [num_wires] */);
 
+/* ---- witness checker: which gate, row, constraint or copy does a witness break ----------------------------------
+ * A witness that does not satisfy its circuit goes through glp_prove without complaint and yields a proof that every verifier
+ * rejects with "Mismatch between evaluation and opening of quotient polynomial".  glp_witness_check evaluates, on the rows of H,
+ * every gate's unfiltered constraints (the bodies the quotient kernels evaluate on the LDE) and every copy constraint, for
+ * num_proofs witnesses [num_proofs][num_wires][n] of one circuit in one call, and names what fails.  GLP_OK = the check ran; the
+ * verdict is in the reports (as with glp_fri_verify_many): a witness satisfies the circuit iff its three counts are 0.
+ *   constraints  the gate of a row is read as glp_witness_fill reads it (the selector polynomial of its group holds the gate index,
+ *                every other selector UNUSED; a row whose selectors name no gate is skipped); constraint k is the gate's k-th
+ *                constraint in its own order, k < glp_gate.num_constraints.  PublicInputGate is checked against the Poseidon hash
+ *                of public_inputs[k], the hash glp_prove computes.
+ *   copies       routed position (column j, row i), j < num_routed_wires, fails iff wires[j][i] != wires[j'][i'] where
+ *                sigmas[j][i] == k_is[j'] * w_n^i'.
+ * Refusals (all GLP_ERR_ARG, before the first gate launch): a null pointer; num_proofs outside 1..4096; public_inputs == NULL for a
+ * circuit with public inputs; a host wire word >= p, named by proof and word index (device wires are reduced as they are loaded);
+ * a sigma value that is k_is[j'] * w_n^i' for no (j', i'), named as sigmas[j][i] -- a malformed circuit, not a bad witness.
+ * The witness is only read.  The first check of a circuit decodes its sigmas into positions and keeps them with the circuit (4 bytes per
+ * routed position, freed by glp_circuit_free); later checks of any number of witnesses reuse them.  rows_failed_by_gate_out (NULL or [num_proofs][num_gates]) counts the failing rows per gate. */
+typedef struct {
+    uint64_t failed_constraints;  /* (row, constraint) pairs whose unfiltered value is not 0 mod p */
+    uint64_t failed_rows;         /* rows with at least one of them */
+    uint64_t failed_copies;       /* routed positions (column, row) whose wire differs from the wire at sigma(column, row) */
+    /* first failing constraint in (row, constraint) order; meaningful iff failed_constraints != 0 */
+    uint64_t row;  uint32_t gate, constraint;  uint64_t value;      /* value canonical, != 0 */
+    /* first failing copy in (row, column) order; meaningful iff failed_copies != 0 */
+    uint64_t copy_row;  uint32_t copy_col, to_col;  uint64_t to_row, copy_value, to_value;
+} glp_witness_report;
+GLP_API int glp_witness_check(glp_ctx *ctx, const glp_circuit *circuit, uint32_t num_proofs,
+                              const uint64_t *wires /* [num_proofs][num_wires][n] */, int wires_on_device,
+                              const uint64_t *public_inputs /* [num_proofs][num_public_inputs] or NULL if the circuit has none */,
+                              glp_witness_report *reports_out /* [num_proofs] */,
+                              uint64_t *rows_failed_by_gate_out /* NULL or [num_proofs][num_gates] */);
+
 /* ---- the same proof, stepped by the caller's own transcript -------------------------------------------------
  * `prove_with_partition_witness` is Fiat-Shamir glue around six device stages.  A Rust integration that keeps
  * plonky2's own `Challenger` (so that the transcript is the fork's by construction) calls the stages one by one:

@@ -81,6 +81,26 @@ class _ExtOpenings(C.Structure):
     _fields_ = [("at", C.c_void_p), ("at_next", C.c_void_p), ("proof_stride", C.c_size_t)]
 
 
+class _WitnessReport(C.Structure):
+    _fields_ = [("failed_constraints", C.c_uint64), ("failed_rows", C.c_uint64), ("failed_copies", C.c_uint64), ("row", C.c_uint64),
+                ("gate", C.c_uint32), ("constraint", C.c_uint32), ("value", C.c_uint64), ("copy_row", C.c_uint64), ("copy_col", C.c_uint32),
+                ("to_col", C.c_uint32), ("to_row", C.c_uint64), ("copy_value", C.c_uint64), ("to_value", C.c_uint64)]
+
+
+# GLP_GATE_* of include/glp.h and the names of the gate types (19 is unassigned)
+(GATE_NOOP, GATE_CONSTANT, GATE_PUBLIC_INPUT, GATE_ARITHMETIC, GATE_POSEIDON, GATE_U32_INTERLEAVE, GATE_UNINTERLEAVE_U32, GATE_UNINTERLEAVE_B32,
+ GATE_U32_ARITHMETIC, GATE_U32_ADD_MANY, GATE_U32_SUBTRACTION, GATE_U32_RANGE_CHECK, GATE_COMPARISON, GATE_BASE_SUM, GATE_RANDOM_ACCESS,
+ GATE_ARITHMETIC_EXTENSION, GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING_EXTENSION) = range(19)
+GATE_EXPONENTIATION, GATE_COSET_INTERPOLATION, GATE_POSEIDON_MDS = 20, 21, 22
+GATE_TYPE_NAMES = {
+    GATE_NOOP: "NoopGate", GATE_CONSTANT: "ConstantGate", GATE_PUBLIC_INPUT: "PublicInputGate", GATE_ARITHMETIC: "ArithmeticGate",
+    GATE_POSEIDON: "PoseidonGate", GATE_U32_INTERLEAVE: "U32InterleaveGate", GATE_UNINTERLEAVE_U32: "UninterleaveToU32Gate",
+    GATE_UNINTERLEAVE_B32: "UninterleaveToB32Gate", GATE_U32_ARITHMETIC: "U32ArithmeticGate", GATE_U32_ADD_MANY: "U32AddManyGate",
+    GATE_U32_SUBTRACTION: "U32SubtractionGate", GATE_U32_RANGE_CHECK: "U32RangeCheckGate", GATE_COMPARISON: "ComparisonGate",
+    GATE_BASE_SUM: "BaseSumGate", GATE_RANDOM_ACCESS: "RandomAccessGate", GATE_ARITHMETIC_EXTENSION: "ArithmeticExtensionGate",
+    GATE_MUL_EXTENSION: "MulExtensionGate", GATE_REDUCING: "ReducingGate", GATE_REDUCING_EXTENSION: "ReducingExtensionGate",
+    GATE_EXPONENTIATION: "ExponentiationGate", GATE_COSET_INTERPOLATION: "CosetInterpolationGate", GATE_POSEIDON_MDS: "PoseidonMdsGate",
+}
 LDE_ROW_MAJOR, LDE_COL_MAJOR = 0, 1     # GLP_LDE_* of glp_batch_lde_values
 RUN_SUM, RUN_PRODUCT = 0, 1             # GLP_RUN_* of glp_running_columns
 
@@ -224,6 +244,7 @@ def load_library():
         "glp_prove_batch": [vp, vp, u32, vp, C.c_int, vp, vp],
         "glp_verify_batch": [vp, vp, u32, vp, vp, vp],
         "glp_witness_fill": [vp, vp, vp, C.c_int],
+        "glp_witness_check": [vp, vp, u32, vp, C.c_int, vp, C.POINTER(_WitnessReport), vp],
         "glp_witness_columns": [vp, u32, vp],
         "glp_host_alloc": [vp, sz, C.POINTER(vp)],
         "glp_host_free": [vp, vp],
@@ -1194,6 +1215,30 @@ class Circuit:
         """Row-local witness generation in place on an HBM-resident witness (include/glp.h, glp_witness_fill)."""
         _chk(load_library().glp_witness_fill(self.ctx._h, self._h, C.c_void_p(dev_wires_ptr), 1 if only_advice else 0))
 
+    def check_witness(self, wires=None, public_inputs=None, dev_wires_ptr=None, num_proofs=1, by_gate=False):
+        """glp_witness_check: every gate constraint on the rows of H and every copy constraint of num_proofs witnesses
+        ([num_proofs][num_wires][n]; host array, default desc.wires, or an HBM pointer).  Returns one WitnessReport (num_proofs == 1
+        and a witness without a leading proof axis) or a list of them; with by_gate each report carries rows_failed_by_gate."""
+        K = int(num_proofs)
+        single = K == 1
+        if dev_wires_ptr is None:
+            w = _a(self.desc.wires if wires is None else wires)
+            if w.ndim == 3:
+                K, single = w.shape[0], False
+            if w.size != K * self._wire_elems:
+                raise GlpError(-1, "wires has %d elements, expected num_proofs * num_wires * 2^degree_bits = %d" % (w.size, K * self._wire_elems))
+        pi = _a(self.desc.public_inputs if public_inputs is None and K == 1 else (np.zeros((K, 0), np.uint64) if public_inputs is None else public_inputs))
+        if pi.size != K * self._num_pis:
+            raise GlpError(-1, "%d public inputs, expected num_proofs * %d" % (pi.size, self._num_pis))
+        ng = len(self.desc.gates)
+        rep = (_WitnessReport * K)()
+        rows = np.zeros((K, ng), np.uint64) if by_gate else None
+        _chk(load_library().glp_witness_check(self.ctx._h, self._h, K, C.c_void_p(dev_wires_ptr) if dev_wires_ptr is not None else _p(w),
+                                              0 if dev_wires_ptr is None else 1, _p(pi) if pi.size else None, rep, None if rows is None else _p(rows)))
+        types = [int(g["type"]) for g in self.desc.gates]
+        out = [WitnessReport(rep[k], types, None if rows is None else rows[k]) for k in range(K)]
+        return out[0] if single else out
+
     def witness_columns(self, gate_index):
         """uint8 [num_wires]: 1 = written by witness_fill on rows of that gate, 2 = read as generator input, 0 = untouched."""
         out = np.zeros(int(self.desc.num_wires), np.uint8)
@@ -1226,6 +1271,43 @@ class Circuit:
         _chk(load_library().glp_prove_device(self.ctx._h, self._h, C.c_void_p(dev_wires_ptr), _p(pi) if pi.size else None,
                                              _p(proof)))
         return proof
+
+
+class WitnessReport:
+    """One witness's glp_witness_report (include/glp.h): the three counts, the first failing constraint in (row, constraint) order and the
+    first failing copy in (row, column) order (None where the count is 0); rows_failed_by_gate if it was asked for."""
+    FIELDS = ("failed_constraints", "failed_rows", "failed_copies", "row", "gate", "constraint", "value", "copy_row", "copy_col", "to_col",
+              "to_row", "copy_value", "to_value")
+
+    def __init__(self, c_report, gate_types=None, rows_failed_by_gate=None):
+        for f in self.FIELDS:
+            setattr(self, f, int(getattr(c_report, f)))
+        if not self.failed_constraints:
+            self.row = self.gate = self.constraint = self.value = None
+        if not self.failed_copies:
+            self.copy_row = self.copy_col = self.to_col = self.to_row = self.copy_value = self.to_value = None
+        self.gate_type = gate_types[self.gate] if gate_types is not None and self.gate is not None else None
+        self.rows_failed_by_gate = None if rows_failed_by_gate is None else [int(x) for x in rows_failed_by_gate]
+
+    @property
+    def ok(self):
+        return self.failed_constraints == 0 and self.failed_rows == 0 and self.failed_copies == 0
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f in self.FIELDS)
+
+    def __str__(self):
+        if self.ok:
+            return "witness satisfies the circuit"
+        parts = []
+        if self.failed_constraints:
+            name = GATE_TYPE_NAMES.get(self.gate_type, "type %s" % self.gate_type)
+            parts.append("row %d: gate %d (%s) constraint %d = 0x%x; %d failing rows" % (self.row, self.gate, name, self.constraint, self.value,
+                                                                                     self.failed_rows))
+        if self.failed_copies:
+            parts.append("first broken copy (col %d, row %d) = 0x%x -> (col %d, row %d) = 0x%x; %d broken copies"
+                         % (self.copy_col, self.copy_row, self.copy_value, self.to_col, self.to_row, self.to_value, self.failed_copies))
+        return "; ".join(parts)
 
 
 class StagedWitness:

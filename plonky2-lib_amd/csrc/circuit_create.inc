@@ -91,6 +91,7 @@ void glp_circuit_free(glp_circuit *cc) {
     c->release(cc->dev_gates);
     c->release(cc->dev_limb_desc);
     c->release(cc->dev_consts);
+    c->release(cc->dev_sigma_pos);
     delete cc;
 }
 

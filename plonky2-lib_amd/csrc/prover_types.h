@@ -53,6 +53,7 @@ struct glp_circuit {
     u32 k_ratio = 0;               // g if k_is[j] = g^j for all j with g < 2^32 (then the quotient kernel chains by g), else 0
     u64 *dev_sigmas = nullptr;     // [nr][n] values on H (natural order), for the partial products
     u64 *dev_consts = nullptr;     // [nc][n] values on H (selectors first): which gate sits on a row (witness.hip)
+    mutable u32 *dev_sigma_pos = nullptr;   // [nr][n] sigma decoded into flat positions j' n + i': made by the first glp_witness_check (witness_check.inc)
     // quotient launch plan (built once in glp_circuit_create): which gates share a launch
     u64 *dev_limb_desc = nullptr;  // [group][num_wires][LIMB_SLOTS] column programs of k_quotient_limbs
     // limb gates in groups of up to LIMB_SLOTS = 5 (one set of accumulators in registers per group; the kernel walks the groups in turn):

@@ -1,6 +1,7 @@
 // quotient_kernels.inc -- K6: the gate bodies (gate_terms), the carry-free accumulators they feed (acc.h) and the kernels that evaluate the
 // vanishing polynomial over Z_H.  Included by prover.hip; launched by stage_quotient_eval / stage_quotient_coeffs (prover_stages.inc);
 // the limb-gate launch plan k_quotient_limbs walks is built by build_quotient_plan (circuit_create.inc).
+#include <type_traits>
 #include "acc.h"
 
 struct QArgs {                      // per circuit and FRI domain: the same for every proof of a batch
@@ -66,8 +67,10 @@ __device__ __forceinline__ u64 gate_filter(const QArgs &a, const DevGate &g, siz
 // The unfiltered constraints of one gate, multiplied into the carry-free accumulators ga[c] (+= constraint_k alpha_c^(k0 + k)).
 // HEAD_ONLY (the four base-4 limb gates of plonky2_u32): skip the limb columns -- their range products, base-4 sums and the
 // sum-equals-wire constraints -- which k_quotient_limbs evaluates for all fused gates from ONE read of the wire planes.
-template <int NCH, int TYPE, bool HEAD_ONLY = false>
-__device__ __forceinline__ void gate_terms(const QArgs &a, const QProof &p, const DevGate &g, size_t N, size_t slot, u32 k0, AccHL (&ga)[MAXCH]) {
+// The sink of the constraints is the type of `ga`: the accumulators AccHL[MAXCH] of the quotient kernels, or any other type with a member
+// emit(k, v) that is handed constraint k's value v (a u64, not always canonical) as it stands -- the witness checker's (witness_check.inc).
+template <int NCH, int TYPE, bool HEAD_ONLY = false, class GA>
+__device__ __forceinline__ void gate_terms(const QArgs &a, const QProof &p, const DevGate &g, size_t N, size_t slot, u32 k0, GA &ga) {
     const u32 nt = a.nterms;
     const u64 *W = p.wl + slot;                       // wire j  -> W[j * N]
     const u64 *GC = a.cs + (size_t)a.nsel * N + slot; // gate constant i -> GC[i * N]
@@ -76,7 +79,9 @@ __device__ __forceinline__ void gate_terms(const QArgs &a, const QProof &p, cons
 #define EMIT(k, v)                                                                     \
     do {                                                                               \
         const u64 _v = (v);                                                            \
+        if constexpr (std::is_same<GA, AccHL[MAXCH]>::value) {                         \
         _Pragma("unroll") for (int c2 = 0; c2 < NCH; c2++) acc3_fma(ga[c2], _v, ap + APL_WORDS * ((size_t)c2 * nt + (k)));   \
+        } else ga.emit((u32)(k), _v);                                                  \
     } while (0)
 // Base-4 limb columns LIMBS[j*N], j = COUNT-1 .. 0: eight loads are issued before their values are used (the gate
 // loops have run-time bounds, so the compiler cannot software-pipeline them itself).  Constraint index KIDX may use _j.
