@@ -831,7 +831,14 @@ GLP_API int glp_prove_batch(glp_ctx *ctx, const glp_circuit *circuit, uint32_t n
  * bits, base-4 limbs, inverses, S-box traces, u32 results.  only_advice != 0: only non-routed columns
  * (index >= num_routed_wires) are written, for a caller whose CPU pass already resolved every routed wire -- then the
  * GPU derives the 56 limb columns of the secp256k1 trace (41 % of the witness) and they never cross PCIe.
- * The row's gate is read from the circuit's selector polynomials.  Asynchronous on the ctx stream. */
+ * The row's gate is read from the circuit's selector polynomials.  Asynchronous on the ctx stream.
+ * Inputs outside a gate's domain (plonky2's generators panic or write an unsatisfiable row there) never fault; what is written is
+ * fixed: inputs are read as canonical u64, and a limb or bit generator decomposes only the bits it has wires for -- the low 32 bits
+ * of a u32 result (the result and carry wires themselves get the full field value), num_chunks * chunk_bits bits of a ComparisonGate
+ * input (its result wire is the top bit of 2^chunk_bits + most significant difference), num_limbs digits of a BaseSum value; a
+ * RandomAccessGate copy whose access index is >= 2^bits writes nothing for that copy (the extra constants are still written); a
+ * CosetInterpolationGate row with shift 0 gets shifted point 0.  Such a row fails glp_witness_check, which names it.
+ * tests/witness_fill_restate.py restates all of this, tests/witness_edge_rows.py holds the rows that exercise it. */
 GLP_API int glp_witness_fill(glp_ctx *ctx, const glp_circuit *circuit, uint64_t *dev_wires, int only_advice);
 /* role_out[col] for rows of gate `gate_index`: 1 = written by glp_witness_fill, 2 = read as a generator input, 0 = untouched */
 GLP_API int glp_witness_columns(const glp_circuit *circuit, uint32_t gate_index, uint8_t *role_out /* [num_wires] */);

@@ -97,6 +97,10 @@ def main():
     # version (checksum over header and sections).
     import plonky2_lib_amd as glp
     glp.write_circuit_file(os.path.join(HERE, "zkdsa_2_3_v2.glpc"), desc, with_witness=True)
+    # the 360 Poseidon round constants as data, for the restatements that import nothing from the library or the oracle
+    # (tests/limb_gates_restate.py; pinned there to the reference's known-answer vector)
+    from oracle.gen_poseidon_constants import all_round_constants
+    np.save(os.path.join(HERE, "poseidon_round_constants.npy"), np.array(all_round_constants(), np.uint64))
 
 
 if __name__ == "__main__":

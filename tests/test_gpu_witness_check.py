@@ -1,6 +1,6 @@
-"""glp_witness_check on the GPU (include/glp.h, "witness checker") against tests/witness_check_restate.py and, for the gate types
-that restatement has no body for, against the oracle's prover and verifier as an independent judge.  tests/test_witness_check.py
-pins the restatement first."""
+"""glp_witness_check on the GPU (include/glp.h, "witness checker") against tests/witness_check_restate.py, field for field on every
+gate type, and for the limb gates (types 4-12 and 14) also against the oracle's prover and verifier as a second judge.
+tests/test_witness_check.py and tests/test_limb_gates_restate.py pin the restatement first."""
 import copy
 import ctypes as C
 
@@ -9,6 +9,7 @@ import pytest
 
 import plonky2_lib_amd as glp
 from plonky2_lib_amd import binding, synth
+import limb_gates_restate as lg
 import perm_restate as pr
 import witness_check_restate as wr
 import zeta_identity_recursion as zr
@@ -81,10 +82,19 @@ def test_clean_circuits_cover_every_gate_type():
 
 # ---------------------------------------------------------------------------------------------------- 2. exact reports
 def _roles(desc, t, g):
-    """{role: wire column} to change on a row of gate g, for the gate types the restatement has a body for"""
-    p0 = int(g["p0"])
+    """{role: wire column} to change on a row of gate g: an input, an output and a limb or bit column of the limb gates"""
+    p0, p1 = int(g["p0"]), int(g["p1"])
     if t in synth.RECURSION_GATES:
         return _role_columns(desc, t, g)
+    if t == synth.GATE_COMPARISON:
+        lay = lg.comparison_layout(p0, p1)
+        return {"first input": 0, "result": 2, "most significant diff": 3, "chunk": lay["second_chunks"] + p1 - 1,
+                "chunks equal": lay["equal"], "diff bit": lay["msd_bits"] + lay["chunk_bits"]}
+    if t == synth.GATE_RANDOM_ACCESS:
+        lay = lg.random_access_layout(p0, p1)
+        o = lay["per_copy"] * (lay["copies"] - 1)
+        return {"index": o, "claimed element": o + 1, "index bit": lay["bits"] + p0 * lay["copies"] - 1, "extra constant": lay["extras"]}
+    na = p0 + 3                                   # U32AddMany: wires per op
     return {
         synth.GATE_CONSTANT: {"wire": p0 - 1},
         synth.GATE_PUBLIC_INPUT: {"hash word": 2},
@@ -94,15 +104,21 @@ def _roles(desc, t, g):
         synth.GATE_MUL_EXTENSION: {"multiplicand": 6 * (p0 - 1) + 2, "output": 6 * (p0 - 1) + 5},
         synth.GATE_REDUCING: {"alpha": 3, "coefficient": 6 + p0 - 1, "old accumulator": 4, "output": 0},
         synth.GATE_REDUCING_EXTENSION: {"alpha": 2, "coefficient": 6 + 2 * (p0 - 1) + 1, "accumulator": 6 + 2 * p0, "output": 1},
+        synth.GATE_POSEIDON: {"input": 3, "output": lg.POS_OUT + 5, "swap": lg.POS_SWAP, "delta": lg.POS_DELTA + 1, "first full S-box": lg.POS_FULL0 + 13,
+                              "partial S-box": lg.POS_PARTIAL + 10, "last full S-box": lg.POS_WIRES - 1},
+        synth.GATE_U32_INTERLEAVE: {"input": 2 * (p0 - 1), "output": 2 * (p0 - 1) + 1, "bit": 34 * p0 - 1},
+        synth.GATE_UNINTERLEAVE_U32: {"input": 3 * (p0 - 1), "evens": 3 * (p0 - 1) + 1, "odds": 3 * (p0 - 1) + 2, "bit": 67 * p0 - 1},
+        synth.GATE_UNINTERLEAVE_B32: {"input": 3 * (p0 - 1), "evens": 3 * (p0 - 1) + 1, "odds": 3 * (p0 - 1) + 2, "bit": 67 * p0 - 2},
+        synth.GATE_U32_ARITHMETIC: {"multiplicand": 6 * (p0 - 1) + 1, "addend": 6 * (p0 - 1) + 2, "output low": 6 * (p0 - 1) + 3,
+                                    "output high": 6 * (p0 - 1) + 4, "inverse": 5, "limb": 38 * p0 - 1},
+        synth.GATE_U32_ADD_MANY: {"addend": na * (p1 - 1), "carry in": na * (p1 - 1) + p0, "result": na * (p1 - 1) + p0 + 1,
+                                  "carry out": na * p1 - 1, "result limb": na * p1 + 3, "carry limb": (na + 18) * p1 - 1},
+        synth.GATE_U32_SUBTRACTION: {"x": 5 * (p0 - 1), "borrow in": 5 * (p0 - 1) + 2, "result": 3, "borrow out": 5 * (p0 - 1) + 4, "limb": 21 * p0 - 1},
+        synth.GATE_U32_RANGE_CHECK: {"input": p0 - 1, "limb": 17 * p0 - 1},
     }[t]
 
 
-EXACT = {
-    "arith": lambda: synth.arith_circuit(3, **ARITH3),
-    "ext": lambda: synth.ext_gates_circuit(3),
-    "recursion-default": lambda: synth.recursion_gates_circuit(3, REC(), params=PARAMS["default"]),
-    "recursion-odd": lambda: synth.recursion_gates_circuit(3, REC(), params=PARAMS["odd"]),
-}
+EXACT = {name: make for name, make in CLEAN.items() if not name.endswith("-zk")}            # every family without blinding rows
 
 
 @pytest.mark.parametrize("name", sorted(EXACT))
@@ -121,7 +137,8 @@ def test_reports_equal_the_restatement(ctx, name):
             W = desc.wires.copy()
             _bump(W, col, r, 1 + len(cases))
             cases.append((t, role, W))
-    got = gc.check_witness(np.stack([W for _, _, W in cases]), by_gate=True)         # every case a member of one call
+    pis = np.tile(np.asarray(desc.public_inputs, np.uint64), (len(cases), 1))          # zkdsa has public inputs: one set per member
+    got = gc.check_witness(np.stack([W for _, _, W in cases]), public_inputs=pis, by_gate=True)         # every case a member of one call
     for (t, role, W), rep_gpu in zip(cases, got):
         rep, by_gate = wr.check(desc, W, sigma_map=sm)
         assert rep["failed_constraints"] >= 1, (t, role)
@@ -131,10 +148,13 @@ def test_reports_equal_the_restatement(ctx, name):
 
 def test_exact_reports_cover_every_restated_type():
     seen = {int(g["type"]) for name in EXACT for g in EXACT[name]().gates}
-    assert seen == set(wr.HAS_BODY), sorted(set(wr.HAS_BODY) - seen)
+    assert seen == set(wr.HAS_BODY) == ALL_TYPES, sorted(ALL_TYPES - seen)
 
 
-# ---------------------------------------------------------------------------------------------------- 3. the other types, against the oracle
+# ---------------------------------------------------------------------------------------------------- 3. the limb gates, against the oracle
+OTHER = set(lg.LIMB_GATES)            # the types the oracle campaign judges (the restatement had no body for them when it was written)
+
+
 def gate_width(t, p0, p1):
     """wire columns a gate of the types below constrains, from the gates' definitions (include/glp.h GLP_GATE_*)"""
     cb = -(-p0 // p1) if t == synth.GATE_COMPARISON else 0
@@ -150,7 +170,7 @@ CAMPAIGN_SEED, CAMPAIGN_DRAWS = 2, 8
 
 
 def campaign(desc, seed=CAMPAIGN_SEED, draws=CAMPAIGN_DRAWS):
-    """[(gate index, row, column)]: per gate whose type the restatement has no body for, `draws` single cells on its rows.  Five columns
+    """[(gate index, row, column)]: per gate of a type in OTHER, `draws` single cells on its rows.  Five columns
     are drawn over the whole width of the trace, three over the advice columns the gate leaves unused where it leaves any (a gate as
     wide as the trace -- PoseidonGate at 135 wires, U32RangeCheckGate with 8 limbs at 136 -- constrains every cell of its rows)."""
     rng = np.random.default_rng(seed)
@@ -158,7 +178,7 @@ def campaign(desc, seed=CAMPAIGN_SEED, draws=CAMPAIGN_DRAWS):
     out = []
     for gi, g in enumerate(desc.gates):
         t = int(g["type"])
-        if t in wr.HAS_BODY:
+        if t not in OTHER:
             continue
         rows = zr.gate_rows(desc, gi)
         width = gate_width(t, int(g["p0"]), int(g["p1"]))
@@ -186,11 +206,11 @@ def oracle_verdicts(oracle, desc, cells):
 
 
 def both_verdicts_reached(desc, cells, verdicts):
-    """per gate type of the campaign that leaves a column unused: accepted and rejected both occur"""
+    """per gate type of the campaign (OTHER) that leaves a column unused: accepted and rejected both occur"""
     nw = int(desc.num_wires)
     for gi, g in enumerate(desc.gates):
         t = int(g["type"])
-        if t in wr.HAS_BODY:
+        if t not in OTHER:
             continue
         seen = {v for (gj, _, _), v in zip(cells, verdicts) if gj == gi}
         want = {True, False} if gate_width(t, int(g["p0"]), int(g["p1"])) < nw else {False}
@@ -232,10 +252,10 @@ def test_campaign_against_the_oracle(ctx, oracle, name):
 
 
 def test_campaign_covers_the_other_types():
-    """every gate type without a body in the restatement is on a row of one of the three circuits (and both_verdicts_reached has seen
-    the checker reject a change on it)"""
+    """every limb gate type is on a row of one of the three circuits (and both_verdicts_reached has seen the checker reject a change on
+    it)"""
     seen = {int(g["type"]) for name in CAMPAIGN for g in CAMPAIGN[name]().gates}
-    assert seen - set(wr.HAS_BODY) == ALL_TYPES - set(wr.HAS_BODY)
+    assert seen & OTHER == OTHER == {4, 5, 6, 7, 8, 9, 10, 11, 12, 14} and len(campaign(CAMPAIGN["ecdsa"]())) == 6 * CAMPAIGN_DRAWS
 
 
 # ---------------------------------------------------------------------------------------------------- 4. copies

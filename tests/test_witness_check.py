@@ -113,9 +113,16 @@ def test_restatement_refuses_a_sigma_on_no_coset(circuits):
 
 
 def test_unknown_gate_types_still_get_copies():
+    """every assigned gate type has a body now; the unassigned type 19 is what is left to answer UNKNOWN for"""
     desc = synth.u32_circuit(6)
     rep, by_gate = wr.check(desc)
-    assert rep["failed_constraints"] == wr.UNKNOWN and rep["failed_copies"] == 0 and wr.UNKNOWN in by_gate
+    assert wr.as_tuple(rep) == CLEAN and by_gate == [0] * len(desc.gates)
+    gi = _gate_of_type(desc, synth.GATE_U32_INTERLEAVE)
+    desc.gates[gi] = dict(desc.gates[gi], type=19)
+    assert 19 not in wr.HAS_BODY
+    rep, by_gate = wr.check(desc)
+    assert rep["failed_constraints"] == wr.UNKNOWN and rep["row"] == wr.UNKNOWN and rep["failed_copies"] == 0
+    assert by_gate == [wr.UNKNOWN if i == gi else 0 for i in range(len(desc.gates))]
 
 
 def test_new_function_is_declared_exported_and_bound():

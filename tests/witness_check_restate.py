@@ -2,14 +2,14 @@
 with the report fields of include/glp.h's glp_witness_report and the failing rows per gate.
 
 The gate of a row follows zeta_identity_recursion.gate_rows, the constraints come from zeta_identity_recursion.gate_constraints over
-_Fp (gate types 0-3, 13, 15-18, 20-22), sigma is decoded through a dictionary {k_is[j] w^i: (j, i)}.  Nothing here shares code with
-csrc/.  For a gate type without a body here the rows, gates and copies are still done and the constraint fields are UNKNOWN."""
+_Fp (every assigned gate type; types 4-12 and 14 from tests/limb_gates_restate.py), sigma is decoded through a dictionary {k_is[j] w^i: (j, i)}.  Nothing here shares code with
+csrc/.  For a gate type without a body here (an unassigned one) the rows, gates and copies are still done and the constraint fields are UNKNOWN."""
 import numpy as np
 
 import zeta_identity_recursion as zr
 from zeta_identity import P, _Fp
 
-HAS_BODY = (0, 1, 2, 3, 13, 15, 16, 17, 18, 20, 21, 22)
+HAS_BODY = tuple(range(19)) + (20, 21, 22)        # every assigned gate type; 19 is unassigned
 UNKNOWN = "unknown"
 FIELDS = ("failed_constraints", "failed_rows", "failed_copies", "row", "gate", "constraint", "value", "copy_row", "copy_col", "to_col",
           "to_row", "copy_value", "to_value")

@@ -7,6 +7,7 @@ written from the gates' definitions and share no code with csrc/ or with synth.p
 """
 import numpy as np
 
+import limb_gates_restate as lg
 import zeta_identity as zi
 from zeta_identity import P, _Fp, _Fp2, _alg_mul, challenges, proof_layout
 
@@ -106,9 +107,11 @@ def recursion_constraints(F, g, w):
 
 
 def gate_constraints(F, g, gc, w, pih):
-    """tests/zeta_identity.py's gates and the recursion gates."""
+    """tests/zeta_identity.py's gates, the recursion gates and the limb gates of tests/limb_gates_restate.py (types 4-12 and 14)."""
     if int(g["type"]) in RECURSION + (GATE_BASE_SUM,):
         return recursion_constraints(F, g, w)
+    if int(g["type"]) in lg.LIMB_GATES:
+        return lg.limb_gate_constraints(F, g, gc, w)
     return zi.gate_constraints(F, g, gc, w, pih)
 
 
