@@ -466,8 +466,7 @@ int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg
                 rc = intt_values_to_coeffs(c, in, co, cn, lg);
             } else if (input_kind == BATCH_COEFFS_NATURAL) {
                 StageScope st(c, "bitrev_coeffs", 16.0 * n * cn);
-                for (u32 p0 = 0; p0 < cn && rc == GLP_OK; p0 += 65535)        // bitrev_copy keeps the column in grid.y
-                    rc = bitrev_copy(c, in + (size_t)p0 * n, co + (size_t)p0 * n, std::min<u32>(65535, cn - p0), lg);
+                rc = bitrev_copy(c, in, co, cn, lg);
             } else {
                 StageScope st(c, "copy_coeffs", 16.0 * n * cn);
                 const hipError_t e = hipMemcpyAsync(co, in, (size_t)cn * n * 8, hipMemcpyDeviceToDevice, c->stream);

@@ -130,8 +130,8 @@ struct glp_fri {
             size_t pos = p.first;
             for (const glp_fri_range &r : p.ranges) {
                 const glp_batch *o = ob[r.oracle];
-                for (u32 c0 = 0; c0 < r.num_cols; c0 += 65535) {      // grid.y holds 65535 columns
-                    const u32 cnt = std::min<u32>(65535, r.num_cols - c0);
+                for (u32 c0 = 0; c0 < r.num_cols; c0 += GRID_YZ_MAX) {        // the column rides in grid.y
+                    const u32 cnt = std::min(GRID_YZ_MAX, r.num_cols - c0);
                     hipLaunchKernelGGL(k_open_dot, dim3(nob, cnt, K), dim3(256), 0, c->stream, o->coeffs + (size_t)(r.col_begin + c0) * n, zt[b],
                                        partial + 2 * (size_t)nob * pos, (u32)g.lg, shared(o) ? (size_t)0 : (size_t)o->ncols * n, 2 * n,
                                        nopen * nob * 2);

@@ -32,6 +32,11 @@ constexpr int NTT_INNER_LG = 20;    // above the two-pass limit: per 2^20 block 
 constexpr int NTT_MAX_LG = 24;      //   over A' = n / 2^20 <= 16 blocks (three passes)
 constexpr int NTT_LGB_MAX = 12;
 constexpr int NTT_STRIDED_W = 16;   // columns per strided tile (16 x 8 B = one 128-B line per row)
+// What one launch carries in grid.y (columns, coset planes, outer blocks, channels) or grid.z.  hipDeviceProp_t::maxGridSize is
+// {2^31 - 1, 65536, 65536} on the MI355X; ROCm 7 was seen to run grids past that in y (profiles/r20_wide_columns_tests.txt), but only
+// the reported limit is a promise, and 65535 is inside it on every HIP platform.  Every function whose column count is the caller's
+// walks the columns in ranges of at most this many and offsets its pointers by the range's first column.
+constexpr u32 GRID_YZ_MAX = 65535;
 
 struct NttPlan {
     int lg, lgA, lgB;

@@ -1027,14 +1027,14 @@ static int lde_mid(glp_ctx *c, const u64 *dev_coeffs, u64 *dev_lde, u32 ncols, i
     GLP_HIP(hipGetLastError());
     return GLP_OK;
 }
-// grid.y carries (column, coset plane, outer block): at most 65535.  Wide inputs (the K-proof batches of glp_prove_batch:
+// grid.y carries (column, coset plane, outer block): at most GRID_YZ_MAX.  Wide inputs (the K-proof batches of glp_prove_batch:
 // K * num_wires columns) go through in column chunks.
 int lde_coeffs(glp_ctx *c, const u64 *dev_coeffs, u64 *dev_lde, u32 ncols, int lg, int rate_bits, u64 shift) {
     if (lg < 0 || lg > NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%d outside the supported range 0..%d", lg, NTT_MAX_LG);
     if (rate_bits < 0 || rate_bits > 4) return set_error(GLP_ERR_UNSUPPORTED, "rate_bits=%d outside 0..4", rate_bits);
     if (lg <= 4) return lde_small(c, dev_coeffs, dev_lde, ncols, lg, rate_bits, shift);       // one thread per (column, coset)
     if (lg <= 8) return lde_mid(c, dev_coeffs, dev_lde, ncols, lg, rate_bits, shift);         // all cosets of a column in one tile
-    const u32 per = 65535u >> (rate_bits + (lg > c->two_pass_lg ? lg - NTT_INNER_LG : 0));
+    const u32 per = GRID_YZ_MAX >> (rate_bits + (lg > c->two_pass_lg ? lg - NTT_INNER_LG : 0));
     const size_t n = (size_t)1 << lg;
     for (u32 c0 = 0; c0 < ncols; c0 += per)
         GLP_TRY(lde_coeffs_chunk(c, dev_coeffs + (size_t)c0 * n, dev_lde + ((size_t)c0 * n << rate_bits), std::min(per, ncols - c0), lg, rate_bits, shift));
@@ -1046,7 +1046,7 @@ static int lde_coeffs_chunk(glp_ctx *c, const u64 *dev_coeffs, u64 *dev_lde, u32
     GLP_TRY(get_lde_plan(c, lg, rate_bits, shift, &lp));
     const NttPlan *np = lp->ntt;
     const int R = 1 << rate_bits;
-    if (ncols > 65535u || ((u64)ncols * R << np->lgAo) > 65535u)
+    if (ncols > GRID_YZ_MAX || ((u64)ncols * R << np->lgAo) > GRID_YZ_MAX)
         return set_error(GLP_ERR_UNSUPPORTED, "ncols*2^rate_bits*outer blocks=%llu exceeds grid.y", ((unsigned long long)ncols * R) << np->lgAo);
     if (np->lgAo > 0) {
         // three passes: per 2^20 block the two-pass coset transform with shift^A', the outer twiddle, then A' rows at stride 2^20
@@ -1095,7 +1095,7 @@ int intt_values_to_coeffs(glp_ctx *c, const u64 *dev_values, u64 *dev_coeffs, u3
         GLP_HIP(hipGetLastError());
         return GLP_OK;
     }
-    const u32 per = 65535u >> (lg > c->two_pass_lg ? lg - NTT_INNER_LG : 0);
+    const u32 per = GRID_YZ_MAX >> (lg > c->two_pass_lg ? lg - NTT_INNER_LG : 0);
     const size_t n = (size_t)1 << lg;
     for (u32 c0 = 0; c0 < ncols; c0 += per)
         GLP_TRY(intt_chunk(c, dev_values + (size_t)c0 * n, dev_coeffs + (size_t)c0 * n, std::min(per, ncols - c0), lg));
@@ -1105,7 +1105,7 @@ static int intt_chunk(glp_ctx *c, const u64 *dev_values, u64 *dev_coeffs, u32 nc
     if (ncols == 0) return GLP_OK;
     NttPlan *np;
     GLP_TRY(get_ntt_plan(c, lg, &np));
-    if (ncols > 65535u || ((u64)ncols << np->lgAo) > 65535u) return set_error(GLP_ERR_UNSUPPORTED, "ncols=%u exceeds grid.y", ncols);
+    if (ncols > GRID_YZ_MAX || ((u64)ncols << np->lgAo) > GRID_YZ_MAX) return set_error(GLP_ERR_UNSUPPORTED, "ncols=%u exceeds grid.y", ncols);
     if (np->lgAo > 0) {
         const NttPlan *in = np->inner;
         const int lgAo = np->lgAo, lgM = NTT_INNER_LG;
@@ -1134,31 +1134,33 @@ static int intt_chunk(glp_ctx *c, const u64 *dev_values, u64 *dev_coeffs, u32 nc
 }
 
 int bitrev_copy(glp_ctx *c, const u64 *dev_in, u64 *dev_out, u32 ncols, int lg) {
-    if (ncols == 0) return GLP_OK;
     const size_t n = (size_t)1 << lg;
-    dim3 g((unsigned)((n + 255) / 256), ncols);
-    hipLaunchKernelGGL(k_bitrev_copy, g, dim3(256), 0, c->stream, dev_in, dev_out, lg);
-    GLP_HIP(hipGetLastError());
+    for (u32 c0 = 0; c0 < ncols; c0 += GRID_YZ_MAX) {         // the column rides in grid.y
+        const dim3 g((unsigned)((n + 255) / 256), std::min(GRID_YZ_MAX, ncols - c0));
+        hipLaunchKernelGGL(k_bitrev_copy, g, dim3(256), 0, c->stream, dev_in + (size_t)c0 * n, dev_out + (size_t)c0 * n, lg);
+        GLP_HIP(hipGetLastError());
+    }
     return GLP_OK;
 }
 
 int lde_to_natural(glp_ctx *c, const u64 *dev_lde, u64 *dev_out, u32 ncols, int lg, int rate_bits) {
-    if (ncols == 0) return GLP_OK;
     const size_t N = (size_t)1 << (lg + rate_bits);
-    dim3 g((unsigned)((N + 255) / 256), ncols);
-    hipLaunchKernelGGL(k_lde_to_natural, g, dim3(256), 0, c->stream, dev_lde, dev_out, lg, rate_bits);
-    GLP_HIP(hipGetLastError());
+    for (u32 c0 = 0; c0 < ncols; c0 += GRID_YZ_MAX) {         // the column rides in grid.y
+        const dim3 g((unsigned)((N + 255) / 256), std::min(GRID_YZ_MAX, ncols - c0));
+        hipLaunchKernelGGL(k_lde_to_natural, g, dim3(256), 0, c->stream, dev_lde + (size_t)c0 * N, dev_out + (size_t)c0 * N, lg, rate_bits);
+        GLP_HIP(hipGetLastError());
+    }
     return GLP_OK;
 }
 
 int lde_sub_coset_rows(glp_ctx *c, const u64 *dev_lde, size_t member_stride, u32 K, u32 num_cols, int lg, int rate_bits, int sub_bits,
                        u64 row_begin, u64 num_rows, bool row_major, u64 *dev_out) {
     if (num_cols == 0 || num_rows == 0 || K == 0) return GLP_OK;
-    if (sub_bits < 0 || sub_bits > rate_bits || rate_bits > 4 || row_begin + num_rows > ((u64)1 << (lg + sub_bits)) || K > 65535u)
+    if (sub_bits < 0 || sub_bits > rate_bits || rate_bits > 4 || row_begin + num_rows > ((u64)1 << (lg + sub_bits)) || K > GRID_YZ_MAX)
         return set_error(GLP_ERR_ARG, "lde_sub_coset_rows: window or shape out of range");
     if (!row_major) {
-        for (u32 c0 = 0; c0 < num_cols; c0 += 65535) {        // the column rides in grid.y
-            const dim3 g((unsigned)((num_rows + 255) / 256), std::min(65535u, num_cols - c0), K);
+        for (u32 c0 = 0; c0 < num_cols; c0 += GRID_YZ_MAX) {  // the column rides in grid.y
+            const dim3 g((unsigned)((num_rows + 255) / 256), std::min(GRID_YZ_MAX, num_cols - c0), K);
             hipLaunchKernelGGL(k_lde_rows_colmajor, g, dim3(256), 0, c->stream, dev_lde, dev_out, member_stride, lg, rate_bits, sub_bits,
                                row_begin, num_rows, c0, num_cols);
             GLP_HIP(hipGetLastError());
@@ -1185,8 +1187,8 @@ int lde_sub_coset_rows(glp_ctx *c, const u64 *dev_lde, size_t member_stride, u32
 int coset_values_to_planes(glp_ctx *c, const u64 *dev_in, u64 *dev_out, size_t ncols, int lg, int sub_bits) {
     if (sub_bits < 1 || sub_bits > 4) return set_error(GLP_ERR_ARG, "coset_values_to_planes: sub_bits=%d outside 1..4 (0: the values are the one plane)", sub_bits);
     const size_t n = (size_t)1 << lg;
-    for (size_t c0 = 0; c0 < ncols; c0 += 65535) {            // the column rides in grid.y
-        const dim3 g((unsigned)((n + 255) / 256), (unsigned)std::min<size_t>(65535, ncols - c0));
+    for (size_t c0 = 0; c0 < ncols; c0 += GRID_YZ_MAX) {      // the column rides in grid.y
+        const dim3 g((unsigned)((n + 255) / 256), (unsigned)std::min<size_t>(GRID_YZ_MAX, ncols - c0));
         const u64 *in = dev_in + ((c0 * n) << sub_bits);
         u64 *out = dev_out + ((c0 * n) << sub_bits);
         switch (sub_bits) {

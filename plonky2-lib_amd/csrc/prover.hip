@@ -114,9 +114,9 @@ int glp::coset_planes_to_chunk_coeffs(glp_ctx *c, const u64 *pv, u64 *pV, u64 *o
     const u64 gni = inv(pow(shift, (u64)n));
     u64 x = 1;
     for (u32 cidx = 0; cidx < Rq; cidx++) { q.gn_inv_pow[cidx] = x; x = mul(x, gni); }
-    for (u32 c0 = 0; c0 < channels; c0 += 65535) {            // the channel rides in grid.y; the prover's [K][nch] channels fit one launch
+    for (u32 c0 = 0; c0 < channels; c0 += GRID_YZ_MAX) {      // the channel rides in grid.y; the prover's [K][nch] channels fit one launch
         q.V = pV + (size_t)c0 * Rq * n; q.out = out + (size_t)c0 * Rq * n;
-        hipLaunchKernelGGL(k_quotient_combine, dim3(nblk(n), std::min(65535u, channels - c0)), dim3(256), 0, c->stream, q);
+        hipLaunchKernelGGL(k_quotient_combine, dim3(nblk(n), std::min(GRID_YZ_MAX, channels - c0)), dim3(256), 0, c->stream, q);
         GLP_HIP(hipGetLastError());
     }
     return GLP_OK;
