@@ -44,10 +44,13 @@ __global__ __launch_bounds__(256, 4) void k_leaf_hash_lde(const u64 *__restrict_
                                                        u32 ncols, int lg, int rate_bits, size_t lde_stride, size_t dig_stride) {
     lde += (size_t)blockIdx.y * lde_stride; digests += (size_t)blockIdx.y * dig_stride;
     const size_t N = (size_t)1 << (lg + rate_bits);
-    const size_t pos = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (pos >= N) return;
+    // pos::permute_wave runs on the whole wave: lanes past the end hash row 0 again and only their store is masked
+    const size_t pos0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = pos0 < N;
+    const size_t pos = live ? pos0 : 0;
     const u32 r = (u32)(pos >> lg), q = (u32)(pos & (((size_t)1 << lg) - 1));
     const size_t leaf = ((size_t)bitrev32(r, rate_bits) << lg) | bitrev32(q, lg);
+    const pos::MdsOperands mo = pos::mds_operands();
     u64 s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = 0;
@@ -69,10 +72,10 @@ __global__ __launch_bounds__(256, 4) void k_leaf_hash_lde(const u64 *__restrict_
                 for (int i = 0; i < 8; i++)
                     if (c + 8 + i < ncols) nx[i] = p[(size_t)(c + 8 + i) * N];
             }
-            pos::permute(s);
+            pos::permute_wave(s, mo);
         }
     }
-    store_digest(digests + 4 * leaf, s);
+    if (live) store_digest(digests + 4 * leaf, s);
 }
 
 // Latency form of the leaf hash for small trees (N <= glp_ctx::merkle_coop_max): one leaf per 16-lane group, the
@@ -134,8 +137,10 @@ __global__ __launch_bounds__(256) void k_leaf_hash_lde_quad(const u64 *__restric
 // hash_or_noop of row-major leaves [nleaves][leaf_len]
 __global__ __launch_bounds__(256, 4) void k_leaf_hash_rows(const u64 *__restrict__ rows, u64 *__restrict__ digests,
                                                         size_t nleaves, u32 leaf_len) {
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= nleaves) return;
+    const size_t j0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = j0 < nleaves;
+    const size_t j = live ? j0 : 0;
+    const pos::MdsOperands mo = pos::mds_operands();
     u64 s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = 0;
@@ -147,28 +152,30 @@ __global__ __launch_bounds__(256, 4) void k_leaf_hash_rows(const u64 *__restrict
         for (; c + 8 <= leaf_len; c += 8) {
 #pragma unroll
             for (int i = 0; i < 8; i++) s[i] = p[c + i];
-            pos::permute(s);
+            pos::permute_wave(s, mo);
         }
         if (c < leaf_len) {
 #pragma unroll
             for (int i = 0; i < 8; i++)
                 if (c + i < leaf_len) s[i] = p[c + i];
-            pos::permute(s);
+            pos::permute_wave(s, mo);
         }
     }
-    store_digest(digests + 4 * j, s);
+    if (live) store_digest(digests + 4 * j, s);
 }
 
 // one tree level: out[i] = two_to_one(in[2i], in[2i+1])
 __global__ __launch_bounds__(256) void k_merkle_level(const u64 *__restrict__ in, u64 *__restrict__ out, size_t m, size_t dig_stride) {
     in += (size_t)blockIdx.y * dig_stride; out += (size_t)blockIdx.y * dig_stride;
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
+    const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i0 < m;
+    const size_t i = live ? i0 : 0;
+    const pos::MdsOperands mo = pos::mds_operands();
     const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(in + 8 * i);
     ulonglong2 a = src[0], b = src[1], c2 = src[2], d = src[3];
     u64 s[12] = {a.x, a.y, b.x, b.y, c2.x, c2.y, d.x, d.y, 0, 0, 0, 0};
-    pos::permute(s);
-    store_digest(out + 4 * i, s);
+    pos::permute_wave(s, mo);
+    if (live) store_digest(out + 4 * i, s);
 }
 
 // Small levels: one parent hash per 16-lane group (12 lanes active), 16 hashes per 256-thread workgroup.
@@ -200,14 +207,18 @@ __global__ __launch_bounds__(256) void k_merkle_level_quad(const u64 *__restrict
 }
 
 __global__ void k_permute_states(u64 *states, size_t count) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
+    const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i0 < count;
+    const size_t i = live ? i0 : 0;
+    const pos::MdsOperands mo = pos::mds_operands();
     u64 s[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) s[k] = states[12 * i + k];
-    pos::permute(s);
+    pos::permute_wave(s, mo);
+    if (live) {
 #pragma unroll
-    for (int k = 0; k < 12; k++) states[12 * i + k] = s[k];
+        for (int k = 0; k < 12; k++) states[12 * i + k] = s[k];
+    }
 }
 
 // ---- KeccakHash<25> (KeccakGoldilocksConfig): the same tree with Keccak-256 leaves and nodes (keccak.h) ----------------------

@@ -234,6 +234,96 @@ __device__ __forceinline__ void mds_add_nc(u64 s[12], const u64 *rc) {
     }
 }
 
+// ---- the same layer on the matrix pipe ------------------------------------------------------------------
+// The 12x12 matrix has entries <= 49 and a state splits into bytes, so M s is a sum of int8 dot products: what
+// v_mfma_i32_32x32x32_i8 computes (D = A B + C, A 32x32, B 32x32, one byte per entry).  Lane l (c = l & 31, h = l >> 5) supplies
+// A[row c][k = 16h + j] and B[k = 16h + j][col c] in byte j of its 16 operand bytes and receives D[(reg & 3) + 8 (reg >> 2) + 4h][c]
+// in result register reg.  A is made block-diagonal (a row that half h receives is non-zero only at k in [16h, 16h + 16)), so every
+// lane gets 16 dot products of ITS OWN 16 operand bytes: one state per lane as before, no LDS, no shuffles.
+//   B: the 32-bit halves of four state elements (4q .. 4q+3), each byte u as the signed u - 128 (xor 0x80: the instruction is signed);
+//   D register 4 rl + b: row 4g + rl of M against byte b of those halves -> the coefficient M[4g + rl][4q + e] stands at k = 16h + 4e + b.
+// The circulant part of M makes A depend on (q - g) mod 3 only: three operands; M[0][0]'s extra 8 is one multiply-add per half of row 0.
+// Summed over q through C, |D| <= 128 * 256 < 2^16; the row value is then  sum_b D_b 2^(8b) + 128 * rowsum * 0x01010101, formed with
+// two shift-adds and two v_mad_i64_i32 per half.  (al, ah) are the integers mds_add_nc forms, so the outputs are bit-identical.
+// A matrix instruction acts on the whole wave whatever the execution mask: call only where control flow is wave-uniform.
+static __device__ const u32 MDS_C24[24] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20, 17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
+typedef int v4i32 __attribute__((ext_vector_type(4)));
+typedef int v16i32 __attribute__((ext_vector_type(16)));
+struct MdsOperands { v4i32 a[3]; };           // a[(q - g) mod 3]
+__device__ __forceinline__ MdsOperands mds_operands() {
+    const u32 lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const u32 row = lane & 31, h = lane >> 5, rl = row >> 3, b = row & 3;
+    const bool mine = ((row >> 2) & 1) == h;  // rows (reg & 3) + 8 (reg >> 2) + 4h go to half h
+    MdsOperands mo;
+#pragma unroll
+    for (int d = 0; d < 3; d++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) mo.a[d][e] = mine ? (int)(MDS_C24[12 + 4 * d + e - rl] << (8 * b)) : 0;
+    return mo;
+}
+__device__ __forceinline__ long long mad_i64_i32_one(int a, long long k) {       // a + k, k uniform (an SGPR pair)
+    long long o;
+    asm("v_mad_i64_i32 %0, vcc, %1, 1, %2" : "=&v"(o) : "v"(a), "s"(k) : "vcc");
+    return o;
+}
+__device__ __forceinline__ long long mad_i64_i32_one_v(int a, long long k) {     // the same with k in registers
+    long long o;
+    asm("v_mad_i64_i32 %0, vcc, %1, 1, %2" : "=&v"(o) : "v"(a), "v"(k) : "vcc");
+    return o;
+}
+__device__ __forceinline__ long long mad_i64_i32(int a, int b_uniform, long long c) {
+    long long o;
+    asm("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=&v"(o) : "v"(a), "s"(b_uniform), "v"(c) : "vcc");
+    return o;
+}
+// one 32-bit half of row rl of the group: bytes 2 and 3 of  sum_b D[4 rl + b] 2^(8b) + k  on top of KTERM (bytes 0 and 1, the bias, the constant)
+#define GLP_MDS_WAVE_ROW(D, RL, KTERM) \
+    mad_i64_i32((D)[4 * (RL) + 2] + ((D)[4 * (RL) + 3] << 8), c64k, KTERM)
+__device__ __forceinline__ void mds_add_wave(u64 s[12], const u64 *rc, const MdsOperands &mo) {
+    v4i32 bl[3], bh[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            bl[q][e] = (int)((u32)s[4 * q + e] ^ 0x80808080u);
+            bh[q][e] = (int)((u32)(s[4 * q + e] >> 32) ^ 0x80808080u);
+        }
+    const u32 lo0 = (u32)s[0], hi0 = (u32)(s[0] >> 32);         // M[0][0] = C[0] + 8: the 8 is one multiply-add per half of row 0
+    int c64k = 65536;
+    asm volatile("" : "+s"(c64k));
+    constexpr u64 BIAS = (u64)(128u * 256u) * 0x01010101ull;    // every circulant row sums to 256
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+        // low halves, then high halves into the same sixteen accumulators: 16 live instead of 32
+        long long al[4];
+        {
+            v16i32 d = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int q = 0; q < 3; q++) d = __builtin_amdgcn_mfma_i32_32x32x32_i8(mo.a[(q - g + 3) % 3], bl[q], d, 0, 0, 0);
+#pragma unroll
+            for (int rl = 0; rl < 4; rl++) {
+                const int r = 4 * g + rl, x = d[4 * rl] + (d[4 * rl + 1] << 8);
+                const u64 k = BIAS + (u32)rc[r];
+                al[rl] = GLP_MDS_WAVE_ROW(d, rl, r == 0 ? mad_i64_i32_one_v(x, (long long)((u64)lo0 * 8u + k)) : mad_i64_i32_one(x, (long long)k));
+            }
+        }
+        {
+            v16i32 d = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int q = 0; q < 3; q++) d = __builtin_amdgcn_mfma_i32_32x32x32_i8(mo.a[(q - g + 3) % 3], bh[q], d, 0, 0, 0);
+#pragma unroll
+            for (int rl = 0; rl < 4; rl++) {
+                const int r = 4 * g + rl, x = d[4 * rl] + (d[4 * rl + 1] << 8) + (int)(al[rl] >> 32);
+                const u64 k = BIAS + (rc[r] >> 32);
+                const long long ah = GLP_MDS_WAVE_ROW(d, rl, r == 0 ? mad_i64_i32_one_v(x, (long long)((u64)hi0 * 8u + k)) : mad_i64_i32_one(x, (long long)k));
+                s[r] = fold96_nc(((u64)ah << 32) | (u32)al[rl], (u32)((u64)ah >> 32));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+#undef GLP_MDS_WAVE_ROW
+
 // rounds 3(linear layer)+4..6 merged, 7..22 as four blocks of 4, 23..25 as one block of 3
 static __device__ const pblk::BlkConst<3> PBM[1] = {pblk::make_blk<3, true>(4)};
 static __device__ const pblk::BlkConst<4> PB4[4] = {pblk::make_blk<4, false>(7), pblk::make_blk<4, false>(11),
@@ -304,19 +394,30 @@ static __device__ const FullNext RCN = make_full_next();
 
 // One copy of the S-box layer and of the MDS layer serves both halves (the two full-round phases are the same loop):
 // the whole permutation is ~30 KB of code instead of ~62 KB, inside the 64 KB instruction cache a CU pair shares.
-__device__ __forceinline__ void permute(u64 s[12]) {    // canonical in, canonical out
+// WAVE: the seven full-round linear layers run on the matrix pipe (mds_add_wave); -DGLP_POSEIDON_VALU_MDS keeps them on the VALU everywhere.
+template <bool WAVE>
+__device__ __forceinline__ void permute_body(u64 s[12], const MdsOperands &mo) {    // canonical in, canonical out
+#if defined(GLP_POSEIDON_VALU_MDS)
+    constexpr bool MATRIX = false;
+#else
+    constexpr bool MATRIX = WAVE;
+#endif
+    auto full_mds = [&](const u64 *rcp) __attribute__((always_inline)) {
+        if constexpr (MATRIX) mds_add_wave(s, rcp, mo);
+        else mds_add_nc(s, rcp);
+    };
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = add(s[i], RC[i]);
 #ifdef GLP_POSEIDON_PLAIN_PARTIAL
     int rc = 12;
-    for (int r = 0; r < 4; r++) { sbox_layer_nc(s); mds_add_nc(s, RC + rc); rc += 12; }
+    for (int r = 0; r < 4; r++) { sbox_layer_nc(s); full_mds(RC + rc); rc += 12; }
     for (int r = 0; r < 22; r++) { s[0] = sbox7_nc(s[0]); mds_add_nc(s, RC + rc); rc += 12; }
-    for (int r = 0; r < 3; r++) { sbox_layer_nc(s); mds_add_nc(s, RC + rc); rc += 12; }
+    for (int r = 0; r < 3; r++) { sbox_layer_nc(s); full_mds(RC + rc); rc += 12; }
     sbox_layer_nc(s);
-    mds_add_nc(s, RC_ZERO);
+    full_mds(RC_ZERO);
 #else
 #ifdef GLP_POSEIDON_FLAT       // counting build for profiles/isa_slots.py: the same rounds with no loop at all
-#define GLP_FULL_ROUND(i) sbox_layer_nc(s); mds_add_nc(s, RCN.k[i]);
+#define GLP_FULL_ROUND(i) sbox_layer_nc(s); full_mds(RCN.k[i]);
     GLP_FULL_ROUND(0) GLP_FULL_ROUND(1) GLP_FULL_ROUND(2)
     sbox_layer_nc(s);
     partial_block_nc<3, true>(s, PBM[0]);
@@ -332,7 +433,7 @@ __device__ __forceinline__ void permute(u64 s[12]) {    // canonical in, canonic
         for (int r = 0; r < 4; r++) {
             sbox_layer_nc(s);
             if (half == 0 && r == 3) break;                 // round 3's linear layer is part of the merged block
-            mds_add_nc(s, RCN.k[4 * half + r]);
+            full_mds(RCN.k[4 * half + r]);
         }
         if (half == 0) {
             partial_block_nc<3, true>(s, PBM[0]);           // linear layer of round 3 + rounds 4..6
@@ -346,6 +447,9 @@ __device__ __forceinline__ void permute(u64 s[12]) {    // canonical in, canonic
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = canon(s[i]);
 }
+__device__ __forceinline__ void permute(u64 s[12]) { permute_body<false>(s, MdsOperands{}); }
+// every lane of the wave must arrive, live data or not (mask the store, not the call); mo = mds_operands(), once per kernel
+__device__ __forceinline__ void permute_wave(u64 s[12], const MdsOperands &mo) { permute_body<true>(s, mo); }
 // ---- proof-of-work form -------------------------------------------------------------------------------
 // The grinding loop permutes states that differ in ONE input element (the candidate) and looks at ONE output element.  Round 0
 // therefore collapses to one S-box and twelve multiply-adds per candidate: with c_i = sbox(x_i + rc0_i) for the eleven fixed
@@ -404,7 +508,6 @@ __device__ __forceinline__ u64 permute_tail7(u64 s[12]) { return permute_tail7(s
 // A wave running alone pays ~4 clocks per VALU instruction and 8 per multiply-add, so what counts is the instruction count of one lane:
 // ~120 per round here against ~470 with one state per lane.  Lower throughput (partial rounds idle 11 lanes), so the big levels keep the
 // one-state-per-lane kernel.  x: canonical in, canonical out; all 64 lanes must call it.
-static __device__ const u32 MDS_C24[24] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20, 17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
 template <int J> __device__ __forceinline__ u64 row_bcast(u64 v) {     // every lane of a 16-lane row receives lane J's v (v_mov_b64_dpp)
     return (u64)__builtin_amdgcn_update_dpp((long long)0, (long long)v, 0x150 + J, 0xf, 0xf, true);
 }
@@ -566,6 +669,9 @@ inline void permute(u64 s[12]) {                         // canonical in, canoni
     }
     for (int i = 0; i < 12; i++) s[i] = canon(canon(s[i]));
 }
+struct MdsOperands { int unused; };
+inline MdsOperands mds_operands() { return MdsOperands{}; }
+inline void permute_wave(u64 s[12], const MdsOperands &) { permute(s); }
 inline u64 permute_coop(u64 x, int, int) { return x; }   // device-only; declared for the host parsing pass
 inline void permute_quad(u64 *, int) {}
 // device-only below; declared for the host parsing pass

@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # full rate; multiplies, multiply-adds, every carry-in/carry-out add, compares, selects with an SGPR mask, 64-bit
 # and three-operand forms issue at about half of it.
 HALF_WEIGHT = 1.75     # measured: ~57 vs ~100 lane-ops/clk/CU (profiles/r01_ubench_opcode_rates.txt)
+MFMA_SLOTS = 16        # 32 cycles of the SIMD's matrix pipe per v_mfma_i32_32x32x32_i8, in 2-cycle slots
 FULL = {"v_add_u32_e32", "v_sub_u32_e32", "v_subrev_u32_e32", "v_xor_b32_e32", "v_and_b32_e32", "v_or_b32_e32", "v_mov_b32_e32",
         "v_lshrrev_b32_e32", "v_not_b32_e32", "v_cndmask_b32_e32", "v_accvgpr_write_b32", "v_accvgpr_read_b32"}
 
@@ -40,16 +41,20 @@ def main():
             continue
         m = re.match(r"^\s+([vs]_\w+|ds_\w+|global_\w+)(.*)", l)
         if m:
-            if m.group(1).startswith("s_cbranch") and any(lab in m.group(2) for lab in labels):
+            if m.group(1).startswith("s_cbranch") and m.group(2).strip() in labels:
                 raise SystemExit("backward branch in the flat build: loops were not fully unrolled")
             ops.append(m.group(1))
     c = collections.Counter(ops)
-    valu = sum(v for k, v in c.items() if k.startswith("v_"))
-    slots = sum(v * (1.0 if k in FULL else HALF_WEIGHT) for k, v in c.items() if k.startswith("v_"))
+    # matrix instructions are not VALU work: counted on a line of their own.  One v_mfma_i32_32x32x32_i8 keeps the SIMD's matrix pipe for 32 cycles
+    # = 16 slots, and profiles/r21_poseidon_mfma.txt measures that other waves' VALU work does not hide them: the last figure adds them in full
+    mfma = sum(v for k, v in c.items() if k.startswith("v_mfma"))
+    valu = sum(v for k, v in c.items() if k.startswith("v_") and not k.startswith("v_mfma"))
+    slots = sum(v * (1.0 if k in FULL else HALF_WEIGHT) for k, v in c.items() if k.startswith("v_") and not k.startswith("v_mfma"))
     out = {"build": "-DGLP_POSEIDON_FLAT (all round loops unrolled; the shipped build keeps them rolled: same instructions per round)",
            "mads_per_permutation": c["v_mad_u64_u32"], "valu_instructions": valu, "s_nop": c["s_nop"],
            "full_rate_instructions": sum(v for k, v in c.items() if k in FULL),
-           "slots_per_permutation": slots, "top_opcodes": dict(c.most_common(14))}
+           "slots_per_permutation": slots, "mfma_instructions": mfma, "matrix_pipe_slots": MFMA_SLOTS * mfma,
+           "slots_with_matrix_pipe": slots + MFMA_SLOTS * mfma, "top_opcodes": dict(c.most_common(14))}
     json.dump(out, sys.stdout, indent=1)
     print()
 
