@@ -13,6 +13,9 @@
 //                 total_c and clears it.  Neither has a term bound in reach (2^32 terms).
 // Lane mapping and output are k_perm_quotient's: a block owns 256 consecutive natural indices, lane t computes (plane t / QL, slot
 // t % QL), QL = 256 >> sub_bits, and the results change places in a [plane][slot] tile of pitch QL + 1 behind one barrier.
+// The fetch / decode / dispatch loop below exists three times -- here, in k_gate_program_ext (zeta_check.inc) and in
+// k_gate_program_rows (trace_program.inc) -- and a change to the format belongs in all three: one walker over a machine type made
+// k_gate_program slower (profiles/r22_seam_one_body.txt).
 struct GPArgs {
     const u64 *code;                      // instruction words, zero-padded to a multiple of 4 (opcode 0 does nothing; the check refuses it)
     const u64 *pool;
@@ -183,6 +186,18 @@ int gate_program_check(const char *fn, const glp_gate_program_desc *d, GPInfo &i
     info.cols_named = (u32)(std::unique(named.begin(), named.end()) - named.begin());
     return GLP_OK;
 }
+// what the three evaluators (glp_gate_program_sums, _eval_ext, _rows) ask of the handle, and of the params that go with it
+int gate_program_handle_check(const char *fn, const glp_ctx *c, const glp_gate_program *p) {
+    GLP_REQUIRE(c, "%s: ctx is null", fn);
+    GLP_REQUIRE(p, "%s: program is null", fn);
+    GLP_REQUIRE(p->ctx == c, "%s: program belongs to another ctx", fn);
+    return GLP_OK;
+}
+int gate_program_params_check(const char *fn, const glp_gate_program *p, const u64 *params, u32 K) {
+    GLP_REQUIRE(params || p->nparams == 0, "%s: params is null, the program has num_params = %u", fn, p->nparams);
+    if (p->nparams) GLP_TRY(perm_challenges_check(fn, "params", params, K, p->nparams));
+    return GLP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -240,13 +255,11 @@ void glp_gate_program_free(glp_gate_program *p) {
 int glp_gate_program_sums(glp_ctx *c, const glp_gate_program *p, uint32_t num_proofs, const glp_batch *const *oracles, uint32_t sub_bits,
                           uint32_t num_challenges, const uint64_t *alphas, const uint64_t *params, uint64_t *out, int out_on_device) {
     static const char *fn = "glp_gate_program_sums";
-    GLP_REQUIRE(c, "%s: ctx is null", fn);
-    GLP_REQUIRE(p, "%s: program is null", fn);
-    GLP_REQUIRE(p->ctx == c, "%s: program belongs to another ctx", fn);
+    GLP_TRY(gate_program_handle_check(fn, c, p));
     GLP_REQUIRE(oracles, "%s: oracles is null", fn);
     GLP_REQUIRE(out, "%s: out is null", fn);
     const u32 K = num_proofs, nch = num_challenges;
-    GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
+    GLP_TRY(seam_num_proofs_check(fn, K));
     GLP_REQUIRE(nch >= 1 && nch <= (u32)MAXCH, "%s: num_challenges = %u outside 1..%d", fn, nch, MAXCH);
     for (u32 o = 0; o < p->noracles; o++) {
         const glp_batch *b = oracles[o];
@@ -261,8 +274,7 @@ int glp_gate_program_sums(glp_ctx *c, const glp_gate_program *p, uint32_t num_pr
     const u32 lg = (u32)oracles[0]->lg, rb = (u32)oracles[0]->rate_bits;
     GLP_REQUIRE(sub_bits <= rb, "%s: sub_bits = %u is more than rate_bits = %u", fn, sub_bits, rb);
     GLP_TRY(perm_challenges_check(fn, "alphas", alphas, K, nch));
-    GLP_REQUIRE(params || p->nparams == 0, "%s: params is null, the program has num_params = %u", fn, p->nparams);
-    if (p->nparams) GLP_TRY(perm_challenges_check(fn, "params", params, K, p->nparams));
+    GLP_TRY(gate_program_params_check(fn, p, params, K));
     GLP_TRY(bind(c));
     const size_t n = (size_t)1 << lg, N = n << rb, M = n << sub_bits, words = (size_t)K * nch * M;
     Scratch tmp(c);
@@ -276,10 +288,7 @@ int glp_gate_program_sums(glp_ctx *c, const glp_gate_program *p, uint32_t num_pr
             tk[o] = (u64)(uintptr_t)(b->lde + (b->K == 1 ? 0 : (size_t)k * (b->ncols + b->salt) * N));
         }
         tk += GLP_GP_MAX_ORACLES;
-        for (u32 i = 0; i < nch; i++) {
-            u64 x = 1;
-            for (u32 e = 0; e < p->maxc; e++) { tk[(size_t)i * p->maxc + e] = x; x = mul(x, alphas[(size_t)k * nch + i]); }
-        }
+        for (u32 i = 0; i < nch; i++) alpha_powers(alphas[(size_t)k * nch + i], p->maxc, tk + (size_t)i * p->maxc);
         if (p->nparams) memcpy(tk + (size_t)nch * p->maxc, params + (size_t)k * p->nparams, (size_t)p->nparams * 8);
     }
     u64 *dev_tab;
@@ -297,12 +306,7 @@ int glp_gate_program_sums(glp_ctx *c, const glp_gate_program *p, uint32_t num_pr
         StageScope st(c, "gate_program.sums", 8.0 * M * K * ((double)p->cols_named + nch));
         const dim3 grid(nblk(M), K);
         const size_t lds = ((size_t)p->nregs * 256 + (size_t)nch * PQ_TILE) * 8;      // at most 24 * 2 KB + 4 * 2112 B < 64 KB
-        switch (nch) {
-        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gate_program<1>), grid, dim3(256), lds, c->stream, a); break;
-        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gate_program<2>), grid, dim3(256), lds, c->stream, a); break;
-        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gate_program<3>), grid, dim3(256), lds, c->stream, a); break;
-        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gate_program<4>), grid, dim3(256), lds, c->stream, a); break;
-        }
+        GLP_LAUNCH_NCH(k_gate_program, nch, grid, dim3(256), lds, c->stream, a);
         GLP_HIP(hipGetLastError());
     }
     if (!out_on_device) GLP_TRY(d2h(c, out, dev_out, words * 8));

@@ -11,7 +11,8 @@
 
 // k_perm_quotient: the loop of k_quotient<NCH, 0> (quotient_kernels.inc) -- eight wire and eight sigma loads in flight, the lazy
 // non-canonical product chain, beta k_j x chained by k_ratio when k_j = g^j, Acc160 against whole alpha powers, L_0 from k_l0_table --
-// over operands the seam hands in:
+// over operands the seam hands in.  The loop is a second copy, and a change to the chain belongs in both: a shared __forceinline__ body
+// made k_quotient<2, 0> slower (profiles/r22_seam_one_body.txt).
 //   sg / wl / zl      coset-major LDEs [columns][R][n] of three batches, `*_stride` words from one proof to the next (the leaf width
 //                     times N, so the 4 salt planes of a salted batch are stepped over; 0 for sigmas shared by all proofs); sg points
 //                     at the first sigma column
@@ -142,6 +143,12 @@ int perm_challenges_check(const char *fn, const char *name, const u64 *v, u32 K,
                 (unsigned long long)v[bad == cnt ? 0 : bad]);
     return GLP_OK;
 }
+// the number of proofs one seam call takes in lock step
+constexpr u32 SEAM_MAX_PROOFS = 4096;
+int seam_num_proofs_check(const char *fn, u32 K) {
+    GLP_REQUIRE(K >= 1 && K <= SEAM_MAX_PROOFS, "%s: num_proofs = %u outside 1..%u", fn, K, SEAM_MAX_PROOFS);
+    return GLP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -163,7 +170,7 @@ int glp_perm_zs_commit(glp_ctx *c, const glp_perm_desc *desc, uint32_t num_proof
     GLP_REQUIRE(wires, "%s: wires is null", fn);
     GLP_REQUIRE(sigmas, "%s: sigmas is null", fn);
     const u32 K = num_proofs;
-    GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
+    GLP_TRY(seam_num_proofs_check(fn, K));
     // an argument error here, as every refusal of this entry point (batch_shape_check's is GLP_ERR_UNSUPPORTED)
     GLP_REQUIRE(hasher == GLP_HASH_POSEIDON || hasher == GLP_HASH_KECCAK25, "%s: hasher = %u is not one of GLP_HASH_*", fn, hasher);
     GLP_TRY(batch_shape_check(fn, K, s.nzp, s.lg, rate_bits, cap_height, hasher, BATCH_MAX_BYTES));
@@ -214,7 +221,7 @@ int glp_perm_quotient_values(glp_ctx *c, const glp_perm_desc *desc, uint32_t num
     GLP_REQUIRE(zs_oracle, "%s: zs_oracle is null", fn);
     GLP_REQUIRE(out, "%s: out is null", fn);
     const u32 K = num_proofs;
-    GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
+    GLP_TRY(seam_num_proofs_check(fn, K));
     const glp_batch *sb = sigmas_oracle, *wb = wires_oracle, *zb = zs_oracle;
     GLP_REQUIRE(sb->ctx == c && wb->ctx == c && zb->ctx == c, "%s: an oracle belongs to another ctx", fn);
     GLP_REQUIRE((u32)wb->lg == s.lg && (u32)sb->lg == s.lg && (u32)zb->lg == s.lg, "%s: log_n disagrees: desc %u, sigmas_oracle %d, wires_oracle %d, zs_oracle %d",
@@ -248,8 +255,7 @@ int glp_perm_quotient_values(glp_ctx *c, const glp_perm_desc *desc, uint32_t num
         for (u32 i = 0; i < nch; i++) {
             tk[i] = betas[(size_t)k * nch + i];
             tk[MAXCH + i] = gammas[(size_t)k * nch + i];
-            u64 x = 1;
-            for (u32 e = 0; e < nt; e++) { tk[2 * MAXCH + i * nt + e] = x; x = mul(x, alphas[(size_t)k * nch + i]); }
+            alpha_powers(alphas[(size_t)k * nch + i], nt, tk + 2 * MAXCH + (size_t)i * nt);
         }
     }
     u64 *dev_tab, *l0t;
@@ -263,15 +269,10 @@ int glp_perm_quotient_values(glp_ctx *c, const glp_perm_desc *desc, uint32_t num
 
     PQArgs a;
     memset(&a, 0, sizeof(a));
-    QArgs la;                            // what k_l0_table reads: lg, w_n, n_field, shift_r, zh
-    memset(&la, 0, sizeof(la));
-    const u64 WM = root_of_unity((int)(s.lg + sub_bits)), gn = pow(GEN, (u64)n), wS = root_of_unity((int)sub_bits);
-    for (u32 r = 0; r < S; r++) {
-        la.shift_r[r] = a.shift_r[r] = mul(GEN, pow(WM, (u64)r));
-        la.zh[r] = sub(mul(gn, pow(wS, (u64)r)), 1);          // Z_H(g W_M^(q S + r)) = g^n w_S^r - 1
-        a.zh_inv[r] = inv(la.zh[r]);
-    }
-    la.w_n = a.w_n = root_of_unity((int)s.lg); la.n_field = (u64)n % P; la.lg = s.lg;
+    L0Args la;
+    coset_plane_tables((int)s.lg, (int)sub_bits, S, 1, la, a.zh_inv);
+    memcpy(a.shift_r, la.shift_r, sizeof(u64) * S);
+    a.w_n = la.w_n;
     a.sg = sb->lde + (size_t)sigma_col_begin * N; a.wl = wb->lde; a.zl = zb->lde;
     a.sg_stride = sb->K == 1 ? 0 : (size_t)(sb->ncols + sb->salt) * N;
     a.wl_stride = (size_t)(wb->ncols + wb->salt) * N; a.zl_stride = (size_t)(zb->ncols + zb->salt) * N;
@@ -282,12 +283,7 @@ int glp_perm_quotient_values(glp_ctx *c, const glp_perm_desc *desc, uint32_t num
         hipLaunchKernelGGL(k_l0_table, dim3(nblk(n)), dim3(256), 0, c->stream, la, l0t, S);
         GLP_HIP(hipGetLastError());
         const dim3 grid(nblk(M), K);
-        switch (nch) {
-        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_perm_quotient<1>), grid, dim3(256), 0, c->stream, a); break;
-        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_perm_quotient<2>), grid, dim3(256), 0, c->stream, a); break;
-        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_perm_quotient<3>), grid, dim3(256), 0, c->stream, a); break;
-        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_perm_quotient<4>), grid, dim3(256), 0, c->stream, a); break;
-        }
+        GLP_LAUNCH_NCH(k_perm_quotient, nch, grid, dim3(256), 0, c->stream, a);
         GLP_HIP(hipGetLastError());
     }
     if (!out_on_device) GLP_TRY(d2h(c, out, dev_out, words * 8));

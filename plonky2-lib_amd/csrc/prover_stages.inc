@@ -43,6 +43,16 @@ ProveGeo prove_geo(const glp_circuit *cc, u32 K) {
 inline size_t per_proof(int oracle, size_t words) { return oracle ? words : 0; }
 inline size_t oracle_cols(const glp_batch *const ob[4]) { return (size_t)ob[0]->ncols + ob[1]->ncols + ob[2]->ncols + ob[3]->ncols; }
 
+// a kernel template over the number of challenges, 1..MAXCH (checked by the caller), launched for a run-time nch
+#define GLP_LAUNCH_NCH(kernel, nch, grid, block, lds, stream, ...)                                                  \
+    switch (nch) {                                                                                                  \
+    case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<1>), grid, block, lds, stream, __VA_ARGS__); break;           \
+    case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<2>), grid, block, lds, stream, __VA_ARGS__); break;           \
+    case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<3>), grid, block, lds, stream, __VA_ARGS__); break;           \
+    default: hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<4>), grid, block, lds, stream, __VA_ARGS__); break;          \
+    }
+static_assert(MAXCH == 4, "GLP_LAUNCH_NCH instantiates 1..4");
+
 // K5 without a circuit: what the kernels read of the permutation argument.  The library's own drivers fill it from the circuit
 // (stage_partial_products below), the seam from the caller's description (perm_seam.inc).
 struct PermGeo { int lg; u32 nw, nr, nch, npp, qdf, K; };
@@ -72,12 +82,7 @@ int launch_partial_products(glp_ctx *c, const PermGeo &g, const u64 *wires, cons
         GLP_HIP(hipGetLastError());
         return GLP_OK;
     }
-    switch (nch) {
-    case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pp_rows<1>), dim3(nblocks, K), dim3(256), 0, c->stream, a); break;
-    case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pp_rows<2>), dim3(nblocks, K), dim3(256), 0, c->stream, a); break;
-    case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pp_rows<3>), dim3(nblocks, K), dim3(256), 0, c->stream, a); break;
-    default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pp_rows<4>), dim3(nblocks, K), dim3(256), 0, c->stream, a); break;
-    }
+    GLP_LAUNCH_NCH(k_pp_rows, nch, dim3(nblocks, K), dim3(256), 0, c->stream, a);
     GLP_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_pp_block_tot, dim3(nblocks, nch, K), dim3(256), 0, c->stream, zp, tot, lg, nblocks, a.zp_stride);
     hipLaunchKernelGGL(k_pp_scan_tot, dim3(nch, K), dim3(256), 0, c->stream, tot, nblocks);
@@ -92,18 +97,31 @@ int stage_partial_products(glp_ctx *c, const ProveGeo &g, const u64 *wires, cons
     return launch_partial_products(c, pg, wires, g.cc->dev_sigmas, g.cc->dev_k_is, betas, gammas, chal, zp, dens, tot);
 }
 
+// out[e] = alpha^e, e < count
+void alpha_powers(u64 alpha, u32 count, u64 *out) {
+    u64 x = 1;
+    for (u32 e = 0; e < count; e++) { out[e] = x; x = mul(x, alpha); }
+}
 // alpha powers twice: whole (permutation terms) and as 22-bit limbs of m and m 2^32 (gate constraints, AccHL):
 // whole[nch][nterms], limbs[nch][nterms][APL_WORDS]
 void alpha_power_table(const u64 *alphas, u32 nch, u32 nterms, u64 *whole, u64 *limbs) {
     for (u32 i = 0; i < nch; i++) {
-        u64 x = 1;
-        for (u32 t = 0; t < nterms; t++) {
-            const size_t e = (size_t)i * nterms + t;
-            whole[e] = x;
-            apl_words(x, limbs + APL_WORDS * e);
-            x = mul(x, alphas[i]);
-        }
+        alpha_powers(alphas[i], nterms, whole + (size_t)i * nterms);
+        for (size_t e = (size_t)i * nterms; e < (size_t)(i + 1) * nterms; e++) apl_words(whole[e], limbs + APL_WORDS * e);
     }
+}
+// The evaluated planes of the coset g <W>, W of order 2^(lg + plane_bits): plane i of `planes` is LDE plane r = i step of 2^plane_bits.
+// Fills what k_l0_table reads and zh_inv[i] = 1 / Z_H on that plane.
+void coset_plane_tables(int lg, int plane_bits, u32 planes, u32 step, L0Args &la, u64 *zh_inv) {
+    memset(&la, 0, sizeof(la));
+    const u64 W = root_of_unity(lg + plane_bits), gn = pow(GEN, (u64)1 << lg), wR = root_of_unity(plane_bits);
+    for (u32 i = 0; i < planes; i++) {
+        const u32 r = i * step;
+        la.shift_r[i] = mul(GEN, pow(W, (u64)r));
+        la.zh[i] = sub(mul(gn, pow(wR, (u64)r)), 1);       // Z_H(g W^(q 2^plane_bits + r)) = g^n w_R^r - 1
+        zh_inv[i] = inv(la.zh[i]);
+    }
+    la.w_n = root_of_unity(lg); la.n_field = ((u64)1 << lg) % P; la.lg = (u32)lg;
 }
 // the per-proof quotient arguments over the committed wires and Z oracles.  dev_apow: [K][nch * nterms] whole powers, the limb forms
 // of all proofs after them.  dev_pp: [K][3 MAXCH] betas, gammas, public-input hash; nullptr: one proof, the caller writes them into qp.
@@ -122,14 +140,10 @@ int stage_quotient_eval(glp_ctx *c, const ProveGeo &g, const QProof &qp, const Q
     const u32 nch = g.nch;
     QArgs a;
     a.cs = cc->cs->lde; a.gates = cc->dev_gates; a.k_is = cc->dev_k_is; a.k_ratio = cc->k_ratio;
-    const u64 WN = root_of_unity(g.lg + g.rb), gn = pow(GEN, (u64)g.n), wR = root_of_unity(g.rb);
-    for (u32 rq = 0; rq < g.Rq; rq++) {
-        const u32 r = rq * g.step;
-        a.shift_r[rq] = mul(GEN, pow(WN, (u64)r));
-        a.zh[rq] = sub(mul(gn, pow(wR, (u64)r)), 1);      // Z_H(g W^(qR + r)) = g^n w_R^r - 1
-        a.zh_inv[rq] = inv(a.zh[rq]);
-    }
-    a.w_n = root_of_unity(g.lg); a.n_field = (u64)g.n % P;
+    L0Args la;
+    coset_plane_tables(g.lg, g.rb, g.Rq, g.step, la, a.zh_inv);
+    memcpy(a.shift_r, la.shift_r, sizeof(u64) * g.Rq); memcpy(a.zh, la.zh, sizeof(u64) * g.Rq);
+    a.w_n = la.w_n; a.n_field = la.n_field;
     a.lg = (u32)g.lg; a.rb = (u32)g.rb; a.step = g.step; a.nc = g.nc; a.nsel = d.num_selectors; a.nr = g.nr; a.nw = g.nw;
     a.nch = nch; a.npp = g.npp; a.qdf = g.qdf; a.num_gates = d.num_gates; a.nterms = g.nterms;
     a.many_selectors = d.num_selectors > 1;
@@ -137,7 +151,7 @@ int stage_quotient_eval(glp_ctx *c, const ProveGeo &g, const QProof &qp, const Q
     // gate type compiled on its own; other challenge counts take the monolithic kernel
     a.gate_mode = nch == 2 ? 1 : 0;
     a.l0 = l0t;
-    hipLaunchKernelGGL(k_l0_table, dim3(nblk(g.n)), dim3(256), 0, c->stream, a, l0t, g.Rq);
+    hipLaunchKernelGGL(k_l0_table, dim3(nblk(g.n)), dim3(256), 0, c->stream, la, l0t, g.Rq);
     GLP_HIP(hipGetLastError());
     LightArgs lg_;
     lg_.count = cc->light_count; lg_.arith_gi = cc->arith_gi; lg_.arith_ops = cc->arith_ops;

@@ -37,7 +37,8 @@ __device__ __forceinline__ QProof q_proof(const QProof &p0, const QBatch &b) {
 }
 // L_0 on the evaluated planes.  One thread owns position q of every plane and inverts the Rq denominators n (x_rq - 1)
 // with ONE field inversion (Montgomery's trick) instead of one per point inside k_quotient.
-__global__ __launch_bounds__(256) void k_l0_table(QArgs a, u64 *out, u32 Rq) {
+struct L0Args { u64 shift_r[MAXR], zh[MAXR]; u64 w_n, n_field; u32 lg; };      // filled by coset_plane_tables (prover_stages.inc)
+__global__ __launch_bounds__(256) void k_l0_table(L0Args a, u64 *out, u32 Rq) {
     const size_t n = (size_t)1 << a.lg;
     const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= n) return;
@@ -527,6 +528,8 @@ __global__ __launch_bounds__(256, GATES == 1 ? 3 : 4) void k_quotient(QArgs a, Q
         const u64 t = mul(l0, sub(zx[c], 1));
         _Pragma("unroll") for (int c2 = 0; c2 < NCH; c2++) acc_fma(pa[c2], t, p.apow[c2 * nt + c]);
     }
+    // NOTE: the chunk loop below exists a second time, in k_perm_quotient (perm_seam.inc), over the seam's operands: a change to the
+    // chain belongs in both.  One shared body was tried and measured slower here (profiles/r22_seam_one_body.txt).
     u64 bkx[MAXCH];                                    // beta_c k_j x for the next wire j (k_ratio path)
     _Pragma("unroll") for (int c = 0; c < NCH; c++) bkx[c] = mul_nc(p.betas[c], x);
     const u32 k0 = nch + nch * nchunks;

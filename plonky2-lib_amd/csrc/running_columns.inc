@@ -190,7 +190,7 @@ int glp_running_columns(glp_ctx *c, uint32_t kind, uint32_t num_proofs, uint32_t
     GLP_REQUIRE(totals_out, "%s: totals_out is null", fn);
     GLP_REQUIRE(kind == GLP_RUN_SUM || kind == GLP_RUN_PRODUCT, "%s: kind = %u is not one of GLP_RUN_*", fn, kind);
     const u32 K = num_proofs, A = num_args, T = num_terms, lg = log_n;
-    GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
+    GLP_TRY(seam_num_proofs_check(fn, K));
     GLP_REQUIRE(A >= 1 && A <= 16, "%s: num_args = %u outside 1..16", fn, A);
     GLP_REQUIRE(T >= 1 && T <= 64, "%s: num_terms = %u outside 1..64", fn, T);
     GLP_REQUIRE(lg <= (u32)NTT_MAX_LG, "%s: log_n = %u is more than %d", fn, lg, NTT_MAX_LG);

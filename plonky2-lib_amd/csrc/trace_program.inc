@@ -75,14 +75,12 @@ extern "C" {
 int glp_gate_program_rows(glp_ctx *c, const glp_gate_program *p, uint32_t num_proofs, uint32_t log_n, const uint64_t *const *inputs,
                           const uint32_t *input_members, int inputs_on_device, const uint64_t *params, uint64_t *out, int out_on_device) {
     static const char *fn = "glp_gate_program_rows";
-    GLP_REQUIRE(c, "%s: ctx is null", fn);
-    GLP_REQUIRE(p, "%s: program is null", fn);
-    GLP_REQUIRE(p->ctx == c, "%s: program belongs to another ctx", fn);
+    GLP_TRY(gate_program_handle_check(fn, c, p));
     GLP_REQUIRE(inputs, "%s: inputs is null", fn);
     GLP_REQUIRE(input_members, "%s: input_members is null", fn);
     GLP_REQUIRE(out, "%s: out is null", fn);
     const u32 K = num_proofs, lg = log_n;
-    GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
+    GLP_TRY(seam_num_proofs_check(fn, K));
     GLP_REQUIRE(lg <= (u32)NTT_MAX_LG, "%s: log_n = %u is more than %d", fn, lg, NTT_MAX_LG);
     // the shape: one gate, closed by END IMM(1) (p->end_* were taken down when the program was made)
     GLP_REQUIRE(p->num_ends == 1, "%s: instruction %u, field op: END before the last instruction (the program has %u); a program on the rows of H is a single gate",
@@ -101,8 +99,7 @@ int glp_gate_program_rows(glp_ctx *c, const glp_gate_program *p, uint32_t num_pr
     }
     GLP_REQUIRE((size_t)K * p->maxc <= BATCH_MAX_BYTES / (8 * n), "%s: out too large (num_proofs * num_out * 2^log_n words)", fn);
     GLP_REQUIRE(in_cols <= BATCH_MAX_BYTES / (8 * n), "%s: inputs too large (members * columns * 2^log_n words)", fn);
-    GLP_REQUIRE(params || p->nparams == 0, "%s: params is null, the program has num_params = %u", fn, p->nparams);
-    if (p->nparams) GLP_TRY(perm_challenges_check(fn, "params", params, K, p->nparams));
+    GLP_TRY(gate_program_params_check(fn, p, params, K));
     if (!inputs_on_device)
         for (u32 o = 0; o < p->noracles; o++) GLP_TRY(rows_words_check(fn, "inputs", o, inputs[o], (size_t)input_members[o] * p->oracle_cols[o] * n));
     GLP_TRY(bind(c));

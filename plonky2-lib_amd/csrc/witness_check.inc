@@ -207,7 +207,7 @@ int glp_witness_check(glp_ctx *c, const glp_circuit *cc, uint32_t num_proofs, co
     GLP_REQUIRE(reports_out, "%s: reports_out is null", fn);
     const glp_circuit_desc &d = cc->d;
     const u32 K = num_proofs, lg = d.degree_bits, nw = d.num_wires, nr = d.num_routed_wires, ng = d.num_gates, npi = d.num_public_inputs;
-    GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
+    GLP_TRY(seam_num_proofs_check(fn, K));
     GLP_REQUIRE(public_inputs || npi == 0, "%s: public_inputs is null, the circuit has num_public_inputs = %u", fn, npi);
     const size_t n = (size_t)1 << lg, per_proof = (size_t)nw * n;
     GLP_REQUIRE((size_t)nw * n <= ((size_t)1 << 32), "%s: num_wires * 2^degree_bits = %zu positions exceed the 2^32 a decoded sigma addresses", fn, per_proof);

@@ -194,14 +194,12 @@ int glp_gate_program_eval_ext(glp_ctx *c, const glp_gate_program *p, uint32_t nu
                               const glp_ext_openings *openings, int inputs_on_device, const uint64_t *alphas, const uint64_t *params,
                               uint64_t *out, int out_on_device) {
     static const char *fn = "glp_gate_program_eval_ext";
-    GLP_REQUIRE(c, "%s: ctx is null", fn);
-    GLP_REQUIRE(p, "%s: program is null", fn);
-    GLP_REQUIRE(p->ctx == c, "%s: program belongs to another ctx", fn);
+    GLP_TRY(gate_program_handle_check(fn, c, p));
     GLP_REQUIRE(points, "%s: points is null", fn);
     GLP_REQUIRE(openings, "%s: openings is null", fn);
     GLP_REQUIRE(out, "%s: out is null", fn);
     const u32 K = num_proofs, nch = num_challenges;
-    GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
+    GLP_TRY(seam_num_proofs_check(fn, K));
     GLP_REQUIRE(nch >= 1 && nch <= (u32)MAXCH, "%s: num_challenges = %u outside 1..%d", fn, nch, MAXCH);
     char name[32];
     for (u32 o = 0; o < p->noracles; o++) {
@@ -210,8 +208,7 @@ int glp_gate_program_eval_ext(glp_ctx *c, const glp_gate_program *p, uint32_t nu
     }
     if (!inputs_on_device) GLP_TRY(ext_points_check(fn, "points", points, K, 2));
     GLP_TRY(perm_challenges_check(fn, "alphas", alphas, K, nch));
-    GLP_REQUIRE(params || p->nparams == 0, "%s: params is null, the program has num_params = %u", fn, p->nparams);
-    if (p->nparams) GLP_TRY(perm_challenges_check(fn, "params", params, K, p->nparams));
+    GLP_TRY(gate_program_params_check(fn, p, params, K));
     GLP_TRY(bind(c));
     Scratch tmp(c);
     ZXArgs a;
@@ -237,12 +234,7 @@ int glp_gate_program_eval_ext(glp_ctx *c, const glp_gate_program *p, uint32_t nu
         StageScope stg(c, "gate_program.eval_ext", 8.0 * K * (2.0 * p->cols_named + 2.0 * nch + 2));
         const dim3 grid((K + ZX_BLOCK - 1) / ZX_BLOCK);
         const size_t lds = (size_t)p->nregs * 2 * ZX_BLOCK * 8;      // at most 24 KB
-        switch (nch) {
-        case 1: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gate_program_ext<1>), grid, dim3(ZX_BLOCK), lds, c->stream, a); break;
-        case 2: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gate_program_ext<2>), grid, dim3(ZX_BLOCK), lds, c->stream, a); break;
-        case 3: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gate_program_ext<3>), grid, dim3(ZX_BLOCK), lds, c->stream, a); break;
-        default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gate_program_ext<4>), grid, dim3(ZX_BLOCK), lds, c->stream, a); break;
-        }
+        GLP_LAUNCH_NCH(k_gate_program_ext, nch, grid, dim3(ZX_BLOCK), lds, c->stream, a);
         GLP_HIP(hipGetLastError());
     }
     if (!out_on_device) GLP_TRY(d2h(c, out, dev_out, words * 8));
@@ -264,7 +256,7 @@ int glp_perm_check_zeta(glp_ctx *c, const glp_perm_desc *desc, uint32_t num_proo
     GLP_REQUIRE(quotient, "%s: quotient is null", fn);
     GLP_REQUIRE(status_out, "%s: status_out is null", fn);
     const u32 K = num_proofs, nch = s.nch, chunks = num_quotient_chunks;
-    GLP_REQUIRE(K >= 1 && K <= 4096, "%s: num_proofs = %u outside 1..4096", fn, K);
+    GLP_TRY(seam_num_proofs_check(fn, K));
     GLP_REQUIRE(chunks >= 1 && chunks <= 256, "%s: num_quotient_chunks = %u outside 1..256", fn, chunks);
     GLP_TRY(ext_openings_check(fn, "sigmas", sigmas, s.nr, 0, K, inputs_on_device));
     GLP_TRY(ext_openings_check(fn, "wires", wires, s.nr, 0, K, inputs_on_device));

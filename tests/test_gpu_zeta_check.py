@@ -101,7 +101,7 @@ def _restated_sums(desc, prog, proof, zeta, alphas, pih):
 
 
 # ------------------------------------------------------------------ 1. traced programs at zeta
-@pytest.mark.parametrize("nch", [1, 2, 4])
+@pytest.mark.parametrize("nch", [1, 2, 3, 4])
 @pytest.mark.parametrize("name", ["arith", "ext", "recursion"])
 def test_traced_programs_at_zeta(ctx, proved, name, nch):
     descs, prog, _check, proofs, digests, g = proved(name)
