@@ -57,7 +57,9 @@ GLP_API int glp_device_count(void);
  *   GLP_MERKLE_COOP_MAX   (default 4096), GLP_MERKLE_QUAD_MAX (default 32768): Poseidon leaf hashing spreads one sponge over 12 of 16 lanes up to
  *                         the first many leaves per launch, over a quad of lanes up to the second, and keeps one sponge per lane above it
  *                         (FRI layers alike; Merkle levels: 12 of 16 lanes up to 8192 parents, a quad up to the second threshold)
- *   GLP_HOST_THREADS      (read on the first glp_prove_batch of a context): host threads for the transcripts of a batch */
+ *   GLP_HOST_THREADS      (read on the first glp_prove_batch of a context): host threads for the transcripts of a batch
+ *   GLP_WITNESS_NARROW_MAX (read when a witness plan is made; default 256): a wave of glp_witness_generate with more units than this gets
+ *                         launches of its own while num_proofs is below the CU count ("witness generation, the dataflow half") */
 GLP_API int glp_ctx_create(int device_id, glp_ctx **out);
 GLP_API void glp_ctx_destroy(glp_ctx *ctx);
 GLP_API int glp_ctx_synchronize(glp_ctx *ctx);
@@ -842,6 +844,87 @@ GLP_API int glp_prove_batch(glp_ctx *ctx, const glp_circuit *circuit, uint32_t n
 GLP_API int glp_witness_fill(glp_ctx *ctx, const glp_circuit *circuit, uint64_t *dev_wires, int only_advice);
 /* role_out[col] for rows of gate `gate_index`: 1 = written by glp_witness_fill, 2 = read as a generator input, 0 = untouched */
 GLP_API int glp_witness_columns(const glp_circuit *circuit, uint32_t gate_index, uint8_t *role_out /* [num_wires] */);
+
+/* ---- witness generation, the dataflow half ----------------------------------------------------------------------
+ * The other half of `generate_partial_witness`: values travel between rows along the copy constraints, and a generator runs once its
+ * inputs are known.  The caller hands over only the values it sets itself -- the `pw.set_target` values and whatever its generators
+ * that are NOT gate generators produce -- and the GPU derives every other reachable cell in HBM, for num_proofs witnesses of one
+ * circuit in lock step.  The result is what glp_prove_device / glp_prove_batch (wires_on_device) / glp_witness_check consume.
+ *
+ * UNITS.  A unit is one independent generator of a row (the loops of glp_witness_fill, one by one):
+ *   ConstantGate 1 (no inputs) | ArithmeticGate p0 (unit i reads wires 4i..4i+2, writes 4i+3) | PoseidonGate 1 | U32Interleave p0 |
+ *   UninterleaveToU32 / ToB32 p0 | U32Arithmetic p0 (each owns its limb range) | U32AddMany p1 | U32Subtraction p0 |
+ *   U32RangeCheck p0 (one per input) | Comparison 1 | BaseSum 1 | RandomAccess copies + 1 (the last writes the extra constants, no
+ *   inputs) | ArithmeticExtension, MulExtension p0 | Reducing, ReducingExtension 1 | Exponentiation, CosetInterpolation, PoseidonMds 1 |
+ *   Noop, PublicInput 0.
+ * glp_witness_unit_columns gives a unit's roles as glp_witness_columns does for the row; the union over a gate's units is exactly
+ * glp_witness_columns and no column is written by two units.  glp_witness_num_units is 0 for a bad index.
+ *
+ * THE PLAN (host, once per circuit and input set).  A cell is named by its flat position col * n + row, col < num_wires (the encoding
+ * of the decoded sigmas).  The copy classes are the cycles of the decoded permutation; a non-routed cell is a class of its own.
+ *   Class wave.   The wave of a class is the minimum over its members of: 0 for an input cell; the wave of the unit that writes the
+ *                 member.  A class with neither is never known.
+ *   Source.       The class's source is the member that attains the minimum.  Ties go to the smallest flat position.
+ *   Unit wave.    The wave of a unit is 1 + the maximum wave of the classes of the cells it reads.  It is 1 for a unit with no inputs.
+ *                 Gate constants and selectors are always known.
+ *   Stuck units.  A unit that reads a never-known class is stuck, and so is everything downstream of it.  Dependency cycles are
+ *                 included.  Stuck units are counted.  The first stuck unit is named.  Stuck units are never run.
+ *   Order within wave w.  Wave 0 is the scatter of the inputs.  In every other wave, first every unit of wave w runs.  Then every
+ *                 class whose wave is w is copied from its source to all its other members.
+ *   cell_waves.   The unit's wave for a cell a unit writes (a unit that is not stuck); the class's wave for any other known cell; -1
+ *                 for a cell that is never known.
+ * An input cell whose class also contains a unit's output is allowed (plonky2 allows setting such a target too); if the two values
+ * disagree, glp_witness_check reports the broken copy.  The stuck-unit report tells a caller which inputs it forgot: the named unit
+ * reads a cell (glp_witness_unit_columns role 2, cell_waves -1) that nothing provides.
+ * Refusals of glp_witness_plan_create (GLP_ERR_ARG, each names the field; all but the last two, which need the decoded permutation, are decided before any launch): a null pointer; a
+ * circuit of another context; num_wires * n >= 2^32 (the bound of the decoded sigma, less the one position the planner keeps for
+ * "none"); a cell out of range; a cell listed twice; two input
+ * cells in one copy class (both named); a malformed sigma (as glp_witness_check).  The plan keeps its lists in HBM (per wave the units
+ * (row, gate, unit) sorted by row and the copies (source, destination), the wave offsets, the input positions) and refers to the
+ * circuit, which must outlive it; free it before its context is destroyed.  The planner is host code: at 2^20 rows x 80 routed
+ * columns it walks 84 M cells, and it holds about 40 bytes of host memory per cell of num_wires * n while it runs (5-6 GB at 2^20 x
+ * 136; GLP_ERR_UNSUPPORTED if that cannot be had) and 4 bytes per cell afterwards (cell_waves).
+ *
+ * GENERATION.  glp_witness_generate scatters input_values (host, [num_proofs][num_inputs] in the order of input_cells, canonical: a
+ * word >= p is refused by proof and index) and runs the waves on the ctx stream.  The call first waits for the work queued on that
+ * stream before it and copies the input values (so input_values may be reused at once); the kernels are then asynchronous, like
+ * glp_witness_fill.  A plan holds the value buffer of the generation in flight: it serves one glp_witness_generate at a time, not two
+ * callers at once, although it is passed as const.  num_proofs is 1..4096, the size cap is glp_witness_check's.  Cells the plan never reaches keep what the buffer
+ * held, or are 0 with GLP_WITNESS_GEN_ZERO_FIRST.  For inputs consistent with the circuit the result is a deterministic function of
+ * the inputs; for inconsistent inputs nothing faults and every cell holds a value that one of its sources produced.  Two forms run the
+ * same per-unit body: walked waves (one 256-lane workgroup per proof walks a run of consecutive waves, a block barrier between the
+ * units and the copies of a wave) and wide waves (one launch for a wave's units, one for its copies, grid.y = proof).  A wave is wide
+ * while num_proofs is below the CU count and it holds more than GLP_WITNESS_NARROW_MAX units (environment variable, read when a plan
+ * is made; default 256; 0 makes every wave wide, a value above any wave walks them all).  No workgroup hands anything to another
+ * inside a launch.
+ * glp_witness_read_cells (synchronous) reads cells of generated witnesses back: the public inputs of a generated witness are
+ * themselves outputs (zkdsa's public key and signature), and glp_prove_batch needs them on the host.
+ *
+ * NOT done here: generators that are not gate generators (`EqualityGenerator`, the nonnative generators of the secp256k1 gadgets:
+ * their outputs are inputs here, so that circuit keeps a CPU pass for those cells); zero-knowledge blinding rows (their random advice
+ * comes from no generator: list those cells as inputs); a device-side planner.
+ * tests/witness_plan_restate.py restates the units, the classes, the rule and generation. */
+typedef struct glp_witness_plan glp_witness_plan;
+struct glp_witness_plan_info {           /* a struct tag, not a typedef: the accessor below carries the same name */
+    uint32_t num_waves;                  /* highest wave that holds a unit; 0 if none */
+    uint64_t num_units, num_stuck_units, num_copies, num_cells_known;
+    uint64_t widest_wave_units;
+    uint64_t stuck_row; uint32_t stuck_gate, stuck_unit;   /* first stuck unit in (row, unit) order, iff num_stuck_units */
+};
+#define GLP_WITNESS_GEN_ZERO_FIRST 1u   /* zero the buffers first: plonky2's full_witness leaves every unset wire 0 */
+GLP_API uint32_t glp_witness_num_units(const glp_circuit *c, uint32_t gate_index);   /* 0 for a bad index */
+GLP_API int glp_witness_unit_columns(const glp_circuit *c, uint32_t gate_index, uint32_t unit,
+                                     uint8_t *role_out /* [num_wires], roles of glp_witness_columns */);
+GLP_API int  glp_witness_plan_create(glp_ctx *ctx, const glp_circuit *c, const uint64_t *input_cells, uint32_t num_inputs,
+                                     glp_witness_plan **out);
+GLP_API int  glp_witness_plan_info(const glp_witness_plan *p, struct glp_witness_plan_info *out);
+GLP_API int  glp_witness_plan_cell_waves(const glp_witness_plan *p, int32_t *waves_out /* [num_wires][n] */);
+GLP_API void glp_witness_plan_free(glp_witness_plan *p);
+GLP_API int glp_witness_generate(glp_ctx *ctx, const glp_witness_plan *p, uint32_t num_proofs,
+                                 const uint64_t *input_values /* host [num_proofs][num_inputs], order of input_cells, canonical */,
+                                 uint64_t *dev_wires /* HBM [num_proofs][num_wires][n] */, uint32_t flags);
+GLP_API int glp_witness_read_cells(glp_ctx *ctx, const glp_circuit *c, uint32_t num_proofs, const uint64_t *dev_wires,
+                                   const uint64_t *cells, uint32_t num_cells, uint64_t *out /* host [num_proofs][num_cells] */);
 
 /* ---- witness checker: which gate, row, constraint or copy does a witness break ----------------------------------
  * A witness that does not satisfy its circuit goes through glp_prove without complaint and yields a proof that every verifier

@@ -87,6 +87,12 @@ class _WitnessReport(C.Structure):
                 ("to_col", C.c_uint32), ("to_row", C.c_uint64), ("copy_value", C.c_uint64), ("to_value", C.c_uint64)]
 
 
+class _WitnessPlanInfo(C.Structure):
+    _fields_ = [("num_waves", C.c_uint32), ("num_units", C.c_uint64), ("num_stuck_units", C.c_uint64), ("num_copies", C.c_uint64),
+                ("num_cells_known", C.c_uint64), ("widest_wave_units", C.c_uint64), ("stuck_row", C.c_uint64), ("stuck_gate", C.c_uint32),
+                ("stuck_unit", C.c_uint32)]
+
+
 # GLP_GATE_* of include/glp.h and the names of the gate types (19 is unassigned)
 (GATE_NOOP, GATE_CONSTANT, GATE_PUBLIC_INPUT, GATE_ARITHMETIC, GATE_POSEIDON, GATE_U32_INTERLEAVE, GATE_UNINTERLEAVE_U32, GATE_UNINTERLEAVE_B32,
  GATE_U32_ARITHMETIC, GATE_U32_ADD_MANY, GATE_U32_SUBTRACTION, GATE_U32_RANGE_CHECK, GATE_COMPARISON, GATE_BASE_SUM, GATE_RANDOM_ACCESS,
@@ -246,6 +252,13 @@ def load_library():
         "glp_witness_fill": [vp, vp, vp, C.c_int],
         "glp_witness_check": [vp, vp, u32, vp, C.c_int, vp, C.POINTER(_WitnessReport), vp],
         "glp_witness_columns": [vp, u32, vp],
+        "glp_witness_unit_columns": [vp, u32, u32, vp],
+        "glp_witness_plan_create": [vp, vp, vp, u32, C.POINTER(vp)],
+        "glp_witness_plan_info": [vp, C.POINTER(_WitnessPlanInfo)],
+        "glp_witness_plan_cell_waves": [vp, vp],
+        "glp_witness_plan_free": [vp],
+        "glp_witness_generate": [vp, vp, u32, vp, vp, u32],
+        "glp_witness_read_cells": [vp, vp, u32, vp, vp, u32, vp],
         "glp_host_alloc": [vp, sz, C.POINTER(vp)],
         "glp_host_free": [vp, vp],
         "glp_witness_stage": [vp, vp, vp, u32, C.POINTER(vp)],
@@ -284,6 +297,9 @@ def load_library():
     L.glp_session_end.restype = None
     L.glp_circuit_file_close.restype = None
     L.glp_witness_free.restype = None
+    L.glp_witness_plan_free.restype = None
+    L.glp_witness_num_units.restype = u32
+    L.glp_witness_num_units.argtypes = [vp, u32]
     L.glp_gate_program_free.restype = None
     _lib = L
     return L
@@ -321,9 +337,12 @@ class Context:
         self._h = C.c_void_p()
         _chk(L.glp_ctx_create(int(device), C.byref(self._h)))
         self.device = device
+        self._plans = weakref.WeakSet()    # witness plans: a glp_witness_plan must be freed before its context, host tables and all
 
     def close(self):
         if getattr(self, "_h", None):
+            for plan in list(getattr(self, "_plans", ())):
+                plan.free()
             load_library().glp_ctx_destroy(self._h)
             self._h = None
 
@@ -1245,6 +1264,32 @@ class Circuit:
         _chk(load_library().glp_witness_columns(self._h, int(gate_index), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def witness_units(self, gate_index):
+        """The units of a row of that gate (include/glp.h, "witness generation, the dataflow half"): uint8 [num_units][num_wires], one
+        row of glp_witness_unit_columns roles per unit (1 = written, 2 = read, 0 = untouched)."""
+        L = load_library()
+        nu = int(L.glp_witness_num_units(self._h, int(gate_index)))
+        out = np.zeros((nu, int(self.desc.num_wires)), np.uint8)
+        for u in range(nu):
+            _chk(L.glp_witness_unit_columns(self._h, int(gate_index), u, out[u].ctypes.data_as(C.c_void_p)))
+        return out
+
+    def witness_plan(self, input_cells):
+        """glp_witness_plan_create: input_cells = flat positions col * n + row of the cells the caller sets -> WitnessPlan."""
+        cells = _a(input_cells).reshape(-1)
+        h = C.c_void_p()
+        _chk(load_library().glp_witness_plan_create(self.ctx._h, self._h, _p(cells) if cells.size else None, cells.size, C.byref(h)))
+        plan = WitnessPlan(self, h, cells.size)
+        self.ctx._plans.add(plan)
+        return plan
+
+    def read_cells(self, dev_wires_ptr, cells, K=1):
+        """glp_witness_read_cells: the cells (flat positions) of K HBM-resident witnesses -> uint64 [K][len(cells)]."""
+        cells = _a(cells).reshape(-1)
+        out = np.empty((int(K), cells.size), np.uint64)
+        _chk(load_library().glp_witness_read_cells(self.ctx._h, self._h, int(K), C.c_void_p(dev_wires_ptr), _p(cells), cells.size, _p(out)))
+        return out
+
     def stage_witness(self, host_wires, routed_only=False):
         """glp_witness_stage: start uploading a witness on the context's copy stream ([num_wires][n], or with routed_only the routed
         columns [num_routed_wires][n] -- the advice columns are then derived on the GPU); returns a StagedWitness for prove_staged."""
@@ -1308,6 +1353,55 @@ class WitnessReport:
             parts.append("first broken copy (col %d, row %d) = 0x%x -> (col %d, row %d) = 0x%x; %d broken copies"
                          % (self.copy_col, self.copy_row, self.copy_value, self.to_col, self.to_row, self.to_value, self.failed_copies))
         return "; ".join(parts)
+
+
+class WitnessPlan:
+    """A glp_witness_plan (include/glp.h, "witness generation, the dataflow half"): which unit runs in which wave and which cell is
+    copied from which, for one circuit and one set of input cells.  The circuit must outlive it; closing the context frees the plans
+    made on it first (glp_witness_plan_free needs the context alive), so no order of free() and close() leaks the plan's host tables.
+    One plan serves one generate() at a time."""
+    INFO = ("num_waves", "num_units", "num_stuck_units", "num_copies", "num_cells_known", "widest_wave_units", "stuck_row", "stuck_gate",
+            "stuck_unit")
+
+    def __init__(self, circuit, handle, num_inputs):
+        self.circuit, self._h, self.num_inputs = circuit, handle, int(num_inputs)
+
+    @property
+    def info(self):
+        """dict of glp_witness_plan_info; the stuck_* fields are None unless num_stuck_units."""
+        raw = _WitnessPlanInfo()
+        _chk(load_library().glp_witness_plan_info(self._h, C.byref(raw)))
+        out = {f: int(getattr(raw, f)) for f in self.INFO}
+        if not out["num_stuck_units"]:
+            out["stuck_row"] = out["stuck_gate"] = out["stuck_unit"] = None
+        return out
+
+    def cell_waves(self):
+        d = self.circuit.desc
+        out = np.empty((int(d.num_wires), 1 << int(d.degree_bits)), np.int32)
+        _chk(load_library().glp_witness_plan_cell_waves(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def generate(self, dev_ptr, inputs, K=1, zero_first=False):
+        """glp_witness_generate: inputs [K][num_inputs] in the order of the plan's input cells -> K witnesses at dev_ptr
+        ([K][num_wires][n] in HBM).  Asynchronous on the context's stream."""
+        v = _a(inputs).reshape(-1)
+        if v.size != int(K) * self.num_inputs:
+            raise GlpError(-1, "inputs has %d elements, expected num_proofs * num_inputs = %d" % (v.size, int(K) * self.num_inputs))
+        _chk(load_library().glp_witness_generate(self.circuit.ctx._h, self._h, int(K), _p(v) if v.size else None, C.c_void_p(dev_ptr),
+                                                 1 if zero_first else 0))
+
+    def free(self):
+        if getattr(self, "_h", None):
+            if getattr(self.circuit.ctx, "_h", None):
+                load_library().glp_witness_plan_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class StagedWitness:

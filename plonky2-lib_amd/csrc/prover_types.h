@@ -53,7 +53,7 @@ struct glp_circuit {
     u32 k_ratio = 0;               // g if k_is[j] = g^j for all j with g < 2^32 (then the quotient kernel chains by g), else 0
     u64 *dev_sigmas = nullptr;     // [nr][n] values on H (natural order), for the partial products
     u64 *dev_consts = nullptr;     // [nc][n] values on H (selectors first): which gate sits on a row (witness.hip)
-    mutable u32 *dev_sigma_pos = nullptr;   // [nr][n] sigma decoded into flat positions j' n + i': made by the first glp_witness_check (witness_check.inc)
+    mutable u32 *dev_sigma_pos = nullptr;   // [nr][n] sigma decoded into flat positions j' n + i': made by witness_sigma_decode (witness_check.inc) for the first caller
     // quotient launch plan (built once in glp_circuit_create): which gates share a launch
     u64 *dev_limb_desc = nullptr;  // [group][num_wires][LIMB_SLOTS] column programs of k_quotient_limbs
     // limb gates in groups of up to LIMB_SLOTS = 5 (one set of accumulators in registers per group; the kernel walks the groups in turn):
@@ -67,6 +67,9 @@ struct glp_circuit {
     std::vector<u64> cs_cap;
     Layout L;
 };
+
+// dev_sigma_pos on first use (witness_check.inc); shared by glp_witness_check and glp_witness_plan_create (witness.hip)
+int witness_sigma_decode(glp_ctx *c, const glp_circuit *cc, const char *fn);
 
 // ------------------------------------------------------------------------------------------ transcript
 struct Challenger {   // iop/challenger.rs, overwrite-mode duplex sponge; challenges pop from the END of the rate

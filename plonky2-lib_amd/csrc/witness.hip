@@ -1,8 +1,9 @@
-// witness.hip -- the row-local half of witness generation on the GPU.
+// witness.hip -- witness generation on the GPU: the row-local half (glp_witness_fill) and, over the same
+// per-unit body, the dataflow half (glp_witness_plan_*, glp_witness_generate: second part of this file).
 //
 // plonky2's `generate_partial_witness` (iop/generator.rs) runs every gate's `SimpleGenerator`s as their
-// dependencies become known.  Two kinds of work hide in it: the copy-constraint DATAFLOW between rows (serial,
-// irregular: stays on the CPU with the reference's gadget code) and the ROW-LOCAL generators that derive a row's
+// dependencies become known.  Two kinds of work hide in it: the copy-constraint DATAFLOW between rows (irregular:
+// planned once per circuit on the host, then walked wave by wave on the GPU) and the ROW-LOCAL generators that derive a row's
 // remaining wires from that row's own inputs -- bit and limb decompositions, inverses, S-box traces.  The second
 // kind is most of the witness by volume (56 of 136 columns of the secp256k1 trace are base-4 limbs) and is
 // embarrassingly row-parallel: one thread per trace row here, written straight into the HBM witness that
@@ -21,6 +22,8 @@
 //                           ExponentiationGenerator, InterpolationGenerator (CosetInterpolationGate), PoseidonMdsGenerator
 // Every value written is a canonical field element; inputs are read as canonical u64 exactly as
 // `to_canonical_u64()` hands them to the Rust generators.
+#include <stdlib.h>
+#include <new>
 #include "common.h"
 #include "poseidon.h"
 #include "prover_types.h"
@@ -40,35 +43,42 @@ __device__ __forceinline__ u64 winv(u64 a) {          // a != 0
     return r;
 }
 
-// One thread = one trace row.  Rows of one gate type are contiguous in every circuit the builder emits, so a wave
-// rarely sees more than one `case`.
-__global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
-    const size_t n = (size_t)1 << a.lg;
-    const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= n) return;
-    // the row's gate: the selector polynomial of its group holds the gate index, every other selector UNUSED
-    u32 gi = 0xFFFFFFFFu;
-    for (u32 s = 0; s < a.nsel; s++) {
-        const u64 v = a.consts[(size_t)s * n + row];
-        if (a.nsel == 1 || v != 0xFFFFFFFFull) gi = (u32)v;
+// How many independent generators (units) a row of a gate has; the table of include/glp.h ("witness generation, the dataflow half").
+GLF_HD u32 witness_gate_units(u32 type, u32 p0, u32 p1) {
+    switch (type) {
+    case GLP_GATE_ARITHMETIC: case GLP_GATE_U32_INTERLEAVE: case GLP_GATE_UNINTERLEAVE_U32: case GLP_GATE_UNINTERLEAVE_B32:
+    case GLP_GATE_U32_ARITHMETIC: case GLP_GATE_U32_SUBTRACTION: case GLP_GATE_U32_RANGE_CHECK:
+    case GLP_GATE_ARITHMETIC_EXTENSION: case GLP_GATE_MUL_EXTENSION: return p0;
+    case GLP_GATE_U32_ADD_MANY: return p1;
+    case GLP_GATE_RANDOM_ACCESS: return (p1 & 0xFFFF) + 1;
+    case GLP_GATE_NOOP: case GLP_GATE_PUBLIC_INPUT: return 0;
+    case GLP_GATE_CONSTANT: case GLP_GATE_POSEIDON: case GLP_GATE_COMPARISON: case GLP_GATE_BASE_SUM: case GLP_GATE_REDUCING:
+    case GLP_GATE_REDUCING_EXTENSION: case GLP_GATE_EXPONENTIATION: case GLP_GATE_COSET_INTERPOLATION: case GLP_GATE_POSEIDON_MDS: return 1;
+    default: return 0;
     }
-    if (gi >= a.num_gates) return;
-    const DevGate g = a.gates[gi];
-    u64 *W = a.wires + row;                                    // wire j -> W[j * n]
-    const u64 *GC = a.consts + (size_t)a.nsel * n + row;       // gate constant i -> GC[i * n]
+}
+
+// One unit of one row: generator `unit` (< witness_gate_units) of gate g on the row W points at (wire j -> W[j * n], gate constant
+// i -> GC[i * n]).  k_witness_fill runs every unit of a row; the wave kernels below run the units a plan lists.  WHICH = 1 keeps only
+// the gates with one unit per op, WHICH = 2 only those with one unit per row (k_witness_fill loops over the first kind alone, so that
+// nothing of a PoseidonGate row is hoisted out of a loop it runs once); 0 keeps all.
+template <int WHICH = 0>
+__device__ __forceinline__ void witness_unit(const WArgs &a, const DevGate &g, u64 *W, const u64 *GC, size_t n, u32 unit) {
     const u32 nr = a.only_advice ? a.nr : 0xFFFFFFFFu;         // only_advice: columns < nr (routed) are never written
+    constexpr bool ONE = WHICH != 1, PER_OP = WHICH != 2;      // which cases this instance keeps: gates of one unit per row, gates of one per op
+    const u32 i = unit;                                        // the op of a gate with one generator per op
 #define WR(col, val) do { const u32 _c = (col); if (!a.only_advice || _c >= nr) W[(size_t)_c * n] = (val); } while (0)
 #define RD(col) W[(size_t)(col) * n]
     switch (g.type) {
-    case GLP_GATE_CONSTANT:
-        for (u32 i = 0; i < g.p0; i++) WR(i, GC[(size_t)i * n]);
+    case GLP_GATE_CONSTANT: if (!ONE) break;
+        for (u32 k = 0; k < g.p0; k++) WR(k, GC[(size_t)k * n]);
         break;
-    case GLP_GATE_ARITHMETIC: {
+    case GLP_GATE_ARITHMETIC: if (!PER_OP) break; {
         const u64 c0 = GC[0], c1 = GC[n];
-        for (u32 i = 0; i < g.p0; i++) WR(4 * i + 3, add(mul(mul(RD(4 * i), RD(4 * i + 1)), c0), mul(RD(4 * i + 2), c1)));
+        WR(4 * i + 3, add(mul(mul(RD(4 * i), RD(4 * i + 1)), c0), mul(RD(4 * i + 2), c1)));
         break;
     }
-    case GLP_GATE_POSEIDON: {
+    case GLP_GATE_POSEIDON: if (!ONE) break; {
         // gates/poseidon.rs PoseidonGenerator: swap -> delta, then the round-by-round trace; the wires hold the S-box INPUTS
         u64 st[12];
         const u64 swap = RD(24);
@@ -104,9 +114,9 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         for (u32 i = 0; i < 12; i++) WR(12 + i, st[i]);
         break;
     }
-    case GLP_GATE_U32_INTERLEAVE:
+    case GLP_GATE_U32_INTERLEAVE: if (!PER_OP) break;
         // [REF src/u32/gates/interleave_u32.rs:289-318]: bit wire k = bit (31 - k) of x (big-endian), x_interleaved = sum bit 4^(31-k)
-        for (u32 i = 0; i < g.p0; i++) {
+        {
             const u64 x = RD(2 * i);
             u64 xi = 0;
             for (u32 k = 0; k < 32; k++) {
@@ -118,10 +128,10 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         }
         break;
     case GLP_GATE_UNINTERLEAVE_U32:
-    case GLP_GATE_UNINTERLEAVE_B32:
+    case GLP_GATE_UNINTERLEAVE_B32: if (!PER_OP) break;
         // [REF src/u32/gates/uninterleave_to_u32.rs:332-369, uninterleave_to_b32.rs:335-372]: 64 big-endian bits of
         // x_interleaved; even-position bits (shift + 1) -> x_evens, odd -> x_odds, weights 2^(31-j) (U32) or 4^(31-j) (B32)
-        for (u32 i = 0; i < g.p0; i++) {
+        {
             const u64 x = RD(3 * i);
             u64 ev = 0, od = 0;
             for (u32 j = 0; j < 32; j++) {
@@ -136,9 +146,9 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
             WR(3 * i + 2, canon(od));
         }
         break;
-    case GLP_GATE_U32_ARITHMETIC:
+    case GLP_GATE_U32_ARITHMETIC: if (!PER_OP) break;
         // plonky2_u32 arithmetic_u32.rs U32ArithmeticGenerator: output = m0 m1 + addend in the field, as a canonical u64
-        for (u32 i = 0; i < g.p0; i++) {
+        {
             const u64 out = add(mul(RD(6 * i), RD(6 * i + 1)), RD(6 * i + 2));
             const u64 lo = out & 0xFFFFFFFFull, hi = out >> 32;
             WR(6 * i + 3, lo);
@@ -148,10 +158,10 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
             for (u32 j = 0; j < 32; j++) WR(6 * g.p0 + 32 * i + j, (out >> (2 * j)) & 3);
         }
         break;
-    case GLP_GATE_U32_ADD_MANY: {
+    case GLP_GATE_U32_ADD_MANY: if (!PER_OP) break; {
         // plonky2_u32 add_many_u32.rs U32AddManyGenerator: sum of the addends and the carry, split at bit 32
         const u32 na = g.p0, nops = g.p1, wd = na + 3;
-        for (u32 i = 0; i < nops; i++) {
+        {
             u64 sum = RD(wd * i + na);
             for (u32 j = 0; j < na; j++) sum = add(sum, RD(wd * i + j));
             const u64 res = sum & 0xFFFFFFFFull, car = sum >> 32;
@@ -162,10 +172,10 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         }
         break;
     }
-    case GLP_GATE_U32_SUBTRACTION:
+    case GLP_GATE_U32_SUBTRACTION: if (!PER_OP) break;
         // plonky2_u32 subtraction_u32.rs U32SubtractionGenerator: x - y - borrow in the field; a wrapped result (> 2^32)
         // means a borrow, and 2^32 is added back
-        for (u32 i = 0; i < g.p0; i++) {
+        {
             const u64 r0 = sub(sub(RD(5 * i), RD(5 * i + 1)), RD(5 * i + 2));
             const u64 bo = r0 > (1ull << 32) ? 1 : 0;
             const u64 res = add(r0, bo << 32);
@@ -174,14 +184,14 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
             for (u32 j = 0; j < 16; j++) WR(5 * g.p0 + 16 * i + j, (res >> (2 * j)) & 3);
         }
         break;
-    case GLP_GATE_U32_RANGE_CHECK:
+    case GLP_GATE_U32_RANGE_CHECK: if (!PER_OP) break;
         // plonky2_u32 range_check_u32.rs U32RangeCheckGenerator: 16 base-4 limbs per input, little-endian
-        for (u32 i = 0; i < g.p0; i++) {
+        {
             const u64 v = RD(i);
             for (u32 j = 0; j < 16; j++) WR(g.p0 + 16 * i + j, (v >> (2 * j)) & 3);
         }
         break;
-    case GLP_GATE_COMPARISON: {
+    case GLP_GATE_COMPARISON: if (!ONE) break; {
         // plonky2_u32 comparison.rs ComparisonGenerator (first <= second): chunks, equality dummies, chunk-equal flags,
         // intermediate values, most significant diff, its bits, result
         const u32 nb = g.p0, ncx = g.p1, cb = (nb + ncx - 1) / ncx;
@@ -206,32 +216,33 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         WR(2, (top >> cb) & 1);
         break;
     }
-    case GLP_GATE_BASE_SUM: {
+    case GLP_GATE_BASE_SUM: if (!ONE) break; {
         // gates/base_sum.rs BaseSplitGenerator: little-endian digits of the sum in base B
         u64 v = RD(0);
         for (u32 j = 0; j < g.p0; j++) { WR(1 + j, v % g.p1); v /= g.p1; }
         break;
     }
-    case GLP_GATE_RANDOM_ACCESS: {
+    case GLP_GATE_RANDOM_ACCESS: if (!PER_OP) break; {
         // gates/random_access.rs RandomAccessGenerator: index bits (little-endian) and the claimed element list[index];
         // the gate's extra constants are plain ConstantGenerators
         const u32 bits = g.p0, copies = g.p1 & 0xFFFF, nextra = g.p1 >> 16, vs = 1u << bits;
         const u32 routed = (2 + vs) * copies + nextra;
-        for (u32 cpy = 0; cpy < copies; cpy++) {
-            const u32 o = (2 + vs) * cpy;
+        if (unit < copies) {
+            const u32 cpy = unit, o = (2 + vs) * cpy;
             const u64 idx = RD(o);
             if (idx < vs) {                       // the Rust generator indexes the list: an out-of-range index panics there
                 WR(o + 1, RD(o + 2 + (u32)idx));
                 for (u32 b = 0; b < bits; b++) WR(routed + bits * cpy + b, (idx >> b) & 1);
             }
+        } else {                                  // the last unit: the extra constants
+            for (u32 e = 0; e < nextra; e++) WR((2 + vs) * copies + e, GC[(size_t)e * n]);
         }
-        for (u32 e = 0; e < nextra; e++) WR((2 + vs) * copies + e, GC[(size_t)e * n]);
         break;
     }
-    case GLP_GATE_ARITHMETIC_EXTENSION: {
+    case GLP_GATE_ARITHMETIC_EXTENSION: if (!PER_OP) break; {
         // gates/arithmetic_extension.rs ArithmeticExtensionGenerator: output = c0 m0 m1 + c1 addend over F_p^2
         const u64 c0 = GC[0], c1 = GC[n];
-        for (u32 i = 0; i < g.p0; i++) {
+        {
             const u32 o = 8 * i;
             const ext2 t = e_add(e_scale(e_mul(e_make(RD(o), RD(o + 1)), e_make(RD(o + 2), RD(o + 3))), c0), e_scale(e_make(RD(o + 4), RD(o + 5)), c1));
             WR(o + 6, t.a);
@@ -239,10 +250,10 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         }
         break;
     }
-    case GLP_GATE_MUL_EXTENSION: {
+    case GLP_GATE_MUL_EXTENSION: if (!PER_OP) break; {
         // gates/multiplication_extension.rs MulExtensionGenerator: output = c0 m0 m1 over F_p^2
         const u64 c0 = GC[0];
-        for (u32 i = 0; i < g.p0; i++) {
+        {
             const u32 o = 6 * i;
             const ext2 t = e_scale(e_mul(e_make(RD(o), RD(o + 1)), e_make(RD(o + 2), RD(o + 3))), c0);
             WR(o + 4, t.a);
@@ -251,7 +262,7 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         break;
     }
     case GLP_GATE_REDUCING:
-    case GLP_GATE_REDUCING_EXTENSION: {
+    case GLP_GATE_REDUCING_EXTENSION: if (!ONE) break; {
         // gates/reducing.rs ReducingGenerator, gates/reducing_extension.rs ReducingExtensionGenerator: acc_i = acc_{i-1} alpha +
         // coeff_i from acc_{-1} = old_acc; acc_0 .. acc_{N-2} from wire 6 + cw N (routed or advice), acc_{N-1} = output (wires 0, 1)
         const u32 nco = g.p0, cw = g.type == GLP_GATE_REDUCING ? 1u : 2u, accs = 6 + cw * nco;
@@ -266,7 +277,7 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         }
         break;
     }
-    case GLP_GATE_EXPONENTIATION: {
+    case GLP_GATE_EXPONENTIATION: if (!ONE) break; {
         // gates/exponentiation.rs ExponentiationGenerator: square-and-multiply from the most significant bit; intermediate_i
         // at wire n + 2 + i, output = the last intermediate
         const u32 nb = g.p0;
@@ -279,7 +290,7 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         WR(nb + 1, cur);
         break;
     }
-    case GLP_GATE_COSET_INTERPOLATION: {
+    case GLP_GATE_COSET_INTERPOLATION: if (!ONE) break; {
         // gates/coset_interpolation.rs InterpolationGenerator: shifted point = evaluation point / shift, then the barycentric chain
         // of quotient_kernels.inc `gate_terms` with its checkpoints (the intermediates) and the evaluation value
         const u32 np = 1u << g.p0, d = g.p1, ni = (np - 2) / (d - 1);
@@ -305,7 +316,7 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
         WR(o_pt + 3, ev.b);
         break;
     }
-    case GLP_GATE_POSEIDON_MDS: {
+    case GLP_GATE_POSEIDON_MDS: if (!ONE) break; {
         // gates/poseidon_mds.rs PoseidonMdsGenerator: the MDS layer on each F_p^2 component of the 12 inputs
         for (u32 cmp = 0; cmp < 2; cmp++) {
             u64 st[12];
@@ -319,6 +330,32 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
     }
 #undef WR
 #undef RD
+}
+
+// the row's gate: the selector polynomial of its group holds the gate index, every other selector UNUSED
+__device__ __forceinline__ u32 witness_row_gate(const u64 *consts, u32 nsel, size_t n, size_t row) {
+    u32 gi = 0xFFFFFFFFu;
+    for (u32 s = 0; s < nsel; s++) {
+        const u64 v = consts[(size_t)s * n + row];
+        if (nsel == 1 || v != 0xFFFFFFFFull) gi = (u32)v;
+    }
+    return gi;
+}
+
+// One thread = one trace row: every unit of the row.  Rows of one gate type are contiguous in every circuit the builder emits, so a
+// wave rarely sees more than one `case`.
+__global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
+    const size_t n = (size_t)1 << a.lg;
+    const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const u32 gi = witness_row_gate(a.consts, a.nsel, n, row);
+    if (gi >= a.num_gates) return;
+    const DevGate g = a.gates[gi];
+    const u32 nu = witness_gate_units(g.type, g.p0, g.p1);
+    u64 *W = a.wires + row;
+    const u64 *GC = a.consts + (size_t)a.nsel * n + row;
+    if (nu) witness_unit<2>(a, g, W, GC, n, 0);                          // a gate with one unit per row: nothing for the others
+    for (u32 u = 0; u < nu; u++) witness_unit<1>(a, g, W, GC, n, u);    // a gate with one unit per op: nothing for the others
 }
 
 }  // namespace
@@ -338,42 +375,44 @@ extern "C" int glp_witness_fill(glp_ctx *c, const glp_circuit *cc, uint64_t *dev
     return GLP_OK;
 }
 
-// Which wire columns glp_witness_fill writes on rows of gate `gate_index` (1) and which it reads as inputs (2); 0 = untouched.
-extern "C" int glp_witness_columns(const glp_circuit *cc, uint32_t gate_index, uint8_t *role_out /* [num_wires] */) {
-    GLP_REQUIRE(cc && role_out, "null argument");
-    GLP_REQUIRE(gate_index < cc->d.num_gates, "gate index out of range");
-    const glp_gate &g = cc->gates[gate_index];
-    const u32 nw = cc->d.num_wires;
+namespace {
+constexpr u32 ALL_UNITS = 0xFFFFFFFFu;
+// Which wire columns unit `unit` of a row of gate g writes (1) and which it reads as inputs (2); 0 = untouched.  ALL_UNITS: the whole
+// row, what glp_witness_fill does -- the union of the units, by construction.
+void witness_unit_roles(const glp_gate &g, u32 nw, u32 unit, uint8_t *role_out) {
     memset(role_out, 0, nw);
     auto out = [&](u32 c0, u32 cnt) { for (u32 i = 0; i < cnt && c0 + i < nw; i++) role_out[c0 + i] = 1; };
     auto in = [&](u32 c0, u32 cnt) { for (u32 i = 0; i < cnt && c0 + i < nw; i++) role_out[c0 + i] = 2; };
+    const u32 u0 = unit == ALL_UNITS ? 0 : unit, u1 = unit == ALL_UNITS ? witness_gate_units(g.type, g.p0, g.p1) : unit + 1;   // the ops of a per-op gate
     switch (g.type) {
     case GLP_GATE_CONSTANT: out(0, g.p0); break;
-    case GLP_GATE_ARITHMETIC: for (u32 i = 0; i < g.p0; i++) { in(4 * i, 3); out(4 * i + 3, 1); } break;
+    case GLP_GATE_ARITHMETIC: for (u32 i = u0; i < u1; i++) { in(4 * i, 3); out(4 * i + 3, 1); } break;
     case GLP_GATE_POSEIDON: in(0, 12); out(12, 12); in(24, 1); out(25, 110); break;
-    case GLP_GATE_U32_INTERLEAVE: for (u32 i = 0; i < g.p0; i++) { in(2 * i, 1); out(2 * i + 1, 1); } out(2 * g.p0, 32 * g.p0); break;
+    case GLP_GATE_U32_INTERLEAVE: for (u32 i = u0; i < u1; i++) { in(2 * i, 1); out(2 * i + 1, 1); out(2 * g.p0 + 32 * i, 32); } break;
     case GLP_GATE_UNINTERLEAVE_U32: case GLP_GATE_UNINTERLEAVE_B32:
-        for (u32 i = 0; i < g.p0; i++) { in(3 * i, 1); out(3 * i + 1, 2); } out(3 * g.p0, 64 * g.p0); break;
-    case GLP_GATE_U32_ARITHMETIC: for (u32 i = 0; i < g.p0; i++) { in(6 * i, 3); out(6 * i + 3, 3); } out(6 * g.p0, 32 * g.p0); break;
+        for (u32 i = u0; i < u1; i++) { in(3 * i, 1); out(3 * i + 1, 2); out(3 * g.p0 + 64 * i, 64); } break;
+    case GLP_GATE_U32_ARITHMETIC: for (u32 i = u0; i < u1; i++) { in(6 * i, 3); out(6 * i + 3, 3); out(6 * g.p0 + 32 * i, 32); } break;
     case GLP_GATE_U32_ADD_MANY: {
         const u32 wd = g.p0 + 3;
-        for (u32 i = 0; i < g.p1; i++) { in(wd * i, g.p0 + 1); out(wd * i + g.p0 + 1, 2); }
-        out(wd * g.p1, 18 * g.p1);
+        for (u32 i = u0; i < u1; i++) { in(wd * i, g.p0 + 1); out(wd * i + g.p0 + 1, 2); out(wd * g.p1 + 18 * i, 18); }
         break;
     }
-    case GLP_GATE_U32_SUBTRACTION: for (u32 i = 0; i < g.p0; i++) { in(5 * i, 3); out(5 * i + 3, 2); } out(5 * g.p0, 16 * g.p0); break;
-    case GLP_GATE_U32_RANGE_CHECK: in(0, g.p0); out(g.p0, 16 * g.p0); break;
+    case GLP_GATE_U32_SUBTRACTION: for (u32 i = u0; i < u1; i++) { in(5 * i, 3); out(5 * i + 3, 2); out(5 * g.p0 + 16 * i, 16); } break;
+    case GLP_GATE_U32_RANGE_CHECK: for (u32 i = u0; i < u1; i++) { in(i, 1); out(g.p0 + 16 * i, 16); } break;
     case GLP_GATE_COMPARISON: { const u32 cb = (g.p0 + g.p1 - 1) / g.p1; in(0, 2); out(2, 2 + 5 * g.p1 + cb + 1); break; }
     case GLP_GATE_BASE_SUM: in(0, 1); out(1, g.p0); break;
     case GLP_GATE_RANDOM_ACCESS: {
         const u32 bits = g.p0, copies = g.p1 & 0xFFFF, nextra = g.p1 >> 16, vs = 1u << bits;
-        for (u32 cpy = 0; cpy < copies; cpy++) { const u32 o = (2 + vs) * cpy; in(o, 1); out(o + 1, 1); in(o + 2, vs); }
-        out((2 + vs) * copies, nextra);
-        out((2 + vs) * copies + nextra, bits * copies);
+        for (u32 cpy = u0; cpy < u1 && cpy < copies; cpy++) {
+            const u32 o = (2 + vs) * cpy;
+            in(o, 1); out(o + 1, 1); in(o + 2, vs);
+            out((2 + vs) * copies + nextra + bits * cpy, bits);
+        }
+        if (u1 == copies + 1) out((2 + vs) * copies, nextra);       // the last unit: the extra constants
         break;
     }
-    case GLP_GATE_ARITHMETIC_EXTENSION: for (u32 i = 0; i < g.p0; i++) { in(8 * i, 6); out(8 * i + 6, 2); } break;
-    case GLP_GATE_MUL_EXTENSION: for (u32 i = 0; i < g.p0; i++) { in(6 * i, 4); out(6 * i + 4, 2); } break;
+    case GLP_GATE_ARITHMETIC_EXTENSION: for (u32 i = u0; i < u1; i++) { in(8 * i, 6); out(8 * i + 6, 2); } break;
+    case GLP_GATE_MUL_EXTENSION: for (u32 i = u0; i < u1; i++) { in(6 * i, 4); out(6 * i + 4, 2); } break;
     case GLP_GATE_REDUCING: case GLP_GATE_REDUCING_EXTENSION: {
         const u32 cw = g.type == GLP_GATE_REDUCING ? 1u : 2u;
         out(0, 2); in(2, 4 + cw * g.p0); out(6 + cw * g.p0, 2 * (g.p0 - 1));
@@ -388,5 +427,424 @@ extern "C" int glp_witness_columns(const glp_circuit *cc, uint32_t gate_index, u
     case GLP_GATE_POSEIDON_MDS: in(0, 24); out(24, 24); break;
     default: break;
     }
+}
+}  // namespace
+
+// Which wire columns glp_witness_fill writes on rows of gate `gate_index` (1) and which it reads as inputs (2); 0 = untouched.
+extern "C" int glp_witness_columns(const glp_circuit *cc, uint32_t gate_index, uint8_t *role_out /* [num_wires] */) {
+    GLP_REQUIRE(cc && role_out, "null argument");
+    GLP_REQUIRE(gate_index < cc->d.num_gates, "gate index out of range");
+    witness_unit_roles(cc->gates[gate_index], cc->d.num_wires, ALL_UNITS, role_out);
     return GLP_OK;
+}
+
+extern "C" uint32_t glp_witness_num_units(const glp_circuit *cc, uint32_t gate_index) {
+    if (!cc || gate_index >= cc->d.num_gates) return 0;
+    const glp_gate &g = cc->gates[gate_index];
+    return witness_gate_units(g.type, g.p0, g.p1);
+}
+
+extern "C" int glp_witness_unit_columns(const glp_circuit *cc, uint32_t gate_index, uint32_t unit, uint8_t *role_out /* [num_wires] */) {
+    static const char *fn = "glp_witness_unit_columns";
+    GLP_REQUIRE(cc, "%s: circuit is null", fn);
+    GLP_REQUIRE(role_out, "%s: role_out is null", fn);
+    GLP_REQUIRE(gate_index < cc->d.num_gates, "%s: gate_index = %u, the circuit has %u gates", fn, gate_index, cc->d.num_gates);
+    const glp_gate &g = cc->gates[gate_index];
+    const u32 nu = witness_gate_units(g.type, g.p0, g.p1);
+    GLP_REQUIRE(unit < nu, "%s: unit = %u, a row of gate %u has %u units", fn, unit, gate_index, nu);
+    witness_unit_roles(g, cc->d.num_wires, unit, role_out);
+    return GLP_OK;
+}
+
+// ------------------------------------------------------------------------------------------ the dataflow half
+// include/glp.h, "witness generation, the dataflow half": the host plans once per circuit and input set which unit runs in which wave
+// and which cell is copied from which; the kernels below walk those lists.  Every index a kernel uses was built and range-checked by the
+// planner: no value read from a witness is an address (RandomAccessGate's index keeps its idx < vs guard in witness_unit).
+namespace {
+struct WUnit { u32 row, gu; };          // gu = gate << 16 | unit
+struct WCopy { u32 src, dst; };         // flat positions col * n + row
+struct WGen {
+    WArgs a;                            // a.wires: proof 0
+    const WUnit *units;                 // wave w: units[unit_off[w] .. unit_off[w + 1]), sorted by row; wave 0 holds none
+    const WCopy *copies;                // wave w: copies[copy_off[w] .. copy_off[w + 1])
+    const u32 *unit_off, *copy_off, *inputs;
+    const u64 *vals;                    // [K][num_inputs]
+    u32 num_inputs, nw;
+};
+constexpr u32 WGEN_MAX_PROOFS = 4096;   // as glp_witness_check
+constexpr u32 WITNESS_NARROW_MAX_DEFAULT = 256;
+
+// the units of wave w (wave 0: the scatter of the inputs) of one proof, lane `first` of `stride`
+__device__ __forceinline__ void wg_units(const WGen &g, u64 *W, const u64 *vals, size_t n, u32 w, size_t first, size_t stride) {
+    if (w == 0) {
+        for (size_t i = first; i < g.num_inputs; i += stride) W[g.inputs[i]] = vals[i];
+        return;
+    }
+    const size_t end = g.unit_off[w + 1];
+    for (size_t i = g.unit_off[w] + first; i < end; i += stride) {
+        const WUnit u = g.units[i];
+        const DevGate gate = g.a.gates[u.gu >> 16];
+        witness_unit(g.a, gate, W + u.row, g.a.consts + (size_t)g.a.nsel * n + u.row, n, u.gu & 0xFFFFu);
+    }
+}
+__device__ __forceinline__ void wg_copies(const WGen &g, u64 *W, u32 w, size_t first, size_t stride) {
+    const size_t end = g.copy_off[w + 1];
+    for (size_t i = g.copy_off[w] + first; i < end; i += stride) {
+        const WCopy c = g.copies[i];
+        W[c.dst] = W[c.src];
+    }
+}
+// Walked waves: one workgroup per proof walks waves w0 .. w1.  All traffic of a proof stays in its workgroup, so plain global stores,
+// drained, followed by the block barrier hand a wave's values to the next.
+__global__ __launch_bounds__(256) void k_witness_waves(WGen g, u32 w0, u32 w1) {
+    const size_t n = (size_t)1 << g.a.lg;
+    u64 *W = g.a.wires + (size_t)blockIdx.x * g.nw * n;
+    const u64 *vals = g.vals + (size_t)blockIdx.x * g.num_inputs;
+    for (u32 w = w0; w <= w1; w++) {
+        wg_units(g, W, vals, n, w, threadIdx.x, 256);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        wg_copies(g, W, w, threadIdx.x, 256);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+}
+// Wide waves: one lane per unit (per copy), blockIdx.y = proof; the stream orders the two launches.
+__global__ __launch_bounds__(256) void k_witness_units(WGen g, u32 w) {
+    const size_t n = (size_t)1 << g.a.lg;
+    wg_units(g, g.a.wires + (size_t)blockIdx.y * g.nw * n, g.vals + (size_t)blockIdx.y * g.num_inputs, n, w, (size_t)blockIdx.x * 256 + threadIdx.x,
+             (size_t)gridDim.x * 256);
+}
+__global__ __launch_bounds__(256) void k_witness_copies(WGen g, u32 w) {
+    const size_t n = (size_t)1 << g.a.lg;
+    wg_copies(g, g.a.wires + (size_t)blockIdx.y * g.nw * n, w, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
+}
+__global__ __launch_bounds__(256) void k_witness_read_cells(const u64 *wires, const u32 *cells, u64 *out, u32 num_cells, size_t per_proof) {
+    const u32 i = blockIdx.x * 256 + threadIdx.x;
+    if (i < num_cells) out[(size_t)blockIdx.y * num_cells + i] = wires[(size_t)blockIdx.y * per_proof + cells[i]];
+}
+constexpr u32 NONE = 0xFFFFFFFFu;
+}  // namespace
+
+struct glp_witness_plan {
+    glp_ctx *ctx = nullptr;
+    const glp_circuit *cc = nullptr;
+    u32 num_inputs = 0, narrow_max = WITNESS_NARROW_MAX_DEFAULT;
+    struct glp_witness_plan_info info;
+    std::vector<u32> unit_off, copy_off;           // [num_waves + 2]
+    std::vector<int32_t> cell_waves;               // [num_wires][n]
+    WUnit *dev_units = nullptr;
+    WCopy *dev_copies = nullptr;
+    u32 *dev_unit_off = nullptr, *dev_copy_off = nullptr, *dev_inputs = nullptr;
+    mutable u64 *dev_vals = nullptr;               // [vals_cap] the input values of the generation in flight: a plan serves one at a time
+    mutable size_t vals_cap = 0;
+};
+
+extern "C" void glp_witness_plan_free(glp_witness_plan *p) {
+    if (!p) return;
+    glp_ctx *c = p->ctx;
+    if (bind(c) == GLP_OK) (void)hipStreamSynchronize(c->stream);
+    c->release(p->dev_units); c->release(p->dev_copies); c->release(p->dev_unit_off); c->release(p->dev_copy_off);
+    c->release(p->dev_inputs); c->release(p->dev_vals);
+    delete p;
+}
+
+// glp_witness_plan_create without its allocation guard
+static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs, glp_witness_plan **out) {
+    GLP_REQUIRE(c, "%s: ctx is null", fn);
+    GLP_REQUIRE(cc, "%s: circuit is null", fn);
+    GLP_REQUIRE(out, "%s: out is null", fn);
+    GLP_REQUIRE(input_cells || num_inputs == 0, "%s: input_cells is null, num_inputs = %u", fn, num_inputs);
+    GLP_REQUIRE(cc->ctx == c, "%s: circuit belongs to another ctx", fn);
+    const glp_circuit_desc &d = cc->d;
+    const u32 lg = d.degree_bits, nw = d.num_wires, nr = d.num_routed_wires, ng = d.num_gates, nsel = d.num_selectors;
+    const size_t n = (size_t)1 << lg, cells = (size_t)nw * n;
+    // one short of the decoded sigma's 2^32: position 2^32 - 1 is the planner's "none"
+    GLP_REQUIRE(cells < ((size_t)1 << 32), "%s: num_wires * 2^degree_bits = %zu positions, a plan addresses fewer than 2^32 (the bound of the decoded sigma)", fn, cells);
+    GLP_REQUIRE(ng <= 0xFFFF, "%s: num_gates = %u, a plan names at most 65535 gates", fn, ng);
+    for (u32 i = 0; i < num_inputs; i++)
+        GLP_REQUIRE(input_cells[i] < cells, "%s: input_cells[%u] = %llu is out of range (num_wires * 2^degree_bits = %zu cells)", fn, i,
+                    (unsigned long long)input_cells[i], cells);
+    // which input names a cell (NONE: none); a cell listed twice is refused
+    std::vector<u32> input_at(cells, NONE);
+    for (u32 i = 0; i < num_inputs; i++) {
+        u32 &at = input_at[(size_t)input_cells[i]];
+        GLP_REQUIRE(at == NONE, "%s: input_cells[%u] = %llu is listed twice (also input_cells[%u])", fn, i, (unsigned long long)input_cells[i], at);
+        at = i;
+    }
+    GLP_TRY(bind(c));
+    GLP_TRY(witness_sigma_decode(c, cc, fn));
+
+    // the copy classes: the cycles of the decoded permutation, named by their smallest position; a non-routed cell is its own class
+    std::vector<u32> cls(cells);
+    {
+        std::vector<u32> pos((size_t)nr * n);
+        GLP_TRY(d2h(c, pos.data(), cc->dev_sigma_pos, pos.size() * sizeof(u32)));
+        for (size_t p = 0; p < cells; p++) cls[p] = NONE;
+        for (size_t p = 0; p < pos.size(); p++) {                 // ascending: the first cell of a cycle met is its smallest
+            if (cls[p] != NONE) continue;
+            for (size_t q = p; cls[q] == NONE; q = pos[q]) {
+                cls[q] = (u32)p;
+                GLP_REQUIRE(pos[q] < pos.size(), "%s: the decoded permutation leaves the routed columns", fn);
+            }
+        }
+        for (size_t p = pos.size(); p < cells; p++) cls[p] = (u32)p;
+    }
+    // class_wave by class name: 0 for a class with an input, -1 = not (yet) known; two inputs in one class are refused
+    std::vector<int32_t> class_wave(cells, -1);
+    {
+        std::vector<u32> class_input(num_inputs ? cells : 0, NONE);
+        for (u32 i = 0; i < num_inputs; i++) {
+            u32 &first = class_input[cls[(size_t)input_cells[i]]];
+            GLP_REQUIRE(first == NONE, "%s: input_cells[%u] = %llu and input_cells[%u] = %llu lie in one copy class: one value per class", fn, first,
+                        (unsigned long long)input_cells[first], i, (unsigned long long)input_cells[i]);
+            first = i;
+            class_wave[cls[(size_t)input_cells[i]]] = 0;
+        }
+    }
+    // the gate of every row, as k_witness_fill reads it
+    std::vector<u32> row_gate(n, NONE);
+    {
+        std::vector<u64> sel((size_t)nsel * n);
+        GLP_TRY(d2h(c, sel.data(), cc->dev_consts, sel.size() * 8));
+        for (size_t r = 0; r < n; r++) {
+            u32 gi = NONE;
+            for (u32 s = 0; s < nsel; s++) { const u64 v = sel[(size_t)s * n + r]; if (nsel == 1 || v != 0xFFFFFFFFull) gi = (u32)v; }
+            row_gate[r] = gi < ng ? gi : NONE;
+        }
+    }
+    // per gate and unit: the columns read and written
+    std::vector<std::vector<std::vector<u32>>> g_in(ng), g_out(ng);
+    {
+        std::vector<uint8_t> role(nw);
+        for (u32 gi = 0; gi < ng; gi++) {
+            const glp_gate &g = cc->gates[gi];
+            const u32 nu = witness_gate_units(g.type, g.p0, g.p1);
+            GLP_REQUIRE(nu <= 0xFFFF, "%s: gate %u has %u units per row, a plan names at most 65535", fn, gi, nu);
+            g_in[gi].resize(nu); g_out[gi].resize(nu);
+            for (u32 u = 0; u < nu; u++) {
+                witness_unit_roles(g, nw, u, role.data());
+                for (u32 col = 0; col < nw; col++) { if (role[col] == 2) g_in[gi][u].push_back(col); if (role[col] == 1) g_out[gi][u].push_back(col); }
+            }
+        }
+    }
+    // the units in (row, unit) order; unit k of the plan = unit k - row_first[row] of its row
+    std::vector<size_t> row_first(n + 1, 0);
+    for (size_t r = 0; r < n; r++) row_first[r + 1] = row_first[r] + (row_gate[r] == NONE ? 0 : g_in[row_gate[r]].size());
+    const size_t nu_total = row_first[n];
+    GLP_REQUIRE(nu_total < NONE, "%s: %zu units exceed the 2^32 - 1 a plan addresses", fn, nu_total);
+    std::vector<u32> unit_row(nu_total);
+    for (size_t r = 0; r < n; r++) for (size_t k = row_first[r]; k < row_first[r + 1]; k++) unit_row[k] = (u32)r;
+    // the writer of every cell, and per class the units that wait for it (one entry per cell read in a class not known from the inputs)
+    std::vector<u32> writer(cells, NONE), pending(nu_total, 0);
+    std::vector<size_t> reader_off(cells + 1, 0);
+    for (size_t k = 0; k < nu_total; k++) {
+        const size_t r = unit_row[k];
+        const u32 gi = row_gate[r], u = (u32)(k - row_first[r]);
+        for (u32 col : g_out[gi][u]) writer[(size_t)col * n + r] = (u32)k;
+        for (u32 col : g_in[gi][u]) { const u32 cl = cls[(size_t)col * n + r]; if (class_wave[cl] < 0) { reader_off[cl + 1]++; pending[k]++; } }
+    }
+    for (size_t p = 0; p < cells; p++) reader_off[p + 1] += reader_off[p];
+    std::vector<u32> readers(reader_off[cells]);
+    {
+        std::vector<size_t> fill(reader_off.begin(), reader_off.end() - 1);
+        for (size_t k = 0; k < nu_total; k++) {
+            const size_t r = unit_row[k];
+            const u32 gi = row_gate[r], u = (u32)(k - row_first[r]);
+            for (u32 col : g_in[gi][u]) { const u32 cl = cls[(size_t)col * n + r]; if (class_wave[cl] < 0) readers[fill[cl]++] = (u32)k; }
+        }
+    }
+    // the waves: a unit is ready once every class it reads is known; its wave is one more than the wave that made the last one known
+    std::vector<int32_t> unit_wave(nu_total, -1);
+    std::vector<u32> ready, next;
+    for (size_t k = 0; k < nu_total; k++) if (pending[k] == 0) ready.push_back((u32)k);
+    u32 num_waves = 0;
+    uint64_t widest = 0;
+    while (!ready.empty()) {
+        num_waves++;
+        widest = std::max<uint64_t>(widest, ready.size());
+        next.clear();
+        for (u32 k : ready) unit_wave[k] = (int32_t)num_waves;
+        for (u32 k : ready) {
+            const size_t r = unit_row[k];
+            for (u32 col : g_out[row_gate[r]][k - row_first[r]]) {
+                const u32 cl = cls[(size_t)col * n + r];
+                if (class_wave[cl] >= 0) continue;
+                class_wave[cl] = (int32_t)num_waves;
+                for (size_t i = reader_off[cl]; i < reader_off[cl + 1]; i++) if (--pending[readers[i]] == 0) next.push_back(readers[i]);
+            }
+        }
+        ready.swap(next);
+    }
+    std::unique_ptr<glp_witness_plan> p(new glp_witness_plan);
+    p->ctx = c; p->cc = cc; p->num_inputs = num_inputs;
+    if (const char *e = getenv("GLP_WITNESS_NARROW_MAX")) p->narrow_max = (u32)std::min<unsigned long long>(strtoull(e, nullptr, 10), 0xFFFFFFFFull);
+    struct glp_witness_plan_info &info = p->info;
+    memset(&info, 0, sizeof(info));
+    info.num_waves = num_waves; info.num_units = nu_total; info.widest_wave_units = widest;
+    // the lists: units by wave in (row, unit) order, the source of every known class, the copies by wave in order of the destination
+    p->unit_off.assign(num_waves + 2, 0);
+    p->copy_off.assign(num_waves + 2, 0);
+    for (size_t k = 0; k < nu_total; k++) {
+        if (unit_wave[k] > 0) { p->unit_off[unit_wave[k] + 1]++; continue; }
+        if (!info.num_stuck_units++) { info.stuck_row = unit_row[k]; info.stuck_gate = row_gate[unit_row[k]]; info.stuck_unit = (u32)(k - row_first[unit_row[k]]); }
+    }
+    for (u32 w = 0; w <= num_waves; w++) p->unit_off[w + 1] += p->unit_off[w];
+    std::vector<WUnit> units(p->unit_off[num_waves + 1]);
+    {
+        std::vector<u32> fill(p->unit_off.begin(), p->unit_off.end() - 1);
+        for (size_t k = 0; k < nu_total; k++)
+            if (unit_wave[k] > 0) units[fill[unit_wave[k]]++] = WUnit{unit_row[k], row_gate[unit_row[k]] << 16 | (u32)(k - row_first[unit_row[k]])};
+    }
+    std::vector<u32> source(cells, NONE);        // by class name
+    p->cell_waves.assign(cells, -1);
+    for (size_t q = 0; q < cells; q++) {
+        const u32 cl = cls[q];
+        const int32_t cw = class_wave[cl];
+        if (cw < 0) continue;
+        const bool written = writer[q] != NONE && unit_wave[writer[q]] > 0;
+        p->cell_waves[q] = written ? unit_wave[writer[q]] : cw;
+        info.num_cells_known++;
+        if (source[cl] == NONE && (cw == 0 ? input_at[q] != NONE : (written && unit_wave[writer[q]] == cw))) source[cl] = (u32)q;
+    }
+    for (size_t q = 0; q < cells; q++) if (class_wave[cls[q]] >= 0 && source[cls[q]] != q) p->copy_off[class_wave[cls[q]] + 1]++;
+    for (u32 w = 0; w <= num_waves; w++) {
+        GLP_REQUIRE((size_t)p->copy_off[w] + p->copy_off[w + 1] < NONE, "%s: the copies exceed the 2^32 - 1 a plan addresses", fn);
+        p->copy_off[w + 1] += p->copy_off[w];
+    }
+    info.num_copies = p->copy_off[num_waves + 1];
+    std::vector<WCopy> copies(info.num_copies);
+    {
+        std::vector<u32> fill(p->copy_off.begin(), p->copy_off.end() - 1);
+        for (size_t q = 0; q < cells; q++) {
+            const u32 cl = cls[q];
+            if (class_wave[cl] >= 0 && source[cl] != q) copies[fill[class_wave[cl]]++] = WCopy{source[cl], (u32)q};
+        }
+    }
+    std::vector<u32> in32(num_inputs);
+    for (u32 i = 0; i < num_inputs; i++) in32[i] = (u32)input_cells[i];
+    int rc = GLP_OK;
+    auto up = [&](auto **dev, const auto &v) {
+        if (rc != GLP_OK) return;
+        const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(v[0]);
+        rc = c->alloc((void **)dev, bytes);
+        if (rc == GLP_OK && !v.empty()) rc = h2d(c, *dev, v.data(), v.size() * sizeof(v[0]));
+    };
+    up(&p->dev_units, units); up(&p->dev_copies, copies); up(&p->dev_unit_off, p->unit_off); up(&p->dev_copy_off, p->copy_off); up(&p->dev_inputs, in32);
+    if (rc != GLP_OK) { glp_witness_plan_free(p.release()); return rc; }
+    *out = p.release();
+    return GLP_OK;
+}
+
+extern "C" int glp_witness_plan_create(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs, glp_witness_plan **out) {
+    static const char *fn = "glp_witness_plan_create";
+    try {
+        return witness_plan_build(fn, c, cc, input_cells, num_inputs, out);
+    } catch (const std::bad_alloc &) {       // the planner's host tables: about 40 bytes per cell
+        return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
+    }
+}
+
+extern "C" int glp_witness_plan_info(const glp_witness_plan *p, struct glp_witness_plan_info *out) {
+    GLP_REQUIRE(p, "glp_witness_plan_info: plan is null");
+    GLP_REQUIRE(out, "glp_witness_plan_info: out is null");
+    *out = p->info;
+    return GLP_OK;
+}
+
+extern "C" int glp_witness_plan_cell_waves(const glp_witness_plan *p, int32_t *waves_out) {
+    GLP_REQUIRE(p, "glp_witness_plan_cell_waves: plan is null");
+    GLP_REQUIRE(waves_out, "glp_witness_plan_cell_waves: waves_out is null");
+    memcpy(waves_out, p->cell_waves.data(), p->cell_waves.size() * sizeof(int32_t));
+    return GLP_OK;
+}
+
+extern "C" int glp_witness_generate(glp_ctx *c, const glp_witness_plan *p, uint32_t num_proofs, const uint64_t *input_values, uint64_t *dev_wires,
+                                    uint32_t flags) {
+    static const char *fn = "glp_witness_generate";
+    GLP_REQUIRE(c, "%s: ctx is null", fn);
+    GLP_REQUIRE(p, "%s: plan is null", fn);
+    GLP_REQUIRE(dev_wires, "%s: dev_wires is null", fn);
+    GLP_REQUIRE(p->ctx == c, "%s: plan belongs to another ctx", fn);
+    GLP_REQUIRE(input_values || p->num_inputs == 0, "%s: input_values is null, the plan has %u inputs", fn, p->num_inputs);
+    GLP_REQUIRE((flags & ~GLP_WITNESS_GEN_ZERO_FIRST) == 0, "%s: flags = 0x%x has bits other than GLP_WITNESS_GEN_ZERO_FIRST", fn, flags);
+    const u32 K = num_proofs, ni = p->num_inputs;
+    GLP_REQUIRE(K >= 1 && K <= WGEN_MAX_PROOFS, "%s: num_proofs = %u outside 1..%u", fn, K, WGEN_MAX_PROOFS);
+    const glp_circuit *cc = p->cc;
+    const u32 nw = cc->d.num_wires;
+    const size_t n = (size_t)1 << cc->d.degree_bits;
+    GLP_REQUIRE((size_t)K * nw <= BATCH_MAX_BYTES / (8 * n), "%s: wires too large (num_proofs * num_wires * 2^degree_bits words)", fn);
+    for (u32 k = 0; k < K && ni; k++) {
+        const size_t bad = first_noncanonical(input_values + (size_t)k * ni, ni);
+        GLP_REQUIRE(bad == ni, "%s: input_values: proof %u, input %zu = 0x%016llx is not a canonical field element (>= p)", fn, k, bad,
+                    (unsigned long long)input_values[(size_t)k * ni + (bad == ni ? 0 : bad)]);
+    }
+    GLP_TRY(bind(c));
+    const glp_witness_plan *pm = p;                                // the value buffer grows with the largest batch seen
+    const size_t nvals = (size_t)K * ni;
+    if (nvals > pm->vals_cap) {
+        GLP_HIP(hipStreamSynchronize(c->stream));
+        c->release(pm->dev_vals);
+        pm->dev_vals = nullptr; pm->vals_cap = 0;
+        GLP_TRY(c->alloc((void **)&pm->dev_vals, nvals * 8));
+        pm->vals_cap = nvals;
+    }
+    if (nvals) GLP_TRY(h2d(c, pm->dev_vals, input_values, nvals * 8));
+    WGen g;
+    memset(&g, 0, sizeof(g));
+    g.a.wires = dev_wires; g.a.consts = cc->dev_consts; g.a.gates = cc->dev_gates;
+    g.a.lg = cc->d.degree_bits; g.a.nsel = cc->d.num_selectors; g.a.num_gates = cc->d.num_gates; g.a.only_advice = 0; g.a.nr = cc->d.num_routed_wires;
+    g.units = p->dev_units; g.copies = p->dev_copies; g.unit_off = p->dev_unit_off; g.copy_off = p->dev_copy_off; g.inputs = p->dev_inputs;
+    g.vals = p->dev_vals; g.num_inputs = ni; g.nw = nw;
+    StageScope st(c, "witness_generate", 16.0 * K * p->info.num_cells_known);
+    if (flags & GLP_WITNESS_GEN_ZERO_FIRST) GLP_HIP(hipMemsetAsync(dev_wires, 0, (size_t)K * nw * n * 8, c->stream));
+    // a wave is wide (one launch for its units, one for its copies) while the proofs alone do not fill the chip and it holds more than
+    // narrow_max units; runs of the other waves are walked by one workgroup per proof
+    const u32 nwaves = p->info.num_waves;
+    auto wide = [&](u32 w) { const size_t cnt = w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w]; return K < (u32)c->num_cus && cnt > p->narrow_max; };
+    for (u32 w = 0; w <= nwaves;) {
+        if (wide(w)) {
+            const size_t cnt = w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w], ncp = p->copy_off[w + 1] - p->copy_off[w];
+            hipLaunchKernelGGL(k_witness_units, dim3((unsigned)((cnt + 255) / 256), K), dim3(256), 0, c->stream, g, w);
+            if (ncp) hipLaunchKernelGGL(k_witness_copies, dim3((unsigned)((ncp + 255) / 256), K), dim3(256), 0, c->stream, g, w);
+            w++;
+        } else {
+            u32 w1 = w;
+            while (w1 < nwaves && !wide(w1 + 1)) w1++;
+            hipLaunchKernelGGL(k_witness_waves, dim3(K), dim3(256), 0, c->stream, g, w, w1);
+            w = w1 + 1;
+        }
+        GLP_HIP(hipGetLastError());
+    }
+    return GLP_OK;
+}
+
+extern "C" int glp_witness_read_cells(glp_ctx *c, const glp_circuit *cc, uint32_t num_proofs, const uint64_t *dev_wires, const uint64_t *cells,
+                                      uint32_t num_cells, uint64_t *out) {
+    static const char *fn = "glp_witness_read_cells";
+    GLP_REQUIRE(c, "%s: ctx is null", fn);
+    GLP_REQUIRE(cc, "%s: circuit is null", fn);
+    GLP_REQUIRE(dev_wires, "%s: dev_wires is null", fn);
+    GLP_REQUIRE(cells, "%s: cells is null", fn);
+    GLP_REQUIRE(out, "%s: out is null", fn);
+    GLP_REQUIRE(cc->ctx == c, "%s: circuit belongs to another ctx", fn);
+    GLP_REQUIRE(num_proofs >= 1 && num_proofs <= WGEN_MAX_PROOFS, "%s: num_proofs = %u outside 1..%u", fn, num_proofs, WGEN_MAX_PROOFS);
+    GLP_REQUIRE(num_cells >= 1, "%s: num_cells is 0", fn);
+    const size_t per_proof = (size_t)cc->d.num_wires << cc->d.degree_bits;
+    GLP_REQUIRE(per_proof < ((size_t)1 << 32), "%s: num_wires * 2^degree_bits = %zu positions, cells are named below 2^32", fn, per_proof);
+    std::vector<u32> c32(num_cells);
+    for (u32 i = 0; i < num_cells; i++) {
+        GLP_REQUIRE(cells[i] < per_proof, "%s: cells[%u] = %llu is out of range (num_wires * 2^degree_bits = %zu cells)", fn, i, (unsigned long long)cells[i], per_proof);
+        c32[i] = (u32)cells[i];
+    }
+    GLP_TRY(bind(c));
+    Scratch tmp(c);
+    u32 *dev_cells;
+    u64 *dev_out;
+    GLP_TRY(tmp.array(&dev_cells, num_cells));
+    GLP_TRY(tmp.words(&dev_out, (size_t)num_proofs * num_cells));
+    GLP_TRY(h2d(c, dev_cells, c32.data(), (size_t)num_cells * 4));
+    hipLaunchKernelGGL(k_witness_read_cells, dim3((num_cells + 255) / 256, num_proofs), dim3(256), 0, c->stream, dev_wires, dev_cells, dev_out, num_cells, per_proof);
+    GLP_HIP(hipGetLastError());
+    return d2h(c, out, dev_out, (size_t)num_proofs * num_cells * 8);
 }

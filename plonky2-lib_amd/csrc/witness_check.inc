@@ -195,6 +195,45 @@ int wc_launch_gate(glp_ctx *c, const WcArgs &w, u32 type, u32 gi, u32 K) {
 }
 }  // namespace
 
+// The permutation decoded into flat positions, made by the first caller that needs it (glp_witness_check, glp_witness_plan_create:
+// `fn` names it in a refusal) and kept with the circuit (DESIGN.md section 7: 8.6 of a check's 9.7 ms at 2^20 rows).  The ctx is bound.
+int witness_sigma_decode(glp_ctx *c, const glp_circuit *cc, const char *fn) {
+    if (cc->dev_sigma_pos) return GLP_OK;
+    const u32 lg = cc->d.degree_bits, nr = cc->d.num_routed_wires;
+    const size_t n = (size_t)1 << lg;
+    Scratch tmp(c);
+    std::vector<u64> tab(2 * (size_t)nr + lg);
+    for (u32 j = 0; j < nr; j++) { tab[j] = pow(cc->k_is[j], (u64)n); tab[nr + j] = inv(cc->k_is[j]); }
+    u64 wi = inv(root_of_unity((int)lg));
+    for (u32 b = 0; b < lg; b++) { tab[2 * (size_t)nr + b] = wi; wi = mul(wi, wi); }
+    u64 *dev_tab;
+    u32 *pos = nullptr;
+    unsigned long long *bad;
+    GLP_TRY(tmp.words(&dev_tab, tab.size()));
+    GLP_TRY(h2d(c, dev_tab, tab.data(), tab.size() * 8));
+    GLP_TRY(tmp.array(&bad, 1));
+    GLP_HIP(hipMemsetAsync(bad, 0xFF, 8, c->stream));
+    GLP_TRY(c->alloc((void **)&pos, (size_t)nr * n * sizeof(u32)));
+    unsigned long long first_bad = 0;
+    int rc = GLP_OK;
+    {
+        StageScope st(c, "witness_check.sigma", 12.0 * nr * n);
+        hipLaunchKernelGGL(k_witness_check_sigma, dim3(nblk(n), nr), dim3(256), 0, c->stream, cc->dev_sigmas, dev_tab, pos, bad, lg, nr);
+        if (hipGetLastError() != hipSuccess) rc = set_error(GLP_ERR_HIP, "%s: the sigma decode could not be launched", fn);
+    }
+    if (rc == GLP_OK) rc = d2h(c, &first_bad, bad, 8);
+    if (rc == GLP_OK && first_bad != ~0ull)
+        rc = set_error(GLP_ERR_ARG, "%s: sigmas[%zu][%zu] is k_is[j'] * w_n^i' for no (j', i'): the circuit's permutation is malformed", fn,
+                       (size_t)first_bad / n, (size_t)first_bad % n);
+    if (rc != GLP_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        c->release(pos);
+        return rc;
+    }
+    cc->dev_sigma_pos = pos;
+    return GLP_OK;
+}
+
 extern "C" {
 
 int glp_witness_check(glp_ctx *c, const glp_circuit *cc, uint32_t num_proofs, const uint64_t *wires, int wires_on_device, const uint64_t *public_inputs,
@@ -230,38 +269,7 @@ int glp_witness_check(glp_ctx *c, const glp_circuit *cc, uint32_t num_proofs, co
     w.consts = cc->dev_consts; w.gates = cc->dev_gates;
     w.lg = lg; w.nsel = d.num_selectors; w.num_gates = ng; w.nw = nw; w.nr = nr; w.res_stride = WC_BY_GATE + ng;
 
-    // the permutation, decoded by the first check of a circuit and kept with it (DESIGN.md section 7: 8.6 of a check's 9.7 ms at 2^20 rows)
-    if (!cc->dev_sigma_pos) {
-        std::vector<u64> tab(2 * (size_t)nr + lg);
-        for (u32 j = 0; j < nr; j++) { tab[j] = pow(cc->k_is[j], (u64)n); tab[nr + j] = inv(cc->k_is[j]); }
-        u64 wi = inv(root_of_unity((int)lg));
-        for (u32 b = 0; b < lg; b++) { tab[2 * (size_t)nr + b] = wi; wi = mul(wi, wi); }
-        u64 *dev_tab;
-        u32 *pos = nullptr;
-        unsigned long long *bad;
-        GLP_TRY(tmp.words(&dev_tab, tab.size()));
-        GLP_TRY(h2d(c, dev_tab, tab.data(), tab.size() * 8));
-        GLP_TRY(tmp.array(&bad, 1));
-        GLP_HIP(hipMemsetAsync(bad, 0xFF, 8, c->stream));
-        GLP_TRY(c->alloc((void **)&pos, (size_t)nr * n * sizeof(u32)));
-        unsigned long long first_bad = 0;
-        int rc = GLP_OK;
-        {
-            StageScope st(c, "witness_check.sigma", 12.0 * nr * n);
-            hipLaunchKernelGGL(k_witness_check_sigma, dim3(nblk(n), nr), dim3(256), 0, c->stream, cc->dev_sigmas, dev_tab, pos, bad, lg, nr);
-            if (hipGetLastError() != hipSuccess) rc = set_error(GLP_ERR_HIP, "%s: the sigma decode could not be launched", fn);
-        }
-        if (rc == GLP_OK) rc = d2h(c, &first_bad, bad, 8);
-        if (rc == GLP_OK && first_bad != ~0ull)
-            rc = set_error(GLP_ERR_ARG, "%s: sigmas[%zu][%zu] is k_is[j'] * w_n^i' for no (j', i'): the circuit's permutation is malformed", fn,
-                           (size_t)first_bad / n, (size_t)first_bad % n);
-        if (rc != GLP_OK) {
-            (void)hipStreamSynchronize(c->stream);
-            c->release(pos);
-            return rc;
-        }
-        cc->dev_sigma_pos = pos;
-    }
+    GLP_TRY(witness_sigma_decode(c, cc, fn));
     w.pos = cc->dev_sigma_pos;
 
     GLP_TRY(tmp.input(wires, wires_on_device, (size_t)K * per_proof, &w.wires));
