@@ -847,8 +847,8 @@ GLP_API int glp_witness_columns(const glp_circuit *circuit, uint32_t gate_index,
 
 /* ---- witness generation, the dataflow half ----------------------------------------------------------------------
  * The other half of `generate_partial_witness`: values travel between rows along the copy constraints, and a generator runs once its
- * inputs are known.  The caller hands over only the values it sets itself -- the `pw.set_target` values and whatever its generators
- * that are NOT gate generators produce -- and the GPU derives every other reachable cell in HBM, for num_proofs witnesses of one
+ * inputs are known.  The caller hands over only the values it sets itself -- the `pw.set_target` values; generators that belong to no
+ * gate run as FREE UNITS, below -- and the GPU derives every other reachable cell in HBM, for num_proofs witnesses of one
  * circuit in lock step.  The result is what glp_prove_device / glp_prove_batch (wires_on_device) / glp_witness_check consume.
  *
  * UNITS.  A unit is one independent generator of a row (the loops of glp_witness_fill, one by one):
@@ -900,10 +900,44 @@ GLP_API int glp_witness_columns(const glp_circuit *circuit, uint32_t gate_index,
  * glp_witness_read_cells (synchronous) reads cells of generated witnesses back: the public inputs of a generated witness are
  * themselves outputs (zkdsa's public key and signature), and glp_prove_batch needs them on the host.
  *
- * NOT done here: generators that are not gate generators (`EqualityGenerator`, the nonnative generators of the secp256k1 gadgets:
- * their outputs are inputs here, so that circuit keeps a CPU pass for those cells); zero-knowledge blinding rows (their random advice
- * comes from no generator: list those cells as inputs); a device-side planner.
- * tests/witness_plan_restate.py restates the units, the classes, the rule and generation. */
+ * FREE UNITS.  A generator that belongs to no gate -- plonky2's `EqualityGenerator` (recalled, unpinned) and the BigUint / nonnative
+ * generators of the secp256k1 gadgets [REF src/ecdsa/gadgets/nonnative.rs:453-830, biguint.rs:322-349, glv.rs:106-133] -- is a free
+ * unit of glp_witness_plan_create_ex: a kind (GLP_WGEN_*), an index into moduli[] and a run of cells[]: the input cells, then the
+ * output cells, operands in the kind's order, limbs little-endian, len[] cells per operand.  A virtual target is named through any
+ * wire it was placed on; an output operand's cell may be GLP_WGEN_NO_CELL (a target that was placed nowhere: it is not written).  With
+ * them a secp256k1 witness comes from the 40 words a caller sets per signature (msg, r, s, pk.x, pk.y; a builder that leaves the unused
+ * operations of partly filled rows unwired, as the Python builders do, also lists their cells as inputs of value 0).  The rule extends to them:
+ *   a free unit reads the classes of its input cells and is the writer of its output cells; its wave is 1 + the maximum wave of the
+ *   classes it reads, 1 if it reads none; it is stuck under the same rule as a gate unit; class wave, source (ties to the smallest
+ *   flat position), copies and cell_waves treat a free writer exactly like a gate writer; within a wave gate units and free units both
+ *   run before the copies.  In glp_witness_plan_info num_units, num_stuck_units, widest_wave_units and stuck_* keep counting gate units
+ *   only; num_waves is the highest wave that holds any unit; glp_witness_plan_free_info has the free counts (first_stuck_free_unit: an
+ *   index into units[], iff num_stuck_free_units).
+ * Semantics are the reference's `run_once` bodies.  The nonnative kinds first reduce every operand modulo m
+ * (`from_noncanonical_biguint`); NONNATIVE_ADD overflows when a + b > m, strictly (a + b = m gives sum = m, overflow = 0); NONNATIVE_INV's
+ * div is floor(x inv / m); GLV_SECP256K1 is `decompose_secp256k1_scalar` (rounding division by n, signs by comparison with n / 2).
+ * Outside a generator's domain (the Rust code panics there) nothing faults and the result is fixed: an operand cell >= 2^32 is read as
+ * its low 32 bits; a divisor of 0 gives div = rem = 0; x = 0 (mod m) or gcd(x, m) != 1 gives inv = div = 0; a result wider than the cells
+ * the unit has for it is written truncated to those limbs; MULTI_ADD's overflow is the low limb of the quotient; EQUALITY is field
+ * arithmetic, inv = 1 / (x - y) or 0 when x = y.  Such witnesses fail glp_witness_check, which names the row.  Every loop of the limb
+ * arithmetic (csrc/biguint_dev.h, one text for device and host) has a trip count fixed by limb counts or a compile-time bound, and no
+ * value read from a witness becomes a cell position (one count is taken from values: BIGUINT_DIV_REM divides by the divisor's limbs up
+ * to its highest non-zero one, bounded by the declared count, at most 8).  One lane runs one free unit, in the units step of either form (walked waves: before
+ * the first barrier; wide waves: a launch of their own); a wave counts as wide by its gate and free units together.  The per-wave free
+ * list (offsets, unit records, cell runs, moduli) lies in HBM beside the units and the copies.  An 8-limb modulus with 8-limb operands
+ * runs a fully unrolled instance, a device function of its own that keeps its limbs in registers (no scratch, no spills in the
+ * compiler's report); every other shape runs a general-length instance, also a function of its own, whose arrays lie in scratch.
+ * Refusals of glp_witness_plan_create_ex beyond those above (GLP_ERR_ARG, each names the unit and the field, none needs a launch): an
+ * unknown kind; a len outside the kind's shape (EQUALITY: four operands of 1 cell; an overflow cell count other than 1 for ADD,
+ * MULTI_ADD, SUB; GLV: 8, 4, 4, 1, 1; unused entries not 0); an operand longer than GLP_WGEN_MAX_LIMBS; a divisor (BIGUINT_DIV_REM's b)
+ * longer than 8 limbs; modulus >= num_moduli for kinds 2..6, modulus != 0 otherwise; a modulus that is even or below 3 (a modulus has
+ * no declared length: its limbs run to its highest non-zero one); an input cell out of range; an output cell out of range that is not
+ * GLP_WGEN_NO_CELL; a run that leaves cells[]; an output cell written by two free units; an output cell that a gate unit of that row
+ * also writes.  An output cell whose class holds an input is allowed, as above.  glp_witness_plan_create is the num_units = 0 case.
+ *
+ * NOT done here: zero-knowledge blinding rows (their random advice comes from no generator: list those cells as inputs); a
+ * device-side planner; generators the rebuilt circuits do not contain (`WireSplitGenerator`, `LowHighGenerator`).
+ * tests/witness_plan_restate.py restates the units, the classes, the rule and generation; tests/witness_free_restate.py the free units. */
 typedef struct glp_witness_plan glp_witness_plan;
 struct glp_witness_plan_info {           /* a struct tag, not a typedef: the accessor below carries the same name */
     uint32_t num_waves;                  /* highest wave that holds a unit; 0 if none */
@@ -917,6 +951,31 @@ GLP_API int glp_witness_unit_columns(const glp_circuit *c, uint32_t gate_index, 
                                      uint8_t *role_out /* [num_wires], roles of glp_witness_columns */);
 GLP_API int  glp_witness_plan_create(glp_ctx *ctx, const glp_circuit *c, const uint64_t *input_cells, uint32_t num_inputs,
                                      glp_witness_plan **out);
+#define GLP_WGEN_EQUALITY            1u  /* in: x, y (1 cell each)   out: equal, inv                       (plonky2, recalled) */
+#define GLP_WGEN_NONNATIVE_ADD       2u  /* in: a, b                 out: sum, overflow (1 cell)            nonnative.rs:475-490 */
+#define GLP_WGEN_NONNATIVE_MULTI_ADD 3u  /* in: len[0] summands of len[1] limbs   out: sum, overflow (1 cell, u32)  :553-576 */
+#define GLP_WGEN_NONNATIVE_SUB       4u  /* in: a, b                 out: diff, overflow (1 cell)           :648-663 */
+#define GLP_WGEN_NONNATIVE_MUL       5u  /* in: a, b                 out: prod, overflow (limbs)            :727-740 */
+#define GLP_WGEN_NONNATIVE_INV       6u  /* in: x                    out: inv, div                          :797-809 */
+#define GLP_WGEN_BIGUINT_DIV_REM     7u  /* in: a, b                 out: div, rem            biguint.rs:342-349 */
+#define GLP_WGEN_GLV_SECP256K1       8u  /* in: k (8 limbs)          out: k1, k2 (4 limbs each), k1_neg, k2_neg   glv.rs */
+#define GLP_WGEN_MAX_LIMBS          18u  /* an operand; a modulus or a divisor has at most 8 */
+#define GLP_WGEN_NO_CELL 0xFFFFFFFFFFFFFFFFull   /* an output cell that is not written */
+typedef struct {
+    uint32_t kind, modulus;      /* modulus: index into moduli[] for kinds 2..6, otherwise 0 */
+    uint32_t cell_begin;         /* this unit's run in cells[]: operands in the kind's order, inputs first, limbs little-endian */
+    uint16_t len[6];             /* limb (cell) count per operand in that order; unused entries 0 */
+} glp_witness_free_unit;
+struct glp_witness_plan_free_info {      /* a struct tag, as glp_witness_plan_info */
+    uint64_t num_free_units, num_stuck_free_units;
+    uint64_t first_stuck_free_unit;      /* index into units[], iff num_stuck_free_units */
+    uint64_t widest_wave_free_units;
+};
+GLP_API int glp_witness_plan_create_ex(glp_ctx *ctx, const glp_circuit *c, const uint64_t *input_cells, uint32_t num_inputs,
+                                       const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
+                                       const uint32_t *moduli /* [num_moduli][8], little-endian u32 limbs */, uint32_t num_moduli,
+                                       glp_witness_plan **out);
+GLP_API int glp_witness_plan_free_info(const glp_witness_plan *p, struct glp_witness_plan_free_info *out);
 GLP_API int  glp_witness_plan_info(const glp_witness_plan *p, struct glp_witness_plan_info *out);
 GLP_API int  glp_witness_plan_cell_waves(const glp_witness_plan *p, int32_t *waves_out /* [num_wires][n] */);
 GLP_API void glp_witness_plan_free(glp_witness_plan *p);

@@ -93,6 +93,23 @@ class _WitnessPlanInfo(C.Structure):
                 ("stuck_unit", C.c_uint32)]
 
 
+class _WitnessFreeUnit(C.Structure):          # glp_witness_free_unit
+    _fields_ = [("kind", C.c_uint32), ("modulus", C.c_uint32), ("cell_begin", C.c_uint32), ("len", C.c_uint16 * 6)]
+
+
+class _WitnessPlanFreeInfo(C.Structure):
+    _fields_ = [("num_free_units", C.c_uint64), ("num_stuck_free_units", C.c_uint64), ("first_stuck_free_unit", C.c_uint64),
+                ("widest_wave_free_units", C.c_uint64)]
+
+
+# GLP_WGEN_* of include/glp.h: the kinds of free units, their largest operand, the output cell that is not written
+(WGEN_EQUALITY, WGEN_NONNATIVE_ADD, WGEN_NONNATIVE_MULTI_ADD, WGEN_NONNATIVE_SUB, WGEN_NONNATIVE_MUL, WGEN_NONNATIVE_INV, WGEN_BIGUINT_DIV_REM,
+ WGEN_GLV_SECP256K1) = range(1, 9)
+WGEN_MAX_LIMBS = 18
+WGEN_NO_CELL = 0xFFFFFFFFFFFFFFFF
+FREE_UNIT_DTYPE = np.dtype([("kind", np.uint32), ("modulus", np.uint32), ("cell_begin", np.uint32), ("len", np.uint16, (6,))])
+
+
 # GLP_GATE_* of include/glp.h and the names of the gate types (19 is unassigned)
 (GATE_NOOP, GATE_CONSTANT, GATE_PUBLIC_INPUT, GATE_ARITHMETIC, GATE_POSEIDON, GATE_U32_INTERLEAVE, GATE_UNINTERLEAVE_U32, GATE_UNINTERLEAVE_B32,
  GATE_U32_ARITHMETIC, GATE_U32_ADD_MANY, GATE_U32_SUBTRACTION, GATE_U32_RANGE_CHECK, GATE_COMPARISON, GATE_BASE_SUM, GATE_RANDOM_ACCESS,
@@ -254,6 +271,8 @@ def load_library():
         "glp_witness_columns": [vp, u32, vp],
         "glp_witness_unit_columns": [vp, u32, u32, vp],
         "glp_witness_plan_create": [vp, vp, vp, u32, C.POINTER(vp)],
+        "glp_witness_plan_create_ex": [vp, vp, vp, u32, vp, u32, vp, sz, vp, u32, C.POINTER(vp)],
+        "glp_witness_plan_free_info": [vp, C.POINTER(_WitnessPlanFreeInfo)],
         "glp_witness_plan_info": [vp, C.POINTER(_WitnessPlanInfo)],
         "glp_witness_plan_cell_waves": [vp, vp],
         "glp_witness_plan_free": [vp],
@@ -1274,11 +1293,37 @@ class Circuit:
             _chk(L.glp_witness_unit_columns(self._h, int(gate_index), u, out[u].ctypes.data_as(C.c_void_p)))
         return out
 
-    def witness_plan(self, input_cells):
-        """glp_witness_plan_create: input_cells = flat positions col * n + row of the cells the caller sets -> WitnessPlan."""
+    def witness_plan(self, input_cells, free_units=None, moduli=None):
+        """glp_witness_plan_create(_ex): input_cells = flat positions col * n + row of the cells the caller sets -> WitnessPlan.
+        free_units = (units, cells): the generators that belong to no gate (include/glp.h, FREE UNITS) as a FREE_UNIT_DTYPE array
+        (or anything np.asarray makes one of: rows of kind, modulus, cell_begin, len[6]) and the uint64 cells their runs point into;
+        moduli = uint32 [num_moduli][8], little-endian limbs."""
         cells = _a(input_cells).reshape(-1)
         h = C.c_void_p()
-        _chk(load_library().glp_witness_plan_create(self.ctx._h, self._h, _p(cells) if cells.size else None, cells.size, C.byref(h)))
+        if free_units is None:
+            if moduli is not None:
+                raise GlpError(-1, "moduli without free_units")
+            _chk(load_library().glp_witness_plan_create(self.ctx._h, self._h, _p(cells) if cells.size else None, cells.size, C.byref(h)))
+        else:
+            units, fcells = free_units
+            units = np.ascontiguousarray(units)
+            if units.dtype != FREE_UNIT_DTYPE:
+                raw = np.ascontiguousarray(units, dtype=np.int64).reshape(-1, 9)
+                if raw.size and (raw.min() < 0 or raw[:, :3].max() >= 1 << 32 or raw[:, 3:].max() >= 1 << 16):
+                    raise GlpError(-1, "free_units: a field does not fit its C type (uint32 kind, modulus, cell_begin; uint16 len[6])")
+                units = np.zeros(raw.shape[0], FREE_UNIT_DTYPE)
+                units["kind"], units["modulus"], units["cell_begin"], units["len"] = raw[:, 0], raw[:, 1], raw[:, 2], raw[:, 3:]
+            assert units.itemsize == C.sizeof(_WitnessFreeUnit) == 24
+            fcells = _a(fcells).reshape(-1)
+            mod = np.ascontiguousarray(np.zeros((0, 8)) if moduli is None else moduli, dtype=np.uint32)
+            if mod.size % 8:
+                raise GlpError(-1, "moduli has %d words, expected num_moduli * 8" % mod.size)
+            if units.size >= 1 << 32 or mod.size // 8 >= 1 << 32:
+                raise GlpError(-1, "free_units or moduli too long for a uint32 count")
+            _chk(load_library().glp_witness_plan_create_ex(self.ctx._h, self._h, _p(cells) if cells.size else None, cells.size,
+                                                           units.ctypes.data_as(C.c_void_p) if units.size else None, units.size,
+                                                           _p(fcells) if fcells.size else None, fcells.size,
+                                                           mod.ctypes.data_as(C.c_void_p) if mod.size else None, mod.size // 8, C.byref(h)))
         plan = WitnessPlan(self, h, cells.size)
         self.ctx._plans.add(plan)
         return plan
@@ -1374,6 +1419,16 @@ class WitnessPlan:
         out = {f: int(getattr(raw, f)) for f in self.INFO}
         if not out["num_stuck_units"]:
             out["stuck_row"] = out["stuck_gate"] = out["stuck_unit"] = None
+        return out
+
+    @property
+    def free_info(self):
+        """dict of glp_witness_plan_free_info; first_stuck_free_unit is None unless num_stuck_free_units."""
+        raw = _WitnessPlanFreeInfo()
+        _chk(load_library().glp_witness_plan_free_info(self._h, C.byref(raw)))
+        out = {f: int(getattr(raw, f)) for f, _ in _WitnessPlanFreeInfo._fields_}
+        if not out["num_stuck_free_units"]:
+            out["first_stuck_free_unit"] = None
         return out
 
     def cell_waves(self):

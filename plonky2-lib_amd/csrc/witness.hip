@@ -27,6 +27,7 @@
 #include "common.h"
 #include "poseidon.h"
 #include "prover_types.h"
+#include "biguint_dev.h"
 
 namespace {
 
@@ -463,6 +464,8 @@ extern "C" int glp_witness_unit_columns(const glp_circuit *cc, uint32_t gate_ind
 namespace {
 struct WUnit { u32 row, gu; };          // gu = gate << 16 | unit
 struct WCopy { u32 src, dst; };         // flat positions col * n + row
+typedef glp_witness_free_unit WFree;    // a free unit as the caller gave it; cell_begin points into the plan's 32-bit copy of cells[]
+static_assert(sizeof(WFree) == 24, "glp_witness_free_unit: three u32 and six u16");
 struct WGen {
     WArgs a;                            // a.wires: proof 0
     const WUnit *units;                 // wave w: units[unit_off[w] .. unit_off[w + 1]), sorted by row; wave 0 holds none
@@ -470,7 +473,11 @@ struct WGen {
     const u32 *unit_off, *copy_off, *inputs;
     const u64 *vals;                    // [K][num_inputs]
     u32 num_inputs, nw;
+    const WFree *free_units;            // wave w: free_units[free_off[w] .. free_off[w + 1]), in the caller's order; null without free units
+    const u32 *free_off, *free_cells;   // a unit's run: its input cells, then its output cells (NONE: not written)
+    const u32 *moduli;                  // [num_moduli][8]
 };
+constexpr u32 NONE = 0xFFFFFFFFu;
 constexpr u32 WGEN_MAX_PROOFS = 4096;   // as glp_witness_check
 constexpr u32 WITNESS_NARROW_MAX_DEFAULT = 256;
 
@@ -487,6 +494,51 @@ __device__ __forceinline__ void wg_units(const WGen &g, u64 *W, const u64 *vals,
         witness_unit(g.a, gate, W + u.row, g.a.consts + (size_t)g.a.nsel * n + u.row, n, u.gu & 0xFFFFu);
     }
 }
+// One free unit (include/glp.h, FREE UNITS) on one lane: operand limbs are the low 32 bits of the cells of its run.  The cells were
+// range-checked by the planner; a value read from the witness is a limb, never a cell.  The two instances of the limb arithmetic are
+// functions of their own, not inlined into the kernels: the register budget of the 8-limb one (every count a compile-time 8, its limbs
+// in VGPRs) is then its own, whatever the gate units and the general-length instance beside it need, and the compiler's resource report
+// names it (profiles/kernel_resources.sh witness.hip).
+struct WFreeIo {                          // a unit's cells: rd(i) = limb i of its inputs, wr(i, v) = output cell i
+    u64 *W; const u32 *in, *out;
+    __device__ __forceinline__ u32 operator()(int i) const { return (u32)W[in[i]]; }
+    __device__ __forceinline__ void operator()(int i, u32 v) const { const u32 c = out[i]; if (c != NONE) W[c] = v; }
+};
+__device__ __noinline__ void witness_free_unit8(u64 *W, const u32 *run, const u32 *mod, u32 kind) {
+    const uint16_t len[6] = {8, 8, 8, (uint16_t)(kind == GLP_WGEN_NONNATIVE_MUL ? 8 : 1), 0, 0};
+    u32 m[big::MAX_MOD];
+    for (int i = 0; i < big::MAX_MOD; i++) m[i] = mod[i];
+    const WFreeIo io = {W, run, run + (kind == GLP_WGEN_NONNATIVE_INV ? 8 : 16)};
+    big::run_unit<true>(kind, len, m, 8, io, io, nullptr);
+}
+__device__ __noinline__ void witness_free_unit_any(u64 *W, const u32 *run, const u32 *mod, const WFree *u) {
+    const WFree unit = *u;
+    u32 m[big::MAX_MOD];
+    for (int i = 0; i < big::MAX_MOD; i++) m[i] = mod ? mod[i] : 0;
+    const WFreeIo io = {W, run, run + big::num_in(unit.kind, unit.len)};
+    big::run_unit<false>(unit.kind, unit.len, m, big::used_limbs(m, big::MAX_MOD), io, io, nullptr);
+}
+__device__ __forceinline__ void witness_free_unit(const WGen &g, u64 *W, const WFree *u) {
+    const u32 kind = u->kind;
+    const u32 *run = g.free_cells + u->cell_begin;
+    if (kind == GLP_WGEN_EQUALITY) {
+        const u64 d = sub(W[run[0]], W[run[1]]);
+        if (run[2] != NONE) W[run[2]] = d == 0 ? 1 : 0;
+        if (run[3] != NONE) W[run[3]] = d ? winv(d) : 0;
+        return;
+    }
+    const bool has_modulus = kind >= GLP_WGEN_NONNATIVE_ADD && kind <= GLP_WGEN_NONNATIVE_INV;
+    const u32 *mod = has_modulus ? g.moduli + (size_t)u->modulus * big::MAX_MOD : nullptr;
+    if (has_modulus && big::all8(kind, u->len, mod[big::MAX_MOD - 1] ? 8 : 0)) witness_free_unit8(W, run, mod, kind);
+    else witness_free_unit_any(W, run, mod, u);
+}
+// the free units of wave w of one proof, lane `first` of `stride`; they read what earlier waves left and write cells nothing else
+// of the wave touches, so they share the units step with wg_units
+__device__ __forceinline__ void wg_free(const WGen &g, u64 *W, u32 w, size_t first, size_t stride) {
+    if (!g.free_units || w == 0) return;
+    const size_t end = g.free_off[w + 1];
+    for (size_t i = g.free_off[w] + first; i < end; i += stride) witness_free_unit(g, W, g.free_units + i);
+}
 __device__ __forceinline__ void wg_copies(const WGen &g, u64 *W, u32 w, size_t first, size_t stride) {
     const size_t end = g.copy_off[w + 1];
     for (size_t i = g.copy_off[w] + first; i < end; i += stride) {
@@ -496,12 +548,15 @@ __device__ __forceinline__ void wg_copies(const WGen &g, u64 *W, u32 w, size_t f
 }
 // Walked waves: one workgroup per proof walks waves w0 .. w1.  All traffic of a proof stays in its workgroup, so plain global stores,
 // drained, followed by the block barrier hand a wave's values to the next.
+// FREE = false is the kernel of a plan without free units: nothing of the limb arithmetic is in it.
+template <bool FREE>
 __global__ __launch_bounds__(256) void k_witness_waves(WGen g, u32 w0, u32 w1) {
     const size_t n = (size_t)1 << g.a.lg;
     u64 *W = g.a.wires + (size_t)blockIdx.x * g.nw * n;
     const u64 *vals = g.vals + (size_t)blockIdx.x * g.num_inputs;
     for (u32 w = w0; w <= w1; w++) {
         wg_units(g, W, vals, n, w, threadIdx.x, 256);
+        if (FREE) wg_free(g, W, w, threadIdx.x, 256);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         wg_copies(g, W, w, threadIdx.x, 256);
@@ -515,6 +570,11 @@ __global__ __launch_bounds__(256) void k_witness_units(WGen g, u32 w) {
     wg_units(g, g.a.wires + (size_t)blockIdx.y * g.nw * n, g.vals + (size_t)blockIdx.y * g.num_inputs, n, w, (size_t)blockIdx.x * 256 + threadIdx.x,
              (size_t)gridDim.x * 256);
 }
+// the free units of a wide wave: one lane per unit, 64-lane workgroups so that the few long lanes of a wave spread over the chip
+__global__ __launch_bounds__(64) void k_witness_free(WGen g, u32 w) {
+    const size_t n = (size_t)1 << g.a.lg;
+    wg_free(g, g.a.wires + (size_t)blockIdx.y * g.nw * n, w, (size_t)blockIdx.x * 64 + threadIdx.x, (size_t)gridDim.x * 64);
+}
 __global__ __launch_bounds__(256) void k_witness_copies(WGen g, u32 w) {
     const size_t n = (size_t)1 << g.a.lg;
     wg_copies(g, g.a.wires + (size_t)blockIdx.y * g.nw * n, w, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
@@ -523,7 +583,6 @@ __global__ __launch_bounds__(256) void k_witness_read_cells(const u64 *wires, co
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i < num_cells) out[(size_t)blockIdx.y * num_cells + i] = wires[(size_t)blockIdx.y * per_proof + cells[i]];
 }
-constexpr u32 NONE = 0xFFFFFFFFu;
 }  // namespace
 
 struct glp_witness_plan {
@@ -536,6 +595,10 @@ struct glp_witness_plan {
     WUnit *dev_units = nullptr;
     WCopy *dev_copies = nullptr;
     u32 *dev_unit_off = nullptr, *dev_copy_off = nullptr, *dev_inputs = nullptr;
+    struct glp_witness_plan_free_info free_info;
+    std::vector<u32> free_off;                     // [num_waves + 2]; empty without free units
+    WFree *dev_free_units = nullptr;
+    u32 *dev_free_off = nullptr, *dev_free_cells = nullptr, *dev_moduli = nullptr;
     mutable u64 *dev_vals = nullptr;               // [vals_cap] the input values of the generation in flight: a plan serves one at a time
     mutable size_t vals_cap = 0;
 };
@@ -546,15 +609,36 @@ extern "C" void glp_witness_plan_free(glp_witness_plan *p) {
     if (bind(c) == GLP_OK) (void)hipStreamSynchronize(c->stream);
     c->release(p->dev_units); c->release(p->dev_copies); c->release(p->dev_unit_off); c->release(p->dev_copy_off);
     c->release(p->dev_inputs); c->release(p->dev_vals);
+    c->release(p->dev_free_units); c->release(p->dev_free_off); c->release(p->dev_free_cells); c->release(p->dev_moduli);
     delete p;
 }
 
-// glp_witness_plan_create without its allocation guard
-static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs, glp_witness_plan **out) {
+// The shape of a free unit's kind: which of len[0..5] are operands, which of them are single cells, which is a divisor.  0 = unknown kind.
+struct WFreeShape { u32 operands; u32 single; int divisor; };     // bit i of single: len[i] must be 1
+static WFreeShape witness_free_shape(u32 kind) {
+    switch (kind) {
+    case GLP_WGEN_EQUALITY: return {4, 0xF, -1};
+    case GLP_WGEN_NONNATIVE_ADD: case GLP_WGEN_NONNATIVE_SUB: return {4, 0x8, -1};
+    case GLP_WGEN_NONNATIVE_MULTI_ADD: return {4, 0x8, -1};
+    case GLP_WGEN_NONNATIVE_MUL: return {4, 0, -1};
+    case GLP_WGEN_NONNATIVE_INV: return {3, 0, -1};
+    case GLP_WGEN_BIGUINT_DIV_REM: return {4, 0, 1};
+    case GLP_WGEN_GLV_SECP256K1: return {5, 0x18, -1};
+    default: return {0, 0, -1};
+    }
+}
+
+// glp_witness_plan_create_ex without its allocation guard; glp_witness_plan_create is its num_units = 0 case
+static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
+                              const glp_witness_free_unit *funits, uint32_t nf, const uint64_t *fcells, size_t num_fcells, const uint32_t *moduli,
+                              uint32_t num_moduli, glp_witness_plan **out) {
     GLP_REQUIRE(c, "%s: ctx is null", fn);
     GLP_REQUIRE(cc, "%s: circuit is null", fn);
     GLP_REQUIRE(out, "%s: out is null", fn);
     GLP_REQUIRE(input_cells || num_inputs == 0, "%s: input_cells is null, num_inputs = %u", fn, num_inputs);
+    GLP_REQUIRE(funits || nf == 0, "%s: units is null, num_units = %u", fn, nf);
+    GLP_REQUIRE(fcells || num_fcells == 0, "%s: cells is null, num_cells = %zu", fn, num_fcells);
+    GLP_REQUIRE(moduli || num_moduli == 0, "%s: moduli is null, num_moduli = %u", fn, num_moduli);
     GLP_REQUIRE(cc->ctx == c, "%s: circuit belongs to another ctx", fn);
     const glp_circuit_desc &d = cc->d;
     const u32 lg = d.degree_bits, nw = d.num_wires, nr = d.num_routed_wires, ng = d.num_gates, nsel = d.num_selectors;
@@ -572,7 +656,99 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
         GLP_REQUIRE(at == NONE, "%s: input_cells[%u] = %llu is listed twice (also input_cells[%u])", fn, i, (unsigned long long)input_cells[i], at);
         at = i;
     }
+    // the moduli and the free units: shapes, runs and cells
+    GLP_REQUIRE(num_fcells < NONE, "%s: num_cells = %zu, a plan addresses fewer than 2^32 - 1", fn, num_fcells);
+    for (u32 i = 0; i < num_moduli; i++) {
+        const uint32_t *m = moduli + (size_t)i * 8;
+        GLP_REQUIRE(m[0] & 1, "%s: moduli[%u] is even", fn, i);
+        GLP_REQUIRE(big::used_limbs(m, 8) > 1 || m[0] >= 3, "%s: moduli[%u] = %u is below 3", fn, i, m[0]);
+    }
+    std::vector<u32> fcells32(num_fcells), f_ni(nf), f_no(nf);
+    for (size_t i = 0; i < num_fcells; i++) fcells32[i] = fcells[i] < cells ? (u32)fcells[i] : NONE;      // outputs may be GLP_WGEN_NO_CELL; checked per run below
+    for (u32 f = 0; f < nf; f++) {
+        const glp_witness_free_unit &u = funits[f];
+        const WFreeShape sh = witness_free_shape(u.kind);
+        GLP_REQUIRE(sh.operands, "%s: units[%u].kind = %u is not a GLP_WGEN_* kind", fn, f, u.kind);
+        const bool has_modulus = u.kind >= GLP_WGEN_NONNATIVE_ADD && u.kind <= GLP_WGEN_NONNATIVE_INV;
+        if (has_modulus) GLP_REQUIRE(u.modulus < num_moduli, "%s: units[%u].modulus = %u, num_moduli = %u", fn, f, u.modulus, num_moduli);
+        else GLP_REQUIRE(u.modulus == 0, "%s: units[%u].modulus = %u, kind %u has no modulus: 0", fn, f, u.modulus, u.kind);
+        for (u32 i = 0; i < 6; i++) {
+            const u32 l = u.len[i];
+            if (i >= sh.operands) { GLP_REQUIRE(l == 0, "%s: units[%u].len[%u] = %u, kind %u has %u operands: unused entries are 0", fn, f, i, l, u.kind, sh.operands); continue; }
+            if (sh.single >> i & 1) { GLP_REQUIRE(l == 1, "%s: units[%u].len[%u] = %u, that operand of kind %u is 1 cell", fn, f, i, l, u.kind); continue; }
+            if (u.kind == GLP_WGEN_NONNATIVE_MULTI_ADD && i == 0) continue;                                   // the number of summands
+            if ((int)i == sh.divisor) GLP_REQUIRE(l <= 8, "%s: units[%u].len[%u] = %u, a divisor has at most 8 limbs", fn, f, i, l);
+            GLP_REQUIRE(l <= GLP_WGEN_MAX_LIMBS, "%s: units[%u].len[%u] = %u, an operand has at most GLP_WGEN_MAX_LIMBS = %u limbs", fn, f, i, l, GLP_WGEN_MAX_LIMBS);
+            if (u.kind == GLP_WGEN_GLV_SECP256K1) GLP_REQUIRE(l == (i ? 4u : 8u), "%s: units[%u].len[%u] = %u, GLV_SECP256K1 has k of 8 and k1, k2 of 4 limbs", fn, f, i, l);
+        }
+        f_ni[f] = big::num_in(u.kind, u.len); f_no[f] = big::num_out(u.kind, u.len);
+        GLP_REQUIRE((size_t)u.cell_begin + f_ni[f] + f_no[f] <= num_fcells, "%s: units[%u].cell_begin = %u: its run of %u cells leaves cells[] (num_cells = %zu)", fn, f,
+                    u.cell_begin, f_ni[f] + f_no[f], num_fcells);
+        for (u32 i = 0; i < f_ni[f] + f_no[f]; i++) {
+            const uint64_t cell = fcells[(size_t)u.cell_begin + i];
+            GLP_REQUIRE(cell < cells || (i >= f_ni[f] && cell == GLP_WGEN_NO_CELL), "%s: units[%u]: cells[%zu] = %llu is out of range (num_wires * 2^degree_bits = %zu cells)", fn, f,
+                        (size_t)u.cell_begin + i, (unsigned long long)cell, cells);
+        }
+    }
     GLP_TRY(bind(c));
+    // the gate of every row, as k_witness_fill reads it
+    std::vector<u32> row_gate(n, NONE);
+    {
+        std::vector<u64> sel((size_t)nsel * n);
+        GLP_TRY(d2h(c, sel.data(), cc->dev_consts, sel.size() * 8));
+        for (size_t r = 0; r < n; r++) {
+            u32 gi = NONE;
+            for (u32 s = 0; s < nsel; s++) { const u64 v = sel[(size_t)s * n + r]; if (nsel == 1 || v != 0xFFFFFFFFull) gi = (u32)v; }
+            row_gate[r] = gi < ng ? gi : NONE;
+        }
+    }
+    // per gate and unit: the columns read and written
+    std::vector<std::vector<std::vector<u32>>> g_in(ng), g_out(ng);
+    {
+        std::vector<uint8_t> role(nw);
+        for (u32 gi = 0; gi < ng; gi++) {
+            const glp_gate &g = cc->gates[gi];
+            const u32 nu = witness_gate_units(g.type, g.p0, g.p1);
+            GLP_REQUIRE(nu <= 0xFFFF, "%s: gate %u has %u units per row, a plan names at most 65535", fn, gi, nu);
+            g_in[gi].resize(nu); g_out[gi].resize(nu);
+            for (u32 u = 0; u < nu; u++) {
+                witness_unit_roles(g, nw, u, role.data());
+                for (u32 col = 0; col < nw; col++) { if (role[col] == 2) g_in[gi][u].push_back(col); if (role[col] == 1) g_out[gi][u].push_back(col); }
+            }
+        }
+    }
+    // the units in (row, unit) order; unit k of the plan = unit k - row_first[row] of its row; the free units follow: unit nu_total + f
+    std::vector<size_t> row_first(n + 1, 0);
+    for (size_t r = 0; r < n; r++) row_first[r + 1] = row_first[r] + (row_gate[r] == NONE ? 0 : g_in[row_gate[r]].size());
+    const size_t nu_total = row_first[n], nk = nu_total + nf;
+    GLP_REQUIRE(nk < NONE, "%s: %zu units exceed the 2^32 - 1 a plan addresses", fn, nk);
+    std::vector<u32> unit_row(nu_total);
+    for (size_t r = 0; r < n; r++) for (size_t k = row_first[r]; k < row_first[r + 1]; k++) unit_row[k] = (u32)r;
+    auto for_in = [&](size_t k, auto &&visit) {            // the cells unit k reads / writes
+        if (k < nu_total) { const size_t r = unit_row[k]; for (u32 col : g_in[row_gate[r]][k - row_first[r]]) visit((size_t)col * n + r); return; }
+        const u32 f = (u32)(k - nu_total);
+        for (u32 i = 0; i < f_ni[f]; i++) visit((size_t)fcells32[(size_t)funits[f].cell_begin + i]);
+    };
+    auto for_out = [&](size_t k, auto &&visit) {
+        if (k < nu_total) { const size_t r = unit_row[k]; for (u32 col : g_out[row_gate[r]][k - row_first[r]]) visit((size_t)col * n + r); return; }
+        const u32 f = (u32)(k - nu_total);
+        for (u32 i = 0; i < f_no[f]; i++) { const u32 cell = fcells32[(size_t)funits[f].cell_begin + f_ni[f] + i]; if (cell != NONE) visit((size_t)cell); }
+    };
+    // the writer of every cell; a free unit may not write what another unit writes
+    std::vector<u32> writer(cells, NONE);
+    for (size_t k = 0; k < nu_total; k++) for_out(k, [&](size_t q) { writer[q] = (u32)k; });
+    for (u32 f = 0; f < nf; f++) {
+        int rc = GLP_OK;
+        for_out(nu_total + f, [&](size_t q) {
+            if (rc != GLP_OK) return;
+            const u32 wk = writer[q];
+            if (wk == NONE) { writer[q] = (u32)(nu_total + f); return; }
+            if (wk >= nu_total) rc = set_error(GLP_ERR_ARG, "%s: units[%u]: output cell %zu is also written by units[%u]", fn, f, q, (u32)(wk - nu_total));
+            else rc = set_error(GLP_ERR_ARG, "%s: units[%u]: output cell %zu (column %zu, row %zu) is also written by unit %u of gate %u of that row", fn, f, q, q / n, q % n,
+                                (u32)(wk - row_first[unit_row[wk]]), row_gate[unit_row[wk]]);
+        });
+        if (rc != GLP_OK) return rc;
+    }
     GLP_TRY(witness_sigma_decode(c, cc, fn));
 
     // the copy classes: the cycles of the decoded permutation, named by their smallest position; a non-routed cell is its own class
@@ -602,78 +778,39 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
             class_wave[cls[(size_t)input_cells[i]]] = 0;
         }
     }
-    // the gate of every row, as k_witness_fill reads it
-    std::vector<u32> row_gate(n, NONE);
-    {
-        std::vector<u64> sel((size_t)nsel * n);
-        GLP_TRY(d2h(c, sel.data(), cc->dev_consts, sel.size() * 8));
-        for (size_t r = 0; r < n; r++) {
-            u32 gi = NONE;
-            for (u32 s = 0; s < nsel; s++) { const u64 v = sel[(size_t)s * n + r]; if (nsel == 1 || v != 0xFFFFFFFFull) gi = (u32)v; }
-            row_gate[r] = gi < ng ? gi : NONE;
-        }
-    }
-    // per gate and unit: the columns read and written
-    std::vector<std::vector<std::vector<u32>>> g_in(ng), g_out(ng);
-    {
-        std::vector<uint8_t> role(nw);
-        for (u32 gi = 0; gi < ng; gi++) {
-            const glp_gate &g = cc->gates[gi];
-            const u32 nu = witness_gate_units(g.type, g.p0, g.p1);
-            GLP_REQUIRE(nu <= 0xFFFF, "%s: gate %u has %u units per row, a plan names at most 65535", fn, gi, nu);
-            g_in[gi].resize(nu); g_out[gi].resize(nu);
-            for (u32 u = 0; u < nu; u++) {
-                witness_unit_roles(g, nw, u, role.data());
-                for (u32 col = 0; col < nw; col++) { if (role[col] == 2) g_in[gi][u].push_back(col); if (role[col] == 1) g_out[gi][u].push_back(col); }
-            }
-        }
-    }
-    // the units in (row, unit) order; unit k of the plan = unit k - row_first[row] of its row
-    std::vector<size_t> row_first(n + 1, 0);
-    for (size_t r = 0; r < n; r++) row_first[r + 1] = row_first[r] + (row_gate[r] == NONE ? 0 : g_in[row_gate[r]].size());
-    const size_t nu_total = row_first[n];
-    GLP_REQUIRE(nu_total < NONE, "%s: %zu units exceed the 2^32 - 1 a plan addresses", fn, nu_total);
-    std::vector<u32> unit_row(nu_total);
-    for (size_t r = 0; r < n; r++) for (size_t k = row_first[r]; k < row_first[r + 1]; k++) unit_row[k] = (u32)r;
-    // the writer of every cell, and per class the units that wait for it (one entry per cell read in a class not known from the inputs)
-    std::vector<u32> writer(cells, NONE), pending(nu_total, 0);
+    // per class the units that wait for it (one entry per cell read in a class not known from the inputs)
+    std::vector<u32> pending(nk, 0);
     std::vector<size_t> reader_off(cells + 1, 0);
-    for (size_t k = 0; k < nu_total; k++) {
-        const size_t r = unit_row[k];
-        const u32 gi = row_gate[r], u = (u32)(k - row_first[r]);
-        for (u32 col : g_out[gi][u]) writer[(size_t)col * n + r] = (u32)k;
-        for (u32 col : g_in[gi][u]) { const u32 cl = cls[(size_t)col * n + r]; if (class_wave[cl] < 0) { reader_off[cl + 1]++; pending[k]++; } }
-    }
+    for (size_t k = 0; k < nk; k++)
+        for_in(k, [&](size_t q) { const u32 cl = cls[q]; if (class_wave[cl] < 0) { reader_off[cl + 1]++; pending[k]++; } });
     for (size_t p = 0; p < cells; p++) reader_off[p + 1] += reader_off[p];
     std::vector<u32> readers(reader_off[cells]);
     {
         std::vector<size_t> fill(reader_off.begin(), reader_off.end() - 1);
-        for (size_t k = 0; k < nu_total; k++) {
-            const size_t r = unit_row[k];
-            const u32 gi = row_gate[r], u = (u32)(k - row_first[r]);
-            for (u32 col : g_in[gi][u]) { const u32 cl = cls[(size_t)col * n + r]; if (class_wave[cl] < 0) readers[fill[cl]++] = (u32)k; }
-        }
+        for (size_t k = 0; k < nk; k++)
+            for_in(k, [&](size_t q) { const u32 cl = cls[q]; if (class_wave[cl] < 0) readers[fill[cl]++] = (u32)k; });
     }
     // the waves: a unit is ready once every class it reads is known; its wave is one more than the wave that made the last one known
-    std::vector<int32_t> unit_wave(nu_total, -1);
+    std::vector<int32_t> unit_wave(nk, -1);
     std::vector<u32> ready, next;
-    for (size_t k = 0; k < nu_total; k++) if (pending[k] == 0) ready.push_back((u32)k);
+    for (size_t k = 0; k < nk; k++) if (pending[k] == 0) ready.push_back((u32)k);
     u32 num_waves = 0;
-    uint64_t widest = 0;
+    uint64_t widest = 0, widest_free = 0;
     while (!ready.empty()) {
         num_waves++;
-        widest = std::max<uint64_t>(widest, ready.size());
+        uint64_t wave_free = 0;
+        for (u32 k : ready) wave_free += k >= nu_total;
+        widest = std::max<uint64_t>(widest, ready.size() - wave_free);
+        widest_free = std::max<uint64_t>(widest_free, wave_free);
         next.clear();
         for (u32 k : ready) unit_wave[k] = (int32_t)num_waves;
-        for (u32 k : ready) {
-            const size_t r = unit_row[k];
-            for (u32 col : g_out[row_gate[r]][k - row_first[r]]) {
-                const u32 cl = cls[(size_t)col * n + r];
-                if (class_wave[cl] >= 0) continue;
+        for (u32 k : ready)
+            for_out(k, [&](size_t q) {
+                const u32 cl = cls[q];
+                if (class_wave[cl] >= 0) return;
                 class_wave[cl] = (int32_t)num_waves;
                 for (size_t i = reader_off[cl]; i < reader_off[cl + 1]; i++) if (--pending[readers[i]] == 0) next.push_back(readers[i]);
-            }
-        }
+            });
         ready.swap(next);
     }
     std::unique_ptr<glp_witness_plan> p(new glp_witness_plan);
@@ -682,6 +819,9 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
     struct glp_witness_plan_info &info = p->info;
     memset(&info, 0, sizeof(info));
     info.num_waves = num_waves; info.num_units = nu_total; info.widest_wave_units = widest;
+    struct glp_witness_plan_free_info &finfo = p->free_info;
+    memset(&finfo, 0, sizeof(finfo));
+    finfo.num_free_units = nf; finfo.widest_wave_free_units = widest_free;
     // the lists: units by wave in (row, unit) order, the source of every known class, the copies by wave in order of the destination
     p->unit_off.assign(num_waves + 2, 0);
     p->copy_off.assign(num_waves + 2, 0);
@@ -695,6 +835,20 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
         std::vector<u32> fill(p->unit_off.begin(), p->unit_off.end() - 1);
         for (size_t k = 0; k < nu_total; k++)
             if (unit_wave[k] > 0) units[fill[unit_wave[k]]++] = WUnit{unit_row[k], row_gate[unit_row[k]] << 16 | (u32)(k - row_first[unit_row[k]])};
+    }
+    // the free units by wave, in the caller's order
+    std::vector<WFree> free_list;
+    if (nf) {
+        p->free_off.assign(num_waves + 2, 0);
+        for (u32 f = 0; f < nf; f++) {
+            const int32_t uw = unit_wave[nu_total + f];
+            if (uw > 0) { p->free_off[uw + 1]++; continue; }
+            if (!finfo.num_stuck_free_units++) finfo.first_stuck_free_unit = f;
+        }
+        for (u32 w = 0; w <= num_waves; w++) p->free_off[w + 1] += p->free_off[w];
+        free_list.resize(p->free_off[num_waves + 1]);
+        std::vector<u32> fill(p->free_off.begin(), p->free_off.end() - 1);
+        for (u32 f = 0; f < nf; f++) if (unit_wave[nu_total + f] > 0) free_list[fill[unit_wave[nu_total + f]]++] = funits[f];
     }
     std::vector<u32> source(cells, NONE);        // by class name
     p->cell_waves.assign(cells, -1);
@@ -731,18 +885,40 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
         if (rc == GLP_OK && !v.empty()) rc = h2d(c, *dev, v.data(), v.size() * sizeof(v[0]));
     };
     up(&p->dev_units, units); up(&p->dev_copies, copies); up(&p->dev_unit_off, p->unit_off); up(&p->dev_copy_off, p->copy_off); up(&p->dev_inputs, in32);
+    if (nf) {
+        const std::vector<u32> mod32(moduli, moduli + (size_t)num_moduli * 8);
+        up(&p->dev_free_units, free_list); up(&p->dev_free_off, p->free_off); up(&p->dev_free_cells, fcells32); up(&p->dev_moduli, mod32);
+    }
     if (rc != GLP_OK) { glp_witness_plan_free(p.release()); return rc; }
     *out = p.release();
     return GLP_OK;
 }
 
-extern "C" int glp_witness_plan_create(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs, glp_witness_plan **out) {
-    static const char *fn = "glp_witness_plan_create";
+extern "C" int glp_witness_plan_create_ex(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
+                                          const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
+                                          const uint32_t *moduli, uint32_t num_moduli, glp_witness_plan **out) {
+    static const char *fn = "glp_witness_plan_create_ex";
     try {
-        return witness_plan_build(fn, c, cc, input_cells, num_inputs, out);
+        return witness_plan_build(fn, c, cc, input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, out);
     } catch (const std::bad_alloc &) {       // the planner's host tables: about 40 bytes per cell
         return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
     }
+}
+
+extern "C" int glp_witness_plan_create(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs, glp_witness_plan **out) {
+    static const char *fn = "glp_witness_plan_create";
+    try {
+        return witness_plan_build(fn, c, cc, input_cells, num_inputs, nullptr, 0, nullptr, 0, nullptr, 0, out);
+    } catch (const std::bad_alloc &) {
+        return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
+    }
+}
+
+extern "C" int glp_witness_plan_free_info(const glp_witness_plan *p, struct glp_witness_plan_free_info *out) {
+    GLP_REQUIRE(p, "glp_witness_plan_free_info: plan is null");
+    GLP_REQUIRE(out, "glp_witness_plan_free_info: out is null");
+    *out = p->free_info;
+    return GLP_OK;
 }
 
 extern "C" int glp_witness_plan_info(const glp_witness_plan *p, struct glp_witness_plan_info *out) {
@@ -796,22 +972,27 @@ extern "C" int glp_witness_generate(glp_ctx *c, const glp_witness_plan *p, uint3
     g.a.lg = cc->d.degree_bits; g.a.nsel = cc->d.num_selectors; g.a.num_gates = cc->d.num_gates; g.a.only_advice = 0; g.a.nr = cc->d.num_routed_wires;
     g.units = p->dev_units; g.copies = p->dev_copies; g.unit_off = p->dev_unit_off; g.copy_off = p->dev_copy_off; g.inputs = p->dev_inputs;
     g.vals = p->dev_vals; g.num_inputs = ni; g.nw = nw;
+    const bool has_free = !p->free_off.empty();
+    if (has_free) { g.free_units = p->dev_free_units; g.free_off = p->dev_free_off; g.free_cells = p->dev_free_cells; g.moduli = p->dev_moduli; }
     StageScope st(c, "witness_generate", 16.0 * K * p->info.num_cells_known);
     if (flags & GLP_WITNESS_GEN_ZERO_FIRST) GLP_HIP(hipMemsetAsync(dev_wires, 0, (size_t)K * nw * n * 8, c->stream));
     // a wave is wide (one launch for its units, one for its copies) while the proofs alone do not fill the chip and it holds more than
     // narrow_max units; runs of the other waves are walked by one workgroup per proof
     const u32 nwaves = p->info.num_waves;
-    auto wide = [&](u32 w) { const size_t cnt = w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w]; return K < (u32)c->num_cus && cnt > p->narrow_max; };
+    auto free_count = [&](u32 w) -> size_t { return has_free ? p->free_off[w + 1] - p->free_off[w] : 0; };      // wave 0 holds none
+    auto wide = [&](u32 w) { const size_t cnt = (w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w]) + free_count(w); return K < (u32)c->num_cus && cnt > p->narrow_max; };
     for (u32 w = 0; w <= nwaves;) {
         if (wide(w)) {
-            const size_t cnt = w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w], ncp = p->copy_off[w + 1] - p->copy_off[w];
-            hipLaunchKernelGGL(k_witness_units, dim3((unsigned)((cnt + 255) / 256), K), dim3(256), 0, c->stream, g, w);
+            const size_t cnt = w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w], ncp = p->copy_off[w + 1] - p->copy_off[w], nfr = free_count(w);
+            if (cnt) hipLaunchKernelGGL(k_witness_units, dim3((unsigned)((cnt + 255) / 256), K), dim3(256), 0, c->stream, g, w);
+            if (nfr) hipLaunchKernelGGL(k_witness_free, dim3((unsigned)((nfr + 63) / 64), K), dim3(64), 0, c->stream, g, w);
             if (ncp) hipLaunchKernelGGL(k_witness_copies, dim3((unsigned)((ncp + 255) / 256), K), dim3(256), 0, c->stream, g, w);
             w++;
         } else {
             u32 w1 = w;
             while (w1 < nwaves && !wide(w1 + 1)) w1++;
-            hipLaunchKernelGGL(k_witness_waves, dim3(K), dim3(256), 0, c->stream, g, w, w1);
+            if (has_free) hipLaunchKernelGGL(k_witness_waves<true>, dim3(K), dim3(256), 0, c->stream, g, w, w1);
+            else hipLaunchKernelGGL(k_witness_waves<false>, dim3(K), dim3(256), 0, c->stream, g, w, w1);
             w = w1 + 1;
         }
         GLP_HIP(hipGetLastError());

@@ -28,6 +28,10 @@ from .synth import (GATE_ARITHMETIC, GATE_CONSTANT, GATE_POSEIDON, GATE_PUBLIC_I
 
 P = gl.P
 M32 = (1 << 32) - 1
+# GLP_WGEN_* of include/glp.h: the kinds of generators that belong to no gate (free units of glp_witness_plan_create_ex)
+(WGEN_EQUALITY, WGEN_NONNATIVE_ADD, WGEN_NONNATIVE_MULTI_ADD, WGEN_NONNATIVE_SUB, WGEN_NONNATIVE_MUL, WGEN_NONNATIVE_INV, WGEN_BIGUINT_DIV_REM,
+ WGEN_GLV_SECP256K1) = range(1, 9)
+WGEN_NO_CELL = 0xFFFFFFFFFFFFFFFF
 
 
 def _interleave(x):
@@ -69,6 +73,21 @@ def _batch_inverse(values):
     return out
 
 
+def _op_input_columns(gate, p0, p1, i):
+    """the wires operation i of a row of a gate with several operations reads (the units of include/glp.h, "witness generation, the
+    dataflow half")"""
+    if gate == GATE_ARITHMETIC: return range(4 * i, 4 * i + 3)
+    if gate == GATE_U32_ARITHMETIC: return range(6 * i, 6 * i + 3)
+    if gate == GATE_U32_SUBTRACTION: return range(5 * i, 5 * i + 3)
+    if gate == GATE_U32_INTERLEAVE: return [2 * i]
+    if gate in (GATE_UNINTERLEAVE_U32, GATE_UNINTERLEAVE_B32): return [3 * i]
+    if gate == synth.GATE_U32_ADD_MANY: return range((p0 + 3) * i, (p0 + 3) * i + p0 + 1)
+    if gate == synth.GATE_RANDOM_ACCESS:
+        o = (2 + (1 << p0)) * i
+        return [o] + list(range(o + 2, o + 2 + (1 << p0)))
+    return []                                                  # ConstantGate: no inputs
+
+
 class GadgetBuilder:
     """Targets are integer ids; `self.val[t]` is the value the witness assigns."""
 
@@ -85,6 +104,8 @@ class GadgetBuilder:
         self._consts = {}
         self._poseidon_rows = []       # (row, 12 input values): S-box traces are filled at build()
         self.public_inputs = []
+        self._free = []                # one entry per generator that belongs to no gate: (kind, modulus, input operands, output operands), targets
+        self.witness_input_targets = []   # the targets a caller sets (`pw.set_target`): build() names their cells in `witness_inputs`
         self.n_arith = nr // 4
         self.n_u32a = min(nr // 6, nw // 38)
         self.n_sub = min(nr // 5, nw // 21)
@@ -115,6 +136,10 @@ class GadgetBuilder:
         assert col < self.cfg.num_routed_wires
         self._cell_t.append(t); self._cell_r.append(row); self._cell_c.append(col)
 
+    def _record_free(self, kind, modulus, ins, outs):
+        """a generator that belongs to no gate was emulated: remember its operands (lists of targets), for build()"""
+        self._free.append((kind, int(modulus), [list(o) for o in ins], [list(o) for o in outs]))
+
     def _wire(self, row, col, value):
         """a fresh target living in cell (row, col)"""
         t = self.target(value)
@@ -126,7 +151,7 @@ class GadgetBuilder:
         cur = self._open.get(key)
         if cur is None or cur[1] == num_ops:
             self.rows.append([gate, p0, p1, consts])
-            cur = self._open[key] = [len(self.rows) - 1, 0]
+            cur = self._open[key] = [len(self.rows) - 1, 0, num_ops, gate, p0, p1]
         cur[1] += 1
         self.stats[gate] = self.stats.get(gate, 0) + 1
         return cur[0], cur[1] - 1
@@ -295,6 +320,7 @@ class GadgetBuilder:
         equal = self.target(1 if d == 0 else 0)
         not_equal = self.not_(equal)
         inv = self.target(pow(d, P - 2, P) if d else 0)
+        self._record_free(WGEN_EQUALITY, 0, [[x], [y]], [[equal], [inv]])
         diff = self.sub(x, y)
         self.assert_zero(self.mul(diff, equal))
         self.assert_zero(self.sub(self.mul(diff, inv), not_equal))
@@ -447,7 +473,68 @@ class GadgetBuilder:
         c.pi_hash = np.array(pi_hash, dtype=np.uint64)
         c.gadget_rows = nrows
         c.gate_ops = {synth._GATE_META[g][1].split(" ")[0].split("(")[0]: n for g, n in sorted(self.stats.items())}
+        self._attach_free_units(c, ct, cr, cc, par, 1 << log_n)
         return c
+
+    def _attach_free_units(self, c, ct, cr, cc, par, n):
+        """The recorded free generators in the C layout of glp_witness_plan_create_ex (include/glp.h, FREE UNITS): c.free_units int64
+        [num][9] = kind, modulus index, cell_begin, len[6]; c.free_cells uint64 (a unit's input cells, then its output cells, flat
+        positions col * n + row); c.moduli uint32 [num_moduli][8]; c.witness_inputs uint64, the cells of witness_input_targets.  A
+        target is named through the first wire it was placed on.  An input target that was placed nowhere itself (sub_nonnative's `a`
+        is only connected) is named through the first wire of its copy class (`par`: every target's class root); one whose whole class
+        was placed nowhere is an error.  An output target that was placed nowhere is WGEN_NO_CELL (dropped: not written)."""
+        def first_cells(keys):
+            uniq, first = np.unique(keys, return_index=True)
+            return uniq, cc[first] * n + cr[first]
+
+        def lookup(table, t):
+            uniq, flat = table
+            if not len(uniq):
+                return np.zeros(t.size, bool), np.zeros(t.size, np.int64)
+            at = np.minimum(np.searchsorted(uniq, t), len(uniq) - 1)
+            return uniq[at] == t, flat[at]
+        own, by_class = first_cells(ct), first_cells(par[ct])
+
+        def cells_of(targets, what, optional=False):
+            t = np.asarray(targets, dtype=np.int64)
+            if t.size == 0:
+                return np.zeros(0, np.uint64)
+            hit, cell = lookup(own, t)
+            if optional:
+                return np.where(hit, cell, WGEN_NO_CELL).astype(np.uint64)
+            hit2, cell2 = lookup(by_class, par[t])
+            if not (hit | hit2).all():
+                raise ValueError("%s: target %d and its copy class were placed on no wire" % (what, int(t[~(hit | hit2)][0])))
+            return np.where(hit, cell, cell2).astype(np.uint64)
+        moduli, units, ins, outs = {}, [], [], []
+        begin = 0
+        for f, (kind, m, in_ops, out_ops) in enumerate(self._free):
+            ops = in_ops + out_ops
+            assert len(ops) <= 6 and all(len(o) < 1 << 16 for o in ops)
+            mi = moduli.setdefault(m, len(moduli)) if m else 0
+            units.append([kind, mi, begin] + [len(o) for o in ops] + [0] * (6 - len(ops)))
+            ins.append((f, [t for o in in_ops for t in o]))
+            outs.append([t for o in out_ops for t in o])
+            begin += sum(len(o) for o in ops)
+        # resolve all inputs and all outputs at once, then interleave them per unit
+        in_cells = cells_of([t for _, ts in ins for t in ts], "a free generator's input")
+        out_cells = cells_of([t for ts in outs for t in ts], "", optional=True)
+        runs, i0, o0 = [], 0, 0
+        for (_, ti), to in zip(ins, outs):
+            runs += [in_cells[i0:i0 + len(ti)], out_cells[o0:o0 + len(to)]]
+            i0 += len(ti); o0 += len(to)
+        c.free_units = np.array(units, dtype=np.int64).reshape(-1, 9)
+        c.free_cells = np.concatenate(runs) if runs else np.zeros(0, np.uint64)
+        c.moduli = np.array([[(m >> (32 * i)) & M32 for i in range(8)] for m in moduli], dtype=np.uint32).reshape(-1, 8)
+        c.witness_inputs = cells_of(self.witness_input_targets, "witness_input_targets")
+        # The operations a partly filled row has left over read cells that nothing is wired to (plonky2 wires such slots to zero; this
+        # builder leaves them alone and their wires 0).  Their generators still have to run -- an unused U32ArithmeticGate operation
+        # holds inverse = 1 / (2^32 - 1) -- so a plan lists these cells as inputs of value 0, next to witness_inputs.
+        zero = []
+        for row, used, num_ops, gate, p0, p1 in self._open.values():
+            for i in range(used, num_ops):
+                zero += [col * n + row for col in _op_input_columns(gate, p0, p1, i)]
+        c.witness_zero_inputs = np.array(zero, dtype=np.uint64)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

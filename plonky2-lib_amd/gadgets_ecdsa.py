@@ -21,7 +21,8 @@ Nothing here touches the GPU or the oracle.
 import numpy as np
 
 from . import synth
-from .gadgets import GadgetBuilder, M32, P
+from .gadgets import (GadgetBuilder, M32, P, WGEN_BIGUINT_DIV_REM, WGEN_GLV_SECP256K1, WGEN_NONNATIVE_ADD, WGEN_NONNATIVE_INV, WGEN_NONNATIVE_MUL,
+                      WGEN_NONNATIVE_SUB)
 from .synth import GATE_BASE_SUM, GATE_COMPARISON, GATE_RANDOM_ACCESS, GATE_U32_ADD_MANY, GATE_U32_RANGE_CHECK
 
 # ---- secp256k1, native
@@ -298,6 +299,7 @@ class EcdsaBuilder(GadgetBuilder):
         va, vb = self.val_of(a), self.val_of(b)
         div = self.virtual_biguint(va // vb, 0 if len(b) > len(a) + 1 else len(a) - len(b) + 1)
         rem = self.virtual_biguint(va % vb, len(b))
+        self._record_free(WGEN_BIGUINT_DIV_REM, 0, [a, b], [div, rem])
         self.connect_biguint(a, self.add_biguint(self.mul_biguint(div, b), rem))
         self.connect(self.cmp_biguint(rem, b), self.one())
         return div, rem
@@ -313,6 +315,7 @@ class EcdsaBuilder(GadgetBuilder):
         va, vb = self.val_of(a), self.val_of(b)
         s = self.virtual_nonnative((va + vb) % m)
         overflow = self.target(1 if va + vb >= m else 0)
+        self._record_free(WGEN_NONNATIVE_ADD, m, [a, b], [s, [overflow]])
         sum_expected = self.add_biguint(a, b)
         modulus = self.constant_biguint(m)
         sum_actual = self.add_biguint(s, self.mul_biguint_by_bool(modulus, overflow))
@@ -324,6 +327,7 @@ class EcdsaBuilder(GadgetBuilder):
         va, vb = self.val_of(a), self.val_of(b)
         diff = self.virtual_nonnative((va - vb) % m)
         overflow = self.target(1 if va < vb else 0)
+        self._record_free(WGEN_NONNATIVE_SUB, m, [a, b], [diff, [overflow]])
         self.range_check_u32(diff)
         self.assert_bool(overflow)
         diff_plus_b = self.add_biguint(diff, b)
@@ -336,6 +340,7 @@ class EcdsaBuilder(GadgetBuilder):
         prod = self.virtual_nonnative(va * vb % m)
         modulus = self.constant_biguint(m)
         overflow = self.virtual_biguint(va * vb // m, len(a) + len(b) - len(modulus))
+        self._record_free(WGEN_NONNATIVE_MUL, m, [a, b], [prod, overflow])
         self.range_check_u32(prod)
         self.range_check_u32(overflow)
         prod_expected = self.mul_biguint(a, b)
@@ -350,6 +355,7 @@ class EcdsaBuilder(GadgetBuilder):
         vi = pow(vx, -1, m)
         inv = self.virtual_biguint(vi, len(x))
         div = self.virtual_biguint((vx * vi - 1) // m, len(x))
+        self._record_free(WGEN_NONNATIVE_INV, m, [x], [inv, div])
         product = self.mul_biguint(x, inv)
         expected = self.add_biguint(self.mul_biguint(self.constant_biguint(m), div), self.constant_biguint(1))
         self.connect_biguint(product, expected)
@@ -540,15 +546,22 @@ class EcdsaBuilder(GadgetBuilder):
         return self.curve_add(result, self.constant_affine_point(pt_neg(start)))
 
     # ---- glv.rs
-    def glv_mul(self, p, k):
+    def glv_decompose(self, k):
+        """`decompose_secp256k1_scalar` [REF src/ecdsa/gadgets/glv.rs:51-83]: |k1|, |k2| (4 limbs each) and their signs from the
+        GLVDecompositionGenerator, k1_raw + GLV_S k2_raw = k enforced"""
         vk = self.val_of(k)
         k1v, k2v, n1, n2 = decompose_secp256k1_scalar(vk)
         k1, k2 = self.virtual_biguint(k1v, 4), self.virtual_biguint(k2v, 4)
         k1_neg, k2_neg = self.target(int(n1)), self.target(int(n2))
+        self._record_free(WGEN_GLV_SECP256K1, 0, [k], [k1, k2, [k1_neg], [k2_neg]])
         k1_raw = self.nonnative_conditional_neg(k1, k1_neg, FN)
         k2_raw = self.nonnative_conditional_neg(k2, k2_neg, FN)
         should_be_k = self.add_nonnative(self.mul_nonnative(self.constant_biguint(GLV_S), k2_raw, FN), k1_raw, FN)
         self.connect_biguint(should_be_k, k)
+        return k1, k2, k1_neg, k2_neg
+
+    def glv_mul(self, p, k):
+        k1, k2, k1_neg, k2_neg = self.glv_decompose(k)
         sp = (self.mul_nonnative(self.constant_biguint(GLV_BETA), p[0], FP), p[1])
         return self.curve_msm(self.curve_conditional_neg(p, k1_neg), self.curve_conditional_neg(sp, k2_neg), k1, k2)
 
@@ -633,6 +646,7 @@ def ecdsa_circuit(signatures, config=None, min_log_n=0):
     for msg, (r, s), pk in signatures:
         msg_t, r_t, s_t = eb.virtual_nonnative(msg), eb.virtual_nonnative(r), eb.virtual_nonnative(s)
         pk_t = eb.virtual_affine_point(pk)
+        eb.witness_input_targets += msg_t + r_t + s_t + pk_t[0] + pk_t[1]
         eb.verify_message(msg_t, (r_t, s_t), pk_t)
     return eb.build(min_log_n)
 
