@@ -935,9 +935,48 @@ GLP_API int glp_witness_columns(const glp_circuit *circuit, uint32_t gate_index,
  * GLP_WGEN_NO_CELL; a run that leaves cells[]; an output cell written by two free units; an output cell that a gate unit of that row
  * also writes.  An output cell whose class holds an input is allowed, as above.  glp_witness_plan_create is the num_units = 0 case.
  *
+ * UNIT PROGRAMS.  A generator this library does not know -- plonky2's small non-gate generators (`WireSplitGenerator`,
+ * `LowHighGenerator`, quotient), or the generator of a caller-defined gate whose rows the caller declares as NoopGate in the circuit it
+ * plans with (a Noop row has no units) -- is stated as the caller states a constraint: a straight-line program in the instruction word
+ * of GLP_GP_INSTR (opcode, dst, a, b and the 27-bit operands as there, bit 63 zero), run as a free unit of kind GLP_WGEN_PROGRAM by
+ * glp_witness_plan_create_prog.  This is the fourth reading of that format, for one unit of one proof:
+ *     GLP_GP_REG, GLP_GP_IMM       as in a gate program
+ *     GLP_GP_COL                   oracle 0 only; payload j < num_inputs: the canonical 64-bit value of the unit's j-th input cell (the
+ *                                  whole word, not its low 32 bits)
+ *     GLP_GP_COL_NEXT, _PARAM, _X  refused
+ *     ADD, SUB, MUL, MOV           as in a gate program
+ *     EMIT a                       writes a to the unit's output cell number t, t counting the EMITs from the start of the program; the
+ *                                  number of EMITs is num_outputs
+ *     END                          exactly one, the last instruction, operand IMM of a pool word 1 (the shape glp_gate_program_rows asks for)
+ *     GLP_WP_OP_INV0 dst, a        1 / a, or 0 when a = 0 (a^(p-2), a fixed-length exponentiation)
+ *     GLP_WP_OP_BITS dst, a, b     b an IMM whose pool word is lo + 256 * width (GLP_WP_BITS_RANGE), width >= 1, lo + width <= 64:
+ *                                  (a >> lo) & (2^width - 1) on the canonical integer of a
+ *     GLP_WP_OP_LT   dst, a, b     1 if canonical a < canonical b, else 0
+ * Every result is canonical.  There are no branches and no loops, and nothing read from a witness becomes an address or a trip count.
+ * Left out on purpose: integer products wider than the field (the U32 gate generators are gate units already).
+ * glp_witness_program_check refuses (GLP_ERR_ARG, "instruction <i>, field <op|dst|a|b>: ...", or naming the description's field): an
+ * unknown opcode or bit 63; a destination or a second operand in an instruction that has none; a register >= num_regs; a register read
+ * before it is written; a pool index out of range; COL with a non-zero oracle or j >= num_inputs; COL_NEXT, PARAM, X or an unknown
+ * operand kind; a BITS operand b that is not an IMM, or whose pool word has width 0, lo + width > 64 or bits above bit 15; a number of
+ * EMITs other than num_outputs; a last instruction that is not END IMM(1); an END before the last instruction; a non-canonical pool
+ * word; num_instructions outside 1..GLP_GP_MAX_INSTRUCTIONS, num_regs outside 1..GLP_GP_MAX_REGS, num_inputs or num_outputs outside
+ * 1..GLP_WP_MAX_CELLS, num_pool above 2^24.
+ * A program unit names its program in `modulus` and has len[0] = num_inputs, len[1] = num_outputs, len[2..5] = 0; its run is the input
+ * cells, then the output cells (GLP_WGEN_NO_CELL: not written).  It is a free unit in every respect of the rule above (wave, stuck,
+ * writer of its outputs, the two "also written" refusals, glp_witness_plan_free_info).  glp_witness_plan_create_prog refuses beyond
+ * glp_witness_plan_create_ex, before any launch, naming the unit and the field: modulus >= num_programs; len[0] or len[1] different from
+ * the program's counts; len[2..5] not 0; a program that glp_witness_program_check refuses ("programs[<p>]: ..." and its message).
+ * glp_witness_plan_create_ex is the num_programs = 0 case of the same body and keeps refusing kind 9 as an unknown kind.
+ * A wave that holds program units is always a wide wave, with one launch more between its units and its copies: the planner sorts the
+ * wave's program units by program and cuts them into chunks of at most 64 units of one program, and one 64-lane workgroup runs one
+ * chunk (grid.y = proof), so that the instruction stream is uniform across the lanes; instruction words and pool come through scalar
+ * loads, the register file lies in LDS.  Walked runs stop before such a wave and resume after it: the walked kernels hold nothing of the
+ * interpreter.  The programs (code and pool, concatenated, with an offset table) lie in HBM with the plan.
+ *
  * NOT done here: zero-knowledge blinding rows (their random advice comes from no generator: list those cells as inputs); a
- * device-side planner; generators the rebuilt circuits do not contain (`WireSplitGenerator`, `LowHighGenerator`).
- * tests/witness_plan_restate.py restates the units, the classes, the rule and generation; tests/witness_free_restate.py the free units. */
+ * device-side planner; integer products wider than the field in a unit program.
+ * tests/witness_plan_restate.py restates the units, the classes, the rule and generation; tests/witness_free_restate.py the free units;
+ * tests/witness_program_restate.py the unit programs. */
 typedef struct glp_witness_plan glp_witness_plan;
 struct glp_witness_plan_info {           /* a struct tag, not a typedef: the accessor below carries the same name */
     uint32_t num_waves;                  /* highest wave that holds a unit; 0 if none */
@@ -975,6 +1014,24 @@ GLP_API int glp_witness_plan_create_ex(glp_ctx *ctx, const glp_circuit *c, const
                                        const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
                                        const uint32_t *moduli /* [num_moduli][8], little-endian u32 limbs */, uint32_t num_moduli,
                                        glp_witness_plan **out);
+/* UNIT PROGRAMS: see the block above.  Opcodes 7..9 exist in unit programs only (glp_gate_program_check keeps refusing them). */
+#define GLP_WP_OP_INV0 7u                /* dst, a:     1 / a, or 0 when a = 0 */
+#define GLP_WP_OP_BITS 8u                /* dst, a, b:  b an IMM whose pool word is lo + 256 * width; (a >> lo) & (2^width - 1) */
+#define GLP_WP_OP_LT   9u                /* dst, a, b:  1 if canonical a < canonical b, else 0 */
+#define GLP_WP_MAX_CELLS 4096u
+#define GLP_WP_BITS_RANGE(lo, width) ((uint64_t)(lo) + 256u * (uint64_t)(width))
+typedef struct {
+    const uint64_t *code;  uint32_t num_instructions;   /* 1..GLP_GP_MAX_INSTRUCTIONS */
+    const uint64_t *pool;  uint32_t num_pool;           /* canonical words */
+    uint32_t num_regs;                                  /* 1..GLP_GP_MAX_REGS */
+    uint32_t num_inputs, num_outputs;                   /* cells a unit of this program reads / writes; each 1..GLP_WP_MAX_CELLS */
+} glp_witness_program_desc;
+GLP_API int glp_witness_program_check(const glp_witness_program_desc *d);   /* host only, no context */
+#define GLP_WGEN_PROGRAM 9u   /* modulus = index into programs[]; len[0] = num_inputs, len[1] = num_outputs, len[2..5] = 0 */
+GLP_API int glp_witness_plan_create_prog(glp_ctx *ctx, const glp_circuit *c, const uint64_t *input_cells, uint32_t num_inputs,
+                                         const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
+                                         const uint32_t *moduli /* [num_moduli][8] */, uint32_t num_moduli,
+                                         const glp_witness_program_desc *programs, uint32_t num_programs, glp_witness_plan **out);
 GLP_API int glp_witness_plan_free_info(const glp_witness_plan *p, struct glp_witness_plan_free_info *out);
 GLP_API int  glp_witness_plan_info(const glp_witness_plan *p, struct glp_witness_plan_info *out);
 GLP_API int  glp_witness_plan_cell_waves(const glp_witness_plan *p, int32_t *waves_out /* [num_wires][n] */);

@@ -97,6 +97,11 @@ class _WitnessFreeUnit(C.Structure):          # glp_witness_free_unit
     _fields_ = [("kind", C.c_uint32), ("modulus", C.c_uint32), ("cell_begin", C.c_uint32), ("len", C.c_uint16 * 6)]
 
 
+class _WitnessProgramDesc(C.Structure):      # glp_witness_program_desc
+    _fields_ = [("code", C.c_void_p), ("num_instructions", C.c_uint32), ("pool", C.c_void_p), ("num_pool", C.c_uint32), ("num_regs", C.c_uint32),
+                ("num_inputs", C.c_uint32), ("num_outputs", C.c_uint32)]
+
+
 class _WitnessPlanFreeInfo(C.Structure):
     _fields_ = [("num_free_units", C.c_uint64), ("num_stuck_free_units", C.c_uint64), ("first_stuck_free_unit", C.c_uint64),
                 ("widest_wave_free_units", C.c_uint64)]
@@ -105,6 +110,7 @@ class _WitnessPlanFreeInfo(C.Structure):
 # GLP_WGEN_* of include/glp.h: the kinds of free units, their largest operand, the output cell that is not written
 (WGEN_EQUALITY, WGEN_NONNATIVE_ADD, WGEN_NONNATIVE_MULTI_ADD, WGEN_NONNATIVE_SUB, WGEN_NONNATIVE_MUL, WGEN_NONNATIVE_INV, WGEN_BIGUINT_DIV_REM,
  WGEN_GLV_SECP256K1) = range(1, 9)
+WGEN_PROGRAM = 9                               # a unit program: modulus = its index in programs, len = num_inputs, num_outputs
 WGEN_MAX_LIMBS = 18
 WGEN_NO_CELL = 0xFFFFFFFFFFFFFFFF
 FREE_UNIT_DTYPE = np.dtype([("kind", np.uint32), ("modulus", np.uint32), ("cell_begin", np.uint32), ("len", np.uint16, (6,))])
@@ -272,6 +278,8 @@ def load_library():
         "glp_witness_unit_columns": [vp, u32, u32, vp],
         "glp_witness_plan_create": [vp, vp, vp, u32, C.POINTER(vp)],
         "glp_witness_plan_create_ex": [vp, vp, vp, u32, vp, u32, vp, sz, vp, u32, C.POINTER(vp)],
+        "glp_witness_plan_create_prog": [vp, vp, vp, u32, vp, u32, vp, sz, vp, u32, vp, u32, C.POINTER(vp)],
+        "glp_witness_program_check": [C.POINTER(_WitnessProgramDesc)],
         "glp_witness_plan_free_info": [vp, C.POINTER(_WitnessPlanFreeInfo)],
         "glp_witness_plan_info": [vp, C.POINTER(_WitnessPlanInfo)],
         "glp_witness_plan_cell_waves": [vp, vp],
@@ -850,6 +858,32 @@ def gate_program_check(prog, **fields):
     return int(out.value)
 
 
+def witness_program_desc(prog, **fields):
+    """attribute bag (code, pool, num_regs, num_inputs, num_outputs: a witness_program.WitnessProgram) -> (glp_witness_program_desc, the
+    arrays that must stay alive while it is used).  fields: struct fields set afterwards, for descriptions the library is meant to refuse."""
+    code, pool = _a(prog.code), _a(prog.pool)
+    counts = [int(prog.num_regs), int(prog.num_inputs), int(prog.num_outputs)]
+    if min(counts) < 0 or max(counts + [code.size, pool.size]) >= 1 << 32:
+        raise GlpError(-1, "witness program: a count does not fit a uint32")
+    d = _WitnessProgramDesc(code.ctypes.data if code.size else None, code.size, pool.ctypes.data if pool.size else None, pool.size, *counts)
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return d, (code, pool)
+
+
+def witness_program_descs(programs):
+    """a list of such bags -> (a C array of glp_witness_program_desc, what must stay alive)"""
+    pairs = [witness_program_desc(p) for p in programs]
+    arr = (_WitnessProgramDesc * max(len(pairs), 1))(*[d for d, _ in pairs])
+    return arr, [k for _, k in pairs]
+
+
+def witness_program_check(prog, **fields):
+    """glp_witness_program_check (host only, no context): GlpError naming the instruction and the field, or the description's field"""
+    d, _keep = witness_program_desc(prog, **fields)
+    _chk(load_library().glp_witness_program_check(C.byref(d)))
+
+
 class GateProgram:
     """A gate program resident on the GPU (glp_gate_program_create)."""
 
@@ -1293,16 +1327,20 @@ class Circuit:
             _chk(L.glp_witness_unit_columns(self._h, int(gate_index), u, out[u].ctypes.data_as(C.c_void_p)))
         return out
 
-    def witness_plan(self, input_cells, free_units=None, moduli=None):
-        """glp_witness_plan_create(_ex): input_cells = flat positions col * n + row of the cells the caller sets -> WitnessPlan.
+    def witness_plan(self, input_cells, free_units=None, moduli=None, programs=None):
+        """glp_witness_plan_create(_ex, _prog): input_cells = flat positions col * n + row of the cells the caller sets -> WitnessPlan.
         free_units = (units, cells): the generators that belong to no gate (include/glp.h, FREE UNITS) as a FREE_UNIT_DTYPE array
         (or anything np.asarray makes one of: rows of kind, modulus, cell_begin, len[6]) and the uint64 cells their runs point into;
-        moduli = uint32 [num_moduli][8], little-endian limbs."""
+        moduli = uint32 [num_moduli][8], little-endian limbs.  programs = the unit programs (witness_program.WitnessProgram, or any
+        bag of code, pool, num_regs, num_inputs, num_outputs) that units of kind WGEN_PROGRAM name in their modulus field; given
+        (an empty list too), the plan is made by glp_witness_plan_create_prog."""
         cells = _a(input_cells).reshape(-1)
         h = C.c_void_p()
         if free_units is None:
             if moduli is not None:
                 raise GlpError(-1, "moduli without free_units")
+            if programs is not None:
+                raise GlpError(-1, "programs without free_units")
             _chk(load_library().glp_witness_plan_create(self.ctx._h, self._h, _p(cells) if cells.size else None, cells.size, C.byref(h)))
         else:
             units, fcells = free_units
@@ -1320,10 +1358,15 @@ class Circuit:
                 raise GlpError(-1, "moduli has %d words, expected num_moduli * 8" % mod.size)
             if units.size >= 1 << 32 or mod.size // 8 >= 1 << 32:
                 raise GlpError(-1, "free_units or moduli too long for a uint32 count")
-            _chk(load_library().glp_witness_plan_create_ex(self.ctx._h, self._h, _p(cells) if cells.size else None, cells.size,
-                                                           units.ctypes.data_as(C.c_void_p) if units.size else None, units.size,
-                                                           _p(fcells) if fcells.size else None, fcells.size,
-                                                           mod.ctypes.data_as(C.c_void_p) if mod.size else None, mod.size // 8, C.byref(h)))
+            args = (self.ctx._h, self._h, _p(cells) if cells.size else None, cells.size, units.ctypes.data_as(C.c_void_p) if units.size else None,
+                    units.size, _p(fcells) if fcells.size else None, fcells.size, mod.ctypes.data_as(C.c_void_p) if mod.size else None, mod.size // 8)
+            if programs is None:
+                _chk(load_library().glp_witness_plan_create_ex(*args, C.byref(h)))
+            else:
+                if len(programs) >= 1 << 32:
+                    raise GlpError(-1, "programs too long for a uint32 count")
+                descs, _keep = witness_program_descs(programs)
+                _chk(load_library().glp_witness_plan_create_prog(*args, descs if len(programs) else None, len(programs), C.byref(h)))
         plan = WitnessPlan(self, h, cells.size)
         self.ctx._plans.add(plan)
         return plan

@@ -1,5 +1,6 @@
 // witness.hip -- witness generation on the GPU: the row-local half (glp_witness_fill) and, over the same
-// per-unit body, the dataflow half (glp_witness_plan_*, glp_witness_generate: second part of this file).
+// per-unit body, the dataflow half (glp_witness_plan_*, glp_witness_generate: second part of this file; caller-defined generators as
+// unit programs: witness_program.inc).
 //
 // plonky2's `generate_partial_witness` (iop/generator.rs) runs every gate's `SimpleGenerator`s as their
 // dependencies become known.  Two kinds of work hide in it: the copy-constraint DATAFLOW between rows (irregular:
@@ -585,6 +586,8 @@ __global__ __launch_bounds__(256) void k_witness_read_cells(const u64 *wires, co
 }
 }  // namespace
 
+#include "witness_program.inc"
+
 struct glp_witness_plan {
     glp_ctx *ctx = nullptr;
     const glp_circuit *cc = nullptr;
@@ -599,6 +602,12 @@ struct glp_witness_plan {
     std::vector<u32> free_off;                     // [num_waves + 2]; empty without free units
     WFree *dev_free_units = nullptr;
     u32 *dev_free_off = nullptr, *dev_free_cells = nullptr, *dev_moduli = nullptr;
+    std::vector<u32> prog_chunk_off;               // [num_waves + 2] into dev_prog_chunks; empty without program units
+    u32 prog_lds = 0;                              // bytes of LDS a chunk's workgroup asks for: the widest register file of the programs
+    WProgChunk *dev_prog_chunks = nullptr;
+    WFree *dev_prog_units = nullptr;               // by wave, sorted by program
+    WProgEntry *dev_prog_tab = nullptr;
+    u64 *dev_prog_image = nullptr;
     mutable u64 *dev_vals = nullptr;               // [vals_cap] the input values of the generation in flight: a plan serves one at a time
     mutable size_t vals_cap = 0;
 };
@@ -610,6 +619,7 @@ extern "C" void glp_witness_plan_free(glp_witness_plan *p) {
     c->release(p->dev_units); c->release(p->dev_copies); c->release(p->dev_unit_off); c->release(p->dev_copy_off);
     c->release(p->dev_inputs); c->release(p->dev_vals);
     c->release(p->dev_free_units); c->release(p->dev_free_off); c->release(p->dev_free_cells); c->release(p->dev_moduli);
+    c->release(p->dev_prog_chunks); c->release(p->dev_prog_units); c->release(p->dev_prog_tab); c->release(p->dev_prog_image);
     delete p;
 }
 
@@ -628,10 +638,12 @@ static WFreeShape witness_free_shape(u32 kind) {
     }
 }
 
-// glp_witness_plan_create_ex without its allocation guard; glp_witness_plan_create is its num_units = 0 case
+// glp_witness_plan_create_prog without its allocation guard; glp_witness_plan_create_ex is its num_programs = 0 case (with_programs
+// false: kind GLP_WGEN_PROGRAM stays an unknown kind there), glp_witness_plan_create its num_units = 0 case
 static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
                               const glp_witness_free_unit *funits, uint32_t nf, const uint64_t *fcells, size_t num_fcells, const uint32_t *moduli,
-                              uint32_t num_moduli, glp_witness_plan **out) {
+                              uint32_t num_moduli, const glp_witness_program_desc *programs, uint32_t num_programs, bool with_programs,
+                              glp_witness_plan **out) {
     GLP_REQUIRE(c, "%s: ctx is null", fn);
     GLP_REQUIRE(cc, "%s: circuit is null", fn);
     GLP_REQUIRE(out, "%s: out is null", fn);
@@ -639,7 +651,13 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
     GLP_REQUIRE(funits || nf == 0, "%s: units is null, num_units = %u", fn, nf);
     GLP_REQUIRE(fcells || num_fcells == 0, "%s: cells is null, num_cells = %zu", fn, num_fcells);
     GLP_REQUIRE(moduli || num_moduli == 0, "%s: moduli is null, num_moduli = %u", fn, num_moduli);
+    GLP_REQUIRE(programs || num_programs == 0, "%s: programs is null, num_programs = %u", fn, num_programs);
     GLP_REQUIRE(cc->ctx == c, "%s: circuit belongs to another ctx", fn);
+    for (u32 i = 0; i < num_programs; i++) {
+        char where[96];
+        snprintf(where, sizeof(where), "%s: programs[%u]", fn, i);
+        GLP_TRY(witness_program_check(where, programs + i));
+    }
     const glp_circuit_desc &d = cc->d;
     const u32 lg = d.degree_bits, nw = d.num_wires, nr = d.num_routed_wires, ng = d.num_gates, nsel = d.num_selectors;
     const size_t n = (size_t)1 << lg, cells = (size_t)nw * n;
@@ -667,21 +685,30 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
     for (size_t i = 0; i < num_fcells; i++) fcells32[i] = fcells[i] < cells ? (u32)fcells[i] : NONE;      // outputs may be GLP_WGEN_NO_CELL; checked per run below
     for (u32 f = 0; f < nf; f++) {
         const glp_witness_free_unit &u = funits[f];
-        const WFreeShape sh = witness_free_shape(u.kind);
-        GLP_REQUIRE(sh.operands, "%s: units[%u].kind = %u is not a GLP_WGEN_* kind", fn, f, u.kind);
-        const bool has_modulus = u.kind >= GLP_WGEN_NONNATIVE_ADD && u.kind <= GLP_WGEN_NONNATIVE_INV;
-        if (has_modulus) GLP_REQUIRE(u.modulus < num_moduli, "%s: units[%u].modulus = %u, num_moduli = %u", fn, f, u.modulus, num_moduli);
-        else GLP_REQUIRE(u.modulus == 0, "%s: units[%u].modulus = %u, kind %u has no modulus: 0", fn, f, u.modulus, u.kind);
-        for (u32 i = 0; i < 6; i++) {
-            const u32 l = u.len[i];
-            if (i >= sh.operands) { GLP_REQUIRE(l == 0, "%s: units[%u].len[%u] = %u, kind %u has %u operands: unused entries are 0", fn, f, i, l, u.kind, sh.operands); continue; }
-            if (sh.single >> i & 1) { GLP_REQUIRE(l == 1, "%s: units[%u].len[%u] = %u, that operand of kind %u is 1 cell", fn, f, i, l, u.kind); continue; }
-            if (u.kind == GLP_WGEN_NONNATIVE_MULTI_ADD && i == 0) continue;                                   // the number of summands
-            if ((int)i == sh.divisor) GLP_REQUIRE(l <= 8, "%s: units[%u].len[%u] = %u, a divisor has at most 8 limbs", fn, f, i, l);
-            GLP_REQUIRE(l <= GLP_WGEN_MAX_LIMBS, "%s: units[%u].len[%u] = %u, an operand has at most GLP_WGEN_MAX_LIMBS = %u limbs", fn, f, i, l, GLP_WGEN_MAX_LIMBS);
-            if (u.kind == GLP_WGEN_GLV_SECP256K1) GLP_REQUIRE(l == (i ? 4u : 8u), "%s: units[%u].len[%u] = %u, GLV_SECP256K1 has k of 8 and k1, k2 of 4 limbs", fn, f, i, l);
+        if (with_programs && u.kind == GLP_WGEN_PROGRAM) {
+            GLP_REQUIRE(u.modulus < num_programs, "%s: units[%u].modulus = %u, a program unit names its program there and num_programs = %u", fn, f, u.modulus, num_programs);
+            const glp_witness_program_desc &pd = programs[u.modulus];
+            GLP_REQUIRE(u.len[0] == pd.num_inputs, "%s: units[%u].len[0] = %u, programs[%u] has num_inputs = %u", fn, f, u.len[0], u.modulus, pd.num_inputs);
+            GLP_REQUIRE(u.len[1] == pd.num_outputs, "%s: units[%u].len[1] = %u, programs[%u] has num_outputs = %u", fn, f, u.len[1], u.modulus, pd.num_outputs);
+            for (u32 i = 2; i < 6; i++) GLP_REQUIRE(u.len[i] == 0, "%s: units[%u].len[%u] = %u, a program unit has two operands: unused entries are 0", fn, f, i, u.len[i]);
+            f_ni[f] = u.len[0]; f_no[f] = u.len[1];
+        } else {
+            const WFreeShape sh = witness_free_shape(u.kind);
+            GLP_REQUIRE(sh.operands, "%s: units[%u].kind = %u is not a GLP_WGEN_* kind", fn, f, u.kind);
+            const bool has_modulus = u.kind >= GLP_WGEN_NONNATIVE_ADD && u.kind <= GLP_WGEN_NONNATIVE_INV;
+            if (has_modulus) GLP_REQUIRE(u.modulus < num_moduli, "%s: units[%u].modulus = %u, num_moduli = %u", fn, f, u.modulus, num_moduli);
+            else GLP_REQUIRE(u.modulus == 0, "%s: units[%u].modulus = %u, kind %u has no modulus: 0", fn, f, u.modulus, u.kind);
+            for (u32 i = 0; i < 6; i++) {
+                const u32 l = u.len[i];
+                if (i >= sh.operands) { GLP_REQUIRE(l == 0, "%s: units[%u].len[%u] = %u, kind %u has %u operands: unused entries are 0", fn, f, i, l, u.kind, sh.operands); continue; }
+                if (sh.single >> i & 1) { GLP_REQUIRE(l == 1, "%s: units[%u].len[%u] = %u, that operand of kind %u is 1 cell", fn, f, i, l, u.kind); continue; }
+                if (u.kind == GLP_WGEN_NONNATIVE_MULTI_ADD && i == 0) continue;                                   // the number of summands
+                if ((int)i == sh.divisor) GLP_REQUIRE(l <= 8, "%s: units[%u].len[%u] = %u, a divisor has at most 8 limbs", fn, f, i, l);
+                GLP_REQUIRE(l <= GLP_WGEN_MAX_LIMBS, "%s: units[%u].len[%u] = %u, an operand has at most GLP_WGEN_MAX_LIMBS = %u limbs", fn, f, i, l, GLP_WGEN_MAX_LIMBS);
+                if (u.kind == GLP_WGEN_GLV_SECP256K1) GLP_REQUIRE(l == (i ? 4u : 8u), "%s: units[%u].len[%u] = %u, GLV_SECP256K1 has k of 8 and k1, k2 of 4 limbs", fn, f, i, l);
+            }
+            f_ni[f] = big::num_in(u.kind, u.len); f_no[f] = big::num_out(u.kind, u.len);
         }
-        f_ni[f] = big::num_in(u.kind, u.len); f_no[f] = big::num_out(u.kind, u.len);
         GLP_REQUIRE((size_t)u.cell_begin + f_ni[f] + f_no[f] <= num_fcells, "%s: units[%u].cell_begin = %u: its run of %u cells leaves cells[] (num_cells = %zu)", fn, f,
                     u.cell_begin, f_ni[f] + f_no[f], num_fcells);
         for (u32 i = 0; i < f_ni[f] + f_no[f]; i++) {
@@ -836,19 +863,61 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
         for (size_t k = 0; k < nu_total; k++)
             if (unit_wave[k] > 0) units[fill[unit_wave[k]]++] = WUnit{unit_row[k], row_gate[unit_row[k]] << 16 | (u32)(k - row_first[unit_row[k]])};
     }
-    // the free units by wave, in the caller's order
+    // the free units by wave, in the caller's order; program units are listed apart, below
+    auto is_prog = [&](u32 f) { return with_programs && funits[f].kind == GLP_WGEN_PROGRAM; };
+    u32 nf_prog = 0;
+    for (u32 f = 0; f < nf; f++) nf_prog += is_prog(f);
     std::vector<WFree> free_list;
     if (nf) {
-        p->free_off.assign(num_waves + 2, 0);
+        if (nf > nf_prog) p->free_off.assign(num_waves + 2, 0);
         for (u32 f = 0; f < nf; f++) {
             const int32_t uw = unit_wave[nu_total + f];
-            if (uw > 0) { p->free_off[uw + 1]++; continue; }
+            if (uw > 0) { if (!is_prog(f)) p->free_off[uw + 1]++; continue; }
             if (!finfo.num_stuck_free_units++) finfo.first_stuck_free_unit = f;
         }
+    }
+    if (nf > nf_prog) {
         for (u32 w = 0; w <= num_waves; w++) p->free_off[w + 1] += p->free_off[w];
         free_list.resize(p->free_off[num_waves + 1]);
         std::vector<u32> fill(p->free_off.begin(), p->free_off.end() - 1);
-        for (u32 f = 0; f < nf; f++) if (unit_wave[nu_total + f] > 0) free_list[fill[unit_wave[nu_total + f]]++] = funits[f];
+        for (u32 f = 0; f < nf; f++) if (!is_prog(f) && unit_wave[nu_total + f] > 0) free_list[fill[unit_wave[nu_total + f]]++] = funits[f];
+    }
+    // the program units by wave, sorted by program (then in the caller's order), cut into chunks of at most 64 units of one program; the
+    // image: per program its code, zero-padded to a multiple of 4 words (opcode 0 does nothing), then its pool
+    std::vector<WFree> prog_units;
+    std::vector<WProgChunk> prog_chunks;
+    std::vector<WProgEntry> prog_tab;
+    std::vector<u64> prog_image;
+    if (nf_prog) {
+        std::vector<u32> order;
+        for (u32 f = 0; f < nf; f++) if (is_prog(f) && unit_wave[nu_total + f] > 0) order.push_back(f);
+        std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) {
+            const int32_t wx = unit_wave[nu_total + x], wy = unit_wave[nu_total + y];
+            return wx != wy ? wx < wy : funits[x].modulus < funits[y].modulus;
+        });
+        p->prog_chunk_off.assign(num_waves + 2, 0);
+        for (size_t i = 0; i < order.size();) {
+            const u32 f = order[i], w = (u32)unit_wave[nu_total + f], pr = funits[f].modulus;
+            size_t j = i;
+            while (j < order.size() && j - i < 64 && (u32)unit_wave[nu_total + order[j]] == w && funits[order[j]].modulus == pr) j++;
+            prog_chunks.push_back(WProgChunk{pr, (u32)i, (u32)(j - i)});
+            p->prog_chunk_off[w + 1]++;
+            i = j;
+        }
+        for (u32 w = 0; w <= num_waves; w++) p->prog_chunk_off[w + 1] += p->prog_chunk_off[w];
+        for (u32 f : order) prog_units.push_back(funits[f]);
+        for (u32 i = 0; i < num_programs; i++) {
+            const glp_witness_program_desc &pd = programs[i];
+            const u32 words = (pd.num_instructions + 3) & ~3u;
+            WProgEntry e;
+            e.code_off = (u32)prog_image.size(); e.code_words = words; e.pool_off = e.code_off + words; e.num_inputs = pd.num_inputs;
+            GLP_REQUIRE(prog_image.size() + words + pd.num_pool < NONE, "%s: the programs exceed the 2^32 - 1 words a plan addresses", fn);
+            prog_image.insert(prog_image.end(), pd.code, pd.code + pd.num_instructions);
+            prog_image.resize((size_t)e.code_off + words, 0);
+            if (pd.num_pool) prog_image.insert(prog_image.end(), pd.pool, pd.pool + pd.num_pool);
+            prog_tab.push_back(e);
+            p->prog_lds = std::max<u32>(p->prog_lds, pd.num_regs * 64 * 8);
+        }
     }
     std::vector<u32> source(cells, NONE);        // by class name
     p->cell_waves.assign(cells, -1);
@@ -889,6 +958,7 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
         const std::vector<u32> mod32(moduli, moduli + (size_t)num_moduli * 8);
         up(&p->dev_free_units, free_list); up(&p->dev_free_off, p->free_off); up(&p->dev_free_cells, fcells32); up(&p->dev_moduli, mod32);
     }
+    if (nf_prog) { up(&p->dev_prog_chunks, prog_chunks); up(&p->dev_prog_units, prog_units); up(&p->dev_prog_tab, prog_tab); up(&p->dev_prog_image, prog_image); }
     if (rc != GLP_OK) { glp_witness_plan_free(p.release()); return rc; }
     *out = p.release();
     return GLP_OK;
@@ -899,8 +969,20 @@ extern "C" int glp_witness_plan_create_ex(glp_ctx *c, const glp_circuit *cc, con
                                           const uint32_t *moduli, uint32_t num_moduli, glp_witness_plan **out) {
     static const char *fn = "glp_witness_plan_create_ex";
     try {
-        return witness_plan_build(fn, c, cc, input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, out);
+        return witness_plan_build(fn, c, cc, input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, nullptr, 0, false, out);
     } catch (const std::bad_alloc &) {       // the planner's host tables: about 40 bytes per cell
+        return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
+    }
+}
+
+extern "C" int glp_witness_plan_create_prog(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
+                                            const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
+                                            const uint32_t *moduli, uint32_t num_moduli, const glp_witness_program_desc *programs,
+                                            uint32_t num_programs, glp_witness_plan **out) {
+    static const char *fn = "glp_witness_plan_create_prog";
+    try {
+        return witness_plan_build(fn, c, cc, input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, programs, num_programs, true, out);
+    } catch (const std::bad_alloc &) {
         return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
     }
 }
@@ -908,7 +990,7 @@ extern "C" int glp_witness_plan_create_ex(glp_ctx *c, const glp_circuit *cc, con
 extern "C" int glp_witness_plan_create(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs, glp_witness_plan **out) {
     static const char *fn = "glp_witness_plan_create";
     try {
-        return witness_plan_build(fn, c, cc, input_cells, num_inputs, nullptr, 0, nullptr, 0, nullptr, 0, out);
+        return witness_plan_build(fn, c, cc, input_cells, num_inputs, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, false, out);
     } catch (const std::bad_alloc &) {
         return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
     }
@@ -980,12 +1062,22 @@ extern "C" int glp_witness_generate(glp_ctx *c, const glp_witness_plan *p, uint3
     // narrow_max units; runs of the other waves are walked by one workgroup per proof
     const u32 nwaves = p->info.num_waves;
     auto free_count = [&](u32 w) -> size_t { return has_free ? p->free_off[w + 1] - p->free_off[w] : 0; };      // wave 0 holds none
-    auto wide = [&](u32 w) { const size_t cnt = (w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w]) + free_count(w); return K < (u32)c->num_cus && cnt > p->narrow_max; };
+    // a wave with program units is always wide: its chunks get a launch of their own between its units and its copies
+    auto prog_count = [&](u32 w) -> u32 { return p->prog_chunk_off.empty() ? 0 : p->prog_chunk_off[w + 1] - p->prog_chunk_off[w]; };
+    WProgArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.wires = dev_wires; pa.image = p->dev_prog_image; pa.progs = p->dev_prog_tab; pa.chunks = p->dev_prog_chunks; pa.units = p->dev_prog_units;
+    pa.cells = p->dev_free_cells; pa.nw = nw; pa.lg = cc->d.degree_bits;
+    auto wide = [&](u32 w) {
+        const size_t cnt = (w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w]) + free_count(w);
+        return prog_count(w) || (K < (u32)c->num_cus && cnt > p->narrow_max);
+    };
     for (u32 w = 0; w <= nwaves;) {
         if (wide(w)) {
             const size_t cnt = w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w], ncp = p->copy_off[w + 1] - p->copy_off[w], nfr = free_count(w);
             if (cnt) hipLaunchKernelGGL(k_witness_units, dim3((unsigned)((cnt + 255) / 256), K), dim3(256), 0, c->stream, g, w);
             if (nfr) hipLaunchKernelGGL(k_witness_free, dim3((unsigned)((nfr + 63) / 64), K), dim3(64), 0, c->stream, g, w);
+            if (const u32 npc = prog_count(w)) hipLaunchKernelGGL(k_witness_programs, dim3(npc, K), dim3(64), p->prog_lds, c->stream, pa, p->prog_chunk_off[w]);
             if (ncp) hipLaunchKernelGGL(k_witness_copies, dim3((unsigned)((ncp + 255) / 256), K), dim3(256), 0, c->stream, g, w);
             w++;
         } else {

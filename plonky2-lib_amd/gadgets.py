@@ -31,6 +31,7 @@ M32 = (1 << 32) - 1
 # GLP_WGEN_* of include/glp.h: the kinds of generators that belong to no gate (free units of glp_witness_plan_create_ex)
 (WGEN_EQUALITY, WGEN_NONNATIVE_ADD, WGEN_NONNATIVE_MULTI_ADD, WGEN_NONNATIVE_SUB, WGEN_NONNATIVE_MUL, WGEN_NONNATIVE_INV, WGEN_BIGUINT_DIV_REM,
  WGEN_GLV_SECP256K1) = range(1, 9)
+WGEN_PROGRAM = 9                       # a unit program (witness_program.py): the generators the library has no kind for
 WGEN_NO_CELL = 0xFFFFFFFFFFFFFFFF
 
 
@@ -105,6 +106,7 @@ class GadgetBuilder:
         self._poseidon_rows = []       # (row, 12 input values): S-box traces are filled at build()
         self.public_inputs = []
         self._free = []                # one entry per generator that belongs to no gate: (kind, modulus, input operands, output operands), targets
+        self._programs, self._program_index = [], {}      # the unit programs of the WGEN_PROGRAM entries of _free, each once
         self.witness_input_targets = []   # the targets a caller sets (`pw.set_target`): build() names their cells in `witness_inputs`
         self.n_arith = nr // 4
         self.n_u32a = min(nr // 6, nw // 38)
@@ -136,8 +138,19 @@ class GadgetBuilder:
         assert col < self.cfg.num_routed_wires
         self._cell_t.append(t); self._cell_r.append(row); self._cell_c.append(col)
 
-    def _record_free(self, kind, modulus, ins, outs):
-        """a generator that belongs to no gate was emulated: remember its operands (lists of targets), for build()"""
+    def _record_free(self, kind, modulus, ins, outs, program=None):
+        """a generator that belongs to no gate was emulated: remember its operands (lists of targets), for build().  A generator the
+        library has no kind for is a unit program (witness_program.WitnessProgram): kind WGEN_PROGRAM, one input and one output operand
+        of the program's counts; its index among the builder's programs goes where the other kinds keep their modulus."""
+        if kind == WGEN_PROGRAM:
+            ins, outs = [[t for o in ins for t in o]], [[t for o in outs for t in o]]
+            if program is None or (len(ins[0]), len(outs[0])) != (program.num_inputs, program.num_outputs):
+                raise ValueError("a program unit needs its program, and as many targets as the program has inputs and outputs")
+            key = (program.code.tobytes(), program.pool.tobytes(), program.num_regs, program.num_inputs)
+            if key not in self._program_index:
+                self._program_index[key] = len(self._programs)
+                self._programs.append(program)
+            modulus = self._program_index[key]
         self._free.append((kind, int(modulus), [list(o) for o in ins], [list(o) for o in outs]))
 
     def _wire(self, row, col, value):
@@ -362,6 +375,9 @@ class GadgetBuilder:
             part = (v >> (nl * g)) & ((1 << nl) - 1)
             sums.append(self._wire(row, 0, part))
             bits += [self._wire(row, 1 + i, (part >> i) & 1) for i in range(nl)]
+        # the sums come from plonky2's WireSplitGenerator: consecutive ranges of nl bits of x's canonical integer
+        from . import witness_program as wprog
+        self._record_free(WGEN_PROGRAM, 0, [[x]], [sums], program=wprog.wire_split([nl] * k))
         for b in bits[num_bits:]:
             self.assert_zero(b)
         acc = self.zero()
@@ -511,7 +527,7 @@ class GadgetBuilder:
         for f, (kind, m, in_ops, out_ops) in enumerate(self._free):
             ops = in_ops + out_ops
             assert len(ops) <= 6 and all(len(o) < 1 << 16 for o in ops)
-            mi = moduli.setdefault(m, len(moduli)) if m else 0
+            mi = m if kind == WGEN_PROGRAM else moduli.setdefault(m, len(moduli)) if m else 0      # a program unit: m is its program's index
             units.append([kind, mi, begin] + [len(o) for o in ops] + [0] * (6 - len(ops)))
             ins.append((f, [t for o in in_ops for t in o]))
             outs.append([t for o in out_ops for t in o])
@@ -526,6 +542,7 @@ class GadgetBuilder:
         c.free_units = np.array(units, dtype=np.int64).reshape(-1, 9)
         c.free_cells = np.concatenate(runs) if runs else np.zeros(0, np.uint64)
         c.moduli = np.array([[(m >> (32 * i)) & M32 for i in range(8)] for m in moduli], dtype=np.uint32).reshape(-1, 8)
+        c.witness_programs = list(self._programs)             # what the WGEN_PROGRAM rows of free_units name in their modulus field
         c.witness_inputs = cells_of(self.witness_input_targets, "witness_input_targets")
         # The operations a partly filled row has left over read cells that nothing is wired to (plonky2 wires such slots to zero; this
         # builder leaves them alone and their wires 0).  Their generators still have to run -- an unused U32ArithmeticGate operation
@@ -586,6 +603,7 @@ def keccak256_circuit(message, blocks_num=1, config=None, min_log_n=0):
     gb = GadgetBuilder(config)
     limbs = [gb.target(int.from_bytes(padded[4 * i:4 * i + 4], "little")) for i in range(len(padded) // 4)]
     blocks = [gb.target(1 if i < num_actual - 1 else 0) for i in range(blocks_num - 1)]      # add_virtual_bool_target_unsafe
+    gb.witness_input_targets += limbs + blocks               # what set_keccak256_input_target sets [REF src/hash/keccak256.rs:22-37]
     chunks = KECCAK256_R // 64
     zero = gb.zero_u32()
     state = [[zero, zero] for _ in range(25)]
@@ -771,6 +789,8 @@ def smt_inclusion_circuit(tree, key, n_levels=16, enabled=True, config=None, pub
     enabled_t = gb.add_virtual_bool_target_safe(enabled)
     is_old0 = gb.add_virtual_bool_target_safe(w["is_old0"])
     fnc = gb.add_virtual_bool_target_safe(not w["found"])
+    # what set_witness sets [REF src/smt/gadgets/verify/verify_smt.rs:73-94]
+    gb.witness_input_targets += [t for s in siblings for t in s] + root + old_key + old_value + key_t + value_t + [enabled_t, is_old0, fnc]
     # verify_smt_inclusion_proof
     true_t, false_t = gb.constant_bool(True), gb.constant_bool(False)
     hash1_old = _calc_leaf_hash(gb, old_key, old_value)
@@ -902,6 +922,8 @@ def smt_process_circuit(proof, n_levels=16, config=None, public=True, min_log_n=
     is_old0 = gb.add_virtual_bool_target_safe(proof["is_old0"])
     fnc = [gb.add_virtual_bool_target_safe(proof["fnc"][0]), gb.add_virtual_bool_target_safe(proof["fnc"][1])]
     pis = old_key + old_value + new_key + new_value + old_root + new_root
+    # what set_witness sets [REF src/smt/gadgets/process/process_smt.rs:82-117]
+    gb.witness_input_targets += [t for s in siblings for t in s] + pis + [is_old0] + fnc
     # verify_smt_process_proof
     true_t, false_t = gb.constant_bool(True), gb.constant_bool(False)
     zero4 = [gb.zero()] * 4
