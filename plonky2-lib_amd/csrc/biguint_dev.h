@@ -42,7 +42,8 @@ constexpr int MAX_MOD = 8;        // a modulus or a divisor
 // the kinds of include/glp.h
 constexpr uint32_t K_EQUALITY = 1, K_ADD = 2, K_MULTI_ADD = 3, K_SUB = 4, K_MUL = 5, K_INV = 6, K_DIV_REM = 7, K_GLV = 8;
 
-struct Stats { uint64_t qhat_corrections, add_backs; };   // the two correction branches of the division, counted by the host program
+// the two correction branches of the division, counted by the host program; `twice`: the digits whose estimate was corrected both times
+struct Stats { uint64_t qhat_corrections, add_backs, twice; };
 
 template <int CN> BIG_HD void zero(uint32_t *r, int n_) {
     const int n = CN >= 0 ? CN : n_;
@@ -128,7 +129,7 @@ template <int CNA, int CNB> BIG_HD void divrem(uint32_t *q, uint32_t *r, const u
         BIG_UNROLL for (int t = 0; t < 2; t++)
             if (rhat < B && (qhat >= B || qhat * vsec > ((rhat << 32) | u3))) {
                 qhat--; rhat += vtop;
-                if (st) st->qhat_corrections++;
+                if (st) { st->qhat_corrections++; st->twice += t; }       // a correction at t = 1 follows one at t = 0: without it nothing changed
             }
         int64_t k = 0, t = 0;                        // un[j .. j + nb] -= qhat * vn
         BIG_UNROLL for (int i = 0; i < nb; i++) {
