@@ -9,13 +9,25 @@
 // both are raw little-endian u64, NIN words in and NOUT words out per case.  An operation whose .in file is absent is skipped.
 //   device  one kernel per operation, 256 threads per block, one case per thread, each primitive called the way the library
 //           calls it.  Every HIP return code is checked: the first failure ends the program with status 1 and HIP's error text.
-//   host    the GLF_HD functions through their host bodies (and the host-only apl_words); no HIP runtime call is made, so it
-//           runs on a machine without a GPU.  Device-only operations are left out.
+//   host    the GLF_HD functions through their host bodies (and the host-only apl_words and host schedule of poseidon.h); no HIP
+//           runtime call is made, so it runs on a machine without a GPU.  Device-only operations are left out.
 //
 // What a green run proves: the arithmetic of each primitive as hipcc compiles it HERE, with the library's flags.  It does not pin
 // every inlined copy inside the library's kernels, where the surrounding schedule (and so the distance between an inline-assembly
 // block that writes a carry and the one that reads it) differs.  Two chained operations narrow that gap, with one block's result
 // feeding the next and nothing in between: sbox7_nc (four mul_nc_cc back to back) and mul_nc_chain = mul_nc(mul_nc(x, y), y).
+//
+// Of csrc/poseidon.h, layer by layer, each over ANY u64 the layer before may hand it (a whole-permutation test controls only the state
+// that enters round 0, which passes an S-box layer before the first sum sees it):
+//   sbox7_nc, sbox_layer_nc (twelve carry chains under the scheduling barriers), mds_add_nc, mds_add_wave (the int8 matrix pipe),
+//   full_round_nc / full_round_wave = the S-box layer and a linear layer with nothing in between (the shape permute_body and k_quotient
+//   inline), the six partial-round blocks plain and with a hook that replaces the S-box input (k_quotient's wire_in), permute_tail7,
+//   pow_round0_consts, permute (host schedule and permute_body<false>) and permute_wave; on the host pos::host::fold, the six
+//   pos::host::partial_block and pos::host::mds_add.
+//   NOT run here: permute_coop and permute_quad.  They take canonical words and S-box them before any sum, so their unreduced rows
+//   cannot be driven from outside; the Merkle tests cover them against the oracle.
+// The operations that call a matrix instruction (mds_add_wave, full_round_wave, permute_wave) run under k_probe_wave: the instruction
+// acts on all 64 lanes whatever the execution mask, so every lane computes (lanes past the end on row 0) and only the store is masked.
 //
 // Accumulator loops: a row is  N, (flags), then TERMS operand groups; the kernel runs N (clamped to TERMS) terms.  The *_flush
 // forms reduce, add and zero every ACC_MAX_TERMS (ACC3_MAX_TERMS) terms, the pattern of k_open_dot.
@@ -115,6 +127,46 @@ OP_D(mds_add_nc, 24, 12,
      pos::mds_add_nc(s, x + 12);
 #endif
      for (int i = 0; i < 12; i++) y[i] = s[i];)
+// ---- the layers of csrc/poseidon.h (device schedule; the host pass of hipcc does not declare these names) --------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PROBE_DEV(...) __VA_ARGS__
+#define PROBE_HOST(...)
+#else
+#define PROBE_DEV(...)
+#define PROBE_HOST(...) __VA_ARGS__
+#endif
+#define LOAD12 u64 s[12]; for (int i = 0; i < 12; i++) s[i] = x[i];
+#define STORE12 for (int i = 0; i < 12; i++) y[i] = s[i];
+// an operation that calls a matrix instruction: run by k_probe_wave, y is the lane's own array, mo = pos::mds_operands()
+#define OP_W(NAME, NIN_, NOUT_, ...)                                                                \
+    struct op_##NAME {                                                                              \
+        static constexpr u32 NIN = NIN_, NOUT = NOUT_;                                              \
+        static constexpr bool HOST = false, APL = false, WAVE = true;                               \
+        static const char *name() { return #NAME; }                                                 \
+        static PROBE_D void run(const u64 *x, u64 *y, const pos::MdsOperands &mo) { PROBE_DEV(__VA_ARGS__) }  \
+    };
+OP_W(mds_add_wave, 24, 12, LOAD12 pos::mds_add_wave(s, x + 12, mo); STORE12)
+OP_D(sbox_layer_nc, 12, 12, LOAD12 PROBE_DEV(pos::sbox_layer_nc(s);) STORE12)
+OP_D(full_round_nc, 24, 12, LOAD12 PROBE_DEV(pos::sbox_layer_nc(s); pos::mds_add_nc(s, x + 12);) STORE12)
+OP_W(full_round_wave, 24, 12, LOAD12 pos::sbox_layer_nc(s); pos::mds_add_wave(s, x + 12, mo); STORE12)
+// K partial rounds as one block: rounds 3 (linear layer) + 4..6, 7..10, 11..14, 15..18, 19..22, 23..25
+#define PBLOCK_OP(NAME, K, MERGED, KC)                                                              \
+    OP_D(NAME, 12, 12, LOAD12 PROBE_DEV(pos::partial_block_nc<K, MERGED>(s, KC);) STORE12)          \
+    /* row: the state, then the word the hook returns in place of z_j (k_quotient's wire_in); out: the state, then each z_j */  \
+    OP_D(NAME##_hook, 12 + K, 12 + K, LOAD12                                                        \
+         PROBE_DEV(pos::partial_block_nc<K, MERGED>(s, KC, [&](int j, u64 z) { y[12 + j] = z; return x[12 + j]; });) STORE12)
+PBLOCK_OP(pblock_m3, 3, true, pos::PBM[0])
+PBLOCK_OP(pblock_4a, 4, false, pos::PB4[0])
+PBLOCK_OP(pblock_4b, 4, false, pos::PB4[1])
+PBLOCK_OP(pblock_4c, 4, false, pos::PB4[2])
+PBLOCK_OP(pblock_4d, 4, false, pos::PB4[3])
+PBLOCK_OP(pblock_3, 3, false, pos::PB3[0])
+// ---- canonical out (device only) ------------------------------------------------------------------------------------------
+OP_D(tail7, 12, 1, LOAD12 PROBE_DEV(y[0] = pos::permute_tail7(s);))
+OP_D(pow_round0_consts, 13, 12, PROBE_DEV(u64 s[12]; pos::pow_round0_consts(x, (u32)x[12], s); STORE12))
+OP_W(permute_wave, 12, 12, LOAD12 pos::permute_wave(s, mo); STORE12)
+// host: the host schedule of poseidon.h; device: permute_body<false>
+OP_HD(permute, 12, 12, LOAD12 PROBE_DEV(pos::permute_body<false>(s, pos::MdsOperands{});) PROBE_HOST(pos::permute(s);) STORE12)
 // ---- exact ----------------------------------------------------------------------------------------------------------------
 template <int E> PROBE_D void add_shifted(Acc160 &w, u64 v, u32 e) { if (e == (u32)E) acc_add_shifted<E>(w, v); }
 OP_D(acc_add_shifted, 7, 5,           // w0..w4, v, E -> w + (v << E) mod 2^160 for the E of acc2_reduce and acc3_reduce
@@ -199,6 +251,22 @@ struct op_apl_words {
     static const char *name() { return "apl_words"; }
     static void run(const u64 *x, u64 *y) { apl_words(x[0], y); }
 };
+// host only: the host schedule's fold (al, ah, k), its six blocks (any u64 in) and its full-round linear layer (canonical in and out)
+#define OP_H(NAME, NIN_, NOUT_, ...)                                                                \
+    struct op_##NAME {                                                                              \
+        static constexpr u32 NIN = NIN_, NOUT = NOUT_;                                              \
+        static constexpr bool HOST = true, APL = false, DEVICE = false;                             \
+        static const char *name() { return #NAME; }                                                 \
+        static void run(const u64 *x, u64 *y) { PROBE_HOST(__VA_ARGS__) }                           \
+    };
+OP_H(host_fold, 3, 1, y[0] = pos::host::fold(x[0], x[1], x[2]);)
+OP_H(host_pblock_m3, 12, 12, LOAD12 pos::host::partial_block<3, true>(s, pos::host::HPBM); STORE12)
+OP_H(host_pblock_4a, 12, 12, LOAD12 pos::host::partial_block<4, false>(s, pos::host::HPB4[0]); STORE12)
+OP_H(host_pblock_4b, 12, 12, LOAD12 pos::host::partial_block<4, false>(s, pos::host::HPB4[1]); STORE12)
+OP_H(host_pblock_4c, 12, 12, LOAD12 pos::host::partial_block<4, false>(s, pos::host::HPB4[2]); STORE12)
+OP_H(host_pblock_4d, 12, 12, LOAD12 pos::host::partial_block<4, false>(s, pos::host::HPB4[3]); STORE12)
+OP_H(host_pblock_3, 12, 12, LOAD12 pos::host::partial_block<3, false>(s, pos::host::HPB3); STORE12)
+OP_H(host_mds_add, 24, 12, LOAD12 pos::host::mds_add(s, x + 12); STORE12)
 
 // ---- driver ---------------------------------------------------------------------------------------------------------------
 template <class Op>
@@ -206,6 +274,22 @@ __global__ __launch_bounds__(256) void k_probe(const u64 *in, u64 *out, u64 n) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     Op::run(in + i * Op::NIN, out + i * Op::NOUT);
+}
+
+template <class Op, class = void> struct is_wave { static constexpr bool value = false; };
+template <class Op> struct is_wave<Op, std::enable_if_t<Op::WAVE>> { static constexpr bool value = true; };
+// the same for an operation that calls a matrix instruction: control flow is wave-uniform up to the call, every lane computes (the
+// lanes past the end on row 0, as the kernels of merkle.hip do) and only the store is masked
+template <class Op>
+__global__ __launch_bounds__(256) void k_probe_wave(const u64 *in, u64 *out, u64 n) {
+    const u64 i0 = (u64)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i0 < n;
+    const u64 i = live ? i0 : 0;
+    const pos::MdsOperands mo = pos::mds_operands();
+    u64 y[Op::NOUT];
+    Op::run(in + i * Op::NIN, y, mo);
+    if (live)
+        for (u32 k = 0; k < Op::NOUT; k++) out[i * Op::NOUT + k] = y[k];
 }
 
 #define HIP_OK(call)                                                                                \
@@ -248,7 +332,8 @@ static void run_device(const char *op, const std::vector<u64> &in, std::vector<u
         HIP_OK(hipMalloc(&d_out, out.size() * 8));
         HIP_OK(hipMemcpy(d_in, in.data(), in.size() * 8, hipMemcpyHostToDevice));
         HIP_OK(hipMemset(d_out, 0xA5, out.size() * 8));
-        hipLaunchKernelGGL(k_probe<Op>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_out, (u64)n);
+        if constexpr (is_wave<Op>::value) hipLaunchKernelGGL(k_probe_wave<Op>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_out, (u64)n);
+        else hipLaunchKernelGGL(k_probe<Op>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_out, (u64)n);
         HIP_OK(hipGetLastError());
         HIP_OK(hipDeviceSynchronize());
         HIP_OK(hipMemcpy(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost));
@@ -296,9 +381,13 @@ int main(int argc, char **argv) {
         op_add, op_sub, op_neg, op_dbl, op_pow, op_inv, op_e_add, op_e_sub, op_e_neg, op_e_mul, op_e_sqr, op_e_scale, op_e_inv, op_e_pow,
         op_canon, op_mul, op_sqr, op_reduce128, op_reduce96, op_mul_2exp, op_mul_c, op_mul_pow2_c, op_b4_value, op_acc_reduce,
         op_acc2_reduce, op_acc3_reduce, op_mul_nc, op_mul_nc_cc, op_mul_nc_chain, op_fold96_nc, op_fold96_c, op_fold128_nc,
-        op_fold128_mad_nc, op_mul_small_nc, op_add_cnc, op_range_product, op_sbox7_nc, op_mds_add_nc, op_acc_add_shifted,
+        op_fold128_mad_nc, op_mul_small_nc, op_add_cnc, op_range_product, op_sbox7_nc, op_mds_add_nc, op_mds_add_wave, op_sbox_layer_nc,
+        op_full_round_nc, op_full_round_wave, op_pblock_m3, op_pblock_m3_hook, op_pblock_4a, op_pblock_4a_hook, op_pblock_4b, op_pblock_4b_hook,
+        op_pblock_4c, op_pblock_4c_hook, op_pblock_4d, op_pblock_4d_hook, op_pblock_3, op_pblock_3_hook, op_tail7, op_pow_round0_consts,
+        op_permute_wave, op_permute, op_acc_add_shifted,
         op_root_of_unity, op_bitrev32, op_acc_loop, op_acc_flush, op_acc2_loop, op_acc2_flush, op_acc3_loop, op_acc3_flush,
-        op_apl_words>(device, argv[2]);
+        op_apl_words, op_host_fold, op_host_pblock_m3, op_host_pblock_4a, op_host_pblock_4b, op_host_pblock_4c, op_host_pblock_4d,
+        op_host_pblock_3, op_host_mds_add>(device, argv[2]);
     printf("field_probe %s: %u operations\n", argv[1], done);
     return 0;
 }

@@ -15,6 +15,14 @@ take pairs of canonical EDGES as elements, capped to a cross product of at most 
 12 independent folds per row, so it takes 2^13 + 2^13 rows (2 * 10^5 folds); pow runs ~96 products per row and takes 2^13 + 2^13.  The accumulator loops take a few dozen rows of up to
 4096 terms each: the worst case at the term bound, and the same N with uniform and structured operands.
 
+The layers of csrc/poseidon.h (POSEIDON_LAYER_OPS) are modelled from the round definition alone -- M = circulant(MDS_C) + 8 at [0][0], x^7,
+the constants of tests/golden/poseidon_round_constants.npy -- never from the tables of namespace pblk, so make_tab / make_blk are checked
+too.  `block` is the contract of a partial-round block as a plain round loop; `block_linear` propagates the same rounds symbolically and
+gives the model's own row weights (`block_weight`, `fold_bound`, `block_bounds`).  mds_add_nc and mds_add_wave share ONE operand set
+(`mds_layout`): the rows mds_add_nc always had, then byte states (0x00 / 0x7f / 0x80 / 0xff, 2^64 - 1, one-hot / one-cold) four times over,
+shifted so that each sits in four lanes and both halves of a wave, 64 rows with opposite extremes in lanes l and l + 32, and a partial
+wave at the end.  Blocks take 2^10 + 2^10 random states on top of their edges (a block is 36 to 60 S-boxes and products per row in Python).
+
 `witnesses(name)` counts, per carry / borrow event named in WITNESS, the rows where the event fires, computing the intermediate from
 the operands with Python integers.  `accumulator_bounds()` is the arithmetic behind ACC_MAX_TERMS and ACC3_MAX_TERMS.
 
@@ -168,6 +176,270 @@ def _acc3_rows(name, counts, repeats=3):
     return rows
 
 
+# ---- the Poseidon layers: round definition, blocks, operand sets ------------------------------------------------------------------
+# M = circulant(MDS_C) with 8 added at [0][0];  a round is  s <- M sbox(s + rc)  (full: every element, partial: element 0 only).
+MDS_M = tuple(tuple(MDS_C[(c - r) % 12] + (8 if r == c == 0 else 0) for c in range(12)) for r in range(12))
+ZERO12 = (0,) * 12
+# block tag -> (first partial round, K, merged with the linear layer of full round 3): the six blocks of permute_body, in order
+BLOCKS = {"m3": (4, 3, True), "4a": (7, 4, False), "4b": (11, 4, False), "4c": (15, 4, False), "4d": (19, 4, False), "3": (23, 3, False)}
+BYTE_WORDS = (0, 0x7F7F7F7F7F7F7F7F, 0x8080808080808080, M64, 0xFFFFFFFF00000000, 0x00000000FFFFFFFF)
+WAVE_RC = (0, P - 1, EPS)
+WAVE_SHIFTS = (0, 17, 32, 45)
+
+
+@functools.lru_cache(None)
+def round_constants():
+    """RC[r] = the twelve constants of round r, from tests/golden/poseidon_round_constants.npy (data; pinned to the reference elsewhere)"""
+    import numpy as np
+    rc = [int(v) for v in np.load(os.path.join(ROOT, "tests", "golden", "poseidon_round_constants.npy"))]
+    assert len(rc) == 360 and all(v < P for v in rc)
+    return tuple(tuple(rc[12 * r:12 * r + 12]) for r in range(30))
+
+
+def _lin(s, rc):
+    return [(sum(m * v for m, v in zip(MDS_M[r], s)) + rc[r]) % P for r in range(12)]
+
+
+def _sbox_all(s):
+    return [pow(v, 7, P) for v in s]
+
+
+def block(tag, s, w=None):
+    """The contract of a block, as a plain round loop: if merged s <- M s + RC[first]; then for j < K: z_j = s[0],
+    s[0] <- sbox(w_j if hooked else z_j), s <- M s + RC[first + j + 1].  Returns (state, (z_0 .. z_{K-1})), all mod p."""
+    first, k, merged = BLOCKS[tag]
+    rc = round_constants()
+    s = list(s)
+    if merged:
+        s = _lin(s, rc[first])
+    z = []
+    for j in range(k):
+        z.append(s[0] % P)
+        s[0] = pow(s[0] if w is None else w[j], 7, P)
+        s = _lin(s, rc[first + j + 1])
+    return tuple(s), tuple(z)
+
+
+def rounds_from(s, start):
+    """s = the state entering the S-boxes of full round `start` (0 or 1, that round's constants added) -> the permutation's output,
+    chained the way permute_body chains its layers and blocks"""
+    rc = round_constants()
+    for r in range(start, 3):
+        s = _lin(_sbox_all(s), rc[r + 1])
+    s = _sbox_all(s)                              # round 3; its linear layer is the merged block's
+    for tag in BLOCKS:
+        s = block(tag, s)[0]
+    for r in range(26, 30):
+        s = _lin(_sbox_all(s), rc[r + 1] if r < 29 else ZERO12)
+    return tuple(s)
+
+
+def permute(s):
+    return rounds_from([v + c for v, c in zip(s, round_constants()[0])], 0)
+
+
+def pow_round0(r):
+    """(st, pos) -> K: the state entering round 1's S-boxes is K_r + M[r][pos] sbox(candidate + RC[0][pos])"""
+    rc = round_constants()
+    c = [0 if i == r[12] else pow(r[i] + rc[0][i], 7, P) for i in range(12)]
+    return tuple(_lin(c, rc[1]))
+
+
+@functools.lru_cache(None)
+def block_linear(tag):
+    """The same rounds propagated symbolically: every folded row of the block as (coefficients over y_0..y_11, sigma_1..sigma_K; constant),
+    first the rows z_j[0] that feed an S-box (j = 0 only if merged), then the twelve outputs.  Integer matrices, constants mod p: what
+    make_tab / make_blk must have tabulated, reached without their recursion."""
+    first, k, merged = BLOCKS[tag]
+    rc = round_constants()
+    n = 12 + k
+
+    def mul(rows, const, add):
+        return ([[sum(MDS_M[r][i] * rows[i][c] for i in range(12)) for c in range(n)] for r in range(12)],
+                [(sum(MDS_M[r][i] * const[i] for i in range(12)) + add[r]) % P for r in range(12)])
+    rows, const = [[int(c == i) for c in range(n)] for i in range(12)], [0] * 12
+    if merged:
+        rows, const = mul(rows, const, rc[first])
+    zrows = []
+    for j in range(k):
+        if merged or j:
+            zrows.append((tuple(rows[0]), const[0]))
+        rows[0], const[0] = [int(c == 12 + j) for c in range(n)], 0
+        rows, const = mul(rows, const, rc[first + j + 1])
+    return tuple(zrows), tuple((tuple(r), c) for r, c in zip(rows, const))
+
+
+def block_weight(tag):
+    """the largest total coefficient weight of one folded row: the W of  al <= (2^32 - 1) W + 2^32"""
+    zrows, out = block_linear(tag)
+    return max(sum(coef) for coef, _ in zrows + out)
+
+
+def fold_bound():
+    """the largest al / ah a block can hand its fold: (2^32 - 1) W + 2^32, W the largest weight of the three table shapes"""
+    return M32 * max(block_weight(t) for t in ("m3", "4a", "3")) + (1 << 32)
+
+
+def block_folds(tag, s, w=None):
+    """(al, ah, k) of every folded row for the entering state s, with canonical S-box outputs (the host's integers; the device's sigma
+    is some u64 congruent to them): al = sum of low halves times coefficients, ah the same of the high halves, k the row's constant"""
+    zrows, out = block_linear(tag)
+    _, z = block(tag, s, w)
+    sig = [pow(z[j] if w is None else w[j], 7, P) for j in range(BLOCKS[tag][1])]
+    var = list(s) + sig
+    return [(sum(c * (v & M32) for c, v in zip(coef, var)), sum(c * (v >> 32) for c, v in zip(coef, var)), k) for coef, k in zrows + out]
+
+
+def host_fold_steps(al, ah, k):
+    """pos::host::fold in integers: (h, t1, unwrapped t2); the u64 sums must not overflow"""
+    al += k & M32
+    h = ah + (al >> 32) + (k >> 32)
+    assert al <= M64 and h <= M64
+    return h, (h >> 32) * EPS, (((h << 32) | (al & M32)) & M64) + (h >> 32) * EPS
+
+
+def _one_hot_cold(v=M64):
+    return [tuple(v if k == j else 0 for k in range(12)) for j in range(12)] + [tuple(0 if k == j else v for k in range(12)) for j in range(12)]
+
+
+def _state_rows(name, n=1 << 10):
+    """any-u64 states: twelve equal words of every edge (2^64 - 1, p, p + 1 among them), one-hot and one-cold 2^64 - 1, n structured + n uniform"""
+    return [(e,) * 12 for e in EDGES] + _one_hot_cold() + _rows(name, ("any",) * 12, n=n, edges=False)
+
+
+def _canon_state_rows(name, n=1 << 10):
+    one = [tuple(e if k == j else 0 for k in range(12)) for e in EDGES_C for j in range(12)]
+    return [(e,) * 12 for e in EDGES_C] + one + _rows(name, ("canon",) * 12, n=n, edges=False)[n:]
+
+
+def _mds_edge_block():
+    """66 rows: byte states x the three constants, one-hot / one-cold 2^64 - 1, and per output row r and half the state whose half-words
+    are 0xffffffff at the six largest coefficients of row r and 0 elsewhere (all other bytes 0x00)"""
+    rows = [(v,) * 12 + (c,) * 12 for v in BYTE_WORDS for c in WAVE_RC]
+    rows += [s + (WAVE_RC[i % 3],) * 12 for i, s in enumerate(_one_hot_cold())]
+    for r in range(12):
+        top = sorted(range(12), key=lambda c: -MDS_M[r][c])[:6]
+        for half in (0, 1):
+            rows.append(tuple((M32 << (32 * half)) if c in top else 0 for c in range(12)) + (WAVE_RC[(r + half) % 3],) * 12)
+    assert len(rows) == 66
+    return rows
+
+
+@functools.lru_cache(None)
+def mds_layout():
+    """The one operand set of mds_add_nc and mds_add_wave, and where its parts lie: (rows, first row of the wave part, first rows of the
+    four copies of the edge block, first row of the lane-pair stretch).  Row i runs in lane i % 64 (256 threads per block)."""
+    name, n = "mds_add_nc", 1 << 13
+    rows = [(e,) * 12 + (c,) * 12 for e in EDGES for c in EDGES_C]
+    for kind in ("structured", "uniform"):
+        rows.extend(zip(*[_column(kind, name, j, n, canonical=j >= 12) for j in range(24)]))
+    wave_start = len(rows)
+    filler = iter(list(zip(*[_column("uniform", "mds_add_wave", j, 512, canonical=j >= 12) for j in range(24)])))
+
+    def fill(k):
+        rows.extend(next(filler) for _ in range(k))
+    edge, edge_at = _mds_edge_block(), []
+    fill(-len(rows) % 64)
+    for shift in WAVE_SHIFTS:                     # every edge row in four lanes, in both halves of a wave
+        fill(shift)
+        edge_at.append(len(rows))
+        rows.extend(edge)
+        fill(-len(rows) % 64)
+    pair_at = len(rows)                           # lanes l and l + 32 share a column of the matrix instruction: opposite extremes in them
+    lo, hi = [], []
+    for l in range(32):
+        c = (WAVE_RC[l % 3],) * 12
+        if l < 16:
+            a, b = ((0,) * 12, (M64,) * 12)[::1 if l % 2 == 0 else -1]
+        else:
+            a, b = ((0,) * 12 if l % 4 < 2 else (M64,) * 12, next(filler)[:12])[::1 if l % 2 == 0 else -1]
+        lo.append(a + c)
+        hi.append(b + c)
+    rows.extend(lo + hi)
+    rows.extend(edge[:33])                        # the set ends in a partial wave
+    assert len(rows) % 64 == 33 and pair_at % 64 == 0
+    return rows, wave_start, tuple(edge_at), pair_at
+
+
+def mds_edge_lanes():
+    _, _, edge_at, _ = mds_layout()
+    return {(at + i) % 64 for at in edge_at for i in range(66)}
+
+
+def _hook_rows(tag):
+    """the block's states, each followed by the K words the hook returns: 0, 1, p - 1 (sigma = p - 1, the largest canonical S-box
+    output), 2^32 - 1, 2^32 or a uniform word, one chance in six each"""
+    first, k, _ = BLOCKS[tag]
+    rng = random.Random(0x686F6F6B + first)
+    pick = (0, 1, P - 1, M32, 1 << 32, None)
+    rows = []
+    for s in _state_rows("pblock_%s_hook" % tag):
+        w = [pick[rng.randrange(6)] for _ in range(k)]
+        rows.append(s + tuple(rng.getrandbits(64) if v is None else v for v in w))
+    return rows
+
+
+def _twin(row):
+    return tuple(v + P if v + P <= M64 else v for v in row)
+
+
+def _host_fold_rows():
+    bound = fold_bound()
+    rows = []
+    # the two sides of t2 < t1: with a = h >> 32 >= 1, l + a (2^32 - 1) reaches 2^64 exactly at l = (2^32 - a) 2^32 + a.  h and the low
+    # word are then spread over ah, al >> 32, k >> 32 and the carry of al + (u32)k in five ways.
+    for a in (1, 2, 0x7FFFFFFF, (bound >> 32) - 2):
+        h = (a << 32) | ((1 << 32) - a)
+        for low in (a, a - 1):
+            rows += [(low, h, 0), ((1 << 32) + low, h - 1, 0), (low, h - 1, 1 << 32), (low - 1 if low else 0, h, 1 if low else 0),
+                     (M32, h - 1, low + 1)]
+    rows += [(low, h, k) for h in (0, 1, M32) for low in (0, M32) for k in (0, M32)]          # h >> 32 = 0: t1 = 0
+    rows += [(bound, bound, k) for k in (0, 1, EPS, P - 1, M64)] + [(bound, 0, 0), (0, bound, 0)]
+    n = 1 << 14
+    for kind in ("structured", "uniform"):
+        cols = [[v % (bound + 1) for v in _column(kind, "host_fold", j, n)] for j in range(2)] + [_column(kind, "host_fold", 2, n)]
+        rows.extend(zip(*cols))
+    assert all(r[0] <= bound and r[1] <= bound for r in rows)
+    return rows
+
+
+@functools.lru_cache(None)
+def _poseidon_cases(name):
+    if name in ("mds_add_nc", "mds_add_wave"):
+        return mds_layout()[0]
+    if name == "sbox_layer_nc":                   # every edge in every one of the twelve chains
+        return [tuple(EDGES[(i + j) % len(EDGES)] for j in range(12)) for i in range(len(EDGES))] + _state_rows(name)
+    if name in ("full_round_nc", "full_round_wave"):
+        name = "full_round_nc"
+        edge = [(e,) * 12 + (c,) * 12 for e in EDGES for c in WAVE_RC]
+        rnd = []
+        for kind in ("structured", "uniform"):
+            rnd.extend(zip(*[_column(kind, name, j, 1 << 10, canonical=j >= 12) for j in range(24)]))
+        return edge + rnd
+    if name == "host_mds_add":
+        edge = [(e,) * 12 + (c,) * 12 for e in EDGES_C for c in EDGES_C] + [s + (P - 1,) * 12 for s in _one_hot_cold(P - 1)]
+        rnd = []
+        for kind in ("structured", "uniform"):
+            rnd.extend(zip(*[_column(kind, name, j, 1 << 10, canonical=True) for j in range(24)]))
+        return edge + rnd
+    if name == "host_fold":
+        return _host_fold_rows()
+    if name.endswith("_hook"):
+        return _hook_rows(name[len("pblock_"):-len("_hook")])
+    if name.startswith("pblock_") or name.startswith("host_pblock_"):
+        return _state_rows(name)
+    if name in ("permute", "permute_wave"):
+        return _canon_state_rows("permute")
+    if name == "tail7":                           # canonical rows, their twins v + p (where that fits a u64), and non-canonical edges
+        rows = _canon_state_rows(name)
+        return rows + [t for r, t in zip(rows, map(_twin, rows)) if t != r] + [(e,) * 12 for e in EDGES if e >= P]
+    if name == "pow_round0_consts":
+        rows = _canon_state_rows(name)
+        nuni = len(EDGES_C)
+        return [r + (p,) for r in rows[:nuni] for p in range(8)] + [r + (i % 8,) for i, r in enumerate(rows[nuni:])]
+    raise KeyError(name)
+
+
 # ---- constructed rows: (operation, label, row) ----------------------------------------------------------------------------------
 CONSTRUCTED = (
     ("b4_value", "all 16 limbs p - 1", (P - 1,) * 16),
@@ -210,12 +482,34 @@ def _specs():
     add("acc3_loop", 2 + 5 * ACC3_TERMS, 1, CANONICAL)
     add("acc3_flush", 2 + 5 * ACC3_TERMS, 1, CANONICAL)
     add("apl_words", 1, 4, EXACT, host=True, device=False)
+    # the layers of csrc/poseidon.h
+    add("mds_add_wave", 24, 12, CONGRUENT)
+    add("sbox_layer_nc", 12, 12, CONGRUENT)
+    add("full_round_nc", 24, 12, CONGRUENT)
+    add("full_round_wave", 24, 12, CONGRUENT)
+    for tag, (_, k, _) in BLOCKS.items():
+        add("pblock_" + tag, 12, 12, CONGRUENT)
+        add("pblock_%s_hook" % tag, 12 + k, 12 + k, CONGRUENT)
+    add("tail7", 12, 1, CANONICAL)
+    add("pow_round0_consts", 13, 12, CANONICAL)
+    add("permute_wave", 12, 12, CANONICAL)
+    add("permute", 12, 12, CANONICAL, host=True)
+    add("host_fold", 3, 1, CONGRUENT, host=True, device=False)
+    for tag in BLOCKS:
+        add("host_pblock_" + tag, 12, 12, CONGRUENT, host=True, device=False)
+    add("host_mds_add", 24, 12, CANONICAL, host=True, device=False)
     return {o.name: o for o in ops}
 
 
 OPS = _specs()
 HOST_OPS = tuple(n for n, o in OPS.items() if o.host)
 DEVICE_OPS = tuple(n for n, o in OPS.items() if o.device)
+# operations whose operand sets _poseidon_cases builds (mds_add_nc shares its set with mds_add_wave, row for row)
+POSEIDON_LAYER_OPS = ("mds_add_nc",) + tuple(n for n in OPS if n in ("mds_add_wave", "sbox_layer_nc", "full_round_nc", "full_round_wave", "tail7",
+                                                                   "pow_round0_consts", "permute_wave", "permute", "host_fold", "host_mds_add")
+                                             or n.startswith("pblock_") or n.startswith("host_pblock_"))
+# pairs that must agree word for word on their shared operand set (the header of mds_add_wave: "the outputs are bit-identical")
+SAME_WORDS = (("mds_add_wave", "mds_add_nc"), ("full_round_wave", "full_round_nc"), ("permute_wave", "permute"))
 # the range_product bounds the gate bodies pass: 4 (limb gates), 2^cb for 1 <= cb <= 4 (ComparisonGate), the base 2..16 of a BaseSumGate
 RANGE_BOUNDS = ("range", 2, 16)
 
@@ -260,14 +554,8 @@ def _base_cases(name):
             cols.append([SHIFTS[i % 6] for i in range(NRANDOM)])
             rnd.extend(zip(*cols))
         return edge + rnd
-    if name == "mds_add_nc":
-        n = 1 << 13
-        edge = [(e,) * 12 + (c,) * 12 for e in EDGES for c in EDGES_C]
-        rnd = []
-        for kind in ("structured", "uniform"):
-            cols = [_column(kind, name, j, n, canonical=j >= 12) for j in range(24)]
-            rnd.extend(zip(*cols))
-        return edge + rnd
+    if name in POSEIDON_LAYER_OPS:
+        return _poseidon_cases(name)
     if name == "root_of_unity":
         return [(n,) for n in range(33)]
     worst = (M64, M64)
@@ -388,12 +676,23 @@ _REF = {
     "acc2_loop": lambda r: (_terms_sum(r, ACC2_TERMS),), "acc2_flush": lambda r: (_terms_sum(r, ACC2_TERMS),),
     "acc3_loop": lambda r: (_acc3_sum(r),), "acc3_flush": lambda r: (_acc3_sum(r),),
     "apl_words": lambda r: apl_words(r[0]),
+    "mds_add_wave": _mds_add, "host_mds_add": _mds_add, "sbox_layer_nc": lambda r: tuple(_sbox_all(r)),
+    "full_round_nc": lambda r: _mds_add(tuple(_sbox_all(r[:12])) + r[12:]), "full_round_wave": lambda r: _mds_add(tuple(_sbox_all(r[:12])) + r[12:]),
+    "tail7": lambda r: (rounds_from(r, 1)[7],), "pow_round0_consts": pow_round0, "permute": permute, "permute_wave": permute,
+    "host_fold": lambda r: ((r[0] + (r[1] << 32) + r[2]) % P,),
 }
+for _tag in BLOCKS:
+    _REF["pblock_" + _tag] = _REF["host_pblock_" + _tag] = functools.partial(lambda r, t: block(t, r)[0], t=_tag)
+    _REF["pblock_%s_hook" % _tag] = functools.partial(lambda r, t: sum(block(t, r[:12], r[12:]), ()), t=_tag)
 assert set(_REF) == set(OPS)
 
 
 @functools.lru_cache(None)
 def reference(name):
+    for a, b in SAME_WORDS:         # one operand set, one definition: computed once
+        if name == a:
+            assert cases(a) is cases(b) or cases(a) == cases(b)
+            return reference(b)
     f = _REF[name]
     return [f(r) for r in cases(name)]
 
@@ -445,9 +744,113 @@ WITNESS = {
 assert (M64 + M64 * EPS) >> 64 == M32          # h cannot exceed 2^32 - 1: y <= 2^96 - 2^32
 
 
+def _fold_events(units):
+    """units: (64-bit word, top word) handed to a 96-bit fold"""
+    n = sum(1 for u in units if _F96["wraps"](u))
+    return {"final fold wraps": (n, len(units)), "final fold does not wrap": (len(units) - n, len(units))}
+
+
+def wave_row(row):
+    """mds_add_wave in integers, for one row: per output row r and half the four byte dot products D_b (circulant part, bytes as u - 128),
+    the partial sum x = D_0 + 2^8 D_1 (+ the low half's overflow), and the pair (al, ah); asserts that (al, ah) are the integers
+    mds_add_nc forms, which is the claim of the header."""
+    s, rc = row[:12], row[12:]
+    bias = 128 * 256 * 0x01010101
+    out = []
+    for r in range(12):
+        al = ah = 0
+        for half in (0, 1):
+            w = [(v >> (32 * half)) & M32 for v in s]
+            d = [sum(MDS_C[(c - r) % 12] * (((w[c] >> (8 * b)) & 0xFF) - 128) for c in range(12)) for b in range(4)]
+            carry = al >> 32 if half else 0
+            assert carry < 1 << 31
+            x = d[0] + (d[1] << 8) + carry
+            v = x + bias + ((rc[r] >> (32 * half)) & M32) + (8 * w[0] if r == 0 else 0) + ((d[2] + (d[3] << 8)) << 16)
+            assert v == sum(m * u for m, u in zip(MDS_M[r], w)) + ((rc[r] >> (32 * half)) & M32) + carry and 0 <= v <= M64
+            out.append((r, half, d, x))
+            if half:
+                ah = v
+            else:
+                al = v
+        out[-1] += (((ah << 32) | (al & M32)) & M64, ah >> 32)
+    return out
+
+
+def _wave_witnesses():
+    rows, start, _, _ = mds_layout()
+    rows = rows[start:]              # the wave part: edge blocks, lane pairs and their uniform filler (~1200 dot products per row in Python)
+    dmin = dmax = xneg = nd = nx = 0
+    folds = []
+    for row in rows:
+        for t in wave_row(row):
+            nd += 4
+            dmin += sum(1 for v in t[2] if v == -32768)
+            dmax += sum(1 for v in t[2] if v == 127 * 256)
+            nx += 1
+            xneg += t[3] < 0
+            if len(t) > 4:
+                folds.append(t[4:])
+    out = {"D = -32768": (dmin, nd), "D = 127 * 256": (dmax, nd), "x negative": (xneg, nx), "x non-negative": (nx - xneg, nx),
+           "8 lo0 >= 2^32": (sum(1 for r in rows if 8 * (r[0] & M32) > M32), len(rows)),
+           "8 hi0 >= 2^32": (sum(1 for r in rows if 8 * (r[0] >> 32) > M32), len(rows))}
+    out.update(_fold_events(folds))
+    return out
+
+
+def _block_witnesses(tag, hooked):
+    name = "pblock_%s%s" % (tag, "_hook" if hooked else "")
+    folds = []
+    for r in cases(name):
+        for al, ah, k in block_folds(tag, r[:12], r[12:] if hooked else None):
+            al += k & M32
+            ah += (al >> 32) + (k >> 32)
+            assert ah <= M64
+            folds.append((((ah << 32) | (al & M32)) & M64, ah >> 32))
+    return _fold_events(folds)
+
+
+def _host_fold_witnesses():
+    steps = [host_fold_steps(*r) for r in cases("host_fold")]
+    n = len(steps)
+    wraps, hzero = sum(1 for h, t1, t2 in steps if t2 > M64), sum(1 for h, t1, t2 in steps if h >> 32 == 0)
+    return {"t2 < t1": (wraps, n), "t2 >= t1": (n - wraps, n), "h >> 32 = 0": (hzero, n), "h >> 32 != 0": (n - hzero, n)}
+
+
+WITNESS["mds_add_wave"] = _wave_witnesses
+WITNESS["host_fold"] = _host_fold_witnesses
+for _tag in BLOCKS:
+    WITNESS["pblock_" + _tag] = functools.partial(_block_witnesses, _tag, False)
+    WITNESS["pblock_%s_hook" % _tag] = functools.partial(_block_witnesses, _tag, True)
+
+
 def witnesses(name, constructed=True):
+    """event -> rows in which it fires; for the Poseidon layers event -> (units in which it fires, units), a unit being one fold, one byte dot
+    product or one half of one output row"""
+    if callable(WITNESS[name]):
+        return WITNESS[name]()
     rows = cases(name, constructed)
     return {event: sum(1 for r in rows if f(r)) for event, f in WITNESS[name].items()}
+
+
+def block_bounds():
+    """The overflow bound of the blocks from the model's own matrices: per table shape the largest row weight W (below 2^32 - 2, so that
+    al <= (2^32 - 1) W + 2^32 and ah fit 64 bits), reached exactly by the all-ones state of the operand sets."""
+    out = {}
+    for tag in BLOCKS:
+        w = block_weight(tag)
+        assert w + 2 < 1 << 32, (tag, w)
+        ones = (M64,) * 12
+        assert ones in cases("pblock_" + tag) and ones in cases("host_pblock_" + tag)
+        zrows, rows = block_linear(tag)
+        top = 0
+        for (coef, k), (al, ah, k2) in zip(zrows + rows, block_folds(tag, ones)):
+            sig = [pow(z, 7, P) for z in block(tag, ones)[1]]
+            ypart = al - sum(c * (v & M32) for c, v in zip(coef[12:], sig))
+            assert k == k2 and ypart == M32 * sum(coef[:12]), tag          # every half 2^32 - 1: the y-part is (2^32 - 1) x (row sum of G)
+            assert al + (k & M32) <= M32 * w + (1 << 32) and ah + (k >> 32) + (1 << 32) <= M32 * w + (1 << 33)
+            top = max(top, sum(coef[:12]))
+        out[tag] = (w, top)
+    return out
 
 
 def accumulator_bounds():

@@ -1,8 +1,13 @@
 """The one-state-per-lane Poseidon kernels run their seven full-round linear layers on the matrix pipe (pos::permute_wave,
 poseidon.h): an int8 matrix instruction acts on the whole wave, lanes l and l + 32 share one column of it, and the state bytes
 enter as signed values.  Against the CPU oracle, bit for bit: batch sizes around the wave and workgroup edges (the lanes past the
-end run the permutation too and only their store is masked), byte patterns at the ends of the signed range, batches in which lane
-l + 32 alone differs from lane l, and the leaf-hash and tree-level kernels that call the same function."""
+end run the permutation too and only their store is masked), special words in the state that ENTERS the permutation, batches in
+which lane l + 32 alone differs from lane l, and the leaf-hash and tree-level kernels that call the same function.
+
+What this file does not reach is the byte range of the matrix layer itself: an entering word gets round 0's constant added and passes
+an S-box before the first linear layer sees it, so all seven layers receive what are in effect uniformly random bytes.  States of
+0x00 / 0x7f / 0x80 / 0xff bytes and non-canonical words are fed to pos::mds_add_wave directly, in every lane, by the group
+`poseidon_layers` of tests/test_gpu_field_probe.py (operand sets and their reach: tests/field_model.py, tests/test_field_probe.py)."""
 import os
 
 import numpy as np
@@ -13,7 +18,8 @@ import plonky2_lib_amd as glp
 pytestmark = pytest.mark.gpu
 P = glp.P
 COUNTS = [1, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1000]
-# 0, p - 1, and words whose bytes are all 0x00 / 0x7f / 0x80 / 0xff (reduced where they are not field elements)
+# 0, p - 1, and words whose bytes are all 0x00 / 0x7f / 0x80 / 0xff (reduced where they are not field elements).  They exercise the state
+# path (loads, round 0's additions, lanes, stores); they do not survive round 0's S-boxes, so they are not the matrix layer's byte extremes
 SPECIAL = [0, P - 1, 0x7F7F7F7F7F7F7F7F, 0x8080808080808080, 0xFFFFFFFFFFFFFFFF % P, 0xFFFFFFFF00000000, 0x00000000FFFFFFFF,
            0x7F7F7F7F80808080, 0x80808080FFFFFFFF, 0xFFFFFFFF7F7F7F7F % P, 0x000000007F7F7F7F, 0x8080808000000000]
 
