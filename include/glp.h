@@ -652,7 +652,7 @@ GLP_API int glp_fri_verify(glp_ctx *ctx, const glp_fri_verify_desc *desc, const 
  * no lookup tables, zero_knowledge = false unless asked for (glp_circuit_create_ex), quotient_degree_factor a power of two <= 2^rate_bits,
  * D = 2, Poseidon hashing (PoseidonGoldilocksConfig, the `type C` of every reference driver but
  * one [REF src/hash/keccak256.rs:281]).  Gate types a circuit may contain: see GLP_GATE_* (0..18 and 20..22; any other
- * type is GLP_ERR_UNSUPPORTED: the lookup gates, Poseidon2Gate). */
+ * type is GLP_ERR_UNSUPPORTED: the lookup gates, Poseidon2Gate -- unless it comes as GLP_GATE_PROGRAM through glp_circuit_create_prog). */
 enum {
     GLP_GATE_NOOP = 0,             /* plonky2 gates/noop.rs */
     GLP_GATE_CONSTANT = 1,         /* gates/constant.rs, p0 = num_consts */
@@ -681,7 +681,11 @@ enum {
     /* the rest of the recursive verifier's gate set: exp_from_bits, the FRI fold step, Poseidon's linear layer on ext targets */
     GLP_GATE_EXPONENTIATION = 20,       /* gates/exponentiation.rs, p0 = num_power_bits (>= 1, p0 + 2 <= num_routed_wires) */
     GLP_GATE_COSET_INTERPOLATION = 21,  /* gates/coset_interpolation.rs, p0 = subgroup_bits (1..5), p1 = degree (2 <= p1 <= 2^p0) */
-    GLP_GATE_POSEIDON_MDS = 22          /* gates/poseidon_mds.rs, no parameters (48 wires, all routed) */
+    GLP_GATE_POSEIDON_MDS = 22,         /* gates/poseidon_mds.rs, no parameters (48 wires, all routed) */
+    /* a caller-defined gate: its constraints are program p0 of the list handed to glp_circuit_create_prog (GATE PROGRAMS IN A
+     * CIRCUIT, below), p1 = 0, num_constraints = the program's EMIT count.  glp_circuit_create / _ex have no program list and answer
+     * GLP_ERR_UNSUPPORTED for it, as for every type they do not know. */
+    GLP_GATE_PROGRAM = 23
 };
 
 typedef struct {
@@ -735,6 +739,42 @@ GLP_API int glp_circuit_create(glp_ctx *ctx, const glp_circuit_desc *desc, glp_c
  * format.  Salt rule and seed: glp_batch_from_values_salted, glp_ctx_set_salt_seed. */
 #define GLP_CIRCUIT_ZERO_KNOWLEDGE 1u
 GLP_API int glp_circuit_create_ex(glp_ctx *ctx, const glp_circuit_desc *desc, uint32_t flags, glp_circuit **out);
+/* GATE PROGRAMS IN A CIRCUIT.  A gate of type GLP_GATE_PROGRAM brings its unfiltered constraints as a gate program (the instruction
+ * word of GLP_GP_INSTR, "caller-defined gate constraints at the commitment seam" above); every path of the circuit handle honours it:
+ * glp_prove, glp_prove_device, glp_prove_staged, the session, glp_prove_batch, glp_verify / _n, glp_verify_batch and glp_witness_check.
+ * This is the fifth reading of that format, for one gate at one point (a point of the quotient's coset, zeta, or a row of H):
+ *     GLP_GP_COL       num_oracles = 2.  Oracle 0, polynomial c: constant polynomial c of the circuit, selectors first (c < num_constants;
+ *                      the sigmas are not readable).  Oracle 1, polynomial j: wire j (j < num_wires)
+ *     GLP_GP_PARAM     num_params <= 4: word j of the Poseidon hash of the public inputs
+ *     GLP_GP_IMM, GLP_GP_REG, ADD / SUB / MUL / MOV   as in every reading
+ *     GLP_GP_COL_NEXT, GLP_GP_X   refused: a plonky2 gate sees neither the next row nor the point
+ *     EMIT             constraint k of the gate, k = the number of EMITs before it; at most GLP_GATE_PROGRAM_MAX_CONSTRAINTS
+ *     END              exactly one, the last instruction, operand IMM of a pool word 1 (the shape glp_gate_program_rows asks for).  The
+ *                      selector filter is NOT part of the program: the library multiplies by its own, made from the gate's
+ *                      selector_index, group_start, group_end and row as for every built-in gate
+ * The degree of a program is found by walking the code: COL is 1; IMM, PARAM and a register never written 0; ADD, SUB and MOV the
+ * larger of their operands'; MUL the sum; the gate's degree is the largest over its EMIT operands.
+ *
+ * glp_gate_program_circuit_check (host only, no context) states these rules once: it refuses what glp_gate_program_check refuses and,
+ * naming the instruction and the field, num_oracles other than 2, num_params above 4, COL_NEXT, X, an END that is not the last
+ * instruction, an END operand other than IMM of a pool word 1, more than GLP_GATE_PROGRAM_MAX_CONSTRAINTS EMITs.  Outputs (each may be
+ * null): the EMIT count, the degree, and one more than the largest wire / constant polynomial index read (0: none is read).
+ *
+ * glp_circuit_create_prog is glp_circuit_create_ex with a program list (num_programs = 0: exactly glp_circuit_create_ex, type 23
+ * included).  Beyond the refusals of both it refuses, with GLP_ERR_ARG naming the gate index and the field and before anything is
+ * launched or *out is written: p0 >= num_programs; p1 != 0; num_constraints different from the program's EMIT count; a wire index
+ * >= num_wires or a constant index >= num_constants; degree + selector-filter degree > quotient_degree_factor + 1 (the rule the
+ * recursion gates are held to; the filter has one factor per other gate of the group and one more when the circuit has several
+ * selectors).  The programs are copied: the descriptions may be freed after the call.
+ * Witness generation has no built-in generator for a program gate: glp_witness_fill leaves its rows alone and glp_witness_num_units
+ * is 0, so glp_witness_plan_create_prog treats them as it treats NoopGate rows and the caller's unit programs write them.
+ * The circuit hand-off file (below) does not carry programs: a description with a gate of type 23 is written and read like any other,
+ * and its reader passes the programs to glp_circuit_create_prog from elsewhere. */
+#define GLP_GATE_PROGRAM_MAX_CONSTRAINTS 4096u   /* = GLP_GP_MAX_CONSTRAINTS: the kernel's accumulators are Acc160 (2^32 terms); built-in gates hold 512 */
+GLP_API int glp_gate_program_circuit_check(const glp_gate_program_desc *desc, uint32_t *num_constraints_out, uint32_t *degree_out,
+                                           uint32_t *wires_used_out, uint32_t *consts_used_out);
+GLP_API int glp_circuit_create_prog(glp_ctx *ctx, const glp_circuit_desc *desc, uint32_t flags, const glp_gate_program_desc *programs,
+                                    uint32_t num_programs, glp_circuit **out);
 /* 1 if the circuit was created with GLP_CIRCUIT_ZERO_KNOWLEDGE, else 0 */
 GLP_API int glp_circuit_zero_knowledge(const glp_circuit *circuit);
 GLP_API void glp_circuit_free(glp_circuit *circuit);

@@ -7,4 +7,5 @@ from .binding import (GlpError, Context, Batch, Circuit, Session, StagedWitness,
                       FriOpeningsMany, fri_prove_many, fri_verify, fri_verify_many, fri_verify_queries_many, fri_verify_sizes,
                       LDE_ROW_MAJOR, LDE_COL_MAJOR, perm_desc, perm_num_polys, GateProgram, gate_program_check, gate_program_desc,
                       ExtOpenings, plonk_ext_openings, RUN_SUM, RUN_PRODUCT, WitnessReport, WitnessPlan, GATE_TYPE_NAMES,
-                      witness_program_check, witness_program_desc, WGEN_PROGRAM)
+                      witness_program_check, witness_program_desc, WGEN_PROGRAM, gate_program_circuit_check, GATE_PROGRAM,
+                      GATE_PROGRAM_MAX_CONSTRAINTS)

@@ -121,6 +121,8 @@ FREE_UNIT_DTYPE = np.dtype([("kind", np.uint32), ("modulus", np.uint32), ("cell_
  GATE_U32_ARITHMETIC, GATE_U32_ADD_MANY, GATE_U32_SUBTRACTION, GATE_U32_RANGE_CHECK, GATE_COMPARISON, GATE_BASE_SUM, GATE_RANDOM_ACCESS,
  GATE_ARITHMETIC_EXTENSION, GATE_MUL_EXTENSION, GATE_REDUCING, GATE_REDUCING_EXTENSION) = range(19)
 GATE_EXPONENTIATION, GATE_COSET_INTERPOLATION, GATE_POSEIDON_MDS = 20, 21, 22
+GATE_PROGRAM = 23                              # a caller-defined gate: p0 = its program (Circuit(programs=...)); it has no name, reports give its number
+GATE_PROGRAM_MAX_CONSTRAINTS = 4096            # GLP_GATE_PROGRAM_MAX_CONSTRAINTS
 GATE_TYPE_NAMES = {
     GATE_NOOP: "NoopGate", GATE_CONSTANT: "ConstantGate", GATE_PUBLIC_INPUT: "PublicInputGate", GATE_ARITHMETIC: "ArithmeticGate",
     GATE_POSEIDON: "PoseidonGate", GATE_U32_INTERLEAVE: "U32InterleaveGate", GATE_UNINTERLEAVE_U32: "UninterleaveToU32Gate",
@@ -211,6 +213,8 @@ def load_library():
     sigs.update({
         "glp_circuit_create": [vp, C.POINTER(_CircuitDesc), C.POINTER(vp)],
         "glp_circuit_create_ex": [vp, C.POINTER(_CircuitDesc), u32, C.POINTER(vp)],
+        "glp_circuit_create_prog": [vp, C.POINTER(_CircuitDesc), u32, C.POINTER(_GateProgramDesc), u32, C.POINTER(vp)],
+        "glp_gate_program_circuit_check": [C.POINTER(_GateProgramDesc), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)],
         "glp_circuit_zero_knowledge": [vp],
         "glp_circuit_free": [vp],
         "glp_circuit_digest": [vp, vp],
@@ -858,6 +862,15 @@ def gate_program_check(prog, **fields):
     return int(out.value)
 
 
+def gate_program_circuit_check(prog, **fields):
+    """glp_gate_program_circuit_check (host only, no context): the rules a program is held to as a gate of a circuit (GATE_PROGRAM,
+    Circuit(programs=...)) -> (num_constraints, degree, wires_used, consts_used), or GlpError naming the instruction and the field"""
+    d, _keep = prog if isinstance(prog, tuple) else gate_program_desc(prog, **fields)
+    out = [C.c_uint32() for _ in range(4)]
+    _chk(load_library().glp_gate_program_circuit_check(C.byref(d), *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
 def witness_program_desc(prog, **fields):
     """attribute bag (code, pool, num_regs, num_inputs, num_outputs: a witness_program.WitnessProgram) -> (glp_witness_program_desc, the
     arrays that must stay alive while it is used).  fields: struct fields set afterwards, for descriptions the library is meant to refuse."""
@@ -1159,7 +1172,10 @@ class Circuit:
     """Device-resident circuit data: what `builder.build::<C>()` hands the prover
     [REF src/ecdsa/gadgets/ecdsa.rs:298].  `desc` is an attribute bag like synth.Circuit."""
 
-    def __init__(self, ctx, desc):
+    def __init__(self, ctx, desc, programs=None):
+        """programs: the gate programs that gates of type GATE_PROGRAM name in p0 (gate_program.Program objects, any bag
+        gate_program_desc takes, or (glp_gate_program_desc, keep-alive) pairs as it returns them); given (an empty list too), the
+        circuit is made by glp_circuit_create_prog."""
         L = load_library()
         self.ctx, self.desc = ctx, desc
         d, keep = _desc_to_c(desc)
@@ -1168,7 +1184,12 @@ class Circuit:
         self._num_pis = int(len(desc.public_inputs))
         self._h = C.c_void_p()
         self.zero_knowledge = bool(getattr(desc, "zero_knowledge", False))
-        if self.zero_knowledge:
+        if programs is not None:
+            pairs = [p if isinstance(p, tuple) else gate_program_desc(p) for p in programs]
+            arr = (_GateProgramDesc * max(len(pairs), 1))(*[p[0] for p in pairs])
+            _chk(L.glp_circuit_create_prog(ctx._h, C.byref(d), 1 if self.zero_knowledge else 0, arr if pairs else None, len(pairs), C.byref(self._h)))
+            del pairs
+        elif self.zero_knowledge:
             _chk(L.glp_circuit_create_ex(ctx._h, C.byref(d), 1, C.byref(self._h)))     # GLP_CIRCUIT_ZERO_KNOWLEDGE
         else:
             _chk(L.glp_circuit_create(ctx._h, C.byref(d), C.byref(self._h)))

@@ -28,6 +28,7 @@ static int build_quotient_plan(glp_ctx *c, glp_circuit *cc) {
     auto limb_weight = [&](u32 gi) -> u32 { return shape[gi].limb.limbs * shape[gi].limb.ops; };      // limb columns of the gate = its share of the per-point work
     for (u32 gi = 0; gi < d.num_gates; gi++) {
         const glp_gate &g = cc->gates[gi];
+        if (g.type == GLP_GATE_PROGRAM) { cc->program_gates.push_back(gi); continue; }      // k_quotient_gate_program, for every challenge count
         const bool limb_gate = shape[gi].launch == GATE_LAUNCH_LIMB, light = shape[gi].launch == GATE_LAUNCH_LIGHT;
         // alpha indices and wire columns must fit the descriptor fields (10 and 8 bits); glp_circuit_create has already
         // bounded num_constraints by ACC3_MAX_TERMS = 512
@@ -78,6 +79,9 @@ static int build_quotient_plan(glp_ctx *c, glp_circuit *cc) {
     return GLP_OK;
 }
 
+// the in-circuit rules of a gate program (circuit_program.inc)
+namespace { int circuit_program_check(const char *fn, const glp_gate_program_desc *d, CPInfo &info); }
+
 extern "C" {
 
 void glp_circuit_free(glp_circuit *cc) {
@@ -92,14 +96,22 @@ void glp_circuit_free(glp_circuit *cc) {
     c->release(cc->dev_limb_desc);
     c->release(cc->dev_consts);
     c->release(cc->dev_sigma_pos);
+    c->release(cc->dev_programs);
     delete cc;
 }
 
 int glp_circuit_create(glp_ctx *c, const glp_circuit_desc *desc, glp_circuit **out) { return glp_circuit_create_ex(c, desc, 0, out); }
 
 int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t flags, glp_circuit **out) {
+    return glp_circuit_create_prog(c, desc, flags, nullptr, 0, out);
+}
+
+// num_programs = 0 is glp_circuit_create_ex: no gate can name a program, and type 23 is a type this call does not know
+int glp_circuit_create_prog(glp_ctx *c, const glp_circuit_desc *desc, uint32_t flags, const glp_gate_program_desc *programs, uint32_t num_programs,
+                            glp_circuit **out) {
     GLP_REQUIRE(c && desc && out, "null argument");
     *out = nullptr;
+    GLP_REQUIRE(programs || num_programs == 0, "glp_circuit_create_prog: programs is null with num_programs = %u", num_programs);
     GLP_REQUIRE((flags & ~GLP_CIRCUIT_ZERO_KNOWLEDGE) == 0, "unknown circuit flags 0x%x", flags);
     GLP_TRY(bind(c));
     const glp_circuit_desc &d = *desc;
@@ -124,11 +136,30 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
     }
     // Shapes the quotient kernel assumes (gate_shapes.h), checked here so that a malformed description is an error and never an
     // out-of-bounds read on the device: wires / constants / constraints each gate type touches.
+    std::vector<CPInfo> pinfo(num_programs);
+    for (u32 i = 0; i < num_programs; i++) {
+        char who[64];
+        snprintf(who, sizeof(who), "glp_circuit_create_prog: programs[%u]", i);
+        GLP_TRY(circuit_program_check(who, programs + i, pinfo[i]));
+    }
     u32 maxc = 0;
     for (u32 i = 0; i < d.num_gates; i++) {
         const glp_gate &g = d.gates[i];
         GateShape s;
-        if (!gate_type_known(g.type) || !gate_shape(g, s))
+        if (g.type == GLP_GATE_PROGRAM && num_programs) {
+            // the shape of a program gate is what its program reads and emits; held to the degree rule of the recursion gates below
+            GLP_REQUIRE(g.p0 < num_programs, "gate %u (type %u), field p0: program %u, the circuit has num_programs = %u", i, g.type, g.p0, num_programs);
+            GLP_REQUIRE(g.p1 == 0, "gate %u (type %u), field p1: %u, must be 0", i, g.type, g.p1);
+            const CPInfo &pi = pinfo[g.p0];
+            s = GateShape();
+            s.wires = pi.wires; s.constraints = pi.emits; s.degree = pi.degree;
+            GLP_REQUIRE(s.constraints == g.num_constraints, "gate %u (type %u), field num_constraints: %u, program %u has %u EMITs", i, g.type,
+                        g.num_constraints, g.p0, s.constraints);
+            GLP_REQUIRE(s.wires <= d.num_wires, "gate %u (type %u), field p0: program %u reads wire %u, the circuit has num_wires = %u", i, g.type, g.p0,
+                        s.wires - 1, d.num_wires);
+            GLP_REQUIRE(pi.consts <= d.num_constants, "gate %u (type %u), field p0: program %u reads constant polynomial %u, the circuit has num_constants = %u",
+                        i, g.type, g.p0, pi.consts - 1, d.num_constants);
+        } else if (!gate_type_known(g.type) || !gate_shape(g, s))
             return set_error(gate_type_known(g.type) ? GLP_ERR_ARG : GLP_ERR_UNSUPPORTED,
                              "gate %u: type %u with parameters (%u, %u) is not supported", i, g.type, g.p0, g.p1);
         GLP_REQUIRE(s.wires <= d.num_wires, "gate %u (type %u) needs %u wires, circuit has %u", i, g.type, s.wires, d.num_wires);
@@ -136,7 +167,7 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
         GLP_REQUIRE(s.constraints == g.num_constraints, "gate %u (type %u): num_constraints %u, expected %u", i, g.type, g.num_constraints, s.constraints);
         GLP_REQUIRE(s.routed <= d.num_routed_wires, "gate %u (type %u): %u routed inputs, circuit has %u routed wires", i, g.type, s.routed,
                     d.num_routed_wires);
-        if (s.degree) {
+        if (s.degree || g.type == GLP_GATE_PROGRAM) {
             // The quotient is evaluated on quotient_degree_factor cosets, so filter x constraint may have degree quotient_degree_factor + 1
             // at most (what plonky2's selector grouping guarantees for every gate it places): the filter has one factor per other gate of
             // the group, and the UNUSED factor when there are several selectors.
@@ -145,8 +176,8 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
                         "quotient_degree_factor %u + 1", i, g.type, s.degree, g.group_start < g.group_end ? filt : 0, qdf);
         }
         GLP_REQUIRE(g.selector_index < d.num_selectors && g.group_start <= g.row && g.row < g.group_end, "bad selector data for gate %u", i);
-        GLP_REQUIRE(g.num_constraints <= ACC3_MAX_TERMS, "gate %u: %u constraints exceed the %u the quotient accumulators hold", i,
-                    g.num_constraints, ACC3_MAX_TERMS);
+        GLP_REQUIRE(g.type == GLP_GATE_PROGRAM || g.num_constraints <= ACC3_MAX_TERMS, "gate %u: %u constraints exceed the %u the quotient accumulators hold", i,
+                    g.num_constraints, ACC3_MAX_TERMS);      // a program gate: GLP_GATE_PROGRAM_MAX_CONSTRAINTS, held by circuit_program_check
         maxc = std::max(maxc, g.num_constraints);
     }
     GLP_REQUIRE(maxc <= d.num_gate_constraints, "num_gate_constraints smaller than a gate's constraint count");
@@ -187,6 +218,23 @@ int glp_circuit_create_ex(glp_ctx *c, const glp_circuit_desc *desc, uint32_t fla
     GLP_TRY(c->alloc((void **)&cc->dev_consts, (size_t)nc * n * 8));
     GLP_TRY(h2d(c, cc->dev_consts, d.constants, (size_t)nc * n * 8));
     GLP_TRY(build_quotient_plan(c, cc.get()));
+    if (!cc->program_gates.empty()) {              // the programs: host copies for the verifier, one device image for the kernels
+        std::vector<u64> img;
+        for (u32 i = 0; i < num_programs; i++) {
+            const glp_gate_program_desc &pd = programs[i];
+            glp_circuit::Program pr;
+            pr.code.assign(pd.code, pd.code + pd.num_instructions);
+            pr.pool.assign(pd.pool, pd.pool + pd.num_pool);
+            pr.nregs = pd.num_regs; pr.dev_at = img.size();
+            img.insert(img.end(), pr.code.begin(), pr.code.end());
+            img.resize((img.size() + 3) & ~(size_t)3, 0);
+            img.insert(img.end(), pr.pool.begin(), pr.pool.end());
+            img.resize((img.size() + 3) & ~(size_t)3, 0);
+            cc->programs.push_back(std::move(pr));
+        }
+        GLP_TRY(c->alloc((void **)&cc->dev_programs, img.size() * 8));
+        GLP_TRY(h2d(c, cc->dev_programs, img.data(), img.size() * 8));
+    }
     {
         Scratch sc(c);
         u64 *csv;

@@ -15,7 +15,7 @@
 // One translation unit, in this order: the kernels (pp_kernels.inc, quotient_kernels.inc, fri_kernels.inc), the host helpers, the
 // stage functions (prover_stages.inc), the single-proof session and prove_impl, the circuit handle (circuit_create.inc), the
 // byte format (proof_bytes.inc), the prove / session / staged-witness C ABI, openings and FRI of caller-held batches
-// (fri_openings.inc), the permutation argument and the gate programs of a caller-held circuit (perm_seam.inc, gate_program.inc), its identity check at zeta (zeta_check.inc), its own running arguments (trace_program.inc, running_columns.inc), the witness checker (witness_check.inc) and the batch drivers (prover_batch*.inc).
+// (fri_openings.inc), the permutation argument and the gate programs of a caller-held circuit (perm_seam.inc, gate_program.inc), its identity check at zeta (zeta_check.inc), its own running arguments (trace_program.inc, running_columns.inc), the witness checker (witness_check.inc), the program gates of a circuit (circuit_program.inc) and the batch drivers (prover_batch*.inc).
 #include <algorithm>
 #include <string.h>
 #include "batch.h"
@@ -632,4 +632,5 @@ int glp_prove_staged(glp_ctx *c, const glp_circuit *cc, glp_witness *w, const ui
 #include "trace_program.inc"
 #include "running_columns.inc"
 #include "witness_check.inc"
+#include "circuit_program.inc"
 #include "prover_batch_dev.inc"

@@ -133,6 +133,8 @@ void quotient_proof_args(const ProveGeo &g, const glp_batch *wb, const glp_batch
     qb.pp = dev_pp; qb.wl_stride = (size_t)(g.nw + wb->salt) * g.N; qb.zl_stride = (size_t)(g.nzp + zb->salt) * g.N;
     qb.out_stride = (size_t)g.nch * g.Rq * g.n;
 }
+// the gates of type GLP_GATE_PROGRAM, one k_quotient_gate_program launch each (circuit_program.inc)
+int quotient_program_launches(glp_ctx *c, const glp_circuit *cc, u32 nch, dim3 grid, const QArgs &a, const QProof &qp, const QBatch &qbt);
 // K6: the quotient's values on the Rq evaluated planes -> qp.out.  l0t: scratch [Rq][n].
 int stage_quotient_eval(glp_ctx *c, const ProveGeo &g, const QProof &qp, const QBatch &qbt, u64 *l0t) {
     const glp_circuit *cc = g.cc;
@@ -167,7 +169,7 @@ int stage_quotient_eval(glp_ctx *c, const ProveGeo &g, const QProof &qp, const Q
     default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_quotient<4, 1>), grid, dim3(256), 0, c->stream, a, qp, qbt, lg_); break;
     }
     GLP_HIP(hipGetLastError());
-    if (a.gate_mode != 1) return GLP_OK;
+    if (a.gate_mode != 1) return quotient_program_launches(c, cc, nch, grid, a, qp, qbt);      // the monolithic kernel skips type 23
     if (cc->limb_count) {
         LimbArgs la;
         limb_args(cc, la);
@@ -185,7 +187,7 @@ int stage_quotient_eval(glp_ctx *c, const ProveGeo &g, const QProof &qp, const Q
 #undef GLP_GATE_LAUNCH
         GLP_HIP(hipGetLastError());
     }
-    return GLP_OK;
+    return quotient_program_launches(c, cc, nch, grid, a, qp, qbt);
 }
 // values on the planes (qv) -> the quotient chunks' coefficients (qc, bit-reversed order); qV: scratch.  All [K][nch][Rq][n].
 int stage_quotient_coeffs(glp_ctx *c, const ProveGeo &g, u64 *qv, u64 *qV, u64 *qc) {

@@ -66,7 +66,18 @@ struct glp_circuit {
     glp_batch *cs = nullptr;       // constants_sigmas_commitment
     std::vector<u64> cs_cap;
     Layout L;
+    // GLP_GATE_PROGRAM (glp_circuit_create_prog; circuit_program.inc): the programs as the host interpreters read them (the verifier's is
+    // in verifier.hip) and, at dev_programs + dev_at, as k_quotient_gate_program / k_witness_check_program read them: the code,
+    // zero-padded to a multiple of 4 words, then the pool
+    struct Program { std::vector<u64> code, pool; u32 nregs = 0; size_t dev_at = 0; };
+    std::vector<Program> programs;
+    u64 *dev_programs = nullptr;
+    std::vector<u32> program_gates; // the gates of type GLP_GATE_PROGRAM: one k_quotient_gate_program launch each
 };
+
+// what the in-circuit rules of a gate program yield (circuit_program.inc): its EMIT count, its degree, and one more than the largest
+// wire / constant polynomial it reads
+struct CPInfo { u32 emits = 0, degree = 0, wires = 0, consts = 0; };
 
 // dev_sigma_pos on first use (witness_check.inc); shared by glp_witness_check and glp_witness_plan_create (witness.hip)
 int witness_sigma_decode(glp_ctx *c, const glp_circuit *cc, const char *fn);

@@ -382,6 +382,35 @@ struct VChal {
     std::vector<u64> x_index;
 };
 #define FAIL(...) return set_error(GLP_ERR_PROVE, __VA_ARGS__)
+// unfiltered constraints of a gate of type GLP_GATE_PROGRAM at one point: the program read over F_p^2 (the semantics of
+// glp_gate_program_eval_ext for one gate; include/glp.h, "GATE PROGRAMS IN A CIRCUIT").  lc = every constant polynomial, selectors first;
+// glp_circuit_create_prog has checked every index the walk uses.
+void program_constraints(const glp_circuit::Program &pr, const E *lc, const E *w, const u64 pih[4], u32 num_constraints, std::vector<E> &out) {
+    out.assign(num_constraints, ZERO);
+    std::vector<E> regs(pr.nregs, ZERO);
+    u32 k = 0;
+    auto operand = [&](u32 f) -> E {
+        const u32 kind = f & 7, pl = f >> 3;
+        switch (kind) {
+        case GLP_GP_REG: return regs[pl];
+        case GLP_GP_COL: {
+            const u32 col = pl & ((1u << GLP_GP_COL_ORACLE_SHIFT) - 1);
+            return pl >> GLP_GP_COL_ORACLE_SHIFT ? w[col] : lc[col];
+        }
+        case GLP_GP_IMM: return E(pr.pool[pl]);
+        default: return E(pih[pl]);     // GLP_GP_PARAM
+        }
+    };
+    for (const u64 ins : pr.code) {
+        const u32 op = (u32)ins & 15, dst = ((u32)ins >> GLP_GP_DST_SHIFT) & 31;
+        if (op == GLP_GP_OP_END) break;
+        const E a = operand((u32)(ins >> GLP_GP_A_SHIFT) & ((1u << GLP_GP_OPERAND_BITS) - 1));
+        if (op == GLP_GP_OP_EMIT) { out.at(k++) = a; continue; }
+        if (op == GLP_GP_OP_MOV) { regs[dst] = a; continue; }
+        const E b = operand((u32)(ins >> GLP_GP_B_SHIFT) & ((1u << GLP_GP_OPERAND_BITS) - 1));
+        regs[dst] = op == GLP_GP_OP_ADD ? a + b : op == GLP_GP_OP_SUB ? a - b : a * b;
+    }
+}
 // field elements (and Poseidon digests) must be canonical; a KeccakHash<25> digest is 25 bytes in a 4-word slot
 int verify_canonical(const glp_circuit *cc, const u64 *proof) {
     const glp_circuit_desc &d = cc->d;
@@ -459,7 +488,8 @@ int verify_vanishing(const glp_circuit *cc, const u64 *proof, const u64 *betas, 
             for (u32 i = g.group_start; i < g.group_end; i++)
                 if (i != g.row) filter = filter * (E((u64)i) - s);
             if (d.num_selectors > 1) filter = filter * (E((u64)0xFFFFFFFFull) - s);       // UNUSED_SELECTOR
-            gate_constraints(g, lc.data() + d.num_selectors, lw.data(), pih, tmp);
+            if (g.type == GLP_GATE_PROGRAM) program_constraints(cc->programs[g.p0], lc.data(), lw.data(), pih, g.num_constraints, tmp);
+            else gate_constraints(g, lc.data() + d.num_selectors, lw.data(), pih, tmp);
             for (u32 i = 0; i < g.num_constraints; i++) gate_terms[i] = gate_terms[i] + filter * tmp[i];
         }
         terms.insert(terms.end(), gate_terms.begin(), gate_terms.end());

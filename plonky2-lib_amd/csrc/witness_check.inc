@@ -193,6 +193,8 @@ int wc_launch_gate(glp_ctx *c, const WcArgs &w, u32 type, u32 gi, u32 K) {
     GLP_HIP(hipGetLastError());
     return GLP_OK;
 }
+// a gate of type GLP_GATE_PROGRAM: k_witness_check_program (circuit_program.inc)
+int wc_launch_program(glp_ctx *c, const glp_circuit *cc, const WcArgs &w, u32 gi, u32 K);
 }  // namespace
 
 // The permutation decoded into flat positions, made by the first caller that needs it (glp_witness_check, glp_witness_plan_create:
@@ -305,7 +307,10 @@ int glp_witness_check(glp_ctx *c, const glp_circuit *cc, uint32_t num_proofs, co
         StageScope st(c, "witness_check.gates", 8.0 * K * n * (nw + d.num_constants));
         for (u32 fetch = 0; fetch < 2; fetch++) {
             w.fetch = fetch;
-            for (u32 gi = 0; gi < ng; gi++) GLP_TRY(wc_launch_gate(c, w, cc->gates[gi].type, gi, K));
+            for (u32 gi = 0; gi < ng; gi++) {
+                if (cc->gates[gi].type == GLP_GATE_PROGRAM) GLP_TRY(wc_launch_program(c, cc, w, gi, K));
+                else GLP_TRY(wc_launch_gate(c, w, cc->gates[gi].type, gi, K));
+            }
         }
     }
     {

@@ -169,12 +169,49 @@ class Assembler:
                     barrier = len(out)
         return out
 
-    def assemble(self, hoist_emits=False):
-        """-> Program.  Linear scan: a virtual register lives from its first write to its last read (or last write); the registers
+    @staticmethod
+    def _sink(ins):
+        """Every instruction whose result is read exactly once, by an instruction other than EMIT or END, moved down to just before its reader (and what it alone reads with
+        it); results read several times stay where they are, in their order.  A body that builds a list of products and then sums
+        it (an MDS layer) keeps one product alive at a time instead of all of them.  Only for code in which no register is written
+        twice (what a TraceField produces); other code is returned as it is."""
+        uses, defs = {}, {}
+        for idx, i in enumerate(ins):
+            for o in (i.a, i.b):
+                if o is not None and o.kind == REG:
+                    uses[o.index] = uses.get(o.index, 0) + (1 if i.dst is not None else 2)      # an EMIT's or END's operand stays in place
+            if i.dst is not None:
+                if i.dst.index in defs:
+                    return list(ins)
+                defs[i.dst.index] = idx
+        out, placed = [], set()
+        for idx, i in enumerate(ins):
+            if i.dst is not None and uses.get(i.dst.index, 0) == 1:
+                continue                                       # placed with its one reader
+            stack = [idx]
+            while stack:
+                top = stack[-1]
+                if top in placed:
+                    stack.pop()
+                    continue
+                need = [defs[o.index] for o in (ins[top].a, ins[top].b)
+                        if o is not None and o.kind == REG and o.index in defs and defs[o.index] not in placed]
+                if need:
+                    stack.extend(reversed(need))               # operand a's instructions first
+                else:
+                    placed.add(top)
+                    out.append(ins[top])
+                    stack.pop()
+        return out
+
+    def assemble(self, hoist_emits=False, sink_single_use=False):
+        """-> Program.  sink_single_use: see _sink (applied first); hoist_emits: see _hoist.  Linear scan: a virtual register lives from its first write to its last read (or last write); the registers
         an instruction reads for the last time are released before its destination is placed, so a result may overwrite one of its
         own operands.  Raises AssemblerError if more than MAX_REGS are alive at once, if a register is read before it is written, or
         if the program breaks a rule glp_gate_program_check would refuse it for."""
-        ins = self._hoist(self._ins) if hoist_emits else list(self._ins)
+        ins = self._sink(self._ins) if sink_single_use else list(self._ins)
+        if hoist_emits:
+            ins = self._hoist(ins)
         if not ins or ins[-1].op != OP_END:
             raise AssemblerError("the last instruction must be END")
         if len(ins) > MAX_INSTRUCTIONS:
