@@ -25,6 +25,7 @@
 #include "poseidon.h"
 #include "prover_types.h"
 #include "fri_shape.h"      // POW_MAX_BITS and the FRI shape rules
+#include "witness_plan.h"   // witness_row_gate, the gate of a row: one text with k_witness_fill and the witness planner
 
 namespace {
 void make_layout(const glp_circuit_desc &c, Layout &L, bool zk) {

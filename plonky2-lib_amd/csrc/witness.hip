@@ -1,6 +1,8 @@
 // witness.hip -- witness generation on the GPU: the row-local half (glp_witness_fill) and, over the same
 // per-unit body, the dataflow half (glp_witness_plan_*, glp_witness_generate: second part of this file; caller-defined generators as
-// unit programs: witness_program.inc).
+// unit programs: witness_program.inc).  What is here: the generator bodies (witness_unit), the kernels, glp_witness_fill, the role
+// queries, the planner's driver (witness_plan_create), glp_witness_generate and glp_witness_read_cells.  The planner itself -- the unit
+// table, the records of a plan's lists, every check and index of a plan -- is host-only text in witness_plan.h.
 //
 // plonky2's `generate_partial_witness` (iop/generator.rs) runs every gate's `SimpleGenerator`s as their
 // dependencies become known.  Two kinds of work hide in it: the copy-constraint DATAFLOW between rows (irregular:
@@ -29,6 +31,7 @@
 #include "poseidon.h"
 #include "prover_types.h"
 #include "biguint_dev.h"
+#include "witness_plan.h"
 
 namespace {
 
@@ -45,22 +48,7 @@ __device__ __forceinline__ u64 winv(u64 a) {          // a != 0
     return r;
 }
 
-// How many independent generators (units) a row of a gate has; the table of include/glp.h ("witness generation, the dataflow half").
-GLF_HD u32 witness_gate_units(u32 type, u32 p0, u32 p1) {
-    switch (type) {
-    case GLP_GATE_ARITHMETIC: case GLP_GATE_U32_INTERLEAVE: case GLP_GATE_UNINTERLEAVE_U32: case GLP_GATE_UNINTERLEAVE_B32:
-    case GLP_GATE_U32_ARITHMETIC: case GLP_GATE_U32_SUBTRACTION: case GLP_GATE_U32_RANGE_CHECK:
-    case GLP_GATE_ARITHMETIC_EXTENSION: case GLP_GATE_MUL_EXTENSION: return p0;
-    case GLP_GATE_U32_ADD_MANY: return p1;
-    case GLP_GATE_RANDOM_ACCESS: return (p1 & 0xFFFF) + 1;
-    case GLP_GATE_NOOP: case GLP_GATE_PUBLIC_INPUT: return 0;
-    case GLP_GATE_CONSTANT: case GLP_GATE_POSEIDON: case GLP_GATE_COMPARISON: case GLP_GATE_BASE_SUM: case GLP_GATE_REDUCING:
-    case GLP_GATE_REDUCING_EXTENSION: case GLP_GATE_EXPONENTIATION: case GLP_GATE_COSET_INTERPOLATION: case GLP_GATE_POSEIDON_MDS: return 1;
-    default: return 0;
-    }
-}
-
-// One unit of one row: generator `unit` (< witness_gate_units) of gate g on the row W points at (wire j -> W[j * n], gate constant
+// One unit of one row: generator `unit` (< witness_gate_units, witness_plan.h) of gate g on the row W points at (wire j -> W[j * n], gate constant
 // i -> GC[i * n]).  k_witness_fill runs every unit of a row; the wave kernels below run the units a plan lists.  WHICH = 1 keeps only
 // the gates with one unit per op, WHICH = 2 only those with one unit per row (k_witness_fill loops over the first kind alone, so that
 // nothing of a PoseidonGate row is hoisted out of a loop it runs once); 0 keeps all.
@@ -334,17 +322,7 @@ __device__ __forceinline__ void witness_unit(const WArgs &a, const DevGate &g, u
 #undef RD
 }
 
-// the row's gate: the selector polynomial of its group holds the gate index, every other selector UNUSED
-__device__ __forceinline__ u32 witness_row_gate(const u64 *consts, u32 nsel, size_t n, size_t row) {
-    u32 gi = 0xFFFFFFFFu;
-    for (u32 s = 0; s < nsel; s++) {
-        const u64 v = consts[(size_t)s * n + row];
-        if (nsel == 1 || v != 0xFFFFFFFFull) gi = (u32)v;
-    }
-    return gi;
-}
-
-// One thread = one trace row: every unit of the row.  Rows of one gate type are contiguous in every circuit the builder emits, so a
+// One thread = one trace row (its gate: witness_row_gate, witness_plan.h): every unit of the row.  Rows of one gate type are contiguous in every circuit the builder emits, so a
 // wave rarely sees more than one `case`.
 __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
     const size_t n = (size_t)1 << a.lg;
@@ -377,62 +355,8 @@ extern "C" int glp_witness_fill(glp_ctx *c, const glp_circuit *cc, uint64_t *dev
     return GLP_OK;
 }
 
-namespace {
-constexpr u32 ALL_UNITS = 0xFFFFFFFFu;
-// Which wire columns unit `unit` of a row of gate g writes (1) and which it reads as inputs (2); 0 = untouched.  ALL_UNITS: the whole
-// row, what glp_witness_fill does -- the union of the units, by construction.
-void witness_unit_roles(const glp_gate &g, u32 nw, u32 unit, uint8_t *role_out) {
-    memset(role_out, 0, nw);
-    auto out = [&](u32 c0, u32 cnt) { for (u32 i = 0; i < cnt && c0 + i < nw; i++) role_out[c0 + i] = 1; };
-    auto in = [&](u32 c0, u32 cnt) { for (u32 i = 0; i < cnt && c0 + i < nw; i++) role_out[c0 + i] = 2; };
-    const u32 u0 = unit == ALL_UNITS ? 0 : unit, u1 = unit == ALL_UNITS ? witness_gate_units(g.type, g.p0, g.p1) : unit + 1;   // the ops of a per-op gate
-    switch (g.type) {
-    case GLP_GATE_CONSTANT: out(0, g.p0); break;
-    case GLP_GATE_ARITHMETIC: for (u32 i = u0; i < u1; i++) { in(4 * i, 3); out(4 * i + 3, 1); } break;
-    case GLP_GATE_POSEIDON: in(0, 12); out(12, 12); in(24, 1); out(25, 110); break;
-    case GLP_GATE_U32_INTERLEAVE: for (u32 i = u0; i < u1; i++) { in(2 * i, 1); out(2 * i + 1, 1); out(2 * g.p0 + 32 * i, 32); } break;
-    case GLP_GATE_UNINTERLEAVE_U32: case GLP_GATE_UNINTERLEAVE_B32:
-        for (u32 i = u0; i < u1; i++) { in(3 * i, 1); out(3 * i + 1, 2); out(3 * g.p0 + 64 * i, 64); } break;
-    case GLP_GATE_U32_ARITHMETIC: for (u32 i = u0; i < u1; i++) { in(6 * i, 3); out(6 * i + 3, 3); out(6 * g.p0 + 32 * i, 32); } break;
-    case GLP_GATE_U32_ADD_MANY: {
-        const u32 wd = g.p0 + 3;
-        for (u32 i = u0; i < u1; i++) { in(wd * i, g.p0 + 1); out(wd * i + g.p0 + 1, 2); out(wd * g.p1 + 18 * i, 18); }
-        break;
-    }
-    case GLP_GATE_U32_SUBTRACTION: for (u32 i = u0; i < u1; i++) { in(5 * i, 3); out(5 * i + 3, 2); out(5 * g.p0 + 16 * i, 16); } break;
-    case GLP_GATE_U32_RANGE_CHECK: for (u32 i = u0; i < u1; i++) { in(i, 1); out(g.p0 + 16 * i, 16); } break;
-    case GLP_GATE_COMPARISON: { const u32 cb = (g.p0 + g.p1 - 1) / g.p1; in(0, 2); out(2, 2 + 5 * g.p1 + cb + 1); break; }
-    case GLP_GATE_BASE_SUM: in(0, 1); out(1, g.p0); break;
-    case GLP_GATE_RANDOM_ACCESS: {
-        const u32 bits = g.p0, copies = g.p1 & 0xFFFF, nextra = g.p1 >> 16, vs = 1u << bits;
-        for (u32 cpy = u0; cpy < u1 && cpy < copies; cpy++) {
-            const u32 o = (2 + vs) * cpy;
-            in(o, 1); out(o + 1, 1); in(o + 2, vs);
-            out((2 + vs) * copies + nextra + bits * cpy, bits);
-        }
-        if (u1 == copies + 1) out((2 + vs) * copies, nextra);       // the last unit: the extra constants
-        break;
-    }
-    case GLP_GATE_ARITHMETIC_EXTENSION: for (u32 i = u0; i < u1; i++) { in(8 * i, 6); out(8 * i + 6, 2); } break;
-    case GLP_GATE_MUL_EXTENSION: for (u32 i = u0; i < u1; i++) { in(6 * i, 4); out(6 * i + 4, 2); } break;
-    case GLP_GATE_REDUCING: case GLP_GATE_REDUCING_EXTENSION: {
-        const u32 cw = g.type == GLP_GATE_REDUCING ? 1u : 2u;
-        out(0, 2); in(2, 4 + cw * g.p0); out(6 + cw * g.p0, 2 * (g.p0 - 1));
-        break;
-    }
-    case GLP_GATE_EXPONENTIATION: in(0, 1 + g.p0); out(g.p0 + 1, 1 + g.p0); break;
-    case GLP_GATE_COSET_INTERPOLATION: {
-        const u32 np = 1u << g.p0, ni = (np - 2) / (g.p1 - 1);
-        in(0, 3 + 2 * np); out(3 + 2 * np, 2 + 4 * ni + 2);      // shift, values, point | value, intermediates, shifted point
-        break;
-    }
-    case GLP_GATE_POSEIDON_MDS: in(0, 24); out(24, 24); break;
-    default: break;
-    }
-}
-}  // namespace
-
-// Which wire columns glp_witness_fill writes on rows of gate `gate_index` (1) and which it reads as inputs (2); 0 = untouched.
+// Which wire columns glp_witness_fill writes on rows of gate `gate_index` (1) and which it reads as inputs (2); 0 = untouched
+// (witness_unit_roles, witness_plan.h).
 extern "C" int glp_witness_columns(const glp_circuit *cc, uint32_t gate_index, uint8_t *role_out /* [num_wires] */) {
     GLP_REQUIRE(cc && role_out, "null argument");
     GLP_REQUIRE(gate_index < cc->d.num_gates, "gate index out of range");
@@ -461,12 +385,9 @@ extern "C" int glp_witness_unit_columns(const glp_circuit *cc, uint32_t gate_ind
 // ------------------------------------------------------------------------------------------ the dataflow half
 // include/glp.h, "witness generation, the dataflow half": the host plans once per circuit and input set which unit runs in which wave
 // and which cell is copied from which; the kernels below walk those lists.  Every index a kernel uses was built and range-checked by the
-// planner: no value read from a witness is an address (RandomAccessGate's index keeps its idx < vs guard in witness_unit).
+// planner: no value read from a witness is an address (RandomAccessGate's index keeps its idx < vs guard in witness_unit).  The planner
+// is host-only text in witness_plan.h (the records of the lists, the unit table and the six stages); witness_plan_create below drives it.
 namespace {
-struct WUnit { u32 row, gu; };          // gu = gate << 16 | unit
-struct WCopy { u32 src, dst; };         // flat positions col * n + row
-typedef glp_witness_free_unit WFree;    // a free unit as the caller gave it; cell_begin points into the plan's 32-bit copy of cells[]
-static_assert(sizeof(WFree) == 24, "glp_witness_free_unit: three u32 and six u16");
 struct WGen {
     WArgs a;                            // a.wires: proof 0
     const WUnit *units;                 // wave w: units[unit_off[w] .. unit_off[w + 1]), sorted by row; wave 0 holds none
@@ -478,7 +399,6 @@ struct WGen {
     const u32 *free_off, *free_cells;   // a unit's run: its input cells, then its output cells (NONE: not written)
     const u32 *moduli;                  // [num_moduli][8]
 };
-constexpr u32 NONE = 0xFFFFFFFFu;
 constexpr u32 WGEN_MAX_PROOFS = 4096;   // as glp_witness_check
 constexpr u32 WITNESS_NARROW_MAX_DEFAULT = 256;
 
@@ -588,22 +508,15 @@ __global__ __launch_bounds__(256) void k_witness_read_cells(const u64 *wires, co
 
 #include "witness_program.inc"
 
-struct glp_witness_plan {
+struct glp_witness_plan : WPlanKept {              // the figures, cell_waves and the wave offsets stay on the host (witness_plan.h)
     glp_ctx *ctx = nullptr;
     const glp_circuit *cc = nullptr;
     u32 num_inputs = 0, narrow_max = WITNESS_NARROW_MAX_DEFAULT;
-    struct glp_witness_plan_info info;
-    std::vector<u32> unit_off, copy_off;           // [num_waves + 2]
-    std::vector<int32_t> cell_waves;               // [num_wires][n]
     WUnit *dev_units = nullptr;
     WCopy *dev_copies = nullptr;
     u32 *dev_unit_off = nullptr, *dev_copy_off = nullptr, *dev_inputs = nullptr;
-    struct glp_witness_plan_free_info free_info;
-    std::vector<u32> free_off;                     // [num_waves + 2]; empty without free units
     WFree *dev_free_units = nullptr;
     u32 *dev_free_off = nullptr, *dev_free_cells = nullptr, *dev_moduli = nullptr;
-    std::vector<u32> prog_chunk_off;               // [num_waves + 2] into dev_prog_chunks; empty without program units
-    u32 prog_lds = 0;                              // bytes of LDS a chunk's workgroup asks for: the widest register file of the programs
     WProgChunk *dev_prog_chunks = nullptr;
     WFree *dev_prog_units = nullptr;               // by wave, sorted by program
     WProgEntry *dev_prog_tab = nullptr;
@@ -623,329 +536,50 @@ extern "C" void glp_witness_plan_free(glp_witness_plan *p) {
     delete p;
 }
 
-// The shape of a free unit's kind: which of len[0..5] are operands, which of them are single cells, which is a divisor.  0 = unknown kind.
-struct WFreeShape { u32 operands; u32 single; int divisor; };     // bit i of single: len[i] must be 1
-static WFreeShape witness_free_shape(u32 kind) {
-    switch (kind) {
-    case GLP_WGEN_EQUALITY: return {4, 0xF, -1};
-    case GLP_WGEN_NONNATIVE_ADD: case GLP_WGEN_NONNATIVE_SUB: return {4, 0x8, -1};
-    case GLP_WGEN_NONNATIVE_MULTI_ADD: return {4, 0x8, -1};
-    case GLP_WGEN_NONNATIVE_MUL: return {4, 0, -1};
-    case GLP_WGEN_NONNATIVE_INV: return {3, 0, -1};
-    case GLP_WGEN_BIGUINT_DIV_REM: return {4, 0, 1};
-    case GLP_WGEN_GLV_SECP256K1: return {5, 0x18, -1};
-    default: return {0, 0, -1};
-    }
-}
-
-// glp_witness_plan_create_prog without its allocation guard; glp_witness_plan_create_ex is its num_programs = 0 case (with_programs
-// false: kind GLP_WGEN_PROGRAM stays an unknown kind there), glp_witness_plan_create its num_units = 0 case
-static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
-                              const glp_witness_free_unit *funits, uint32_t nf, const uint64_t *fcells, size_t num_fcells, const uint32_t *moduli,
-                              uint32_t num_moduli, const glp_witness_program_desc *programs, uint32_t num_programs, bool with_programs,
-                              glp_witness_plan **out) {
+// The driver of the planner (witness_plan.h) behind the three entry points: the stages in their order, between them what needs the device
+// (the selectors for the gate of every row, the decoded permutation), at the end the upload; it holds the guard of the host tables' allocation.
+static int witness_plan_create(glp_ctx *c, const glp_circuit *cc, const WPlanRequest &rq, glp_witness_plan **out) try {
+    const char *fn = rq.fn;
     GLP_REQUIRE(c, "%s: ctx is null", fn);
     GLP_REQUIRE(cc, "%s: circuit is null", fn);
     GLP_REQUIRE(out, "%s: out is null", fn);
-    GLP_REQUIRE(input_cells || num_inputs == 0, "%s: input_cells is null, num_inputs = %u", fn, num_inputs);
-    GLP_REQUIRE(funits || nf == 0, "%s: units is null, num_units = %u", fn, nf);
-    GLP_REQUIRE(fcells || num_fcells == 0, "%s: cells is null, num_cells = %zu", fn, num_fcells);
-    GLP_REQUIRE(moduli || num_moduli == 0, "%s: moduli is null, num_moduli = %u", fn, num_moduli);
-    GLP_REQUIRE(programs || num_programs == 0, "%s: programs is null, num_programs = %u", fn, num_programs);
+    GLP_TRY(wplan_check_pointers(rq));
     GLP_REQUIRE(cc->ctx == c, "%s: circuit belongs to another ctx", fn);
-    for (u32 i = 0; i < num_programs; i++) {
+    for (u32 i = 0; i < rq.num_programs; i++) {
         char where[96];
         snprintf(where, sizeof(where), "%s: programs[%u]", fn, i);
-        GLP_TRY(witness_program_check(where, programs + i));
+        GLP_TRY(witness_program_check(where, rq.programs + i));
     }
     const glp_circuit_desc &d = cc->d;
-    const u32 lg = d.degree_bits, nw = d.num_wires, nr = d.num_routed_wires, ng = d.num_gates, nsel = d.num_selectors;
-    const size_t n = (size_t)1 << lg, cells = (size_t)nw * n;
-    // one short of the decoded sigma's 2^32: position 2^32 - 1 is the planner's "none"
-    GLP_REQUIRE(cells < ((size_t)1 << 32), "%s: num_wires * 2^degree_bits = %zu positions, a plan addresses fewer than 2^32 (the bound of the decoded sigma)", fn, cells);
-    GLP_REQUIRE(ng <= 0xFFFF, "%s: num_gates = %u, a plan names at most 65535 gates", fn, ng);
-    for (u32 i = 0; i < num_inputs; i++)
-        GLP_REQUIRE(input_cells[i] < cells, "%s: input_cells[%u] = %llu is out of range (num_wires * 2^degree_bits = %zu cells)", fn, i,
-                    (unsigned long long)input_cells[i], cells);
-    // which input names a cell (NONE: none); a cell listed twice is refused
-    std::vector<u32> input_at(cells, NONE);
-    for (u32 i = 0; i < num_inputs; i++) {
-        u32 &at = input_at[(size_t)input_cells[i]];
-        GLP_REQUIRE(at == NONE, "%s: input_cells[%u] = %llu is listed twice (also input_cells[%u])", fn, i, (unsigned long long)input_cells[i], at);
-        at = i;
-    }
-    // the moduli and the free units: shapes, runs and cells
-    GLP_REQUIRE(num_fcells < NONE, "%s: num_cells = %zu, a plan addresses fewer than 2^32 - 1", fn, num_fcells);
-    for (u32 i = 0; i < num_moduli; i++) {
-        const uint32_t *m = moduli + (size_t)i * 8;
-        GLP_REQUIRE(m[0] & 1, "%s: moduli[%u] is even", fn, i);
-        GLP_REQUIRE(big::used_limbs(m, 8) > 1 || m[0] >= 3, "%s: moduli[%u] = %u is below 3", fn, i, m[0]);
-    }
-    std::vector<u32> fcells32(num_fcells), f_ni(nf), f_no(nf);
-    for (size_t i = 0; i < num_fcells; i++) fcells32[i] = fcells[i] < cells ? (u32)fcells[i] : NONE;      // outputs may be GLP_WGEN_NO_CELL; checked per run below
-    for (u32 f = 0; f < nf; f++) {
-        const glp_witness_free_unit &u = funits[f];
-        if (with_programs && u.kind == GLP_WGEN_PROGRAM) {
-            GLP_REQUIRE(u.modulus < num_programs, "%s: units[%u].modulus = %u, a program unit names its program there and num_programs = %u", fn, f, u.modulus, num_programs);
-            const glp_witness_program_desc &pd = programs[u.modulus];
-            GLP_REQUIRE(u.len[0] == pd.num_inputs, "%s: units[%u].len[0] = %u, programs[%u] has num_inputs = %u", fn, f, u.len[0], u.modulus, pd.num_inputs);
-            GLP_REQUIRE(u.len[1] == pd.num_outputs, "%s: units[%u].len[1] = %u, programs[%u] has num_outputs = %u", fn, f, u.len[1], u.modulus, pd.num_outputs);
-            for (u32 i = 2; i < 6; i++) GLP_REQUIRE(u.len[i] == 0, "%s: units[%u].len[%u] = %u, a program unit has two operands: unused entries are 0", fn, f, i, u.len[i]);
-            f_ni[f] = u.len[0]; f_no[f] = u.len[1];
-        } else {
-            const WFreeShape sh = witness_free_shape(u.kind);
-            GLP_REQUIRE(sh.operands, "%s: units[%u].kind = %u is not a GLP_WGEN_* kind", fn, f, u.kind);
-            const bool has_modulus = u.kind >= GLP_WGEN_NONNATIVE_ADD && u.kind <= GLP_WGEN_NONNATIVE_INV;
-            if (has_modulus) GLP_REQUIRE(u.modulus < num_moduli, "%s: units[%u].modulus = %u, num_moduli = %u", fn, f, u.modulus, num_moduli);
-            else GLP_REQUIRE(u.modulus == 0, "%s: units[%u].modulus = %u, kind %u has no modulus: 0", fn, f, u.modulus, u.kind);
-            for (u32 i = 0; i < 6; i++) {
-                const u32 l = u.len[i];
-                if (i >= sh.operands) { GLP_REQUIRE(l == 0, "%s: units[%u].len[%u] = %u, kind %u has %u operands: unused entries are 0", fn, f, i, l, u.kind, sh.operands); continue; }
-                if (sh.single >> i & 1) { GLP_REQUIRE(l == 1, "%s: units[%u].len[%u] = %u, that operand of kind %u is 1 cell", fn, f, i, l, u.kind); continue; }
-                if (u.kind == GLP_WGEN_NONNATIVE_MULTI_ADD && i == 0) continue;                                   // the number of summands
-                if ((int)i == sh.divisor) GLP_REQUIRE(l <= 8, "%s: units[%u].len[%u] = %u, a divisor has at most 8 limbs", fn, f, i, l);
-                GLP_REQUIRE(l <= GLP_WGEN_MAX_LIMBS, "%s: units[%u].len[%u] = %u, an operand has at most GLP_WGEN_MAX_LIMBS = %u limbs", fn, f, i, l, GLP_WGEN_MAX_LIMBS);
-                if (u.kind == GLP_WGEN_GLV_SECP256K1) GLP_REQUIRE(l == (i ? 4u : 8u), "%s: units[%u].len[%u] = %u, GLV_SECP256K1 has k of 8 and k1, k2 of 4 limbs", fn, f, i, l);
-            }
-            f_ni[f] = big::num_in(u.kind, u.len); f_no[f] = big::num_out(u.kind, u.len);
-        }
-        GLP_REQUIRE((size_t)u.cell_begin + f_ni[f] + f_no[f] <= num_fcells, "%s: units[%u].cell_begin = %u: its run of %u cells leaves cells[] (num_cells = %zu)", fn, f,
-                    u.cell_begin, f_ni[f] + f_no[f], num_fcells);
-        for (u32 i = 0; i < f_ni[f] + f_no[f]; i++) {
-            const uint64_t cell = fcells[(size_t)u.cell_begin + i];
-            GLP_REQUIRE(cell < cells || (i >= f_ni[f] && cell == GLP_WGEN_NO_CELL), "%s: units[%u]: cells[%zu] = %llu is out of range (num_wires * 2^degree_bits = %zu cells)", fn, f,
-                        (size_t)u.cell_begin + i, (unsigned long long)cell, cells);
-        }
-    }
+    WPlanCircuit cv = {d.degree_bits, d.num_wires, d.num_routed_wires, d.num_gates, cc->gates.data(), nullptr, nullptr};
+    const size_t n = cv.n();
+    WPlanState s;
+    GLP_TRY(wplan_check_request(rq, cv, s));
+    GLP_TRY(wplan_check_free_units(rq, cv, s));
     GLP_TRY(bind(c));
-    // the gate of every row, as k_witness_fill reads it
-    std::vector<u32> row_gate(n, NONE);
+    std::vector<u32> row_gate(n);
     {
-        std::vector<u64> sel((size_t)nsel * n);
+        std::vector<u64> sel((size_t)d.num_selectors * n);
         GLP_TRY(d2h(c, sel.data(), cc->dev_consts, sel.size() * 8));
-        for (size_t r = 0; r < n; r++) {
-            u32 gi = NONE;
-            for (u32 s = 0; s < nsel; s++) { const u64 v = sel[(size_t)s * n + r]; if (nsel == 1 || v != 0xFFFFFFFFull) gi = (u32)v; }
-            row_gate[r] = gi < ng ? gi : NONE;
-        }
+        for (size_t r = 0; r < n; r++) { const u32 gi = witness_row_gate(sel.data(), d.num_selectors, n, r); row_gate[r] = gi < cv.ng ? gi : NONE; }
     }
-    // per gate and unit: the columns read and written
-    std::vector<std::vector<std::vector<u32>>> g_in(ng), g_out(ng);
-    {
-        std::vector<uint8_t> role(nw);
-        for (u32 gi = 0; gi < ng; gi++) {
-            const glp_gate &g = cc->gates[gi];
-            const u32 nu = witness_gate_units(g.type, g.p0, g.p1);
-            GLP_REQUIRE(nu <= 0xFFFF, "%s: gate %u has %u units per row, a plan names at most 65535", fn, gi, nu);
-            g_in[gi].resize(nu); g_out[gi].resize(nu);
-            for (u32 u = 0; u < nu; u++) {
-                witness_unit_roles(g, nw, u, role.data());
-                for (u32 col = 0; col < nw; col++) { if (role[col] == 2) g_in[gi][u].push_back(col); if (role[col] == 1) g_out[gi][u].push_back(col); }
-            }
-        }
-    }
-    // the units in (row, unit) order; unit k of the plan = unit k - row_first[row] of its row; the free units follow: unit nu_total + f
-    std::vector<size_t> row_first(n + 1, 0);
-    for (size_t r = 0; r < n; r++) row_first[r + 1] = row_first[r] + (row_gate[r] == NONE ? 0 : g_in[row_gate[r]].size());
-    const size_t nu_total = row_first[n], nk = nu_total + nf;
-    GLP_REQUIRE(nk < NONE, "%s: %zu units exceed the 2^32 - 1 a plan addresses", fn, nk);
-    std::vector<u32> unit_row(nu_total);
-    for (size_t r = 0; r < n; r++) for (size_t k = row_first[r]; k < row_first[r + 1]; k++) unit_row[k] = (u32)r;
-    auto for_in = [&](size_t k, auto &&visit) {            // the cells unit k reads / writes
-        if (k < nu_total) { const size_t r = unit_row[k]; for (u32 col : g_in[row_gate[r]][k - row_first[r]]) visit((size_t)col * n + r); return; }
-        const u32 f = (u32)(k - nu_total);
-        for (u32 i = 0; i < f_ni[f]; i++) visit((size_t)fcells32[(size_t)funits[f].cell_begin + i]);
-    };
-    auto for_out = [&](size_t k, auto &&visit) {
-        if (k < nu_total) { const size_t r = unit_row[k]; for (u32 col : g_out[row_gate[r]][k - row_first[r]]) visit((size_t)col * n + r); return; }
-        const u32 f = (u32)(k - nu_total);
-        for (u32 i = 0; i < f_no[f]; i++) { const u32 cell = fcells32[(size_t)funits[f].cell_begin + f_ni[f] + i]; if (cell != NONE) visit((size_t)cell); }
-    };
-    // the writer of every cell; a free unit may not write what another unit writes
-    std::vector<u32> writer(cells, NONE);
-    for (size_t k = 0; k < nu_total; k++) for_out(k, [&](size_t q) { writer[q] = (u32)k; });
-    for (u32 f = 0; f < nf; f++) {
-        int rc = GLP_OK;
-        for_out(nu_total + f, [&](size_t q) {
-            if (rc != GLP_OK) return;
-            const u32 wk = writer[q];
-            if (wk == NONE) { writer[q] = (u32)(nu_total + f); return; }
-            if (wk >= nu_total) rc = set_error(GLP_ERR_ARG, "%s: units[%u]: output cell %zu is also written by units[%u]", fn, f, q, (u32)(wk - nu_total));
-            else rc = set_error(GLP_ERR_ARG, "%s: units[%u]: output cell %zu (column %zu, row %zu) is also written by unit %u of gate %u of that row", fn, f, q, q / n, q % n,
-                                (u32)(wk - row_first[unit_row[wk]]), row_gate[unit_row[wk]]);
-        });
-        if (rc != GLP_OK) return rc;
-    }
+    cv.row_gate = row_gate.data();
+    GLP_TRY(wplan_units(rq, cv, s));
     GLP_TRY(witness_sigma_decode(c, cc, fn));
-
-    // the copy classes: the cycles of the decoded permutation, named by their smallest position; a non-routed cell is its own class
-    std::vector<u32> cls(cells);
     {
-        std::vector<u32> pos((size_t)nr * n);
+        std::vector<u32> pos((size_t)cv.nr * n);
         GLP_TRY(d2h(c, pos.data(), cc->dev_sigma_pos, pos.size() * sizeof(u32)));
-        for (size_t p = 0; p < cells; p++) cls[p] = NONE;
-        for (size_t p = 0; p < pos.size(); p++) {                 // ascending: the first cell of a cycle met is its smallest
-            if (cls[p] != NONE) continue;
-            for (size_t q = p; cls[q] == NONE; q = pos[q]) {
-                cls[q] = (u32)p;
-                GLP_REQUIRE(pos[q] < pos.size(), "%s: the decoded permutation leaves the routed columns", fn);
-            }
-        }
-        for (size_t p = pos.size(); p < cells; p++) cls[p] = (u32)p;
+        cv.pos = pos.data();
+        GLP_TRY(wplan_classes(rq, cv, s));
+        cv.pos = nullptr;
     }
-    // class_wave by class name: 0 for a class with an input, -1 = not (yet) known; two inputs in one class are refused
-    std::vector<int32_t> class_wave(cells, -1);
-    {
-        std::vector<u32> class_input(num_inputs ? cells : 0, NONE);
-        for (u32 i = 0; i < num_inputs; i++) {
-            u32 &first = class_input[cls[(size_t)input_cells[i]]];
-            GLP_REQUIRE(first == NONE, "%s: input_cells[%u] = %llu and input_cells[%u] = %llu lie in one copy class: one value per class", fn, first,
-                        (unsigned long long)input_cells[first], i, (unsigned long long)input_cells[i]);
-            first = i;
-            class_wave[cls[(size_t)input_cells[i]]] = 0;
-        }
-    }
-    // per class the units that wait for it (one entry per cell read in a class not known from the inputs)
-    std::vector<u32> pending(nk, 0);
-    std::vector<size_t> reader_off(cells + 1, 0);
-    for (size_t k = 0; k < nk; k++)
-        for_in(k, [&](size_t q) { const u32 cl = cls[q]; if (class_wave[cl] < 0) { reader_off[cl + 1]++; pending[k]++; } });
-    for (size_t p = 0; p < cells; p++) reader_off[p + 1] += reader_off[p];
-    std::vector<u32> readers(reader_off[cells]);
-    {
-        std::vector<size_t> fill(reader_off.begin(), reader_off.end() - 1);
-        for (size_t k = 0; k < nk; k++)
-            for_in(k, [&](size_t q) { const u32 cl = cls[q]; if (class_wave[cl] < 0) readers[fill[cl]++] = (u32)k; });
-    }
-    // the waves: a unit is ready once every class it reads is known; its wave is one more than the wave that made the last one known
-    std::vector<int32_t> unit_wave(nk, -1);
-    std::vector<u32> ready, next;
-    for (size_t k = 0; k < nk; k++) if (pending[k] == 0) ready.push_back((u32)k);
-    u32 num_waves = 0;
-    uint64_t widest = 0, widest_free = 0;
-    while (!ready.empty()) {
-        num_waves++;
-        uint64_t wave_free = 0;
-        for (u32 k : ready) wave_free += k >= nu_total;
-        widest = std::max<uint64_t>(widest, ready.size() - wave_free);
-        widest_free = std::max<uint64_t>(widest_free, wave_free);
-        next.clear();
-        for (u32 k : ready) unit_wave[k] = (int32_t)num_waves;
-        for (u32 k : ready)
-            for_out(k, [&](size_t q) {
-                const u32 cl = cls[q];
-                if (class_wave[cl] >= 0) return;
-                class_wave[cl] = (int32_t)num_waves;
-                for (size_t i = reader_off[cl]; i < reader_off[cl + 1]; i++) if (--pending[readers[i]] == 0) next.push_back(readers[i]);
-            });
-        ready.swap(next);
-    }
+    GLP_TRY(wplan_waves(rq, cv, s));
+    GLP_TRY(wplan_lists(rq, cv, s));
+    const WPlanLists &L = s.lists;
     std::unique_ptr<glp_witness_plan> p(new glp_witness_plan);
-    p->ctx = c; p->cc = cc; p->num_inputs = num_inputs;
+    p->ctx = c; p->cc = cc; p->num_inputs = rq.num_inputs;
     if (const char *e = getenv("GLP_WITNESS_NARROW_MAX")) p->narrow_max = (u32)std::min<unsigned long long>(strtoull(e, nullptr, 10), 0xFFFFFFFFull);
-    struct glp_witness_plan_info &info = p->info;
-    memset(&info, 0, sizeof(info));
-    info.num_waves = num_waves; info.num_units = nu_total; info.widest_wave_units = widest;
-    struct glp_witness_plan_free_info &finfo = p->free_info;
-    memset(&finfo, 0, sizeof(finfo));
-    finfo.num_free_units = nf; finfo.widest_wave_free_units = widest_free;
-    // the lists: units by wave in (row, unit) order, the source of every known class, the copies by wave in order of the destination
-    p->unit_off.assign(num_waves + 2, 0);
-    p->copy_off.assign(num_waves + 2, 0);
-    for (size_t k = 0; k < nu_total; k++) {
-        if (unit_wave[k] > 0) { p->unit_off[unit_wave[k] + 1]++; continue; }
-        if (!info.num_stuck_units++) { info.stuck_row = unit_row[k]; info.stuck_gate = row_gate[unit_row[k]]; info.stuck_unit = (u32)(k - row_first[unit_row[k]]); }
-    }
-    for (u32 w = 0; w <= num_waves; w++) p->unit_off[w + 1] += p->unit_off[w];
-    std::vector<WUnit> units(p->unit_off[num_waves + 1]);
-    {
-        std::vector<u32> fill(p->unit_off.begin(), p->unit_off.end() - 1);
-        for (size_t k = 0; k < nu_total; k++)
-            if (unit_wave[k] > 0) units[fill[unit_wave[k]]++] = WUnit{unit_row[k], row_gate[unit_row[k]] << 16 | (u32)(k - row_first[unit_row[k]])};
-    }
-    // the free units by wave, in the caller's order; program units are listed apart, below
-    auto is_prog = [&](u32 f) { return with_programs && funits[f].kind == GLP_WGEN_PROGRAM; };
-    u32 nf_prog = 0;
-    for (u32 f = 0; f < nf; f++) nf_prog += is_prog(f);
-    std::vector<WFree> free_list;
-    if (nf) {
-        if (nf > nf_prog) p->free_off.assign(num_waves + 2, 0);
-        for (u32 f = 0; f < nf; f++) {
-            const int32_t uw = unit_wave[nu_total + f];
-            if (uw > 0) { if (!is_prog(f)) p->free_off[uw + 1]++; continue; }
-            if (!finfo.num_stuck_free_units++) finfo.first_stuck_free_unit = f;
-        }
-    }
-    if (nf > nf_prog) {
-        for (u32 w = 0; w <= num_waves; w++) p->free_off[w + 1] += p->free_off[w];
-        free_list.resize(p->free_off[num_waves + 1]);
-        std::vector<u32> fill(p->free_off.begin(), p->free_off.end() - 1);
-        for (u32 f = 0; f < nf; f++) if (!is_prog(f) && unit_wave[nu_total + f] > 0) free_list[fill[unit_wave[nu_total + f]]++] = funits[f];
-    }
-    // the program units by wave, sorted by program (then in the caller's order), cut into chunks of at most 64 units of one program; the
-    // image: per program its code, zero-padded to a multiple of 4 words (opcode 0 does nothing), then its pool
-    std::vector<WFree> prog_units;
-    std::vector<WProgChunk> prog_chunks;
-    std::vector<WProgEntry> prog_tab;
-    std::vector<u64> prog_image;
-    if (nf_prog) {
-        std::vector<u32> order;
-        for (u32 f = 0; f < nf; f++) if (is_prog(f) && unit_wave[nu_total + f] > 0) order.push_back(f);
-        std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) {
-            const int32_t wx = unit_wave[nu_total + x], wy = unit_wave[nu_total + y];
-            return wx != wy ? wx < wy : funits[x].modulus < funits[y].modulus;
-        });
-        p->prog_chunk_off.assign(num_waves + 2, 0);
-        for (size_t i = 0; i < order.size();) {
-            const u32 f = order[i], w = (u32)unit_wave[nu_total + f], pr = funits[f].modulus;
-            size_t j = i;
-            while (j < order.size() && j - i < 64 && (u32)unit_wave[nu_total + order[j]] == w && funits[order[j]].modulus == pr) j++;
-            prog_chunks.push_back(WProgChunk{pr, (u32)i, (u32)(j - i)});
-            p->prog_chunk_off[w + 1]++;
-            i = j;
-        }
-        for (u32 w = 0; w <= num_waves; w++) p->prog_chunk_off[w + 1] += p->prog_chunk_off[w];
-        for (u32 f : order) prog_units.push_back(funits[f]);
-        for (u32 i = 0; i < num_programs; i++) {
-            const glp_witness_program_desc &pd = programs[i];
-            const u32 words = (pd.num_instructions + 3) & ~3u;
-            WProgEntry e;
-            e.code_off = (u32)prog_image.size(); e.code_words = words; e.pool_off = e.code_off + words; e.num_inputs = pd.num_inputs;
-            GLP_REQUIRE(prog_image.size() + words + pd.num_pool < NONE, "%s: the programs exceed the 2^32 - 1 words a plan addresses", fn);
-            prog_image.insert(prog_image.end(), pd.code, pd.code + pd.num_instructions);
-            prog_image.resize((size_t)e.code_off + words, 0);
-            if (pd.num_pool) prog_image.insert(prog_image.end(), pd.pool, pd.pool + pd.num_pool);
-            prog_tab.push_back(e);
-            p->prog_lds = std::max<u32>(p->prog_lds, pd.num_regs * 64 * 8);
-        }
-    }
-    std::vector<u32> source(cells, NONE);        // by class name
-    p->cell_waves.assign(cells, -1);
-    for (size_t q = 0; q < cells; q++) {
-        const u32 cl = cls[q];
-        const int32_t cw = class_wave[cl];
-        if (cw < 0) continue;
-        const bool written = writer[q] != NONE && unit_wave[writer[q]] > 0;
-        p->cell_waves[q] = written ? unit_wave[writer[q]] : cw;
-        info.num_cells_known++;
-        if (source[cl] == NONE && (cw == 0 ? input_at[q] != NONE : (written && unit_wave[writer[q]] == cw))) source[cl] = (u32)q;
-    }
-    for (size_t q = 0; q < cells; q++) if (class_wave[cls[q]] >= 0 && source[cls[q]] != q) p->copy_off[class_wave[cls[q]] + 1]++;
-    for (u32 w = 0; w <= num_waves; w++) {
-        GLP_REQUIRE((size_t)p->copy_off[w] + p->copy_off[w + 1] < NONE, "%s: the copies exceed the 2^32 - 1 a plan addresses", fn);
-        p->copy_off[w + 1] += p->copy_off[w];
-    }
-    info.num_copies = p->copy_off[num_waves + 1];
-    std::vector<WCopy> copies(info.num_copies);
-    {
-        std::vector<u32> fill(p->copy_off.begin(), p->copy_off.end() - 1);
-        for (size_t q = 0; q < cells; q++) {
-            const u32 cl = cls[q];
-            if (class_wave[cl] >= 0 && source[cl] != q) copies[fill[class_wave[cl]]++] = WCopy{source[cl], (u32)q};
-        }
-    }
-    std::vector<u32> in32(num_inputs);
-    for (u32 i = 0; i < num_inputs; i++) in32[i] = (u32)input_cells[i];
+    static_cast<WPlanKept &>(*p) = std::move(static_cast<WPlanKept &>(s.lists));
     int rc = GLP_OK;
     auto up = [&](auto **dev, const auto &v) {
         if (rc != GLP_OK) return;
@@ -953,47 +587,35 @@ static int witness_plan_build(const char *fn, glp_ctx *c, const glp_circuit *cc,
         rc = c->alloc((void **)dev, bytes);
         if (rc == GLP_OK && !v.empty()) rc = h2d(c, *dev, v.data(), v.size() * sizeof(v[0]));
     };
-    up(&p->dev_units, units); up(&p->dev_copies, copies); up(&p->dev_unit_off, p->unit_off); up(&p->dev_copy_off, p->copy_off); up(&p->dev_inputs, in32);
-    if (nf) {
-        const std::vector<u32> mod32(moduli, moduli + (size_t)num_moduli * 8);
-        up(&p->dev_free_units, free_list); up(&p->dev_free_off, p->free_off); up(&p->dev_free_cells, fcells32); up(&p->dev_moduli, mod32);
+    up(&p->dev_units, L.units); up(&p->dev_copies, L.copies); up(&p->dev_unit_off, p->unit_off); up(&p->dev_copy_off, p->copy_off); up(&p->dev_inputs, L.inputs);
+    if (rq.num_units) {
+        const std::vector<u32> mod32(rq.moduli, rq.moduli + (size_t)rq.num_moduli * 8);
+        up(&p->dev_free_units, L.free_units); up(&p->dev_free_off, p->free_off); up(&p->dev_free_cells, L.free_cells); up(&p->dev_moduli, mod32);
     }
-    if (nf_prog) { up(&p->dev_prog_chunks, prog_chunks); up(&p->dev_prog_units, prog_units); up(&p->dev_prog_tab, prog_tab); up(&p->dev_prog_image, prog_image); }
+    if (!p->prog_chunk_off.empty()) { up(&p->dev_prog_chunks, L.prog_chunks); up(&p->dev_prog_units, L.prog_units); up(&p->dev_prog_tab, L.prog_tab); up(&p->dev_prog_image, L.prog_image); }
     if (rc != GLP_OK) { glp_witness_plan_free(p.release()); return rc; }
     *out = p.release();
     return GLP_OK;
+} catch (const std::bad_alloc &) {       // the planner's host tables: about 40 bytes per cell
+    return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", rq.fn);
 }
 
 extern "C" int glp_witness_plan_create_ex(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
                                           const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
                                           const uint32_t *moduli, uint32_t num_moduli, glp_witness_plan **out) {
-    static const char *fn = "glp_witness_plan_create_ex";
-    try {
-        return witness_plan_build(fn, c, cc, input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, nullptr, 0, false, out);
-    } catch (const std::bad_alloc &) {       // the planner's host tables: about 40 bytes per cell
-        return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
-    }
+    // without programs kind GLP_WGEN_PROGRAM stays an unknown kind
+    return witness_plan_create(c, cc, {"glp_witness_plan_create_ex", input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, nullptr, 0, false}, out);
 }
 
 extern "C" int glp_witness_plan_create_prog(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
                                             const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
                                             const uint32_t *moduli, uint32_t num_moduli, const glp_witness_program_desc *programs,
                                             uint32_t num_programs, glp_witness_plan **out) {
-    static const char *fn = "glp_witness_plan_create_prog";
-    try {
-        return witness_plan_build(fn, c, cc, input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, programs, num_programs, true, out);
-    } catch (const std::bad_alloc &) {
-        return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
-    }
+    return witness_plan_create(c, cc, {"glp_witness_plan_create_prog", input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, programs, num_programs, true}, out);
 }
 
 extern "C" int glp_witness_plan_create(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs, glp_witness_plan **out) {
-    static const char *fn = "glp_witness_plan_create";
-    try {
-        return witness_plan_build(fn, c, cc, input_cells, num_inputs, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, false, out);
-    } catch (const std::bad_alloc &) {
-        return set_error(GLP_ERR_UNSUPPORTED, "%s: out of host memory for the planner's tables (about 40 bytes per cell of num_wires * 2^degree_bits)", fn);
-    }
+    return witness_plan_create(c, cc, {"glp_witness_plan_create", input_cells, num_inputs, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, false}, out);
 }
 
 extern "C" int glp_witness_plan_free_info(const glp_witness_plan *p, struct glp_witness_plan_free_info *out) {

@@ -36,15 +36,8 @@ struct WcSink {
         if (k == want) val = v;
     }
 };
-// the gate of a row, as k_witness_fill reads it: the selector polynomial of its group holds the gate index, every other selector UNUSED
-__device__ __forceinline__ u32 wc_row_gate(const WcArgs &w, size_t n, size_t row) {
-    u32 gi = 0xFFFFFFFFu;
-    for (u32 s = 0; s < w.nsel; s++) {
-        const u64 v = w.consts[(size_t)s * n + row];
-        if (w.nsel == 1 || v != 0xFFFFFFFFull) gi = (u32)v;
-    }
-    return gi;
-}
+// the gate of a row, as k_witness_fill and the planner read it (witness_plan.h)
+__device__ __forceinline__ u32 wc_row_gate(const WcArgs &w, size_t n, size_t row) { return witness_row_gate(w.consts, w.nsel, n, row); }
 // sums of cnt and rows and the minimum of key over the workgroup (blockDim.x = 256 = four waves); valid in thread 0
 __device__ __forceinline__ void wc_block_reduce(u64 &cnt, u32 &rows, unsigned long long &key) {
     __shared__ u64 sh_cnt[4];

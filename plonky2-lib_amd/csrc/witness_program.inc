@@ -1,6 +1,7 @@
 // witness_program.inc -- caller-defined generators as unit programs (include/glp.h, "witness generation, the dataflow half", UNIT
 // PROGRAMS): the host check of a program and the kernel that runs a wave's program units.  Included by witness.hip between the wave
-// kernels and the planner; the planner files program units as free units of kind GLP_WGEN_PROGRAM.
+// kernels and the planner's driver; the planner (witness_plan.h, which also holds the chunk and program-table records WProgChunk and
+// WProgEntry) files program units as free units of kind GLP_WGEN_PROGRAM.
 //
 // k_witness_programs is the fourth walker of the gate-program instruction word (after k_gate_program, k_gate_program_ext and
 // k_gate_program_rows) and follows the first: one 64-lane workgroup runs one chunk -- up to 64 units of ONE program, blockIdx.y = proof
@@ -11,8 +12,6 @@
 // Every index was range-checked on the host: registers, pool words and input numbers by witness_program_check, cells by the planner,
 // the number of EMITs against the unit's output cells by both.  A value read from a witness is an operand, never an address or a count.
 namespace {
-struct WProgChunk { u32 prog, first, count; };      // units[first .. first + count) of the plan's program-unit list, count <= 64
-struct WProgEntry { u32 code_off, code_words, pool_off, num_inputs; };      // offsets into the image; code zero-padded to a multiple of 4 words
 struct WProgArgs {
     u64 *wires;                  // proof 0
     const u64 *image;            // every program's code, then its pool
