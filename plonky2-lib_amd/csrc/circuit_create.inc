@@ -1,5 +1,6 @@
-// circuit_create.inc -- the circuit handle: validation of a description against gate_shapes.h, the quotient launch plan, the uploads
-// and the constants/sigmas commitment.  Included by prover.hip after the session.
+// circuit_create.inc -- the circuit handle: the quotient launch plan, the uploads and the constants/sigmas commitment around the host
+// half of circuit_common.h (the rules a description is held to, the verifier's view, the digest), and the entry points that only read
+// the view.  Included by prover.hip after the session.
 
 // Quotient launch plan: the base-4 limb gates (at most LIMB_SLOTS of them) share k_quotient_limbs, the HBM-bound light
 // gates share k_quotient_light, every other gate type keeps its own launch.  Builds the column program of
@@ -79,8 +80,7 @@ static int build_quotient_plan(glp_ctx *c, glp_circuit *cc) {
     return GLP_OK;
 }
 
-// the in-circuit rules of a gate program (circuit_program.inc)
-namespace { int circuit_program_check(const char *fn, const glp_gate_program_desc *d, CPInfo &info); }
+static_assert(CIRCUIT_MAX_DEGREE_BITS == NTT_MAX_LG, "circuit_desc_check refuses what the transforms do not take");
 
 extern "C" {
 
@@ -115,92 +115,13 @@ int glp_circuit_create_prog(glp_ctx *c, const glp_circuit_desc *desc, uint32_t f
     GLP_REQUIRE((flags & ~GLP_CIRCUIT_ZERO_KNOWLEDGE) == 0, "unknown circuit flags 0x%x", flags);
     GLP_TRY(bind(c));
     const glp_circuit_desc &d = *desc;
-    GLP_REQUIRE(d.gates && d.k_is && d.constants && d.sigmas, "null array in circuit description");
-    GLP_REQUIRE(d.num_challenges >= 1 && d.num_challenges <= (u32)MAXCH, "num_challenges=%u outside 1..%d", d.num_challenges, MAXCH);
-    if (d.hasher != GLP_HASH_POSEIDON && d.hasher != GLP_HASH_KECCAK25) return set_error(GLP_ERR_UNSUPPORTED, "hasher %u is not one of GLP_HASH_*", d.hasher);
-    GLP_REQUIRE(d.rate_bits >= 1 && d.rate_bits <= 4, "rate_bits=%u outside 1..4", d.rate_bits);
-    GLP_REQUIRE(d.num_routed_wires <= d.num_wires && d.num_routed_wires > 0, "bad wire counts");
-    if ((int)d.degree_bits > NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "degree_bits=%u > %d", d.degree_bits, NTT_MAX_LG);
-    const u32 qdf = d.quotient_degree_factor;
-    if (qdf == 0 || (qdf & (qdf - 1)) || qdf > (1u << d.rate_bits))
-        return set_error(GLP_ERR_UNSUPPORTED, "quotient_degree_factor=%u must be a power of two <= 2^rate_bits", qdf);
-    GLP_REQUIRE(d.num_partial_products == (d.num_routed_wires + qdf - 1) / qdf - 1, "num_partial_products inconsistent");
-    GLP_REQUIRE(d.num_reductions <= 16 && d.cap_height <= d.degree_bits + d.rate_bits, "bad FRI parameters");
-    GLP_REQUIRE(d.proof_of_work_bits <= POW_MAX_BITS, "proof_of_work_bits=%u: this build searches at most 2^40 candidates and accepts up to %u bits",
-                d.proof_of_work_bits, POW_MAX_BITS);
-    u32 sum_ab = 0;
-    for (u32 i = 0; i < d.num_reductions; i++) {
-        GLP_REQUIRE(d.reduction_arity_bits[i] >= 1 && d.reduction_arity_bits[i] <= 5, "arity_bits outside 1..5");
-        sum_ab += d.reduction_arity_bits[i];
-        GLP_REQUIRE(sum_ab <= d.degree_bits && d.degree_bits + d.rate_bits - sum_ab >= d.cap_height, "FRI reduction deeper than the domain");
-    }
-    // Shapes the quotient kernel assumes (gate_shapes.h), checked here so that a malformed description is an error and never an
-    // out-of-bounds read on the device: wires / constants / constraints each gate type touches.
-    std::vector<CPInfo> pinfo(num_programs);
-    for (u32 i = 0; i < num_programs; i++) {
-        char who[64];
-        snprintf(who, sizeof(who), "glp_circuit_create_prog: programs[%u]", i);
-        GLP_TRY(circuit_program_check(who, programs + i, pinfo[i]));
-    }
-    u32 maxc = 0;
-    for (u32 i = 0; i < d.num_gates; i++) {
-        const glp_gate &g = d.gates[i];
-        GateShape s;
-        if (g.type == GLP_GATE_PROGRAM && num_programs) {
-            // the shape of a program gate is what its program reads and emits; held to the degree rule of the recursion gates below
-            GLP_REQUIRE(g.p0 < num_programs, "gate %u (type %u), field p0: program %u, the circuit has num_programs = %u", i, g.type, g.p0, num_programs);
-            GLP_REQUIRE(g.p1 == 0, "gate %u (type %u), field p1: %u, must be 0", i, g.type, g.p1);
-            const CPInfo &pi = pinfo[g.p0];
-            s = GateShape();
-            s.wires = pi.wires; s.constraints = pi.emits; s.degree = pi.degree;
-            GLP_REQUIRE(s.constraints == g.num_constraints, "gate %u (type %u), field num_constraints: %u, program %u has %u EMITs", i, g.type,
-                        g.num_constraints, g.p0, s.constraints);
-            GLP_REQUIRE(s.wires <= d.num_wires, "gate %u (type %u), field p0: program %u reads wire %u, the circuit has num_wires = %u", i, g.type, g.p0,
-                        s.wires - 1, d.num_wires);
-            GLP_REQUIRE(pi.consts <= d.num_constants, "gate %u (type %u), field p0: program %u reads constant polynomial %u, the circuit has num_constants = %u",
-                        i, g.type, g.p0, pi.consts - 1, d.num_constants);
-        } else if (!gate_type_known(g.type) || !gate_shape(g, s))
-            return set_error(gate_type_known(g.type) ? GLP_ERR_ARG : GLP_ERR_UNSUPPORTED,
-                             "gate %u: type %u with parameters (%u, %u) is not supported", i, g.type, g.p0, g.p1);
-        GLP_REQUIRE(s.wires <= d.num_wires, "gate %u (type %u) needs %u wires, circuit has %u", i, g.type, s.wires, d.num_wires);
-        GLP_REQUIRE(d.num_selectors + s.consts <= d.num_constants, "gate %u (type %u) needs %u constants", i, g.type, s.consts);
-        GLP_REQUIRE(s.constraints == g.num_constraints, "gate %u (type %u): num_constraints %u, expected %u", i, g.type, g.num_constraints, s.constraints);
-        GLP_REQUIRE(s.routed <= d.num_routed_wires, "gate %u (type %u): %u routed inputs, circuit has %u routed wires", i, g.type, s.routed,
-                    d.num_routed_wires);
-        if (s.degree || g.type == GLP_GATE_PROGRAM) {
-            // The quotient is evaluated on quotient_degree_factor cosets, so filter x constraint may have degree quotient_degree_factor + 1
-            // at most (what plonky2's selector grouping guarantees for every gate it places): the filter has one factor per other gate of
-            // the group, and the UNUSED factor when there are several selectors.
-            const u32 filt = g.group_end - g.group_start - 1 + (d.num_selectors > 1 ? 1 : 0);
-            GLP_REQUIRE(g.group_start < g.group_end && s.degree + filt <= qdf + 1, "gate %u (type %u): degree %u with a selector filter of degree %u exceeds "
-                        "quotient_degree_factor %u + 1", i, g.type, s.degree, g.group_start < g.group_end ? filt : 0, qdf);
-        }
-        GLP_REQUIRE(g.selector_index < d.num_selectors && g.group_start <= g.row && g.row < g.group_end, "bad selector data for gate %u", i);
-        GLP_REQUIRE(g.type == GLP_GATE_PROGRAM || g.num_constraints <= ACC3_MAX_TERMS, "gate %u: %u constraints exceed the %u the quotient accumulators hold", i,
-                    g.num_constraints, ACC3_MAX_TERMS);      // a program gate: GLP_GATE_PROGRAM_MAX_CONSTRAINTS, held by circuit_program_check
-        maxc = std::max(maxc, g.num_constraints);
-    }
-    GLP_REQUIRE(maxc <= d.num_gate_constraints, "num_gate_constraints smaller than a gate's constraint count");
-    {   // field arrays from outside: canonical or rejected by name (one host pass, small against the uploads and the commitment below)
-        const size_t nrows = (size_t)1 << d.degree_bits;
-        const u64 *sec[3] = {d.k_is, d.constants, d.sigmas};
-        const size_t cnt[3] = {d.num_routed_wires, (size_t)d.num_constants * nrows, (size_t)d.num_routed_wires * nrows};
-        const char *names[3] = {"k_is", "constants", "sigmas"};
-        for (int i = 0; i < 3; i++) {
-            const size_t bad = first_noncanonical(sec[i], cnt[i]);
-            GLP_REQUIRE(bad == cnt[i], "%s[%zu] = 0x%016llx is not a canonical field element (>= p)", names[i], bad, (unsigned long long)sec[i][bad]);
-        }
-    }
+    GLP_TRY(circuit_desc_check(d, programs, num_programs));
+    GLP_TRY(circuit_fields_check(d, true));
 
     std::unique_ptr<glp_circuit, void (*)(glp_circuit *)> cc(new glp_circuit(), glp_circuit_free);
     cc->ctx = c;
-    cc->d = d;
-    cc->gates.assign(d.gates, d.gates + d.num_gates);
-    cc->k_is.assign(d.k_is, d.k_is + d.num_routed_wires);
+    circuit_common_describe(*cc, d, flags, programs, num_programs);
     cc->k_ratio = coset_shift_ratio(cc->k_is.data(), cc->k_is.size());
-    cc->d.gates = cc->gates.data(); cc->d.k_is = cc->k_is.data(); cc->d.constants = nullptr; cc->d.sigmas = nullptr;
-    cc->zk = (flags & GLP_CIRCUIT_ZERO_KNOWLEDGE) != 0;
-    make_layout(cc->d, cc->L, cc->zk);
     const size_t n = (size_t)1 << d.degree_bits;
     const u32 nc = d.num_constants, nr = d.num_routed_wires;
     GLP_TRY(c->alloc((void **)&cc->dev_gates, sizeof(DevGate) * d.num_gates + 8 * COSET_TABLE_WORDS));      // gate table ++ coset_table
@@ -218,19 +139,14 @@ int glp_circuit_create_prog(glp_ctx *c, const glp_circuit_desc *desc, uint32_t f
     GLP_TRY(c->alloc((void **)&cc->dev_consts, (size_t)nc * n * 8));
     GLP_TRY(h2d(c, cc->dev_consts, d.constants, (size_t)nc * n * 8));
     GLP_TRY(build_quotient_plan(c, cc.get()));
-    if (!cc->program_gates.empty()) {              // the programs: host copies for the verifier, one device image for the kernels
+    if (!cc->program_gates.empty()) {              // the programs: one device image for the kernels
         std::vector<u64> img;
-        for (u32 i = 0; i < num_programs; i++) {
-            const glp_gate_program_desc &pd = programs[i];
-            glp_circuit::Program pr;
-            pr.code.assign(pd.code, pd.code + pd.num_instructions);
-            pr.pool.assign(pd.pool, pd.pool + pd.num_pool);
-            pr.nregs = pd.num_regs; pr.dev_at = img.size();
+        for (const glp_circuit::Program &pr : cc->programs) {
+            cc->dev_at.push_back(img.size());
             img.insert(img.end(), pr.code.begin(), pr.code.end());
             img.resize((img.size() + 3) & ~(size_t)3, 0);
             img.insert(img.end(), pr.pool.begin(), pr.pool.end());
             img.resize((img.size() + 3) & ~(size_t)3, 0);
-            cc->programs.push_back(std::move(pr));
         }
         GLP_TRY(c->alloc((void **)&cc->dev_programs, img.size() * 8));
         GLP_TRY(h2d(c, cc->dev_programs, img.data(), img.size() * 8));
@@ -243,31 +159,9 @@ int glp_circuit_create_prog(glp_ctx *c, const glp_circuit_desc *desc, uint32_t f
         GLP_HIP(hipMemcpyAsync(csv + (size_t)nc * n, cc->dev_sigmas, (size_t)nr * n * 8, hipMemcpyDeviceToDevice, c->stream));
         GLP_TRY(batch_build(c, csv, BATCH_VALUES, nc + nr, (int)d.degree_bits, (int)d.rate_bits, (int)d.cap_height, &cc->cs, nullptr, 1, (int)d.hasher));
     }
-    GLP_TRY(batch_cap_host(c, cc->cs, cc->cs_cap));
-    bool zero = true;
-    for (int i = 0; i < 4; i++) zero = zero && d.circuit_digest[i] == 0;
-    if (zero && d.hasher == GLP_HASH_KECCAK25) {
-        // the same recipe with C::Hasher = KeccakHash<25>: every hash enters as its four 7-byte chunks (BytesHash::to_vec)
-        u64 pad[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, ds[4], e[4];
-        kec::host_hash_no_pad(pad, 12, ds);
-        std::vector<u64> parts;
-        for (size_t i = 0; i < cc->cs_cap.size(); i += 4) { kec::digest_to_elements(&cc->cs_cap[i], e); parts.insert(parts.end(), e, e + 4); }
-        kec::digest_to_elements(ds, e);
-        parts.insert(parts.end(), e, e + 4);
-        parts.push_back(d.degree_bits);
-        kec::host_hash_no_pad(parts.data(), parts.size(), cc->digest);
-    } else if (zero) {
-        // hash_pad([]) = hash_no_pad([1, 0 x 10, 1]); digest = hash_no_pad(cap ++ that ++ [degree_bits])
-        u64 pad[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, ds[4];
-        host_hash_no_pad(pad, 12, ds);
-        std::vector<u64> parts(cc->cs_cap);
-        parts.insert(parts.end(), ds, ds + 4);
-        parts.push_back(d.degree_bits);
-        host_hash_no_pad(parts.data(), parts.size(), cc->digest);
-    } else {
-        memcpy(cc->digest, d.circuit_digest, 32);
-    }
-    memcpy(cc->d.circuit_digest, cc->digest, 32);
+    std::vector<u64> cap;
+    GLP_TRY(batch_cap_host(c, cc->cs, cap));
+    circuit_common_commit(*cc, cap);
     *out = cc.release();
     return GLP_OK;
 }
@@ -284,4 +178,15 @@ int glp_circuit_constants_sigmas_cap(const glp_circuit *cc, uint64_t *cap_out) {
 }
 size_t glp_proof_words(const glp_circuit *cc) { return cc ? cc->L.total : 0; }
 int glp_circuit_zero_knowledge(const glp_circuit *cc) { return cc && cc->zk ? 1 : 0; }
+
+// the proof as bytes (proof_bytes.h)
+size_t glp_proof_bytes_len(const glp_circuit *cc) { return cc ? proof_bytes_len(*cc) : 0; }
+int glp_proof_to_bytes(const glp_circuit *cc, const uint64_t *words, uint8_t *out, size_t len) {
+    GLP_REQUIRE(cc && words && out, "null argument");
+    return proof_to_bytes(*cc, words, out, len);
+}
+int glp_proof_from_bytes(const glp_circuit *cc, const uint8_t *in, size_t len, uint64_t *words) {
+    GLP_REQUIRE(cc && words && in, "null argument");
+    return proof_from_bytes(*cc, in, len, words);
+}
 }  // extern "C"

@@ -11,7 +11,7 @@
 // The design is k_gate_program's (DESIGN.md section 7): instruction words, pool and alpha powers through uniform pointers (scalar loads,
 // four words per load), scalar decode, uniform branches, and the register file in LDS as regs[r][256] with lane t at word r * 256 + t --
 // conflict-free ds_read_b64 / ds_write_b64, a lane touches its own column only, so there is no barrier inside the program.
-// The verifier's reading (F_p^2 at zeta, on the host) is program_constraints in verifier.hip.
+// The verifier's reading (F_p^2 at zeta, on the host) is program_constraints in verify_host.h.
 struct CPArgs {
     const u64 *code;                  // instruction words, zero-padded to a multiple of 4 (opcode 0 does nothing; the check refuses it)
     const u64 *pool;
@@ -125,56 +125,12 @@ __global__ __launch_bounds__(256) void k_witness_check_program(WcArgs w, CPArgs 
 }
 
 namespace {
-// the in-circuit rules on top of glp_gate_program_check's; `fn` names the entry point (and the program) in the message
-int circuit_program_check(const char *fn, const glp_gate_program_desc *d, CPInfo &info) {
-    info = CPInfo();
-    GPInfo gi;
-    GLP_TRY(gate_program_check(fn, d, gi));
-    GLP_REQUIRE(d->num_oracles == 2, "%s: desc.num_oracles = %u: a gate of a circuit reads oracle 0 (the constants) and oracle 1 (the wires)", fn,
-                d->num_oracles);
-    GLP_REQUIRE(d->num_params <= 4, "%s: desc.num_params = %u: the params of a gate of a circuit are the 4 words of the public-input hash", fn,
-                d->num_params);
-    u32 deg[GLP_GP_MAX_REGS] = {0};
-    for (u32 i = 0; i < d->num_instructions; i++) {
-        const u64 ins = d->code[i];
-        const u32 op = (u32)ins & 15, dst = ((u32)ins >> GLP_GP_DST_SHIFT) & 31;
-        const u32 f[2] = {(u32)(ins >> GLP_GP_A_SHIFT) & ((1u << GLP_GP_OPERAND_BITS) - 1), (u32)(ins >> GLP_GP_B_SHIFT) & ((1u << GLP_GP_OPERAND_BITS) - 1)};
-        u32 dg[2] = {0, 0};
-        for (int side = 0; side < (op <= GLP_GP_OP_MUL ? 2 : 1); side++) {
-            const char *field = side ? "b" : "a";
-            const u32 kind = f[side] & 7, pl = f[side] >> 3;
-            GLP_REQUIRE(kind != GLP_GP_COL_NEXT, "%s: instruction %u, field %s: COL_NEXT: a gate of a circuit does not see the next row", fn, i, field);
-            GLP_REQUIRE(kind != GLP_GP_X, "%s: instruction %u, field %s: X: a gate of a circuit does not see the point", fn, i, field);
-            if (kind == GLP_GP_REG) dg[side] = deg[pl];
-            else if (kind == GLP_GP_COL) {
-                const u32 col = pl & ((1u << GLP_GP_COL_ORACLE_SHIFT) - 1);
-                u32 &used = pl >> GLP_GP_COL_ORACLE_SHIFT ? info.wires : info.consts;
-                used = std::max(used, col + 1);
-                dg[side] = 1;
-            }
-        }
-        if (op <= GLP_GP_OP_MOV) {
-            const u64 sum = (u64)dg[0] + dg[1];
-            deg[dst] = op == GLP_GP_OP_MUL ? (u32)std::min<u64>(sum, 0xFFFFFFFFu) : std::max(dg[0], dg[1]);
-        } else if (op == GLP_GP_OP_EMIT) {
-            info.emits++;
-            GLP_REQUIRE(info.emits <= GLP_GATE_PROGRAM_MAX_CONSTRAINTS, "%s: instruction %u, field op: EMIT number %u, more than the %u the quotient accumulators hold",
-                        fn, i, info.emits, GLP_GATE_PROGRAM_MAX_CONSTRAINTS);
-            info.degree = std::max(info.degree, dg[0]);
-        } else {
-            GLP_REQUIRE(i + 1 == d->num_instructions, "%s: instruction %u, field op: END before the last instruction (a gate of a circuit is one gate)", fn, i);
-            const u32 kind = f[0] & 7, pl = f[0] >> 3;
-            GLP_REQUIRE(kind == GLP_GP_IMM && d->pool[pl] == 1, "%s: instruction %u, field a: the operand of END must be IMM of a pool word 1 (the selector filter is "
-                        "the library's)", fn, i);
-        }
-    }
-    return GLP_OK;
-}
+// (the in-circuit rules on top of glp_gate_program_check's are circuit_program_check, circuit_common.h)
 CPArgs circuit_program_args(const glp_circuit *cc, u32 gi) {
     const glp_circuit::Program &pr = cc->programs[cc->gates[gi].p0];
     const u32 words = ((u32)pr.code.size() + 3) & ~3u;
     CPArgs g;
-    g.code = cc->dev_programs + pr.dev_at; g.pool = g.code + words;
+    g.code = cc->dev_programs + cc->dev_at[cc->gates[gi].p0]; g.pool = g.code + words;
     g.ninstr = (u32)pr.code.size(); g.nregs = pr.nregs; g.gi = gi;
     return g;
 }

@@ -10,11 +10,11 @@
 #include <vector>
 #include "../../include/glp.h"
 #include "glf.h"
+#include "host_check.h"    // set_error, GLP_TRY, GLP_REQUIRE, first_noncanonical
 
 namespace glp {
 
 extern thread_local std::string g_last_error;
-int set_error(int code, const char *fmt, ...);
 
 #define GLP_HIP(expr)                                                                          \
     do {                                                                                       \
@@ -23,31 +23,9 @@ int set_error(int code, const char *fmt, ...);
             return glp::set_error(GLP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
                                   __FILE__, __LINE__);                                         \
     } while (0)
-#define GLP_TRY(expr)              \
-    do {                           \
-        int _rc = (expr);          \
-        if (_rc != GLP_OK) return _rc; \
-    } while (0)
-#define GLP_REQUIRE(cond, ...)                                  \
-    do {                                                        \
-        if (!(cond)) return glp::set_error(GLP_ERR_ARG, __VA_ARGS__); \
-    } while (0)
 
 struct NttPlan;
 struct LdePlan;
-
-// index of the first word >= p, or count if every word is a canonical field element (host; the inner loop vectorises).
-// The kernels assume canonical inputs: a word >= p gives a silently wrong proof, so the entry points that take field arrays
-// from outside (circuit description, hand-off file) reject it by name.
-inline size_t first_noncanonical(const u64 *v, size_t count) {
-    for (size_t i0 = 0; i0 < count; i0 += 4096) {
-        const size_t i1 = i0 + 4096 < count ? i0 + 4096 : count;
-        u64 bad = 0;
-        for (size_t i = i0; i < i1; i++) bad |= (u64)(v[i] >= glf::P);
-        if (bad) for (size_t i = i0; i < i1; i++) if (v[i] >= glf::P) return i;
-    }
-    return count;
-}
 
 struct Stage {
     std::string name;

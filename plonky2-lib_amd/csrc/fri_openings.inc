@@ -79,17 +79,11 @@ struct glp_fri {
             for (u32 e = 0; e < b; e++) if (same_point(e, b)) { p.table = e; break; }
             pts.push_back(p);
         }
-        const u32 lgN = (u32)(g.lg + g.rb), depth0 = lgN - (u32)g.cap_height;
-        size_t q = 0;
-        for (const glp_batch *b : ob) q += b->ncols + b->salt + 4 * (size_t)depth0;
-        u32 lg = lgN;
-        for (u32 i = 0; i < nred; i++) { lg -= arity_bits[i]; q += 2 * ((size_t)1 << arity_bits[i]) + 4 * (size_t)(lg - (u32)g.cap_height); }
-        query_stride = q;
-        final_len = 1u << (lg - (u32)g.rb);
-        o_queries = (size_t)nred * g.capn * 4;
-        o_final = o_queries + q * g.nq;
-        o_pow = o_final + 2 * (size_t)final_len;
-        total = o_pow + 1;
+        u32 leaf_len[GLP_FRI_MAX_ORACLES];
+        for (size_t o = 0; o < ob.size(); o++) leaf_len[o] = ob[o]->ncols + ob[o]->salt;
+        const FriProofLayout f = fri_proof_layout((u32)(g.lg + g.rb), (u32)g.rb, (u32)g.cap_height, leaf_len, (u32)ob.size(), arity_bits, nred, g.nq);
+        query_stride = f.query_stride; final_len = f.final_len;
+        o_queries = f.queries; o_final = f.final_poly; o_pow = f.pow; total = f.total;
         words.assign((size_t)K * total, 0);
     }
     glp_fri(const glp_fri &) = delete;

@@ -1,12 +1,49 @@
 // fri_shape.h -- the shape rules of a FriInstanceInfo and its FriParams, one set for the prover (fri_check in fri_openings.inc,
-// which adds what only a glp_batch can answer) and the verifier (fri_verify.inc, which holds caps and no batch).  Host only.
+// which adds what only a glp_batch can answer) and the verifier (fri_verify.inc, which holds caps and no batch); the word layout of
+// a FriProof, one statement for the plonk proof (make_layout, circuit_common.h), the prover's handle (glp_fri, fri_openings.inc) and
+// the verifier's plan (fv_plan, fri_verify.inc); and the status word of a query round, which the kernel (verify_dev.h) and the host
+// restatement (verify_host.h) both speak.  Host only, no context.  A change to the proof format belongs in fri_proof_layout and in
+// binding.fri_proof_words, the caller-side restatement.
 #pragma once
-#include "common.h"
+#include "host_check.h"
 
 namespace glp {
 // One bound for glp_circuit_create, glp_pow_search and the FRI descriptions: with the search capped at 2^40 candidates, 32 bits
 // leaves a failure probability of exp(-2^8).
 constexpr u32 POW_MAX_BITS = 32;
+
+// status word of one (proof, query): 0 = accepted, else check | detail << 8 (detail: oracle for 4, point for 3, reduction for 5 and 6);
+// the check numbers are those of tests/fri_restate.py::verify_fri_proof
+constexpr u32 FV_POINT = 3, FV_INITIAL = 4, FV_FOLD = 5, FV_LAYER = 6, FV_FINAL = 7;
+
+// One FriProof in words: the caps of the reduction layers | per query round the initial leaves and paths of every oracle, then per
+// reduction the 2^arity evaluations (ext) and the path of its layer | the final polynomial (ext) | the proof-of-work witness.
+// Offsets count from the first layer cap; leaf_off[o] is where oracle o's leaf starts inside a query record.  The shape rules above
+// have held for the arguments: the sums and shifts here cannot wrap.
+struct FriProofLayout {
+    u32 depth0 = 0, step_depth[16] = {0}, final_len = 0;
+    size_t leaf_off[GLP_FRI_MAX_ORACLES] = {0}, query_stride = 0, queries = 0, final_poly = 0, pow = 0, total = 0;
+};
+inline FriProofLayout fri_proof_layout(u32 lgN, u32 rate_bits, u32 cap_height, const u32 *leaf_len, u32 num_oracles, const u32 *arity_bits,
+                                       u32 num_reductions, u32 num_query_rounds) {
+    FriProofLayout f;
+    f.depth0 = lgN - cap_height;
+    size_t q = 0;
+    for (u32 o = 0; o < num_oracles; o++) { f.leaf_off[o] = q; q += leaf_len[o] + 4 * (size_t)f.depth0; }
+    u32 lg = lgN;
+    for (u32 r = 0; r < num_reductions; r++) {
+        lg -= arity_bits[r];
+        f.step_depth[r] = lg - cap_height;
+        q += 2 * ((size_t)1 << arity_bits[r]) + 4 * (size_t)f.step_depth[r];
+    }
+    f.query_stride = q;
+    f.final_len = 1u << (lg - rate_bits);
+    f.queries = (size_t)num_reductions * ((size_t)4 << cap_height);
+    f.final_poly = f.queries + q * num_query_rounds;
+    f.pow = f.final_poly + 2 * (size_t)f.final_len;
+    f.total = f.pow + 1;
+    return f;
+}
 
 inline int fri_shape_counts(u32 num_oracles, const void *oracles, u32 num_points, const glp_fri_point *points) {
     GLP_REQUIRE(num_oracles >= 1 && num_oracles <= GLP_FRI_MAX_ORACLES, "num_oracles = %u outside 1..%d", num_oracles, GLP_FRI_MAX_ORACLES);

@@ -70,34 +70,22 @@ int fv_plan(const glp_fri_verify_desc *d, FVPlan &p) {
                             d->reduction_arity_bits, d->proof_of_work_bits, d->num_query_rounds));
     p.nor = d->num_oracles; p.npts = d->num_points; p.cap_height = d->cap_height; p.capn = 1u << d->cap_height; p.depth0 = p.lgN - d->cap_height;
     p.nred = d->num_reductions; p.nq = d->num_query_rounds; p.pow_bits = d->proof_of_work_bits; p.hasher = (int)d->hasher;
-    u32 leaf_off[GLP_FRI_MAX_ORACLES];
-    size_t q = 0;
     for (u32 o = 0; o < p.nor; o++) {
         p.leaf_len[o] = ncols[o] + (d->oracles[o].salted ? GLP_SALT_SIZE : 0);
         p.shared[o] = d->oracles[o].shared != 0;
-        GLP_REQUIRE(q <= 0x7FFFFFFFu, "oracles: a query record of more than 2^31 words");
-        leaf_off[o] = (u32)q;
-        q += p.leaf_len[o] + 4 * (size_t)p.depth0;
     }
-    u32 lg = p.lgN;
-    for (u32 r = 0; r < p.nred; r++) {
-        p.ab[r] = d->reduction_arity_bits[r];
-        lg -= p.ab[r];
-        p.step_depth[r] = lg - d->cap_height;
-        q += 2 * ((size_t)1 << p.ab[r]) + 4 * (size_t)p.step_depth[r];
-    }
-    p.query_stride = q;
-    p.final_len = 1u << (lg - d->rate_bits);
-    p.o_queries = (size_t)p.nred * p.capn * 4;
-    p.o_final = p.o_queries + q * p.nq;
-    p.o_pow = p.o_final + 2 * (size_t)p.final_len;
-    p.total = p.o_pow + 1;
+    for (u32 r = 0; r < p.nred; r++) p.ab[r] = d->reduction_arity_bits[r];
+    const FriProofLayout f = fri_proof_layout(p.lgN, d->rate_bits, d->cap_height, p.leaf_len, p.nor, p.ab, p.nred, p.nq);
+    for (u32 o = 0; o < p.nor; o++) GLP_REQUIRE(f.leaf_off[o] <= 0x7FFFFFFFu, "oracles: a query record of more than 2^31 words");
+    for (u32 r = 0; r < p.nred; r++) p.step_depth[r] = f.step_depth[r];
+    p.query_stride = f.query_stride; p.final_len = f.final_len;
+    p.o_queries = f.queries; p.o_final = f.final_poly; p.o_pow = f.pow; p.total = f.total;
     for (u32 b = 0; b < p.npts; b++) {
         const glp_fri_point &pt = d->points[b];
         p.first[b] = (u32)p.nopen; p.len[b] = 0; p.nranges[b] = pt.num_ranges;
         for (u32 r = 0; r < pt.num_ranges; r++) {
             const glp_fri_range &rg = pt.ranges[r];
-            p.prog.push_back(leaf_off[rg.oracle]); p.prog.push_back(rg.col_begin); p.prog.push_back(rg.num_cols);
+            p.prog.push_back((u32)f.leaf_off[rg.oracle]); p.prog.push_back(rg.col_begin); p.prog.push_back(rg.num_cols);
             p.len[b] += rg.num_cols;
         }
         p.nopen += p.len[b];

@@ -110,82 +110,7 @@ struct glp_gate_program {
 };
 
 namespace {
-struct GPInfo { u32 maxc, cols_named, next_mask; };
-// the rules of glp_gate_program_check; `fn` names the entry point in the message
-int gate_program_check(const char *fn, const glp_gate_program_desc *d, GPInfo &info) {
-    GLP_REQUIRE(d, "%s: desc is null", fn);
-    GLP_REQUIRE(d->num_regs >= 1 && d->num_regs <= GLP_GP_MAX_REGS, "%s: desc.num_regs = %u outside 1..%u", fn, d->num_regs, GLP_GP_MAX_REGS);
-    GLP_REQUIRE(d->num_oracles >= 1 && d->num_oracles <= GLP_GP_MAX_ORACLES, "%s: desc.num_oracles = %u outside 1..%u", fn, d->num_oracles,
-                GLP_GP_MAX_ORACLES);
-    GLP_REQUIRE(d->oracle_cols, "%s: desc.oracle_cols is null", fn);
-    GLP_REQUIRE(d->num_instructions >= 1, "%s: desc.num_instructions is 0: an empty program", fn);
-    GLP_REQUIRE(d->num_instructions <= GLP_GP_MAX_INSTRUCTIONS, "%s: desc.num_instructions = %u is more than %u", fn, d->num_instructions,
-                GLP_GP_MAX_INSTRUCTIONS);
-    GLP_REQUIRE(d->code, "%s: desc.code is null", fn);
-    GLP_REQUIRE(d->pool || d->num_pool == 0, "%s: desc.pool is null with num_pool = %u", fn, d->num_pool);
-    GLP_REQUIRE(d->num_pool <= (1u << 24) && d->num_params <= (1u << 24), "%s: desc.num_pool = %u or num_params = %u is more than 2^24", fn,
-                d->num_pool, d->num_params);
-    const size_t bad = first_noncanonical(d->pool, d->num_pool);
-    GLP_REQUIRE(bad == d->num_pool, "%s: desc.pool[%zu] = 0x%016llx is not a canonical field element (>= p)", fn, bad,
-                (unsigned long long)d->pool[bad == d->num_pool ? 0 : bad]);
-    u32 written = 0, emits = 0;
-    std::vector<u32> named;
-    info.maxc = 0; info.next_mask = 0;
-    for (u32 i = 0; i < d->num_instructions; i++) {
-        const u64 ins = d->code[i];
-        const u32 op = (u32)ins & 15, dst = ((u32)ins >> GLP_GP_DST_SHIFT) & 31;
-        const u32 fa = (u32)(ins >> GLP_GP_A_SHIFT) & ((1u << GLP_GP_OPERAND_BITS) - 1), fb = (u32)(ins >> GLP_GP_B_SHIFT) & ((1u << GLP_GP_OPERAND_BITS) - 1);
-        GLP_REQUIRE(op >= GLP_GP_OP_ADD && op <= GLP_GP_OP_END && !(ins >> 63), "%s: instruction %u, field op: 0x%016llx has the unknown opcode %u%s", fn, i,
-                    (unsigned long long)ins, op, ins >> 63 ? " (bit 63 is set)" : "");
-        const bool has_dst = op <= GLP_GP_OP_MOV, has_b = op <= GLP_GP_OP_MUL;
-        if (has_dst) GLP_REQUIRE(dst < d->num_regs, "%s: instruction %u, field dst: register %u is not below num_regs = %u", fn, i, dst, d->num_regs);
-        else GLP_REQUIRE(dst == 0, "%s: instruction %u, field dst: %u in an instruction without a destination", fn, i, dst);
-        if (!has_b) GLP_REQUIRE(fb == 0, "%s: instruction %u, field b: 0x%x in an instruction with one operand", fn, i, fb);
-        for (int side = 0; side < (has_b ? 2 : 1); side++) {
-            const char *field = side ? "b" : "a";
-            const u32 f = side ? fb : fa, kind = f & 7, pl = f >> 3;
-            switch (kind) {
-            case GLP_GP_REG:
-                GLP_REQUIRE(pl < d->num_regs, "%s: instruction %u, field %s: register %u is not below num_regs = %u", fn, i, field, pl, d->num_regs);
-                GLP_REQUIRE(written >> pl & 1, "%s: instruction %u, field %s: register %u is read before it is written", fn, i, field, pl);
-                break;
-            case GLP_GP_COL: case GLP_GP_COL_NEXT: {
-                const u32 o = pl >> GLP_GP_COL_ORACLE_SHIFT, col = pl & ((1u << GLP_GP_COL_ORACLE_SHIFT) - 1);
-                GLP_REQUIRE(o < d->num_oracles, "%s: instruction %u, field %s: oracle index %u is not below num_oracles = %u", fn, i, field, o, d->num_oracles);
-                GLP_REQUIRE(col < d->oracle_cols[o], "%s: instruction %u, field %s: column index %u is not below oracle_cols[%u] = %u", fn, i, field, col, o,
-                            d->oracle_cols[o]);
-                named.push_back(pl);
-                if (kind == GLP_GP_COL_NEXT) info.next_mask |= 1u << o;
-                break;
-            }
-            case GLP_GP_IMM:
-                GLP_REQUIRE(pl < d->num_pool, "%s: instruction %u, field %s: pool index %u is not below num_pool = %u", fn, i, field, pl, d->num_pool);
-                break;
-            case GLP_GP_PARAM:
-                GLP_REQUIRE(pl < d->num_params, "%s: instruction %u, field %s: param index %u is not below num_params = %u", fn, i, field, pl, d->num_params);
-                break;
-            case GLP_GP_X:
-                GLP_REQUIRE(pl == 0, "%s: instruction %u, field %s: X with the payload %u", fn, i, field, pl);
-                break;
-            default:
-                GLP_REQUIRE(false, "%s: instruction %u, field %s: unknown operand kind %u", fn, i, field, kind);
-            }
-        }
-        if (has_dst) written |= 1u << dst;
-        if (op == GLP_GP_OP_EMIT) {
-            emits++;
-            GLP_REQUIRE(emits <= GLP_GP_MAX_CONSTRAINTS, "%s: instruction %u, field op: EMIT number %u of one gate, more than %u", fn, i, emits, GLP_GP_MAX_CONSTRAINTS);
-        } else if (op == GLP_GP_OP_END) {
-            info.maxc = std::max(info.maxc, emits);
-            emits = 0;
-        }
-        if (i + 1 == d->num_instructions)
-            GLP_REQUIRE(op == GLP_GP_OP_END, "%s: instruction %u, field op: the last instruction is not END", fn, i);
-    }
-    std::sort(named.begin(), named.end());
-    info.cols_named = (u32)(std::unique(named.begin(), named.end()) - named.begin());
-    return GLP_OK;
-}
+// the rules of glp_gate_program_check are gate_program_check (circuit_common.h: host only, shared with the circuit description's checks)
 // what the three evaluators (glp_gate_program_sums, _eval_ext, _rows) ask of the handle, and of the params that go with it
 int gate_program_handle_check(const char *fn, const glp_ctx *c, const glp_gate_program *p) {
     GLP_REQUIRE(c, "%s: ctx is null", fn);

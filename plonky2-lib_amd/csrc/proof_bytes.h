@@ -1,12 +1,16 @@
-// proof_bytes.inc -- the proof as bytes (util/serialization.rs): words little-endian, u8 sibling count before each Merkle path.
-// Included by prover.hip.
+// proof_bytes.h -- the proof as bytes (util/serialization.rs): words little-endian, u8 sibling count before each Merkle path.  Reads
+// the verifier's view of the circuit alone (circuit_common.h): host only, no context.  proof_from_bytes parses bytes from outside;
+// examples/verify_host.cpp runs it under the host sanitizers.  The entry points glp_proof_* are in circuit_create.inc.
+#pragma once
+#include "circuit_common.h"
+
 namespace {
 // calls f(offset_words, count_words, kind) for the pieces of a proof in order.  PW_FIELD: field elements; PW_DIGESTS: digests of
 // the proof's hasher, 4 words each (caps); PW_PATH: a Merkle path (digests, preceded by a one-byte sibling count on the wire)
 enum { PW_FIELD = 0, PW_DIGESTS = 1, PW_PATH = 2 };
-template <class F> void walk_proof(const glp_circuit *cc, F f) {
-    const Layout &L = cc->L;
-    const glp_circuit_desc &d = cc->d;
+template <class F> void walk_proof(const CircuitCommon &cc, F f) {
+    const Layout &L = cc.L;
+    const glp_circuit_desc &d = cc.d;
     f((size_t)0, L.openings, PW_DIGESTS);                                   // wires, Z / partial products, quotient caps
     f(L.openings, L.fri_caps - L.openings, PW_FIELD);                       // openings
     f(L.fri_caps, L.queries - L.fri_caps, PW_DIGESTS);                      // commit-phase caps
@@ -24,26 +28,21 @@ template <class F> void walk_proof(const glp_circuit *cc, F f) {
     }
     f(L.final_poly, L.total - L.final_poly, PW_FIELD);     // final poly, pow witness, public inputs
 }
-}  // namespace
 
 // bytes of one digest on the wire: a Poseidon HashOut is 4 field elements, a KeccakHash<25> digest 25 bytes
-static size_t digest_wire_bytes(const glp_circuit *cc) { return cc->d.hasher == GLP_HASH_KECCAK25 ? 25 : 32; }
+size_t digest_wire_bytes(const CircuitCommon &cc) { return cc.d.hasher == GLP_HASH_KECCAK25 ? 25 : 32; }
 
-extern "C" {
-
-size_t glp_proof_bytes_len(const glp_circuit *cc) {
-    if (!cc) return 0;
+size_t proof_bytes_len(const CircuitCommon &cc) {
     size_t bytes = 0;
     const size_t db = digest_wire_bytes(cc);
     walk_proof(cc, [&](size_t, size_t cnt, int kind) { bytes += kind == PW_FIELD ? cnt * 8 : (cnt / 4) * db + (kind == PW_PATH ? 1 : 0); });
     return bytes;
 }
 
-int glp_proof_to_bytes(const glp_circuit *cc, const uint64_t *words, uint8_t *out, size_t len) {
-    GLP_REQUIRE(cc && words && out, "null argument");
-    GLP_REQUIRE(len == glp_proof_bytes_len(cc), "bytes_len must equal glp_proof_bytes_len()");
+int proof_to_bytes(const CircuitCommon &cc, const uint64_t *words, uint8_t *out, size_t len) {
+    GLP_REQUIRE(len == proof_bytes_len(cc), "bytes_len must equal glp_proof_bytes_len()");
     size_t o = 0;
-    const bool kec25 = cc->d.hasher == GLP_HASH_KECCAK25;
+    const bool kec25 = cc.d.hasher == GLP_HASH_KECCAK25;
     walk_proof(cc, [&](size_t off, size_t cnt, int kind) {
         if (kind == PW_PATH) out[o++] = (uint8_t)(cnt / 4);
         for (size_t i = 0; i < cnt; i++) {
@@ -55,12 +54,11 @@ int glp_proof_to_bytes(const glp_circuit *cc, const uint64_t *words, uint8_t *ou
     return GLP_OK;
 }
 
-int glp_proof_from_bytes(const glp_circuit *cc, const uint8_t *in, size_t len, uint64_t *words) {
-    GLP_REQUIRE(cc && words && in, "null argument");
-    GLP_REQUIRE(len == glp_proof_bytes_len(cc), "byte length does not match this circuit");
+int proof_from_bytes(const CircuitCommon &cc, const uint8_t *in, size_t len, uint64_t *words) {
+    GLP_REQUIRE(len == proof_bytes_len(cc), "byte length does not match this circuit");
     size_t o = 0;
     int bad = 0;
-    const bool kec25 = cc->d.hasher == GLP_HASH_KECCAK25;
+    const bool kec25 = cc.d.hasher == GLP_HASH_KECCAK25;
     walk_proof(cc, [&](size_t off, size_t cnt, int kind) {
         if (kind == PW_PATH && in[o++] != (uint8_t)(cnt / 4)) bad = 1;
         for (size_t i = 0; i < cnt; i++) {
@@ -76,4 +74,4 @@ int glp_proof_from_bytes(const glp_circuit *cc, const uint8_t *in, size_t len, u
     if (bad == 2) return set_error(GLP_ERR_ARG, "non-canonical field element in proof bytes");
     return GLP_OK;
 }
-}  // extern "C"
+}  // namespace

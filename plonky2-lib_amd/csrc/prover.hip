@@ -13,8 +13,8 @@
 // query paths (KBs) in and challenges out.
 //
 // One translation unit, in this order: the kernels (pp_kernels.inc, quotient_kernels.inc, fri_kernels.inc), the host helpers, the
-// stage functions (prover_stages.inc), the single-proof session and prove_impl, the circuit handle (circuit_create.inc), the
-// byte format (proof_bytes.inc), the prove / session / staged-witness C ABI, openings and FRI of caller-held batches
+// stage functions (prover_stages.inc), the single-proof session and prove_impl, the circuit handle and the entry points of the byte
+// format (circuit_create.inc, over circuit_common.h and proof_bytes.h), the prove / session / staged-witness C ABI, openings and FRI of caller-held batches
 // (fri_openings.inc), the permutation argument and the gate programs of a caller-held circuit (perm_seam.inc, gate_program.inc), its identity check at zeta (zeta_check.inc), its own running arguments (trace_program.inc, running_columns.inc), the witness checker (witness_check.inc), the program gates of a circuit (circuit_program.inc) and the batch drivers (prover_batch*.inc).
 #include <algorithm>
 #include <string.h>
@@ -23,43 +23,10 @@
 #include "merkle.h"
 #include "ntt.h"
 #include "poseidon.h"
+#include "proof_bytes.h"
 #include "prover_types.h"
 #include "fri_shape.h"      // POW_MAX_BITS and the FRI shape rules
 #include "witness_plan.h"   // witness_row_gate, the gate of a row: one text with k_witness_fill and the witness planner
-
-namespace {
-void make_layout(const glp_circuit_desc &c, Layout &L, bool zk) {
-    const u32 cap = 1u << c.cap_height, nch = c.num_challenges;
-    memset(&L, 0, sizeof(L));
-    L.oracle_cols[0] = c.num_constants + c.num_routed_wires;
-    L.oracle_cols[1] = c.num_wires;
-    L.oracle_cols[2] = nch * (1 + c.num_partial_products);
-    L.oracle_cols[3] = nch * c.quotient_degree_factor;
-    for (int k = 0; k < 4; k++) L.leaf_len[k] = L.oracle_cols[k] + (zk && k > 0 ? SALT_SIZE : 0);
-    L.nopen = (size_t)c.num_constants + c.num_routed_wires + c.num_wires + 2 * nch + nch * c.num_partial_products +
-              nch * c.quotient_degree_factor;
-    L.openings = 3 * (size_t)cap * 4;
-    L.fri_caps = L.openings + 2 * L.nopen;
-    L.queries = L.fri_caps + (size_t)c.num_reductions * cap * 4;
-    const u32 lgN = c.degree_bits + c.rate_bits;
-    L.depth0 = lgN - c.cap_height;
-    size_t q = 0;
-    for (int k = 0; k < 4; k++) q += L.leaf_len[k] + 4 * (size_t)L.depth0;
-    u32 lg = lgN;
-    for (u32 i = 0; i < c.num_reductions; i++) {
-        const u32 ab = c.reduction_arity_bits[i];
-        lg -= ab;
-        L.step_depth[i] = lg - c.cap_height;
-        q += 2 * ((size_t)1 << ab) + 4 * (size_t)L.step_depth[i];
-    }
-    L.query_stride = q;
-    L.final_len = 1u << (lg - c.rate_bits);
-    L.final_poly = L.queries + q * c.num_query_rounds;
-    L.pow = L.final_poly + 2 * (size_t)L.final_len;
-    L.pis = L.pow + 1;
-    L.total = L.pis + c.num_public_inputs;
-}
-}  // namespace
 
 // ------------------------------------------------------------------------------------------ kernels
 __device__ __forceinline__ u64 dpow(u64 b, u64 e) {
@@ -419,7 +386,6 @@ static int prove_impl(glp_ctx *c, const glp_circuit *cc, const u64 *dev_wires, c
 }
 
 #include "circuit_create.inc"
-#include "proof_bytes.inc"
 
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {

@@ -4,6 +4,7 @@
 // (FVArgs), the status word (FV_*) and k_fri_verify_queries.  glp_verify_batch (verifier.hip) launches it on the plonk instance
 // of a circuit, glp_fri_verify* (fri_verify.inc) on the caller's instance.  The per-proof table it reads is FT_* (prover_types.h).
 #pragma once
+#include "fri_shape.h"      // the status word, FV_*
 #include "prover_types.h"
 
 namespace {
@@ -70,10 +71,6 @@ __device__ __forceinline__ bool merkle_bad(const u64 *leaf, u32 len, size_t inde
     return group_or(bad) != 0;
 }
 __device__ __forceinline__ ext2 rd2(const u64 *p) { return e_make(p[0], p[1]); }
-
-// status word of one (proof, query): 0 = accepted, else check | detail << 8 (detail: oracle for 4, point for 3, reduction for 5 and 6);
-// the check numbers are those of tests/fri_restate.py::verify_fri_proof
-constexpr u32 FV_POINT = 3, FV_INITIAL = 4, FV_FOLD = 5, FV_LAYER = 6, FV_FINAL = 7;
 
 struct FVArgs {
     const u64 *proofs;      // [K][total]

@@ -6,7 +6,7 @@
 //     vanishing(zeta) == Z_H(zeta) * reduce_with_powers(quotient chunks, zeta^n).
 // For a seam caller the gate share of vanishing(zeta) is its gate program read over F_p^2: COL is the opening at zeta, COL_NEXT the
 // opening at w_n zeta, X is zeta, IMM and PARAM are embedded base elements and ADD / SUB / MUL are the F_p^2 operations.  The rest is
-// the algebra of verify_vanishing (verifier.hip) with the gate terms handed in.
+// the algebra of verify_vanishing (verify_host.h) with the gate terms handed in.
 //
 // k_gate_program_ext: one lane per proof, one wave per block, so that 4096 proofs spread over 64 CUs.  What is wave-uniform stays on
 // the scalar side exactly as in k_gate_program: instruction words through the uniform pointer into the zero-padded device copy (four

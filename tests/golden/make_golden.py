@@ -72,9 +72,32 @@ def pow_states(log=print):
     np.savez_compressed(os.path.join(HERE, "pow_states.npz"), **out)
 
 
+def gpu_proofs(path=None):
+    """gpu_proofs.npz: the proofs tests/test_verify_host.py needs and the oracle cannot make (extension-field and recursion gates, salted
+    leaves), recorded from glp_prove on a GPU with a fixed salt seed: per circuit of test_verify_host.recorded_circuits its proof and,
+    without zero knowledge, the proof of test_verify_host.broken_witness.  The circuits are rebuilt from their seeds by the test."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import plonky2_lib_amd as glp
+    import test_verify_host as tv
+    out = {}
+    with glp.Context(0) as ctx:
+        ctx.set_salt_seed([11, 22, 33, 44])
+        for name, desc in tv.recorded_circuits().items():
+            gc = glp.Circuit(ctx, desc)
+            out[name + "_proof"] = gc.prove()
+            assert gc.verify(out[name + "_proof"])
+            if not gc.zero_knowledge:
+                out[name + "_broken"] = gc.prove(wires=tv.broken_witness(desc))
+                assert not gc.verify(out[name + "_broken"])
+            gc.free()
+    np.savez_compressed(path or os.path.join(HERE, "gpu_proofs.npz"), **out)
+
+
 def main():
     if sys.argv[1:] == ["pow_states"]:         # on request only: that file alone, about two minutes of hashing
         return pow_states()
+    if sys.argv[1:2] == ["gpu_proofs"]:        # on request only, on a machine with a GPU: that file alone (optionally: where to write it)
+        return gpu_proofs(*sys.argv[2:3])
     o.build()
     rng = np.random.default_rng(0x5EED0001)
     vals = o.rand_field(rng, (5, 32))
