@@ -138,6 +138,13 @@ GLP_API int glp_batch_from_values_h(glp_ctx *ctx, const uint64_t *values, uint32
 #define GLP_SALT_TAG_ZS 1              /* partial_products_and_zs_commitment */
 #define GLP_SALT_TAG_QUOTIENT 2        /* quotient_polys_commitment */
 #define GLP_SALT_TAG_BATCH 3           /* glp_batch_from_values_salted */
+#define GLP_SALT_TAG_WITNESS 4         /* the random cells of a witness plan (glp_witness_plan_create_rand) */
+/* The same PRF gives the random cells of a generated witness (the advice of the blinding rows; "witness generation, the dataflow half",
+ * RANDOM CELLS).  For random cell number i in the caller's order, proof k of the glp_witness_generate call and the seed of that call:
+ *     b = i >> 3, j = i & 7
+ *     value = Poseidon([seed0, seed1, seed2, seed3 + k mod p, GLP_SALT_TAG_WITNESS, b & 0xffffffff, b >> 32, 0, 0, 0, 0, 0])[j]
+ * One permutation yields the eight rate words; the four capacity words are never written anywhere.  The value is a canonical field
+ * element. */
 /* from_values with blinding = true under `hasher`, salts from `seed`.  glp_batch_leaf returns glp_batch_leaf_len() = ncols + 4 words
  * for such a batch; glp_batch_info / glp_batch_coeffs keep counting the ncols polynomials. */
 GLP_API int glp_batch_from_values_salted(glp_ctx *ctx, const uint64_t *values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
@@ -902,14 +909,16 @@ GLP_API int glp_witness_columns(const glp_circuit *circuit, uint32_t gate_index,
  *
  * THE PLAN (host, once per circuit and input set).  A cell is named by its flat position col * n + row, col < num_wires (the encoding
  * of the decoded sigmas).  The copy classes are the cycles of the decoded permutation; a non-routed cell is a class of its own.
- *   Class wave.   The wave of a class is the minimum over its members of: 0 for an input cell; the wave of the unit that writes the
- *                 member.  A class with neither is never known.
- *   Source.       The class's source is the member that attains the minimum.  Ties go to the smallest flat position.
+ *   Class wave.   The wave of a class is the minimum over its members of: 0 for an input cell; 0 for a random cell (RANDOM CELLS,
+ *                 below: a wave-0 source exactly as an input cell is); the wave of the unit that writes the member.  A class with none
+ *                 of these is never known.
+ *   Source.       The class's source is the member that attains the minimum.  Ties go to the smallest flat position, with inputs and
+ *                 random cells alike.
  *   Unit wave.    The wave of a unit is 1 + the maximum wave of the classes of the cells it reads.  It is 1 for a unit with no inputs.
  *                 Gate constants and selectors are always known.
  *   Stuck units.  A unit that reads a never-known class is stuck, and so is everything downstream of it.  Dependency cycles are
  *                 included.  Stuck units are counted.  The first stuck unit is named.  Stuck units are never run.
- *   Order within wave w.  Wave 0 is the scatter of the inputs.  In every other wave, first every unit of wave w runs.  Then every
+ *   Order within wave w.  Wave 0 is the scatter of the inputs and the draw of the random cells.  In every other wave, first every unit of wave w runs.  Then every
  *                 class whose wave is w is copied from its source to all its other members.
  *   cell_waves.   The unit's wave for a cell a unit writes (a unit that is not stuck); the class's wave for any other known cell; -1
  *                 for a cell that is never known.
@@ -1013,8 +1022,25 @@ GLP_API int glp_witness_columns(const glp_circuit *circuit, uint32_t gate_index,
  * loads, the register file lies in LDS.  Walked runs stop before such a wave and resume after it: the walked kernels hold nothing of the
  * interpreter.  The programs (code and pool, concatenated, with an offset table) lie in HBM with the plan.
  *
- * NOT done here: zero-knowledge blinding rows (their random advice comes from no generator: list those cells as inputs); a
- * device-side planner; integer products wider than the field in a unit program.
+ * RANDOM CELLS.  The random advice of a zero-knowledge circuit's blinding rows (plonky2 `blind`: rows of random wires, and pairs of rows
+ * whose routed wires are random and copy-constrained to each other) comes from no generator and need not come from the caller either: a
+ * blinding value only has to be unpredictable, as a salt does.  glp_witness_plan_create_rand takes, after input_cells and num_inputs,
+ * random_cells[num_random] (flat positions), and glp_witness_generate fills them on the device from the PRF stated beside
+ * GLP_SALT_TAG_WITNESS: cell number i of the caller's list gets word i & 7 of the permutation of block i >> 3.  A random cell is a wave-0
+ * source exactly as an input cell is: its class has wave 0, the copies of wave 0 carry the value to the rest of the class (the second
+ * row of a blinding pair: list only the first), cell_waves is 0 for it, num_cells_known counts it; a random cell whose class also holds
+ * a unit's output is allowed, as for inputs, and glp_witness_check reports the broken copy.  For a plan with random cells
+ * glp_witness_generate draws one seed per call, the way the provers draw their salt seed (OS entropy, or the fixed seed of
+ * glp_ctx_set_salt_seed for tests; proof k uses seed3 + k); nothing else about the call changes, input_values stays
+ * [num_proofs][num_inputs], and a plan without random cells draws no seed and launches what it always launched.  One kernel runs once
+ * per call, one lane per block of eight cells (grid.y = proof), with the scatter of the inputs and before the copies of wave 0 in both
+ * forms; wave 0 counts as wide by its inputs and random cells together (its copies are the blinding pairs' second rows).  A zkdsa witness under standard_recursion_zk_config then still comes from 8 words per proof.
+ * Refusals of glp_witness_plan_create_rand beyond those above (GLP_ERR_ARG, each names the field, decided with the input cells'):
+ * random_cells null with num_random > 0; a random cell out of range; listed twice; also listed as an input cell; two random cells, or a
+ * random cell and an input cell, in one copy class (both named).  glp_witness_plan_create_prog is the num_random = 0 case of the same body.
+ *
+ * NOT done here: glp_witness_stage(GLP_WITNESS_ROUTED_ONLY) on a zero-knowledge circuit (refused as before: glp_witness_fill knows no
+ * random cells); a device-side planner; integer products wider than the field in a unit program.
  * tests/witness_plan_restate.py restates the units, the classes, the rule and generation; tests/witness_free_restate.py the free units;
  * tests/witness_program_restate.py the unit programs. */
 typedef struct glp_witness_plan glp_witness_plan;
@@ -1072,6 +1098,13 @@ GLP_API int glp_witness_plan_create_prog(glp_ctx *ctx, const glp_circuit *c, con
                                          const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
                                          const uint32_t *moduli /* [num_moduli][8] */, uint32_t num_moduli,
                                          const glp_witness_program_desc *programs, uint32_t num_programs, glp_witness_plan **out);
+/* RANDOM CELLS: see the block above.  The new pair follows input_cells, num_inputs; everything else is glp_witness_plan_create_prog. */
+GLP_API int glp_witness_plan_create_rand(glp_ctx *ctx, const glp_circuit *c, const uint64_t *input_cells, uint32_t num_inputs,
+                                         const uint64_t *random_cells, uint32_t num_random,
+                                         const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
+                                         const uint32_t *moduli /* [num_moduli][8] */, uint32_t num_moduli,
+                                         const glp_witness_program_desc *programs, uint32_t num_programs, glp_witness_plan **out);
+GLP_API uint32_t glp_witness_plan_num_random(const glp_witness_plan *p);   /* 0 for a null plan */
 GLP_API int glp_witness_plan_free_info(const glp_witness_plan *p, struct glp_witness_plan_free_info *out);
 GLP_API int  glp_witness_plan_info(const glp_witness_plan *p, struct glp_witness_plan_info *out);
 GLP_API int  glp_witness_plan_cell_waves(const glp_witness_plan *p, int32_t *waves_out /* [num_wires][n] */);

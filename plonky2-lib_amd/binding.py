@@ -283,6 +283,7 @@ def load_library():
         "glp_witness_plan_create": [vp, vp, vp, u32, C.POINTER(vp)],
         "glp_witness_plan_create_ex": [vp, vp, vp, u32, vp, u32, vp, sz, vp, u32, C.POINTER(vp)],
         "glp_witness_plan_create_prog": [vp, vp, vp, u32, vp, u32, vp, sz, vp, u32, vp, u32, C.POINTER(vp)],
+        "glp_witness_plan_create_rand": [vp, vp, vp, u32, vp, u32, vp, u32, vp, sz, vp, u32, vp, u32, C.POINTER(vp)],
         "glp_witness_program_check": [C.POINTER(_WitnessProgramDesc)],
         "glp_witness_plan_free_info": [vp, C.POINTER(_WitnessPlanFreeInfo)],
         "glp_witness_plan_info": [vp, C.POINTER(_WitnessPlanInfo)],
@@ -331,6 +332,8 @@ def load_library():
     L.glp_witness_plan_free.restype = None
     L.glp_witness_num_units.restype = u32
     L.glp_witness_num_units.argtypes = [vp, u32]
+    L.glp_witness_plan_num_random.restype = u32
+    L.glp_witness_plan_num_random.argtypes = [vp]
     L.glp_gate_program_free.restype = None
     _lib = L
     return L
@@ -1348,15 +1351,29 @@ class Circuit:
             _chk(L.glp_witness_unit_columns(self._h, int(gate_index), u, out[u].ctypes.data_as(C.c_void_p)))
         return out
 
-    def witness_plan(self, input_cells, free_units=None, moduli=None, programs=None):
-        """glp_witness_plan_create(_ex, _prog): input_cells = flat positions col * n + row of the cells the caller sets -> WitnessPlan.
+    def witness_plan(self, input_cells, free_units=None, moduli=None, programs=None, random_cells=None):
+        """glp_witness_plan_create(_ex, _prog, _rand): input_cells = flat positions col * n + row of the cells the caller sets -> WitnessPlan.
         free_units = (units, cells): the generators that belong to no gate (include/glp.h, FREE UNITS) as a FREE_UNIT_DTYPE array
         (or anything np.asarray makes one of: rows of kind, modulus, cell_begin, len[6]) and the uint64 cells their runs point into;
         moduli = uint32 [num_moduli][8], little-endian limbs.  programs = the unit programs (witness_program.WitnessProgram, or any
         bag of code, pool, num_regs, num_inputs, num_outputs) that units of kind WGEN_PROGRAM name in their modulus field; given
-        (an empty list too), the plan is made by glp_witness_plan_create_prog."""
+        (an empty list too), the plan is made by glp_witness_plan_create_prog.  random_cells = flat positions of the cells that
+        generate() fills from the PRF of include/glp.h (RANDOM CELLS: a built circuit's witness_random_cells); given (an empty list
+        too), the plan is made by glp_witness_plan_create_rand."""
         cells = _a(input_cells).reshape(-1)
         h = C.c_void_p()
+        if random_cells is not None:
+            rnd = _a(random_cells).reshape(-1)
+            if cells.size >= 1 << 32 or rnd.size >= 1 << 32:
+                raise GlpError(-1, "input_cells or random_cells too long for a uint32 count")
+            if free_units is None:
+                if moduli is not None:
+                    raise GlpError(-1, "moduli without free_units")
+                if programs is not None:
+                    raise GlpError(-1, "programs without free_units")
+                free_units = (np.zeros(0, FREE_UNIT_DTYPE), np.zeros(0, np.uint64))
+            if programs is None:
+                programs = []
         if free_units is None:
             if moduli is not None:
                 raise GlpError(-1, "moduli without free_units")
@@ -1381,7 +1398,13 @@ class Circuit:
                 raise GlpError(-1, "free_units or moduli too long for a uint32 count")
             args = (self.ctx._h, self._h, _p(cells) if cells.size else None, cells.size, units.ctypes.data_as(C.c_void_p) if units.size else None,
                     units.size, _p(fcells) if fcells.size else None, fcells.size, mod.ctypes.data_as(C.c_void_p) if mod.size else None, mod.size // 8)
-            if programs is None:
+            if random_cells is not None:
+                if len(programs) >= 1 << 32:
+                    raise GlpError(-1, "programs too long for a uint32 count")
+                descs, _keep = witness_program_descs(programs)
+                _chk(load_library().glp_witness_plan_create_rand(*args[:4], _p(rnd) if rnd.size else None, rnd.size, *args[4:],
+                                                                 descs if len(programs) else None, len(programs), C.byref(h)))
+            elif programs is None:
                 _chk(load_library().glp_witness_plan_create_ex(*args, C.byref(h)))
             else:
                 if len(programs) >= 1 << 32:
@@ -1494,6 +1517,11 @@ class WitnessPlan:
         if not out["num_stuck_free_units"]:
             out["first_stuck_free_unit"] = None
         return out
+
+    @property
+    def num_random(self):
+        """glp_witness_plan_num_random: the cells generate() fills from the PRF."""
+        return int(load_library().glp_witness_plan_num_random(self._h))
 
     def cell_waves(self):
         d = self.circuit.desc

@@ -8,17 +8,18 @@
 //     type p0 p1                                  per gate
 //     row_gate[2^lg]                              -1: a row of no gate
 //     pos[num_routed * 2^lg]                      the decoded permutation, flat positions col * 2^lg + row
-//     null_mask                                   bit 0..4: hand input_cells, units, cells, moduli, programs over as null pointers
+//     null_mask                                   bit 0..4: hand input_cells, units, cells, moduli, programs over as null pointers; bit 5: random_cells
 //     num_inputs  input_cells[num_inputs]
 //     num_units   then per unit: kind modulus cell_begin len[0..5]
 //     num_cells  given  cells[given]              given = num_cells, but for the refusal of a num_cells no machine holds
 //     num_moduli  then per modulus 8 limbs
 //     with_programs  num_programs  then per program: num_inputs num_outputs num_regs num_instructions num_pool
+//     num_random  random_cells[num_random]        optional: input that ends after the programs has no random cells
 // (a program's code and pool are not part of the request: word i of program p's code is p << 32 | i, of its pool 1 << 63 | p << 32 | i.)
 // The stages run in the library's order.  stdout: one line per figure or list, its name first -- info (num_waves num_units
 // num_stuck_units num_copies num_cells_known widest_wave_units stuck_row stuck_gate stuck_unit), free_info (num_free_units
 // num_stuck_free_units first_stuck_free_unit widest_wave_free_units), prog_lds, cell_waves, unit_off, units (row gu ...), copy_off, copies
-// (src dst ...), inputs, free_off, free_units (kind modulus cell_begin len[0..5] ...), free_cells, prog_chunk_off, prog_chunks (prog
+// (src dst ...), inputs, random, free_off, free_units (kind modulus cell_begin len[0..5] ...), free_cells, prog_chunk_off, prog_chunks (prog
 // first count ...), prog_units, prog_tab (code_off code_words pool_off num_inputs ...), prog_image.  A refusal prints
 // "refused <code> <message>" instead and exits with status 3; unusable input exits with status 2.
 //
@@ -100,8 +101,15 @@ int main() {
         d.code = code[p].data(); d.num_instructions = (u32)e; d.pool = pool[p].data(); d.num_pool = (u32)f;
         d.num_regs = (u32)c; d.num_inputs = (u32)a; d.num_outputs = (u32)b;
     }
+    std::vector<uint64_t> random_cells;
+    if (rd(&a)) {                                                // the optional last line
+        NEED(a >= 0 && a <= (1 << 28));
+        random_cells.resize((size_t)a);
+        for (uint64_t &v : random_cells) { unsigned long long x; NEED(rdu(&x)); v = x; }
+    }
     auto ptr = [&](int bit, auto &v) { return null_mask >> bit & 1 ? nullptr : v.data(); };
-    const WPlanRequest rq = {"witness_plan_host", ptr(0, input_cells), (u32)input_cells.size(), ptr(1, units), (u32)units.size(), ptr(2, cells),
+    const WPlanRequest rq = {"witness_plan_host", ptr(0, input_cells), (u32)input_cells.size(), ptr(5, random_cells), (u32)random_cells.size(),
+                             ptr(1, units), (u32)units.size(), ptr(2, cells),
                              (size_t)num_cells, ptr(3, moduli), (u32)(moduli.size() / 8), ptr(4, programs), (u32)programs.size(), with_programs != 0};
     const WPlanCircuit cv = {lg, nw, nr, ng, gates.data(), row_gate.data(), pos.data()};
     WPlanState s;
@@ -128,6 +136,7 @@ int main() {
     words("copy_off", L.copy_off);
     line("copies", L.copies, [](const WCopy &x) { printf(" %u %u", x.src, x.dst); });
     words("inputs", L.inputs);
+    words("random", L.random);
     words("free_off", L.free_off);
     free_units("free_units", L.free_units);
     words("free_cells", L.free_cells);

@@ -504,6 +504,23 @@ __global__ __launch_bounds__(256) void k_witness_read_cells(const u64 *wires, co
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i < num_cells) out[(size_t)blockIdx.y * num_cells + i] = wires[(size_t)blockIdx.y * per_proof + cells[i]];
 }
+// The random cells of a plan (include/glp.h, RANDOM CELLS): one lane per block of eight cells, blockIdx.y = proof.  One permutation of
+// the seed, the tag and the block's number gives the block's eight values (the rate words; the capacity words go nowhere).  The
+// positions were range-checked by the planner; every count here is the 8 of the block, the tail of the last block is masked.
+__global__ __launch_bounds__(256) void k_witness_random(u64 *wires, const u32 *cells, u32 num_random, size_t per_proof, u64 seed0, u64 seed1, u64 seed2,
+                                                        u64 seed3) {
+    const u32 b = blockIdx.x * 256 + threadIdx.x;
+    if ((u64)b * 8 >= num_random) return;
+    const u32 left = num_random - b * 8;                  // >= 1
+    u32 at[8];
+#pragma unroll
+    for (u32 j = 0; j < 8; j++) at[j] = j < left ? cells[(size_t)b * 8 + j] : NONE;
+    u64 s[12] = {seed0, seed1, seed2, add(seed3, (u64)blockIdx.y), (u64)GLP_SALT_TAG_WITNESS, (u64)b, 0 /* b >> 32: a plan lists fewer than 2^32 cells */, 0, 0, 0, 0, 0};
+    pos::permute(s);
+    u64 *W = wires + (size_t)blockIdx.y * per_proof;
+#pragma unroll
+    for (u32 j = 0; j < 8; j++) if (at[j] != NONE) W[at[j]] = s[j];
+}
 }  // namespace
 
 #include "witness_program.inc"
@@ -511,7 +528,8 @@ __global__ __launch_bounds__(256) void k_witness_read_cells(const u64 *wires, co
 struct glp_witness_plan : WPlanKept {              // the figures, cell_waves and the wave offsets stay on the host (witness_plan.h)
     glp_ctx *ctx = nullptr;
     const glp_circuit *cc = nullptr;
-    u32 num_inputs = 0, narrow_max = WITNESS_NARROW_MAX_DEFAULT;
+    u32 num_inputs = 0, num_random = 0, narrow_max = WITNESS_NARROW_MAX_DEFAULT;
+    u32 *dev_random = nullptr;                     // the random cells in the caller's order; null without any
     WUnit *dev_units = nullptr;
     WCopy *dev_copies = nullptr;
     u32 *dev_unit_off = nullptr, *dev_copy_off = nullptr, *dev_inputs = nullptr;
@@ -530,13 +548,13 @@ extern "C" void glp_witness_plan_free(glp_witness_plan *p) {
     glp_ctx *c = p->ctx;
     if (bind(c) == GLP_OK) (void)hipStreamSynchronize(c->stream);
     c->release(p->dev_units); c->release(p->dev_copies); c->release(p->dev_unit_off); c->release(p->dev_copy_off);
-    c->release(p->dev_inputs); c->release(p->dev_vals);
+    c->release(p->dev_inputs); c->release(p->dev_random); c->release(p->dev_vals);
     c->release(p->dev_free_units); c->release(p->dev_free_off); c->release(p->dev_free_cells); c->release(p->dev_moduli);
     c->release(p->dev_prog_chunks); c->release(p->dev_prog_units); c->release(p->dev_prog_tab); c->release(p->dev_prog_image);
     delete p;
 }
 
-// The driver of the planner (witness_plan.h) behind the three entry points: the stages in their order, between them what needs the device
+// The driver of the planner (witness_plan.h) behind the four entry points: the stages in their order, between them what needs the device
 // (the selectors for the gate of every row, the decoded permutation), at the end the upload; it holds the guard of the host tables' allocation.
 static int witness_plan_create(glp_ctx *c, const glp_circuit *cc, const WPlanRequest &rq, glp_witness_plan **out) try {
     const char *fn = rq.fn;
@@ -577,7 +595,7 @@ static int witness_plan_create(glp_ctx *c, const glp_circuit *cc, const WPlanReq
     GLP_TRY(wplan_lists(rq, cv, s));
     const WPlanLists &L = s.lists;
     std::unique_ptr<glp_witness_plan> p(new glp_witness_plan);
-    p->ctx = c; p->cc = cc; p->num_inputs = rq.num_inputs;
+    p->ctx = c; p->cc = cc; p->num_inputs = rq.num_inputs; p->num_random = rq.num_random;
     if (const char *e = getenv("GLP_WITNESS_NARROW_MAX")) p->narrow_max = (u32)std::min<unsigned long long>(strtoull(e, nullptr, 10), 0xFFFFFFFFull);
     static_cast<WPlanKept &>(*p) = std::move(static_cast<WPlanKept &>(s.lists));
     int rc = GLP_OK;
@@ -588,6 +606,7 @@ static int witness_plan_create(glp_ctx *c, const glp_circuit *cc, const WPlanReq
         if (rc == GLP_OK && !v.empty()) rc = h2d(c, *dev, v.data(), v.size() * sizeof(v[0]));
     };
     up(&p->dev_units, L.units); up(&p->dev_copies, L.copies); up(&p->dev_unit_off, p->unit_off); up(&p->dev_copy_off, p->copy_off); up(&p->dev_inputs, L.inputs);
+    if (rq.num_random) up(&p->dev_random, L.random);
     if (rq.num_units) {
         const std::vector<u32> mod32(rq.moduli, rq.moduli + (size_t)rq.num_moduli * 8);
         up(&p->dev_free_units, L.free_units); up(&p->dev_free_off, p->free_off); up(&p->dev_free_cells, L.free_cells); up(&p->dev_moduli, mod32);
@@ -604,18 +623,27 @@ extern "C" int glp_witness_plan_create_ex(glp_ctx *c, const glp_circuit *cc, con
                                           const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
                                           const uint32_t *moduli, uint32_t num_moduli, glp_witness_plan **out) {
     // without programs kind GLP_WGEN_PROGRAM stays an unknown kind
-    return witness_plan_create(c, cc, {"glp_witness_plan_create_ex", input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, nullptr, 0, false}, out);
+    return witness_plan_create(c, cc, {"glp_witness_plan_create_ex", input_cells, num_inputs, nullptr, 0, units, num_units, cells, num_cells, moduli, num_moduli, nullptr, 0, false}, out);
 }
 
 extern "C" int glp_witness_plan_create_prog(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
                                             const glp_witness_free_unit *units, uint32_t num_units, const uint64_t *cells, size_t num_cells,
                                             const uint32_t *moduli, uint32_t num_moduli, const glp_witness_program_desc *programs,
                                             uint32_t num_programs, glp_witness_plan **out) {
-    return witness_plan_create(c, cc, {"glp_witness_plan_create_prog", input_cells, num_inputs, units, num_units, cells, num_cells, moduli, num_moduli, programs, num_programs, true}, out);
+    return witness_plan_create(c, cc, {"glp_witness_plan_create_prog", input_cells, num_inputs, nullptr, 0, units, num_units, cells, num_cells, moduli, num_moduli, programs, num_programs, true}, out);
 }
 
+extern "C" int glp_witness_plan_create_rand(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs,
+                                            const uint64_t *random_cells, uint32_t num_random, const glp_witness_free_unit *units, uint32_t num_units,
+                                            const uint64_t *cells, size_t num_cells, const uint32_t *moduli, uint32_t num_moduli,
+                                            const glp_witness_program_desc *programs, uint32_t num_programs, glp_witness_plan **out) {
+    return witness_plan_create(c, cc, {"glp_witness_plan_create_rand", input_cells, num_inputs, random_cells, num_random, units, num_units, cells, num_cells, moduli, num_moduli, programs, num_programs, true}, out);
+}
+
+extern "C" uint32_t glp_witness_plan_num_random(const glp_witness_plan *p) { return p ? p->num_random : 0; }
+
 extern "C" int glp_witness_plan_create(glp_ctx *c, const glp_circuit *cc, const uint64_t *input_cells, uint32_t num_inputs, glp_witness_plan **out) {
-    return witness_plan_create(c, cc, {"glp_witness_plan_create", input_cells, num_inputs, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, false}, out);
+    return witness_plan_create(c, cc, {"glp_witness_plan_create", input_cells, num_inputs, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, false}, out);
 }
 
 extern "C" int glp_witness_plan_free_info(const glp_witness_plan *p, struct glp_witness_plan_free_info *out) {
@@ -670,6 +698,8 @@ extern "C" int glp_witness_generate(glp_ctx *c, const glp_witness_plan *p, uint3
         pm->vals_cap = nvals;
     }
     if (nvals) GLP_TRY(h2d(c, pm->dev_vals, input_values, nvals * 8));
+    u64 seed[4] = {0, 0, 0, 0};                                    // random cells: one seed per call, proof k draws with seed3 + k
+    if (p->num_random) GLP_TRY(salt_seed_draw(c, seed));
     WGen g;
     memset(&g, 0, sizeof(g));
     g.a.wires = dev_wires; g.a.consts = cc->dev_consts; g.a.gates = cc->dev_gates;
@@ -682,6 +712,12 @@ extern "C" int glp_witness_generate(glp_ctx *c, const glp_witness_plan *p, uint3
     if (flags & GLP_WITNESS_GEN_ZERO_FIRST) GLP_HIP(hipMemsetAsync(dev_wires, 0, (size_t)K * nw * n * 8, c->stream));
     // a wave is wide (one launch for its units, one for its copies) while the proofs alone do not fill the chip and it holds more than
     // narrow_max units; runs of the other waves are walked by one workgroup per proof
+    // the random cells belong to wave 0, beside the scatter of the inputs and before its copies, whichever form wave 0 takes
+    if (p->num_random) {
+        hipLaunchKernelGGL(k_witness_random, dim3((unsigned)(((size_t)p->num_random + 8 * 256 - 1) / (8 * 256)), K), dim3(256), 0, c->stream, dev_wires, p->dev_random, p->num_random,
+                           (size_t)nw * n, seed[0], seed[1], seed[2], seed[3]);
+        GLP_HIP(hipGetLastError());
+    }
     const u32 nwaves = p->info.num_waves;
     auto free_count = [&](u32 w) -> size_t { return has_free ? p->free_off[w + 1] - p->free_off[w] : 0; };      // wave 0 holds none
     // a wave with program units is always wide: its chunks get a launch of their own between its units and its copies
@@ -691,7 +727,7 @@ extern "C" int glp_witness_generate(glp_ctx *c, const glp_witness_plan *p, uint3
     pa.wires = dev_wires; pa.image = p->dev_prog_image; pa.progs = p->dev_prog_tab; pa.chunks = p->dev_prog_chunks; pa.units = p->dev_prog_units;
     pa.cells = p->dev_free_cells; pa.nw = nw; pa.lg = cc->d.degree_bits;
     auto wide = [&](u32 w) {
-        const size_t cnt = (w == 0 ? ni : p->unit_off[w + 1] - p->unit_off[w]) + free_count(w);
+        const size_t cnt = (w == 0 ? (size_t)ni + p->num_random : p->unit_off[w + 1] - p->unit_off[w]) + free_count(w);      // wave 0: inputs and random cells
         return prog_count(w) || (K < (u32)c->num_cus && cnt > p->narrow_max);
     };
     for (u32 w = 0; w <= nwaves;) {

@@ -133,6 +133,7 @@ inline WFreeShape witness_free_shape(u32 kind) {
 struct WPlanRequest {
     const char *fn;
     const uint64_t *input_cells; u32 num_inputs;
+    const uint64_t *random_cells; u32 num_random;      // wave-0 sources as the inputs are; their values come from the PRF (glp_witness_plan_create_rand)
     const glp_witness_free_unit *units; u32 num_units;
     const uint64_t *cells; size_t num_cells;
     const u32 *moduli; u32 num_moduli;               // [num_moduli][8]
@@ -162,6 +163,7 @@ struct WPlanLists : WPlanKept {
     std::vector<WUnit> units;                         // by wave, in (row, unit) order; wave 0 holds none
     std::vector<WCopy> copies;                        // by wave, in order of the destination
     std::vector<u32> inputs, free_cells;              // input_cells and cells[], 32 bits each (NONE: GLP_WGEN_NO_CELL)
+    std::vector<u32> random;                          // random_cells, 32 bits each, in the caller's order
     std::vector<WFree> free_units, prog_units;        // by wave, in the caller's order | sorted by (wave, program), then in the caller's order
     std::vector<WProgChunk> prog_chunks;              // by wave: at most 64 units of one program each
     std::vector<WProgEntry> prog_tab;
@@ -169,7 +171,7 @@ struct WPlanLists : WPlanKept {
 };
 // The planner's tables: each stage reads what the stages before it left and adds its own (the number in front).
 struct WPlanState {
-    std::vector<u32> input_at;                        // 1: [cells] which input names a cell (NONE: none)
+    std::vector<u32> input_at;                        // 1: [cells] which input names a cell, num_inputs + i for random cell i (NONE: none)
     std::vector<u32> f_n[2], fcells32;                // 2: per free unit its input [0] and output [1] cells; cells[] in 32 bits
     std::vector<std::vector<std::vector<u32>>> g[2];  // 3: per gate and unit the columns read [0] and written [1]
     std::vector<size_t> row_first;                    //    [n + 1]: unit k of the plan = unit k - row_first[row] of its row
@@ -206,6 +208,7 @@ inline int wplan_bucket(const char *fn, const char *what, u32 num_waves, Each &&
 // ---- 1. the request: null pointers (the driver checks the programs between the two) | the bounds, the input cells, the moduli
 inline int wplan_check_pointers(const WPlanRequest &rq) {
     WPLAN_REQUIRE(rq.input_cells || rq.num_inputs == 0, "%s: input_cells is null, num_inputs = %u", rq.fn, rq.num_inputs);
+    WPLAN_REQUIRE(rq.random_cells || rq.num_random == 0, "%s: random_cells is null, num_random = %u", rq.fn, rq.num_random);
     WPLAN_REQUIRE(rq.units || rq.num_units == 0, "%s: units is null, num_units = %u", rq.fn, rq.num_units);
     WPLAN_REQUIRE(rq.cells || rq.num_cells == 0, "%s: cells is null, num_cells = %zu", rq.fn, rq.num_cells);
     WPLAN_REQUIRE(rq.moduli || rq.num_moduli == 0, "%s: moduli is null, num_moduli = %u", rq.fn, rq.num_moduli);
@@ -226,6 +229,19 @@ inline int wplan_check_request(const WPlanRequest &rq, const WPlanCircuit &cv, W
         u32 &at = s.input_at[(size_t)rq.input_cells[i]];
         WPLAN_REQUIRE(at == NONE, "%s: input_cells[%u] = %llu is listed twice (also input_cells[%u])", fn, i, (unsigned long long)rq.input_cells[i], at);
         at = i;
+    }
+    // the random cells: wave-0 sources like the inputs, so a cell is one or the other, once
+    WPLAN_REQUIRE((size_t)rq.num_inputs + rq.num_random < NONE, "%s: num_inputs + num_random = %zu, a plan addresses fewer than 2^32 - 1", fn,
+                  (size_t)rq.num_inputs + rq.num_random);
+    for (u32 i = 0; i < rq.num_random; i++)
+        WPLAN_REQUIRE(rq.random_cells[i] < cells, "%s: random_cells[%u] = %llu is out of range (num_wires * 2^degree_bits = %zu cells)", fn, i,
+                      (unsigned long long)rq.random_cells[i], cells);
+    for (u32 i = 0; i < rq.num_random; i++) {
+        const unsigned long long cell = rq.random_cells[i];
+        u32 &at = s.input_at[(size_t)cell];
+        WPLAN_REQUIRE(at == NONE || at < rq.num_inputs, "%s: random_cells[%u] = %llu is listed twice (also random_cells[%u])", fn, i, cell, at - rq.num_inputs);
+        WPLAN_REQUIRE(at == NONE, "%s: random_cells[%u] = %llu is also input_cells[%u]", fn, i, cell, at);
+        at = rq.num_inputs + i;
     }
     WPLAN_REQUIRE(rq.num_cells < NONE, "%s: num_cells = %zu, a plan addresses fewer than 2^32 - 1", fn, rq.num_cells);
     for (u32 i = 0; i < rq.num_moduli; i++) {
@@ -334,14 +350,25 @@ inline int wplan_classes(const WPlanRequest &rq, const WPlanCircuit &cv, WPlanSt
         }
     }
     for (size_t p = routed; p < cells; p++) cls[p] = (u32)p;
-    s.class_wave.assign(cells, -1);                       // two inputs in one class are refused
-    std::vector<u32> class_input(rq.num_inputs ? cells : 0, NONE);
+    s.class_wave.assign(cells, -1);                       // two inputs in one class are refused; so are two random cells, and one of each
+    std::vector<u32> class_input(rq.num_inputs + rq.num_random ? cells : 0, NONE);
     for (u32 i = 0; i < rq.num_inputs; i++) {
         u32 &first = class_input[cls[(size_t)rq.input_cells[i]]];
         WPLAN_REQUIRE(first == NONE, "%s: input_cells[%u] = %llu and input_cells[%u] = %llu lie in one copy class: one value per class", rq.fn, first,
                       (unsigned long long)rq.input_cells[first], i, (unsigned long long)rq.input_cells[i]);
         first = i;
         s.class_wave[cls[(size_t)rq.input_cells[i]]] = 0;
+    }
+    for (u32 i = 0; i < rq.num_random; i++) {
+        const unsigned long long cell = rq.random_cells[i];
+        u32 &first = class_input[cls[(size_t)cell]];
+        if (first != NONE && first >= rq.num_inputs)
+            return glp::set_error(GLP_ERR_ARG, "%s: random_cells[%u] = %llu and random_cells[%u] = %llu lie in one copy class: one value per class", rq.fn,
+                                  first - rq.num_inputs, (unsigned long long)rq.random_cells[first - rq.num_inputs], i, cell);
+        WPLAN_REQUIRE(first == NONE, "%s: random_cells[%u] = %llu and input_cells[%u] = %llu lie in one copy class: one value per class", rq.fn, i, cell, first,
+                      (unsigned long long)rq.input_cells[first]);
+        first = rq.num_inputs + i;
+        s.class_wave[cls[(size_t)cell]] = 0;
     }
     return GLP_OK;
 }
@@ -461,6 +488,7 @@ inline int wplan_lists(const WPlanRequest &rq, const WPlanCircuit &cv, WPlanStat
     }, L.copy_off, L.copies));
     info.num_copies = L.copy_off[num_waves + 1];
     L.inputs.assign(rq.input_cells, rq.input_cells + rq.num_inputs);      // every one is below 2^32
+    L.random.assign(rq.random_cells, rq.random_cells + rq.num_random);
     L.free_cells.swap(s.fcells32);
     return GLP_OK;
 }

@@ -388,7 +388,8 @@ class GadgetBuilder:
 
     # ---- build(): rows -> synth.Builder (selectors, sigmas) + the witness
     def build(self, min_log_n=0, blinding_seed=None):
-        """blinding_seed: with a zero_knowledge config, the seed of the blinding values (tests only; default: OS entropy)"""
+        """blinding_seed: with a zero_knowledge config, the seed of the blinding values (tests only; default: OS entropy).  The cells
+        blind() randomises come through as witness_random_cells (synth.Builder.build): a witness plan's random_cells."""
         from . import poseidon_py as pp
         cfg = self.cfg
         # public-input hash in circuit: hash_n_to_hash_no_pad over the public inputs, PoseidonGate rows (rate 8, overwrite

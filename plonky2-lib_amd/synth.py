@@ -242,6 +242,13 @@ class Builder:
         for col in range(nr):
             self.connect_pairs(r1, col, r2, col)
         self.blinded = True
+        # the cells randomised above, as a witness plan's random_cells (flat positions col * n + row, column by column so that
+        # consecutive entries are consecutive rows): the r rows, row r1 of every pair (r2 is its copy), the unused PublicInputGate wires
+        wires, routed = np.arange(cfg.num_wires, dtype=np.int64)[:, None] * self.n, np.arange(nr, dtype=np.int64)[:, None] * self.n
+        cells = [(wires + np.arange(first_row, first_row + r, dtype=np.int64)).reshape(-1), (routed + r1).reshape(-1)]
+        if pi_row is not None:
+            cells.append(wires[4:, 0] + pi_row)
+        self.random_cells = np.concatenate(cells).astype(np.uint64)
         return end
 
     def connect_cycle(self, rows, cols):
@@ -291,6 +298,8 @@ class Builder:
         c.zero_knowledge = bool(getattr(cfg, "zero_knowledge", False))
         if c.zero_knowledge and not getattr(self, "blinded", False):
             raise ValueError("a zero_knowledge config needs the blinding rows: call blind() before build()")
+        # what blind() randomised, for Circuit.witness_plan(random_cells=...); empty for a circuit without blinding
+        c.witness_random_cells = np.array(getattr(self, "random_cells", ()), dtype=np.uint64)
         return c
 
 
