@@ -59,7 +59,10 @@ GLP_API int glp_device_count(void);
  *                         (FRI layers alike; Merkle levels: 12 of 16 lanes up to 8192 parents, a quad up to the second threshold)
  *   GLP_HOST_THREADS      (read on the first glp_prove_batch of a context): host threads for the transcripts of a batch
  *   GLP_WITNESS_NARROW_MAX (read when a witness plan is made; default 256): a wave of glp_witness_generate with more units than this gets
- *                         launches of its own while num_proofs is below the CU count ("witness generation, the dataflow half") */
+ *                         launches of its own while num_proofs is below the CU count ("witness generation, the dataflow half")
+ *   GLP_POOL_POISON       = 0..255 (default unset; a test switch, slow): every block of the context's device pool, the library's own scratch
+ *                         and glp_dev_alloc alike, is filled with that byte when it is handed out and again when it is returned, on the
+ *                         context's stream, which is drained after each fill.  Results must not depend on it. */
 GLP_API int glp_ctx_create(int device_id, glp_ctx **out);
 GLP_API void glp_ctx_destroy(glp_ctx *ctx);
 GLP_API int glp_ctx_synchronize(glp_ctx *ctx);

@@ -25,6 +25,14 @@ int set_error(int code, const char *fmt, ...) {
 using namespace glp;
 
 // ------------------------------------------------------------------------------------------ ctx
+// GLP_POOL_POISON: every byte of a block is the poison byte when it is handed out and again when it comes back, so no kernel's
+// result can rest on what a fresh hipMalloc block or the block's last user happened to hold.  Only `stream` is drained, never
+// copy_stream: the fill must not order the two streams for a caller that forgot to.
+static int poison_fill(glp_ctx *c, void *p, size_t bytes) {
+    GLP_HIP(hipMemsetAsync(p, c->pool_poison_byte, bytes, c->stream));
+    GLP_HIP(hipStreamSynchronize(c->stream));
+    return GLP_OK;
+}
 int glp_ctx::alloc(void **p, size_t bytes) {
     if (bytes == 0) bytes = 8;
     bytes = (bytes + 255) & ~(size_t)255;
@@ -34,7 +42,7 @@ int glp_ctx::alloc(void **p, size_t bytes) {
         pool.erase(it);
         pool_bytes -= bytes;
         live[*p] = bytes;
-        return GLP_OK;
+        return pool_poison ? poison_fill(this, *p, bytes) : GLP_OK;
     }
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) {
@@ -43,12 +51,13 @@ int glp_ctx::alloc(void **p, size_t bytes) {
     }
     if (e != hipSuccess) return set_error(GLP_ERR_HIP, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
     live[*p] = bytes;
-    return GLP_OK;
+    return pool_poison ? poison_fill(this, *p, bytes) : GLP_OK;
 }
 void glp_ctx::release(void *p) {
     if (!p) return;
     auto it = live.find(p);
     if (it == live.end()) return;
+    if (pool_poison) (void)poison_fill(this, p, it->second);  // the callers have drained the stream: a reader that outlives the release sees poison
     pool.insert({it->second, p});
     pool_bytes += it->second;
     live.erase(it);
@@ -110,6 +119,11 @@ int glp_ctx_create(int device_id, glp_ctx **out) {
     if (const char *e3 = getenv("GLP_NTT_STRIDED32_LW")) { const int v = atoi(e3); if (v == 3 || v == 4) c->strided32_lw = v; }
     if (const char *e4 = getenv("GLP_MERKLE_COOP_MAX")) c->merkle_coop_max = (size_t)strtoull(e4, nullptr, 10);
     if (const char *e5 = getenv("GLP_MERKLE_QUAD_MAX")) c->merkle_quad_max = (size_t)strtoull(e5, nullptr, 10);
+    if (const char *e6 = getenv("GLP_POOL_POISON")) {
+        char *end = nullptr;
+        const long v = strtol(e6, &end, 10);
+        if (end != e6 && *end == 0 && v >= 0 && v <= 255) { c->pool_poison = true; c->pool_poison_byte = (int)v; }
+    }
     GLP_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     {
         hipError_t e2 = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);

@@ -44,6 +44,8 @@ struct glp_ctx {
     std::multimap<size_t, void *> pool;
     std::map<void *, size_t> live;
     size_t pool_bytes = 0;
+    bool pool_poison = false;            // GLP_POOL_POISON = 0..255: alloc and release fill the block with that byte (a test switch; api.hip)
+    int pool_poison_byte = 0;
     std::map<int, glp::NttPlan *> ntt_plans;                       // key: log_n
     std::map<std::pair<std::pair<int, int>, u64>, glp::LdePlan *> lde_plans;  // key: ((log_n, rate_bits), shift)
     unsigned long long lde_clock = 0;                              // LRU stamps for lde_plans
