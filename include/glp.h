@@ -13,7 +13,13 @@
  * Conventions: every function returns GLP_OK (0) or a negative error code and records a message
  * retrievable with glp_last_error() (thread-local).  Pointers are caller-owned HOST memory
  * unless the parameter name starts with `dev_`.  Field elements are canonical uint64_t
- * (< 2^64 - 2^32 + 1); extension elements are two consecutive uint64_t (a + b*X, X^2 = 7).
+ * (< p = 2^64 - 2^32 + 1); extension elements are two consecutive uint64_t (a + b*X, X^2 = 7).
+ * A word >= p in an array of field elements, at every entry point that takes one:
+ *   HOST array     refused: GLP_ERR_ARG before anything is allocated or launched, the message naming the function, the parameter,
+ *                  the position (proof / column / index) and the value; an in-place array is left as it was, no handle comes back.
+ *   DEVICE array   (`dev_*`, or `*_on_device` != 0) reduced mod p once as it is loaded: every result is word for word the result
+ *                  for `input % p`, everything stored or handed back is canonical, a const buffer is not written to.
+ * Seeds are taken mod p.  Each entry point below says "host: refused" / "device: reduced" where its wording is not the rule's own.
  * A glp_ctx is bound to one GPU and one HIP stream; calls on one ctx must be serialised by the
  * caller; distinct ctxs are independent (this is what shards a batch of proofs over 8 GPUs).
  * There is no CPU fallback: without a usable gfx950 device glp_ctx_create fails.
@@ -90,14 +96,14 @@ GLP_API int glp_ctx_stage_count(glp_ctx *ctx);
 GLP_API int glp_ctx_stage_get(glp_ctx *ctx, int index, const char **name, float *ms, double *algorithmic_bytes);
 
 /* ---- primitives (used by the parity tests and by a fine-grained FFI binding) ------------------ */
-/* hash/poseidon.rs `Poseidon::poseidon`: permute `count` states of 12 elements on the GPU. */
+/* hash/poseidon.rs `Poseidon::poseidon`: permute `count` states of 12 elements on the GPU.  A word >= p: refused (host array). */
 GLP_API int glp_poseidon_permute(glp_ctx *ctx, uint64_t *states, size_t count);
 /* field/src/fft.rs `fft` / `ifft` on `ncols` independent columns of n = 2^log_n elements,
- * natural order in and out (values[i] = p(w^i), w = primitive_root_of_unity(log_n)). */
+ * natural order in and out (values[i] = p(w^i), w = primitive_root_of_unity(log_n)).  A word >= p: refused (host arrays), cols unchanged. */
 GLP_API int glp_fft(glp_ctx *ctx, uint64_t *cols, uint32_t ncols, uint32_t log_n);
 GLP_API int glp_ifft(glp_ctx *ctx, uint64_t *cols, uint32_t ncols, uint32_t log_n);
 /* polynomial/mod.rs `lde(rate_bits)` + `coset_fft(shift)`: in [ncols][n] coefficients,
- * out [ncols][n << rate_bits] values, out[c][i] = p_c(shift * W^i), natural order. */
+ * out [ncols][n << rate_bits] values, out[c][i] = p_c(shift * W^i), natural order.  A coefficient >= p: refused (host array). */
 GLP_API int glp_lde(glp_ctx *ctx, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
             uint64_t shift, uint64_t *out);
 
@@ -111,7 +117,9 @@ GLP_API int glp_fill_random_device(glp_ctx *ctx, uint64_t *dev_out, size_t count
  * glp_batch_from_coeffs  = PolynomialBatch::from_coeffs
  * Input layout: column-major [ncols][n], n = 2^log_n, natural order.  No blinding (the salted form is
  * glp_batch_from_values_salted below).
- * The *_device variants take a device pointer on the ctx's GPU (input already resident in HBM). */
+ * The *_device variants take a device pointer on the ctx's GPU (input already resident in HBM).
+ * A word >= p: the host entry points (these, the *_h and the salted one) refuse it naming column and index; the *_device ones reduce it
+ * as it is loaded, and the coefficients a from_coeffs batch keeps (glp_batch_coeffs) are the reduced ones. */
 GLP_API int glp_batch_from_values(glp_ctx *ctx, const uint64_t *values, uint32_t ncols, uint32_t log_n,
                           uint32_t rate_bits, uint32_t cap_height, glp_batch **out);
 GLP_API int glp_batch_from_values_device(glp_ctx *ctx, const uint64_t *dev_values, uint32_t ncols, uint32_t log_n,
@@ -178,7 +186,8 @@ GLP_API int glp_batch_digests(const glp_batch *b, uint64_t *out);
 /* ---- many-proof batches: num_proofs PolynomialBatches of one shape, built and held as one object ---------------------------------
  * The commitments of num_proofs proofs of one circuit that advance in lock step (glp_fri_begin_many below): one transform and one
  * Merkle launch over all of them instead of num_proofs glp_batch_from_* calls.
- *   values / coeffs  [num_proofs][ncols][n], natural order; host memory, or (*_on_device != 0) an HBM pointer on the ctx's GPU
+ *   values / coeffs  [num_proofs][ncols][n], natural order; host memory, or (*_on_device != 0) an HBM pointer on the ctx's GPU.
+ *                    A word >= p: host: refused naming proof, column and index; device: reduced as it is loaded
  *   seed             NULL: no blinding.  Else 4 words: member k is salted with (seed0, seed1, seed2, seed3 + k) and tag
  *                    GLP_SALT_TAG_BATCH, the rule of glp_prove_batch: member k is word for word
  *                    glp_batch_from_values_salted(member k's values, .., {seed0, seed1, seed2, seed3 + k})
@@ -226,7 +235,7 @@ GLP_API int glp_batch_lde_values(const glp_batch *b, uint32_t col_begin, uint32_
                                  uint64_t *out, int out_on_device);
 /* `PolynomialValues::coset_ifft(shift)` in place on host memory, cols [ncols][2^log_n]: natural-order values on shift * <w> in,
  * natural-order coefficients out.  The shape of glp_fft / glp_ifft, and the inverse of glp_lde with rate_bits = 0.  shift must be a
- * non-zero canonical field element (GLP_ERR_ARG otherwise). */
+ * non-zero canonical field element (GLP_ERR_ARG otherwise); a word >= p in cols: refused, cols unchanged. */
 GLP_API int glp_coset_ifft(glp_ctx *ctx, uint64_t *cols, uint32_t ncols, uint32_t log_n, uint64_t shift);
 /* values [num_proofs][num_polys][M], natural order on g <W_M> (the transposed `quotient_values` of `compute_quotient_polys`); host
  * memory, or (values_on_device != 0) an HBM pointer on the ctx's GPU.  Per polynomial `coset_ifft(g)` gives M coefficients, split
@@ -236,7 +245,8 @@ GLP_API int glp_coset_ifft(glp_ctx *ctx, uint64_t *cols, uint32_t ncols, uint32_
  * cap_height)` under `hasher`: word for word glp_batch_many_from_coeffs on those chunks with the same seed (tag
  * GLP_SALT_TAG_BATCH, member k salted with seed3 + k), and glp_batch_from_coeffs_h at num_proofs == 1 without a seed.
  * num_proofs and the size bounds are those of glp_batch_many_from_coeffs; sub_bits in 0..rate_bits (0: one chunk, a plain coset
- * iFFT).  Every accessor, glp_batch_member, glp_fri_begin* and glp_batch_lde_values take the result like any other batch. */
+ * iFFT).  Every accessor, glp_batch_member, glp_fri_begin* and glp_batch_lde_values take the result like any other batch.
+ * A value >= p: host: refused naming proof, column (the polynomial) and index; device: reduced as it is loaded. */
 GLP_API int glp_batch_from_coset_values(glp_ctx *ctx, const uint64_t *values, int values_on_device, uint32_t num_proofs,
                                         uint32_t num_polys, uint32_t log_n, uint32_t sub_bits, uint32_t rate_bits,
                                         uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out);
@@ -267,6 +277,7 @@ GLP_API uint32_t glp_perm_num_polys(const glp_perm_desc *desc);
  * circuit the library can prove, the result's cap is what glp_session_partial_products returns.  A zero denominator (probability about
  * n * num_routed_wires * 2^-64) is not detected, as in the session.
  *   wires    [num_proofs][num_wires][n] values on H      sigmas   [num_routed_wires][n] values on H, shared by all proofs
+ *            a word >= p of either: host: refused by name; device: reduced as it is loaded
  * Size bounds, log_n, rate_bits, cap_height and hasher: those of glp_batch_many_from_values. */
 GLP_API int glp_perm_zs_commit(glp_ctx *ctx, const glp_perm_desc *desc, uint32_t num_proofs,
                                const uint64_t *wires, int wires_on_device, const uint64_t *sigmas, int sigmas_on_device,
@@ -283,6 +294,7 @@ GLP_API int glp_perm_zs_commit(glp_ctx *ctx, const glp_perm_desc *desc, uint32_t
  *                   num_proofs members each (a glp_batch_member view is a batch of one).  Salted or not, each.
  *   gate_sums       NULL, or [num_proofs][num_challenges][M]: the caller's sum_t alpha^t (filtered gate constraint t), natural order on
  *                   the same coset.  With NULL the second summand is absent; the map is linear, so a caller may add its share afterwards.
+ *                   A word >= p: host: refused naming proof, column (the challenge) and index; device: reduced as it is loaded.
  *   out             [num_proofs][num_challenges][M]: what glp_batch_from_coset_values takes with num_polys = num_challenges.  Host
  *                   memory: the call returns after the copy; an HBM pointer: nothing is copied back.
  * Refused beyond the common rules: sub_bits > rate_bits; chunk_size > 2^sub_bits (the chunk check would exceed the quotient's
@@ -824,7 +836,9 @@ GLP_API const uint64_t *glp_circuit_file_public_inputs(const glp_circuit_file *f
  *     final_poly (ext coefficients) | pow_witness | public_inputs
  * The FRI proof-of-work witness is the SMALLEST valid one (the Rust prover's rayon `find_any`
  * returns an arbitrary valid one; every other word of the proof is a deterministic function of
- * the inputs and of that witness). */
+ * the inputs and of that witness).
+ * A word >= p: wires and public_inputs in host memory are refused naming column and index (glp_prove, and the public inputs of
+ * glp_prove_device and glp_prove_staged); dev_wires are reduced as they are loaded, so the proof is that of dev_wires % p. */
 GLP_API int glp_prove(glp_ctx *ctx, const glp_circuit *circuit, const uint64_t *wires, const uint64_t *public_inputs,
                       uint64_t *proof_out);
 GLP_API int glp_prove_device(glp_ctx *ctx, const glp_circuit *circuit, const uint64_t *dev_wires,
@@ -845,6 +859,7 @@ GLP_API int glp_prove_device(glp_ctx *ctx, const glp_circuit *circuit, const uin
  * there by glp_witness_fill(only_advice) before the proof starts -- for the secp256k1 trace 56 of 136 columns (41 %) never cross
  * PCIe.  The proof is word for word the proof of the complete witness provided every advice wire of the witness is either
  * written by a row-local generator or zero (true for witnesses of plonky2's generators; tests/test_gpu_witness.py). */
+/* glp_witness_stage: a word >= p in the columns it copies (all, or the routed ones with GLP_WITNESS_ROUTED_ONLY) is refused (host array). */
 typedef struct glp_witness glp_witness;
 #define GLP_WITNESS_ROUTED_ONLY 1u
 GLP_API int glp_host_alloc(glp_ctx *ctx, size_t bytes, void **host_out);      /* page-locked host memory */
@@ -859,8 +874,9 @@ GLP_API void glp_witness_free(glp_witness *witness);
  * latency when proved one by one; here every device stage is one launch over all num_proofs proofs and every host round trip
  * carries all their caps / openings, while the num_proofs Fiat-Shamir transcripts run on host threads (environment variable GLP_HOST_THREADS; default: the
  * cores this process may use -- affinity mask capped by the cgroup CPU quota -- up to 32; every context has its own pool).  proofs_out[k] is word for word what glp_prove returns for witness k.
- *   wires          [num_proofs][num_wires][n], host memory, or (wires_on_device != 0) an HBM pointer on the ctx's GPU
- *   public_inputs  [num_proofs][num_public_inputs]
+ *   wires          [num_proofs][num_wires][n], host memory, or (wires_on_device != 0) an HBM pointer on the ctx's GPU.  A word >= p:
+ *                  host: refused naming proof, column and index; device: reduced as it is loaded
+ *   public_inputs  [num_proofs][num_public_inputs], host: a word >= p is refused naming proof and index
  *   proofs_out     [num_proofs][glp_proof_words(circuit)]
  * Scope: num_challenges = 2 (every CircuitConfig the reference uses). */
 GLP_API int glp_prove_batch(glp_ctx *ctx, const glp_circuit *circuit, uint32_t num_proofs, const uint64_t *wires, int wires_on_device,
@@ -885,7 +901,7 @@ GLP_API int glp_prove_batch(glp_ctx *ctx, const glp_circuit *circuit, uint32_t n
  * GPU derives the 56 limb columns of the secp256k1 trace (41 % of the witness) and they never cross PCIe.
  * The row's gate is read from the circuit's selector polynomials.  Asynchronous on the ctx stream.
  * Inputs outside a gate's domain (plonky2's generators panic or write an unsatisfiable row there) never fault; what is written is
- * fixed: inputs are read as canonical u64, and a limb or bit generator decomposes only the bits it has wires for -- the low 32 bits
+ * fixed: inputs are reduced mod p as they are loaded (a cell that is not written keeps its word), and a limb or bit generator decomposes only the bits it has wires for -- the low 32 bits
  * of a u32 result (the result and carry wires themselves get the full field value), num_chunks * chunk_bits bits of a ComparisonGate
  * input (its result wire is the top bit of 2^chunk_bits + most significant difference), num_limbs digits of a BaseSum value; a
  * RandomAccessGate copy whose access index is >= 2^bits writes nothing for that copy (the extra constants are still written); a
@@ -1173,7 +1189,9 @@ GLP_API int glp_witness_check(glp_ctx *ctx, const glp_circuit *circuit, uint32_t
  * glp_prove() is this sequence driven by the library's built-in transcript; tests/test_gpu_prove.py drives it with the
  * oracle's Challenger and requires the identical proof. */
 typedef struct glp_session glp_session;
-/* wires: [num_wires][n]; wires_on_device != 0: an HBM pointer that must stay valid until glp_session_end */
+/* wires: [num_wires][n]; wires_on_device != 0: an HBM pointer that must stay valid until glp_session_end.  A word >= p: host wires
+ * and public_inputs are refused by name, no session is made; device wires are reduced as they are loaded.  The pow_witness of
+ * glp_session_queries (and of glp_fri_queries, glp_fri_queries_many) is a field element of the proof: >= p is refused. */
 GLP_API int glp_session_begin(glp_ctx *ctx, const glp_circuit *circuit, const uint64_t *wires, int wires_on_device,
                               const uint64_t *public_inputs, glp_session **out, uint64_t *wires_cap_out /* [2^cap_height][4] */,
                               uint64_t public_inputs_hash_out[4]);

@@ -6,6 +6,7 @@
 #include <string.h>
 #include "batch.h"
 #include "common.h"
+#include "host_pool.h"   // host_field_check: the canonical-form scan of host field arrays
 #include "keccak.h"
 #include "merkle.h"
 #include "ntt.h"
@@ -245,6 +246,11 @@ int glp_poseidon_permute(glp_ctx *c, uint64_t *states, size_t count) {
     GLP_REQUIRE(c && (states || !count), "null argument");
     GLP_TRY(bind(c));
     if (!count) return GLP_OK;
+    {
+        const size_t bad = first_noncanonical_pooled(c, states, count * 12);
+        GLP_REQUIRE(bad == count * 12, "glp_poseidon_permute: states: state %zu, index %zu = 0x%016llx is not a canonical field element (>= p)", bad / 12,
+                    bad % 12, (unsigned long long)states[bad == count * 12 ? 0 : bad]);
+    }
     return on_device_copy(c, states, count * 12, states, count * 12, [&](Scratch &, u64 *a, u64 **res) {
         *res = a;
         return poseidon_permute_states(c, a, count);
@@ -257,6 +263,7 @@ int glp_fft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n) {
     if (!ncols) return GLP_OK;
     if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
     const size_t tot = (size_t)ncols << log_n;
+    GLP_TRY(host_field_check(c, "glp_fft", "cols", cols, 0, ncols, (size_t)1 << log_n));
     return on_device_copy(c, cols, tot, cols, tot, [&](Scratch &s, u64 *a, u64 **res) {
         u64 *b;
         GLP_TRY(s.words(&b, tot));
@@ -272,6 +279,7 @@ int glp_ifft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n) {
     if (!ncols) return GLP_OK;
     if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
     const size_t tot = (size_t)ncols << log_n;
+    GLP_TRY(host_field_check(c, "glp_ifft", "cols", cols, 0, ncols, (size_t)1 << log_n));
     return on_device_copy(c, cols, tot, cols, tot, [&](Scratch &s, u64 *a, u64 **res) {
         u64 *b;
         GLP_TRY(s.words(&b, tot));
@@ -290,6 +298,7 @@ int glp_lde(glp_ctx *c, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, 
     if (!ncols) return GLP_OK;
     if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
     const size_t tot = (size_t)ncols << log_n, TOT = tot << rate_bits;
+    GLP_TRY(host_field_check(c, "glp_lde", "coeffs", coeffs, 0, ncols, (size_t)1 << log_n));
     return on_device_copy(c, coeffs, tot, out, TOT, [&](Scratch &s, u64 *a, u64 **res) {
         u64 *b, *l;
         GLP_TRY(s.words(&b, tot));
@@ -309,6 +318,7 @@ int glp_coset_ifft(glp_ctx *c, uint64_t *cols, uint32_t ncols, uint32_t log_n, u
     if (!ncols) return GLP_OK;
     if (log_n > (uint32_t)NTT_MAX_LG) return set_error(GLP_ERR_UNSUPPORTED, "log_n=%u > %d", log_n, NTT_MAX_LG);
     const size_t tot = (size_t)ncols << log_n;
+    GLP_TRY(host_field_check(c, "glp_coset_ifft", "cols", cols, 0, ncols, (size_t)1 << log_n));
     return on_device_copy(c, cols, tot, cols, tot, [&](Scratch &s, u64 *a, u64 **res) {
         u64 *b;
         GLP_TRY(s.words(&b, tot));
@@ -509,11 +519,12 @@ int batch_build(glp_ctx *c, const u64 *dev_in, int input_kind, u32 ncols, int lg
 }
 
 // the single-batch entry points that take host memory
-static int batch_from_host(glp_ctx *c, const u64 *host, bool from_values, u32 ncols, u32 log_n, u32 rate_bits, u32 cap_height,
+static int batch_from_host(const char *fn, glp_ctx *c, const u64 *host, bool from_values, u32 ncols, u32 log_n, u32 rate_bits, u32 cap_height,
                            glp_batch **out, int hasher = GLP_HASH_POSEIDON, const u64 *salt_seed = nullptr, u32 salt_tag = 0) {
     GLP_REQUIRE(c && host && out, "null argument");
     *out = nullptr;
     GLP_TRY(batch_shape_check(nullptr, 1, ncols, log_n, rate_bits, cap_height, (u32)hasher));
+    GLP_TRY(host_field_check(c, fn, from_values ? "values" : "coeffs", host, 0, ncols, (size_t)1 << log_n));
     GLP_TRY(bind(c));
     Scratch s(c);
     const size_t tot = (size_t)ncols << log_n;
@@ -528,12 +539,13 @@ static int batch_from_host(glp_ctx *c, const u64 *host, bool from_values, u32 nc
 }
 
 // glp_batch_many_from_*: K batches of one shape from [K][ncols][n], host or device memory
-static int batch_many(glp_ctx *c, const u64 *in, int on_device, bool from_values, u32 K, u32 ncols, u32 log_n, u32 rate_bits, u32 cap_height,
+static int batch_many(const char *fn, glp_ctx *c, const u64 *in, int on_device, bool from_values, u32 K, u32 ncols, u32 log_n, u32 rate_bits, u32 cap_height,
                       u32 hasher, const u64 *seed, glp_batch **out) {
     GLP_REQUIRE(c && in && out, "null argument");
     *out = nullptr;
     GLP_REQUIRE(K >= 1 && K <= 4096, "num_proofs = %u outside 1..4096", K);
     GLP_TRY(batch_shape_check(nullptr, K, ncols, log_n, rate_bits, cap_height, hasher, BATCH_MAX_BYTES));
+    if (!on_device) GLP_TRY(host_field_check(c, fn, from_values ? "values" : "coeffs", in, K, ncols, (size_t)1 << log_n));
     GLP_TRY(bind(c));
     u64 sd[4];
     if (seed) for (int i = 0; i < 4; i++) sd[i] = glf::canon(seed[i]);
@@ -554,11 +566,11 @@ extern "C" {
 
 int glp_batch_many_from_values(glp_ctx *c, const uint64_t *values, int values_on_device, uint32_t num_proofs, uint32_t ncols, uint32_t log_n,
                                uint32_t rate_bits, uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out) {
-    return batch_many(c, values, values_on_device, true, num_proofs, ncols, log_n, rate_bits, cap_height, hasher, seed, out);
+    return batch_many("glp_batch_many_from_values", c, values, values_on_device, true, num_proofs, ncols, log_n, rate_bits, cap_height, hasher, seed, out);
 }
 int glp_batch_many_from_coeffs(glp_ctx *c, const uint64_t *coeffs, int coeffs_on_device, uint32_t num_proofs, uint32_t ncols, uint32_t log_n,
                                uint32_t rate_bits, uint32_t cap_height, uint32_t hasher, const uint64_t *seed, glp_batch **out) {
-    return batch_many(c, coeffs, coeffs_on_device, false, num_proofs, ncols, log_n, rate_bits, cap_height, hasher, seed, out);
+    return batch_many("glp_batch_many_from_coeffs", c, coeffs, coeffs_on_device, false, num_proofs, ncols, log_n, rate_bits, cap_height, hasher, seed, out);
 }
 uint32_t glp_batch_num_proofs(const glp_batch *b) { return b ? b->K : 0; }
 int glp_batch_member(const glp_batch *b, uint32_t k, glp_batch **view_out) {
@@ -587,19 +599,19 @@ int glp_batch_caps(const glp_batch *b, uint64_t *caps_out) {
 
 int glp_batch_from_values(glp_ctx *c, const uint64_t *values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
                           uint32_t cap_height, glp_batch **out) {
-    return batch_from_host(c, values, true, ncols, log_n, rate_bits, cap_height, out);
+    return batch_from_host("glp_batch_from_values", c, values, true, ncols, log_n, rate_bits, cap_height, out);
 }
 int glp_batch_from_coeffs(glp_ctx *c, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
                           uint32_t cap_height, glp_batch **out) {
-    return batch_from_host(c, coeffs, false, ncols, log_n, rate_bits, cap_height, out);
+    return batch_from_host("glp_batch_from_coeffs", c, coeffs, false, ncols, log_n, rate_bits, cap_height, out);
 }
 int glp_batch_from_values_h(glp_ctx *c, const uint64_t *values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits, uint32_t cap_height,
                             uint32_t hasher, glp_batch **out) {
-    return batch_from_host(c, values, true, ncols, log_n, rate_bits, cap_height, out, (int)hasher);
+    return batch_from_host("glp_batch_from_values_h", c, values, true, ncols, log_n, rate_bits, cap_height, out, (int)hasher);
 }
 int glp_batch_from_coeffs_h(glp_ctx *c, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, uint32_t rate_bits, uint32_t cap_height,
                             uint32_t hasher, glp_batch **out) {
-    return batch_from_host(c, coeffs, false, ncols, log_n, rate_bits, cap_height, out, (int)hasher);
+    return batch_from_host("glp_batch_from_coeffs_h", c, coeffs, false, ncols, log_n, rate_bits, cap_height, out, (int)hasher);
 }
 int glp_batch_from_values_salted(glp_ctx *c, const uint64_t *values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
                                  uint32_t cap_height, uint32_t hasher, const uint64_t seed[4], glp_batch **out) {
@@ -607,7 +619,7 @@ int glp_batch_from_values_salted(glp_ctx *c, const uint64_t *values, uint32_t nc
     GLP_TRY(bind(c));
     u64 s[4];
     for (int i = 0; i < 4; i++) s[i] = glf::canon(seed[i]);
-    return batch_from_host(c, values, true, ncols, log_n, rate_bits, cap_height, out, (int)hasher, s, GLP_SALT_TAG_BATCH);
+    return batch_from_host("glp_batch_from_values_salted", c, values, true, ncols, log_n, rate_bits, cap_height, out, (int)hasher, s, GLP_SALT_TAG_BATCH);
 }
 int glp_batch_from_values_device(glp_ctx *c, const uint64_t *dev_values, uint32_t ncols, uint32_t log_n, uint32_t rate_bits,
                                  uint32_t cap_height, glp_batch **out) {
@@ -665,6 +677,7 @@ int glp_batch_from_coset_values(glp_ctx *c, const uint64_t *values, int values_o
     const size_t ncols = (size_t)num_polys << (sub_bits & 31);      // the mask keeps the shift defined until sub_bits is refused below
     GLP_TRY(batch_shape_check("glp_batch_from_coset_values", num_proofs, ncols, log_n, rate_bits, cap_height, hasher, BATCH_MAX_BYTES));
     GLP_REQUIRE(sub_bits <= rate_bits, "sub_bits = %u is more than rate_bits = %u", sub_bits, rate_bits);
+    if (!values_on_device) GLP_TRY(host_field_check(c, "glp_batch_from_coset_values", "values", values, num_proofs, num_polys, (size_t)1 << (log_n + sub_bits)));
     GLP_TRY(bind(c));
     u64 sd[4];
     if (seed) for (int i = 0; i < 4; i++) sd[i] = glf::canon(seed[i]);

@@ -264,6 +264,9 @@ struct glp_fri {
             for (u32 q = 0; q < nq; q++)
                 GLP_REQUIRE(indices[(size_t)k * nq + q] < (u64)g.N, "indices[%u][%u] = %llu outside the LDE domain", k, q,
                             (unsigned long long)indices[(size_t)k * nq + q]);
+        for (u32 k = 0; k < K; k++)          // a field element that lands in the proof
+            GLP_REQUIRE(pow_witnesses[k] < P, "glp_fri_queries: pow_witnesses[%u] = 0x%016llx is not a canonical field element (>= p)", k,
+                        (unsigned long long)pow_witnesses[k]);
         for (u32 k = 0; k < K; k++) proof_words(k)[o_pow] = pow_witnesses[k];
         StageScope st(c, "fri.queries", 0.0);
         u64 *dev_idx, *dev_q;

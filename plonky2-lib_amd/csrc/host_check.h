@@ -22,8 +22,9 @@ int set_error(int code, const char *fmt, ...);
     } while (0)
 
 // index of the first word >= p, or count if every word is a canonical field element (host; the inner loop vectorises).
-// The kernels assume canonical inputs: a word >= p gives a silently wrong proof, so the entry points that take field arrays
-// from outside (circuit description, hand-off file) reject it by name.
+// glf::add and glf::sub are right for canonical operands only, so no word >= p gets that far: every entry point that takes a field
+// array from host memory rejects it by name with this scan (large arrays in pieces on the context's host threads: host_pool.h,
+// host_field_check), and the kernels that read a caller's device words reduce them with canon() as they load them.
 inline size_t first_noncanonical(const u64 *v, size_t count) {
     for (size_t i0 = 0; i0 < count; i0 += 4096) {
         const size_t i1 = i0 + 4096 < count ? i0 + 4096 : count;

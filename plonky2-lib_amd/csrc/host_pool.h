@@ -103,4 +103,34 @@ inline HostPool &ctx_host_pool(glp_ctx *c) {
     if (!c->host_pool) { c->host_pool = new HostPool(host_threads()); c->host_pool_free = [](void *q) { delete static_cast<HostPool *>(q); }; }
     return *static_cast<HostPool *>(c->host_pool);       // persistent: thread start-up costs more than a small batch
 }
+
+// first_noncanonical (host_check.h) of a large host array -- a witness, the input of a commitment -- in pieces on the context's host
+// threads, so that the pass stays small beside the upload that follows.  One thread scans 4 MB in well under a millisecond: below a
+// few pieces the fork-join would cost more than it saves.
+inline size_t first_noncanonical_pooled(glp_ctx *c, const u64 *v, size_t count) {
+    constexpr size_t PIECE = (size_t)1 << 19;            // words
+    if (count < 4 * PIECE) return first_noncanonical(v, count);
+    const size_t pieces = (count + PIECE - 1) / PIECE;
+    std::vector<size_t> bad(pieces);
+    ctx_host_pool(c).run(pieces, [&](size_t i) {
+        const size_t i0 = i * PIECE, len = std::min(PIECE, count - i0);
+        const size_t b = first_noncanonical(v + i0, len);
+        bad[i] = b == len ? count : i0 + b;
+    });
+    return *std::min_element(bad.begin(), bad.end());
+}
+// A field array in the caller's host memory, [K][ncols][n] words (K == 0: no proof index; ncols == 0: no column index): every word
+// canonical, or GLP_ERR_ARG naming the function, the parameter, the position and the value.  The rule of glp.h's conventions
+// paragraph for host arrays; the callers run it before they allocate or launch anything.
+inline int host_field_check(glp_ctx *c, const char *fn, const char *name, const u64 *v, size_t K, size_t ncols, size_t n) {
+    const size_t count = (K ? K : 1) * (ncols ? ncols : 1) * n, bad = first_noncanonical_pooled(c, v, count);
+    if (bad == count) return GLP_OK;
+    char where[96];
+    const size_t per_proof = (ncols ? ncols : 1) * n;
+    int at = 0;
+    if (K) at += snprintf(where + at, sizeof(where) - at, "proof %zu, ", bad / per_proof);
+    if (ncols) at += snprintf(where + at, sizeof(where) - at, "column %zu, ", bad % per_proof / n);
+    snprintf(where + at, sizeof(where) - at, "index %zu", bad % n);
+    return set_error(GLP_ERR_ARG, "%s: %s: %s = 0x%016llx is not a canonical field element (>= p)", fn, name, where, (unsigned long long)v[bad]);
+}
 }  // namespace glp

@@ -326,7 +326,7 @@ __global__ void k_bitrev_copy(const u64 *__restrict__ in, u64 *__restrict__ out,
     const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const size_t col = blockIdx.y;
-    out[col * n + bitrev32((u32)p, lg)] = in[col * n + p];
+    out[col * n + bitrev32((u32)p, lg)] = canon(in[col * n + p]);
 }
 // coset-major slot (r, q) -> natural index q * R + r
 __global__ void k_lde_to_natural(const u64 *__restrict__ in, u64 *__restrict__ out, int lg, int rate_bits) {
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void k_outer(const u64 *__restrict__ in, u64 *
     const size_t base = ((size_t)plane << L) * M + q;
     u64 x[A];
 #pragma unroll
-    for (int pbo = 0; pbo < A; pbo++) x[pbo] = in[base + (size_t)pbo * M];
+    for (int pbo = 0; pbo < A; pbo++) x[pbo] = DIF ? canon(in[base + (size_t)pbo * M]) : in[base + (size_t)pbo * M];    // inverse: may be the caller's words
     if (!DIF) {
         if constexpr (TW) {
 #pragma unroll
@@ -688,7 +688,7 @@ __global__ __launch_bounds__(TPB) void k_strided16(const u64 *__restrict__ in, u
         for (int qb = 0; qb < 16; qb++) out[base + (size_t)(g + 16 * qb) * B] = x[qb];
     } else {
 #pragma unroll
-        for (int ia = 0; ia < 16; ia++) x[ia] = in[base + (size_t)(16 * ia + g) * B];     // g = ib
+        for (int ia = 0; ia < 16; ia++) x[ia] = canon(in[base + (size_t)(16 * ia + g) * B]);     // g = ib
         dft_reg_dif<true, 4>(x);                                                               // over ia -> ka at x[ra]
 #pragma unroll
         for (int ra = 0; ra < 16; ra++) {
@@ -727,7 +727,7 @@ __global__ __launch_bounds__(TPB) void k_strided16e(const u64 *__restrict__ in, 
         for (int qa = 0; qa < 16; qa++) lds[(qa * E + g) * Wc + w] = qa == 0 ? x[0] : mul_c(x[qa], tw4096[Wc * kb * qa]);
     } else {
 #pragma unroll
-        for (int ia = 0; ia < 16; ia++) x[ia] = in[base + (size_t)(E * ia + g) * B + w];      // g = ib
+        for (int ia = 0; ia < 16; ia++) x[ia] = canon(in[base + (size_t)(E * ia + g) * B + w]);      // g = ib
         dft_reg_dif<true, 4>(x);                                                                   // over ia -> ka at x[ra]
 #pragma unroll
         for (int ra = 0; ra < 16; ra++) {
@@ -803,7 +803,11 @@ template <bool DIF, int L2, int LW>
 __device__ __forceinline__ void s32_step1(u64 *x, u64 *lds32, const u64 *twl, int g, int w) {
     constexpr int L1 = 5, A1 = 32, A2 = 1 << L2, Wc = 1 << LW, SLAB = (A2 + 1) * Wc;
     if (!DIF) dft_reg_dit<false, L1>(x);           // over ka -> qa
-    else dft_reg_dif<true, L1>(x);                 // over ia -> ka at x[ra]
+    else {
+#pragma unroll
+        for (int r = 0; r < A1; r++) x[r] = canon(x[r]);      // here, not in s32_load: the loads stay in flight until the values are needed
+        dft_reg_dif<true, L1>(x);                  // over ia -> ka at x[ra]
+    }
     const u64 *tw = twl + A1 * g;
 #pragma unroll
     for (int q = 0; q < A1; q++) lds32[q * SLAB + g * Wc + w] = q == 0 ? x[0] : mul_c(x[q], tw[q]);      // q = qa (DIT) / ra (DIF); tw[0] = 1
@@ -922,7 +926,7 @@ __global__ __launch_bounds__(256) void k_intt_small(const u64 *__restrict__ in, 
     if (col >= ncols) return;
     u64 x[n];
 #pragma unroll
-    for (int i = 0; i < n; i++) x[i] = in[(size_t)col * n + i];
+    for (int i = 0; i < n; i++) x[i] = canon(in[(size_t)col * n + i]);
     dft_reg_dif<true, L>(x);
 #pragma unroll
     for (int p = 0; p < n; p++) out[(size_t)col * n + p] = mul_c(x[p], n_inv);

@@ -178,6 +178,8 @@ int glp_perm_zs_commit(glp_ctx *c, const glp_perm_desc *desc, uint32_t num_proof
     GLP_TRY(perm_challenges_check(fn, "gammas", gammas, K, s.nch));
     const size_t n = (size_t)1 << s.lg;
     GLP_REQUIRE((size_t)K * s.nw <= BATCH_MAX_BYTES / (8 * n), "%s: wires too large (num_proofs * num_wires * 2^log_n words)", fn);
+    if (!wires_on_device) GLP_TRY(host_field_check(c, fn, "wires", wires, K, s.nw, n));
+    if (!sigmas_on_device) GLP_TRY(host_field_check(c, fn, "sigmas", sigmas, 0, s.nr, n));
     GLP_TRY(bind(c));
     u64 sd[4];
     if (seed) for (int i = 0; i < 4; i++) sd[i] = canon(seed[i]);
@@ -242,9 +244,10 @@ int glp_perm_quotient_values(glp_ctx *c, const glp_perm_desc *desc, uint32_t num
     GLP_TRY(perm_challenges_check(fn, "betas", betas, K, s.nch));
     GLP_TRY(perm_challenges_check(fn, "gammas", gammas, K, s.nch));
     GLP_TRY(perm_challenges_check(fn, "alphas", alphas, K, s.nch));
-    GLP_TRY(bind(c));
     const u32 nch = s.nch, S = 1u << sub_bits, nt = nch * (s.npp + 2) + 1;
     const size_t n = (size_t)1 << s.lg, N = n << rb, M = n << sub_bits, words = (size_t)K * nch * M;
+    if (gate_sums && !gate_sums_on_device) GLP_TRY(host_field_check(c, fn, "gate_sums", gate_sums, K, nch, M));
+    GLP_TRY(bind(c));
     Scratch tmp(c);
     // one table: k_is [nr], then per proof betas[MAXCH], gammas[MAXCH], alpha powers [nch][nt]
     const u32 tab_stride = 2 * MAXCH + nch * nt;

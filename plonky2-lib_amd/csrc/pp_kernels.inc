@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void k_pp_rows(PPArgs a) {
         _Pragma("unroll") for (int c = 0; c < NCH; c++) { num[c] = 1; den[c] = 1; }
         const u32 j1 = min((chunk + 1) * a.qdf, a.nr);
         for (u32 j = chunk * a.qdf; j < j1; j++) {
-            const u64 w = a.wires[(size_t)j * n + i], s = a.sigmas[(size_t)j * n + i];
+            const u64 w = canon(a.wires[(size_t)j * n + i]), s = canon(a.sigmas[(size_t)j * n + i]);   // a caller's device words: reduced as loaded
             const u64 kx = mul(a.k_is[j], x);
             _Pragma("unroll") for (int c = 0; c < NCH; c++) {
                 num[c] = mul(num[c], add(add(w, mul(betas[c], kx)), gammas[c]));
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_pp_rows_small(PPArgs a) {
         u64 num = 1, den = 1;
         const u32 j1 = min((chunk + 1) * a.qdf, a.nr);
         for (u32 j = chunk * a.qdf; j < j1; j++) {
-            const u64 w = a.wires[(size_t)j * n + i], sg = a.sigmas[(size_t)j * n + i];
+            const u64 w = canon(a.wires[(size_t)j * n + i]), sg = canon(a.sigmas[(size_t)j * n + i]);
             num = mul(num, add(add(w, mul(beta, mul(a.k_is[j], x))), gamma));
             den = mul(den, add(add(w, mul(beta, sg)), gamma));
         }

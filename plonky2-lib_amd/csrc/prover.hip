@@ -20,6 +20,7 @@
 #include <string.h>
 #include "batch.h"
 #include "common.h"
+#include "host_pool.h"   // host_field_check, the transcripts' host threads
 #include "merkle.h"
 #include "ntt.h"
 #include "poseidon.h"
@@ -387,6 +388,16 @@ static int prove_impl(glp_ctx *c, const glp_circuit *cc, const u64 *dev_wires, c
 
 #include "circuit_create.inc"
 
+// The host field arrays of a prove call are canonical or the call is refused by name, before anything is allocated or launched: the
+// witness where it is in host memory, and the public inputs.  K == 0: one proof, no proof index in the message.
+static int host_wires_check(glp_ctx *c, const char *fn, const char *name, const glp_circuit *cc, u32 K, const u64 *host_wires) {
+    return host_field_check(c, fn, name, host_wires, K, cc->d.num_wires, (size_t)1 << cc->d.degree_bits);
+}
+static int public_inputs_check(glp_ctx *c, const char *fn, const glp_circuit *cc, u32 K, const u64 *public_inputs) {
+    if (!public_inputs || !cc->d.num_public_inputs) return GLP_OK;
+    return host_field_check(c, fn, "public_inputs", public_inputs, K, 0, cc->d.num_public_inputs);
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -396,6 +407,8 @@ int glp_session_begin(glp_ctx *c, const glp_circuit *cc, const uint64_t *wires, 
     *out = nullptr;
     GLP_REQUIRE(cc->ctx == c, "circuit belongs to another context");
     GLP_REQUIRE(public_inputs || cc->d.num_public_inputs == 0, "public_inputs is null");
+    if (!wires_on_device) GLP_TRY(host_wires_check(c, "glp_session_begin", "wires", cc, 0, wires));
+    GLP_TRY(public_inputs_check(c, "glp_session_begin", cc, 0, public_inputs));
     GLP_TRY(bind(c));
     std::unique_ptr<glp_session> s(new glp_session(c, cc));
     const u64 *dw = wires;
@@ -489,6 +502,7 @@ int glp_pow_search_h(glp_ctx *c, uint32_t hasher, const uint64_t sponge_state[12
 int glp_session_queries(glp_session *s, uint64_t pow_witness, const uint64_t *indices, uint32_t num_indices) {
     GLP_SESSION_ENTER(s);
     GLP_REQUIRE(indices, "null argument");
+    GLP_REQUIRE(pow_witness < P, "glp_session_queries: pow_witness = 0x%016llx is not a canonical field element (>= p)", (unsigned long long)pow_witness);
     return s->queries(pow_witness, indices, num_indices);
 }
 int glp_session_proof(glp_session *s, uint64_t *proof_out) {
@@ -507,6 +521,7 @@ int glp_prove_device(glp_ctx *c, const glp_circuit *cc, const uint64_t *dev_wire
     GLP_REQUIRE(c && cc && dev_wires && proof_out, "null argument");
     GLP_REQUIRE(cc->ctx == c, "circuit belongs to another context");
     GLP_REQUIRE(public_inputs || cc->d.num_public_inputs == 0, "public_inputs is null");
+    GLP_TRY(public_inputs_check(c, "glp_prove_device", cc, 0, public_inputs));
     GLP_TRY(bind(c));
     return prove_impl(c, cc, dev_wires, public_inputs, proof_out);
 }
@@ -515,6 +530,8 @@ int glp_prove(glp_ctx *c, const glp_circuit *cc, const uint64_t *wires, const ui
     GLP_REQUIRE(c && cc && wires && proof_out, "null argument");
     GLP_REQUIRE(cc->ctx == c, "circuit belongs to another context");
     GLP_REQUIRE(public_inputs || cc->d.num_public_inputs == 0, "public_inputs is null");
+    GLP_TRY(host_wires_check(c, "glp_prove", "wires", cc, 0, wires));
+    GLP_TRY(public_inputs_check(c, "glp_prove", cc, 0, public_inputs));
     GLP_TRY(bind(c));
     const size_t tot = (size_t)cc->d.num_wires << cc->d.degree_bits;
     Scratch sc(c);
@@ -564,6 +581,8 @@ int glp_witness_stage(glp_ctx *c, const glp_circuit *cc, const uint64_t *host_wi
     GLP_TRY(bind(c));
     const size_t n = (size_t)1 << cc->d.degree_bits;
     const u32 nw = cc->d.num_wires, nr = cc->d.num_routed_wires;
+    // only the columns that are copied are read: with GLP_WITNESS_ROUTED_ONLY the routed ones
+    GLP_TRY(host_field_check(c, "glp_witness_stage", "host_wires", host_wires, 0, (flags & GLP_WITNESS_ROUTED_ONLY) ? nr : nw, n));
     std::unique_ptr<glp_witness, void (*)(glp_witness *)> w(new glp_witness(), glp_witness_free);
     w->c = c; w->cc = cc; w->routed_only = (flags & GLP_WITNESS_ROUTED_ONLY) != 0;
     void *dv = nullptr;
@@ -581,6 +600,7 @@ int glp_prove_staged(glp_ctx *c, const glp_circuit *cc, glp_witness *w, const ui
     GLP_REQUIRE(c && cc && w && proof_out, "null argument");
     GLP_REQUIRE(cc->ctx == c && w->c == c && w->cc == cc, "witness, circuit and context do not belong together");
     GLP_REQUIRE(public_inputs || cc->d.num_public_inputs == 0, "public_inputs is null");
+    GLP_TRY(public_inputs_check(c, "glp_prove_staged", cc, 0, public_inputs));
     GLP_TRY(bind(c));
     GLP_HIP(hipStreamWaitEvent(c->stream, w->ready, 0));
     if (w->routed_only && !w->filled) {

@@ -175,6 +175,8 @@ extern "C" int glp_prove_batch(glp_ctx *c, const glp_circuit *cc, uint32_t num_p
     GLP_REQUIRE(cc->ctx == c, "circuit belongs to another context");
     GLP_REQUIRE(public_inputs || cc->d.num_public_inputs == 0, "public_inputs is null");
     GLP_REQUIRE(num_proofs >= 1, "empty batch");
+    if (!wires_on_device) GLP_TRY(host_wires_check(c, "glp_prove_batch", "wires", cc, num_proofs, wires));
+    GLP_TRY(public_inputs_check(c, "glp_prove_batch", cc, num_proofs, public_inputs));
     GLP_TRY(bind(c));
     static const u64 no_pis = 0;
     const u64 *pis = public_inputs ? public_inputs : &no_pis;

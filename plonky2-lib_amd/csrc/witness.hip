@@ -23,8 +23,8 @@
 //                           extra constants of RandomAccessGate), ArithmeticExtensionGenerator, MulExtensionGenerator,
 //                           ReducingGenerator, ReducingExtensionGenerator (F_p^2 values on wire pairs),
 //                           ExponentiationGenerator, InterpolationGenerator (CosetInterpolationGate), PoseidonMdsGenerator
-// Every value written is a canonical field element; inputs are read as canonical u64 exactly as
-// `to_canonical_u64()` hands them to the Rust generators.
+// Every value written is a canonical field element; inputs are reduced mod p as they are loaded, which is the canonical u64
+// that `to_canonical_u64()` hands to the Rust generators.
 #include <stdlib.h>
 #include <new>
 #include "common.h"
@@ -52,13 +52,13 @@ __device__ __forceinline__ u64 winv(u64 a) {          // a != 0
 // i -> GC[i * n]).  k_witness_fill runs every unit of a row; the wave kernels below run the units a plan lists.  WHICH = 1 keeps only
 // the gates with one unit per op, WHICH = 2 only those with one unit per row (k_witness_fill loops over the first kind alone, so that
 // nothing of a PoseidonGate row is hoisted out of a loop it runs once); 0 keeps all.
-template <int WHICH = 0>
+template <int WHICH = 0, bool RAW = false>
 __device__ __forceinline__ void witness_unit(const WArgs &a, const DevGate &g, u64 *W, const u64 *GC, size_t n, u32 unit) {
     const u32 nr = a.only_advice ? a.nr : 0xFFFFFFFFu;         // only_advice: columns < nr (routed) are never written
     constexpr bool ONE = WHICH != 1, PER_OP = WHICH != 2;      // which cases this instance keeps: gates of one unit per row, gates of one per op
     const u32 i = unit;                                        // the op of a gate with one generator per op
 #define WR(col, val) do { const u32 _c = (col); if (!a.only_advice || _c >= nr) W[(size_t)_c * n] = (val); } while (0)
-#define RD(col) W[(size_t)(col) * n]
+#define RD(col) (RAW ? canon(W[(size_t)(col) * n]) : W[(size_t)(col) * n])    // RAW: a caller's device words (glp_witness_fill), reduced mod p as they are loaded
     switch (g.type) {
     case GLP_GATE_CONSTANT: if (!ONE) break;
         for (u32 k = 0; k < g.p0; k++) WR(k, GC[(size_t)k * n]);
@@ -334,8 +334,8 @@ __global__ __launch_bounds__(256) void k_witness_fill(WArgs a) {
     const u32 nu = witness_gate_units(g.type, g.p0, g.p1);
     u64 *W = a.wires + row;
     const u64 *GC = a.consts + (size_t)a.nsel * n + row;
-    if (nu) witness_unit<2>(a, g, W, GC, n, 0);                          // a gate with one unit per row: nothing for the others
-    for (u32 u = 0; u < nu; u++) witness_unit<1>(a, g, W, GC, n, u);    // a gate with one unit per op: nothing for the others
+    if (nu) witness_unit<2, true>(a, g, W, GC, n, 0);                          // a gate with one unit per row: nothing for the others
+    for (u32 u = 0; u < nu; u++) witness_unit<1, true>(a, g, W, GC, n, u);    // a gate with one unit per op: nothing for the others
 }
 
 }  // namespace

@@ -108,6 +108,24 @@ def test_committed_sample_file_current_version():
         _same(cf.desc, synth.zkdsa_circuit(3))
 
 
+def test_the_writer_refuses_a_word_that_is_no_field_element(tmp_path):
+    """glp_circuit_file_write holds the witness and the public inputs to what the reader enforces: a word >= p is named, no file is left"""
+    import copy
+    desc = synth.zkdsa_circuit(3)
+    for word in (glp.P, 2 ** 64 - 1):
+        for field, at in (("wires", (5, 3)), ("public_inputs", (7,))):
+            d = copy.copy(desc)
+            arr = np.array(getattr(desc, field), np.uint64)
+            arr[at] = word
+            setattr(d, field, arr)
+            path = str(tmp_path / ("%s_%x.glpc" % (field, word)))
+            with pytest.raises(glp.GlpError) as e:
+                glp.write_circuit_file(path, d)
+            flat = int(np.ravel_multi_index(at, arr.shape))
+            assert e.value.code == -1 and "%s[%d] = 0x%016x" % (field, flat, word) in str(e.value) and "canonical" in str(e.value)
+    glp.write_circuit_file(str(tmp_path / "good.glpc"), desc)
+
+
 def test_damaged_files_are_errors(tmp_path):
     desc = synth.arith_circuit(5, synth.Config.standard_recursion_config(), seed=2)
     path = str(tmp_path / "c.glpc")

@@ -364,6 +364,11 @@ def test_refusals(ctx, oracle):
     assert code == -3 and "oracles[1]" in msg
     code, msg = _refused(lambda: glp.fri_prove_many(ctx, [m2, m3], ranges, zs, [2], 4, 2, np.zeros((3, 12), np.uint64)))
     assert code == -1 and "K = 2" in msg
+    for word in (glp.P, 2 ** 64 - 1):                          # the one-call form holds the points to the same rule
+        bad = zs.copy()
+        bad[1, 1, 0] = word
+        code, msg = _refused(lambda: glp.fri_prove_many(ctx, [m3], ranges, bad, [2], 4, 2, np.zeros((3, 12), np.uint64)))
+        assert code == -1 and "canonical" in msg and "points[1][1]" in msg
     for b in (shared, m2, m3):
         b.free()
 

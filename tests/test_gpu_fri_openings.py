@@ -277,6 +277,10 @@ def test_steps_out_of_order(ctx, oracle):
     f.commit()
     with pytest.raises(glp.GlpError):
         f.commit()                                         # beta pending
+    for bad in ([glp.P, 0], [1, 2 ** 64 - 1]):
+        with pytest.raises(glp.GlpError) as e:
+            f.fold(bad)                                    # not canonical
+        assert e.value.code == -1 and "beta" in str(e.value) and "canonical" in str(e.value)
     with pytest.raises(glp.GlpError):
         f.final_poly()
     f.fold([1, 2]); f.commit(); f.fold([5, 6])

@@ -303,6 +303,11 @@ def test_refusals(ctx, oracle, case_c3):
     bad[2, 1] = glp.P
     code, msg = stepped(al=bad)
     assert code == -1 and "alphas[2]" in msg
+    for word in (glp.P, 2 ** 64 - 1):
+        bad = be.copy()
+        bad[1, be.shape[1] - 1, 1] = word
+        code, msg = stepped(be=bad)
+        assert code == -1 and "betas[1]" in msg and "canonical" in msg
     # one proof: a damaged proof is GLP_ERR_PROVE with the check in glp_last_error, not an exception
     one = dict(caps=[caps[0]] + [x[0] for x in caps[1:]], **geo)
     assert glp.fri_verify(ctx, c.shapes, c.inst(0).points, ab, pw, nq, openings[0], words[0], c.states[0], c.pend[0], **one) is True

@@ -548,6 +548,9 @@ def test_stepped_session_enforces_order(ctx):
         s.proof()                                      # nothing to hand out yet
     with pytest.raises(glp.GlpError):
         s.partial_products([0xFFFFFFFF00000001] * desc.num_challenges, [7] * desc.num_challenges)   # p itself: not canonical
+    with pytest.raises(glp.GlpError) as e:
+        s.partial_products([5] * desc.num_challenges, [7] * (desc.num_challenges - 1) + [2 ** 64 - 1])    # a gamma: the same
+    assert e.value.code == -1 and "challenge %d" % (desc.num_challenges - 1) in str(e.value) and "canonical" in str(e.value)
     s.partial_products([5] * desc.num_challenges, [7] * desc.num_challenges)
     with pytest.raises(glp.GlpError):
         s.fri_commit()

@@ -431,6 +431,11 @@ def test_refusals(ctx):
         W[1, 5, 3] = v
         refused("wires: proof 1, word %d = 0x%016x" % (word - W[0].size, v), ctx._h, gc._h, 2, wp, 0, pp, reps, None)
         W[1, 5, 3] = keep
+        keep = int(pi[1, 7])
+        pi[1, 7] = v
+        refused("public_inputs: proof 1, word 7 = 0x%016x" % v, ctx._h, gc._h, 2, wp, 0, pp, reps, None)
+        pi[1, 7] = keep
+    assert L.glp_witness_check(ctx._h, gc._h, 2, wp, 0, pp, reps, None) == 0 and not reps[1].failed_constraints
     gc.free()
 
 
